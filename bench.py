@@ -23,8 +23,12 @@ CPU copies of the bitmap, since RCCL refuses two ranks on one device.
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline      the stage that takes longest (`kernel` lists the kernels it sums; --chain-only: k_sketch_probe alone): algorithmic
                 bytes / HIP-event time vs 8 TB/s, the other stages in stage_ms_per_step, K1's own figure in streaming_kernel
-  cpu_baseline  the CPU oracle (oracle/, "port": restated minimap2 decision path, NOT minimap2-rs)
+  cpu_baseline  (--full) the CPU oracle (oracle/, "port": restated minimap2 decision path, NOT minimap2-rs)
                 on the host cores, on a bounded sample of the same records and the same index
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line; everything else it can measure or check (CPU baselines,
+oracle checks, the host-buffer path, weak scaling, the `secondary` object) runs with --full only.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (same arguments, same inputs: two builds compare output for output).
 """
 import argparse
 import json
@@ -77,6 +81,13 @@ def parse():
                     help="headline run (--workload sr, one GPU): skip the `secondary` object - configs[3] (long reads, map-ont) and configs[4] (Kraken2-style) "
                          "measured in the same process AFTER the headline's timed region")
     ap.add_argument("--secondary-cpu-seconds", type=float, default=8.0, help="CPU-oracle sample of each secondary line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: CPU baselines and oracle checks, the real tools if present, the "
+                         "host-buffer path, the fixed cost of a call, weak scaling (N > 1) and the `secondary` object.  Without it a run sets up, warms up, "
+                         "times --steps steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; "
+                         "a fixed, seeded sample of a larger output)")
     return ap.parse_args()
 
 
@@ -128,7 +139,7 @@ def main():
     if a.workload == "e2e-k2":
         return main_e2e_k2(a, rank, world, local, dev)
     out = main_k2(a, rank, world, local, dev, backend) if a.workload == "k2" else main_reads(a, rank, world, local, dev, backend)
-    if out is not None and a.workload == "sr" and world == 1 and not a.chain_only and not a.no_secondary:
+    if out is not None and a.full and a.workload == "sr" and world == 1 and not a.chain_only and not a.no_secondary:
         out["secondary"] = secondary_lines(a, rank, local, dev)
     if out is not None:
         print(json.dumps(out), flush=True)
@@ -152,6 +163,7 @@ def secondary_lines(a, rank, local, dev):
         torch.cuda.empty_cache()
         b = copy.copy(a)
         b.workload, b.steps, b.warmup, b.cpu_seconds, b.gather_bench = name, steps, warm, a.secondary_cpu_seconds, False
+        b.dump_outputs = None       # the dump is the headline's
         b.records = 20_000_000      # the sentinel both workloads read as "BASELINE's own size"
         t0 = time.time()
         try:
@@ -289,12 +301,19 @@ def main_reads(a, rank, world, local, dev, backend):
     ms_step = dt / a.steps * 1e3
     value = n_total * a.steps / dt
     removed_total = n_host
+    flags_out = d_flags                   # what the caller receives: N > 1 the united bitmap of the whole job
     if world > 1 and not ont:
-        removed_total = int(D.gathered_to_flags(B["gathered"], slice_bytes, n_total, world).sum().item())
+        flags_out = D.gathered_to_flags(B["gathered"], slice_bytes, n_total, world)
+        removed_total = int(flags_out.sum().item())
+    if a.dump_outputs and rank == 0:
+        if world > 1 and ont:
+            flags_out = flags_of_cuts(B["gathered"], slice_bytes, cuts)
+        dump_flags(a.dump_outputs, flags_out)
+    del flags_out
 
     # ---- secondary: weak scaling (n_total records PER GPU), N > 1 only ----------------------------------------
     weak = None
-    if world > 1 and not a.no_weak:
+    if world > 1 and a.full and not a.no_weak:
         del B, ctx, d_reads, d_flags, d_off
         torch.cuda.empty_cache()
         Bw = make_batch(rank * n_total, n_total)
@@ -350,23 +369,24 @@ def main_reads(a, rank, world, local, dev, backend):
         gbs, gms = index.gather_bench(1 << 28, 3)
         gather = {"useful_GBs_16B_probes": round(gbs, 1), "ms": round(gms, 3), "probes": 1 << 28}
 
-    # ---- CPU baseline: the oracle on the host cores, same index, bounded sample -------------------------
+    # ---- CPU baseline: the oracle on the host cores, same index, bounded sample (--full) -----------------
+    checks = rank == 0 and world == 1 and a.full and not a.no_cpu
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if checks:
         cpu = cpu_baseline(index, info, d_reads, n_rec, L, a.cpu_seconds, d_flags, d_off if ont else None, a.ont_preset if ont else "sr", a.chain_only)
     strat = None
-    if rank == 0 and world == 1 and not a.no_cpu and not ont and not a.chain_only and ctx_chunk(a, n_rec) >= n_rec:
+    if checks and not ont and not a.chain_only and ctx_chunk(a, n_rec) >= n_rec:
         strat = stratified_parity(index, ctx, info, d_reads, d_flags, n_rec, L)
-    if rank == 0 and world == 1 and not a.no_cpu and ont and not a.chain_only:
+    if checks and ont and not a.chain_only:
         # every read whose answer took one of the long-read stage's rarer paths (of the whole batch: the lists describe the last CALL), plus a random rest
         strat = stratified_parity_long(index, ctx, info, d_reads, d_off, d_flags, n_rec, a.ont_preset, a.cpu_seconds)
     ext_oracle = None
-    if rank == 0 and world == 1 and not a.no_cpu:      # the real tool, when the box has it: `-c -x sr` / `-c -x map-ont`
+    if checks:      # the real tool, when the box has it: `-c -x sr` / `-c -x map-ont`
         ext_oracle = external_oracle(index, d_reads, n_rec, L, d_flags, contigs, P, dev, real_ref, preset=a.ont_preset if ont else "sr", d_off=d_off if ont else None)
 
     # ---- the host-buffer entry point (sh_classify_batch: what a Rust caller binds), PCIe included; never `value` -----------
     host_path = None
-    if rank == 0 and world == 1 and not a.no_cpu and not ont and not a.small:
+    if checks and not ont and not a.small:
         h_reads = d_reads[:n_bases].cpu().numpy()
         h_off = np.arange(n_rec + 1, dtype=np.uint64) * L
         best = None
@@ -381,7 +401,7 @@ def main_reads(a, rank, world, local, dev, backend):
 
     # what a call costs whatever its size (launches, host read-backs between the passes): 10 k records through the same context
     fixed_ms = None
-    if rank == 0 and not ont and n_rec >= 10_000:
+    if rank == 0 and a.full and not ont and n_rec >= 10_000:
         ts = []
         d_flags_small = torch.zeros(10_000, dtype=torch.uint8, device=dev)
         for _ in range(5):
@@ -559,8 +579,13 @@ def main_k2(a, rank, world, local, dev, backend=None):
     value = n_total / (ms_step * 1e-3)
     res = d_out.cpu().numpy().view(K.RESULT_DTYPE).reshape(-1)
     human_total = int((res["taxid"] == 9606).sum())
+    calls_all = None
     if world > 1:
-        human_total = int((D.gathered_to_calls(gathered, slice_len, n_total, world) == 9606).sum().item())
+        calls_all = D.gathered_to_calls(gathered, slice_len, n_total, world)
+        human_total = int((calls_all == 9606).sum().item())
+    if a.dump_outputs and rank == 0:      # N > 1: the whole job's calls, as every rank holds them after the gather (the taxid column)
+        dump_calls(a.dump_outputs, {"taxid": calls_all.cpu().numpy().view(np.uint32)} if world > 1 else {k: res[k] for k in res.dtype.names})
+    del calls_all
     # algorithmic bytes per pair: L1 + L2 + 8 + 4 * P + 4
     alg = n_bases + 8 * n_units + 4 * st["n_probes"] + 4 * n_units
     avg_ms = ms_kernel / max(a.steps, 1)
@@ -570,7 +595,7 @@ def main_k2(a, rank, world, local, dev, backend=None):
             "probe_rate_G_per_s": round(st["n_probes"] / (avg_ms * 1e-3) / 1e9, 2)}
     attach_traffic(roof, "k2", "k_k2_classify", n_rec)
     cpu = None
-    if rank == 0 and not a.no_cpu:
+    if rank == 0 and a.full and not a.no_cpu:
         from oracle import oracle as O
         cells_h, parent_h, ext_h = db.export()
         tab = O.K2Table(cells_h, parent_h, info["value_bits"])
@@ -608,7 +633,7 @@ def main_k2(a, rank, world, local, dev, backend=None):
                "database": {"cells": info["capacity"], "occupied": info["size"], "reference_minimizer_runs": int(n_runs), "nodes": info["n_nodes"],
                             "build_s": round(t_db, 2)},
                "roofline": roof, "cpu_baseline": cpu,
-               "external_oracle": (external_oracle_k2(db, d_reads, n_rec // 2, L, res["taxid"]) if world == 1 and not a.no_cpu else None)}
+               "external_oracle": (external_oracle_k2(db, d_reads, n_rec // 2, L, res["taxid"]) if world == 1 and a.full and not a.no_cpu else None)}
     db.close()
     return out if rank == 0 else None
 
@@ -658,21 +683,24 @@ def main_e2e(a, rank, world, local, dev):
     d_reads = torch.empty(n_rec * L + 64, dtype=torch.uint8, device=dev)
     d_off = torch.empty(n_rec + 1, dtype=torch.int64, device=dev)
     S.synth_reads_device(P, R, 0, n_rec, d_reads, d_off)
-    # expected flags from the device path, in 2 M-record pieces: a whole-batch context would hold (and then free) ~150 GB of HBM,
+    # --full: expected flags from the device path, in 2 M-record pieces: a whole-batch context would hold (and then free) ~150 GB of HBM,
     # and the driver wipes freed VRAM before it is handed out again - the first sh_reads_run below would pay for that
-    piece = min(n_rec, 2_000_000)
-    ctx = S.Context(index, piece, piece * L, L)
-    d_flags = torch.zeros(n_rec, dtype=torch.uint8, device=dev)
-    for r0 in range(0, n_rec, piece):
-        r1 = min(n_rec, r0 + piece)
-        ctx.classify(d_reads[r0 * L:r1 * L], (d_off[r0:r1 + 1] - d_off[r0]).contiguous(), d_flags[r0:r1], None, want_stats=True)
-    torch.cuda.synchronize()
-    fl = d_flags.cpu().numpy().reshape(n_pairs, 2)
-    expect_pairs = int(((fl[:, 0] == 1) | (fl[:, 1] == 1)).sum())      # HashSet union over both files (cleaner.rs:564-570)
+    expect_pairs = None
+    if a.full:
+        piece = min(n_rec, 2_000_000)
+        ctx = S.Context(index, piece, piece * L, L)
+        d_flags = torch.zeros(n_rec, dtype=torch.uint8, device=dev)
+        for r0 in range(0, n_rec, piece):
+            r1 = min(n_rec, r0 + piece)
+            ctx.classify(d_reads[r0 * L:r1 * L], (d_off[r0:r1 + 1] - d_off[r0]).contiguous(), d_flags[r0:r1], None, want_stats=True)
+        torch.cuda.synchronize()
+        fl = d_flags.cpu().numpy().reshape(n_pairs, 2)
+        expect_pairs = int(((fl[:, 0] == 1) | (fl[:, 1] == 1)).sum())      # HashSet union over both files (cleaner.rs:564-570)
+        del ctx, d_flags
     reads = d_reads[:n_rec * L].cpu().numpy().reshape(n_pairs, 2, L)
     r1, r2 = os.path.join(work, "R1.fastq"), os.path.join(work, "R2.fastq")
     in_bytes = fastq_file(r1, reads[:, 0, :], 1, 0) + fastq_file(r2, reads[:, 1, :], 2, 0)
-    del reads, ctx, index, d_reads, d_flags, d_off
+    del reads, index, d_reads, d_off
     torch.cuda.empty_cache()
     t_setup = time.time() - t0
     ext = ".fastq.gz" if a.e2e_gz else ".fastq"
@@ -693,7 +721,9 @@ def main_e2e(a, rank, world, local, dev):
     dt = sum(r[0] for r in runs)
     res = runs[-1][1]
     rep = json.load(open(js))
-    ok = rep["reads_in"] == n_rec and rep["reads_removed"] == 2 * expect_pairs and res["n_depleted_ids"] == expect_pairs
+    ok = None if expect_pairs is None else rep["reads_in"] == n_rec and rep["reads_removed"] == 2 * expect_pairs and res["n_depleted_ids"] == expect_pairs
+    if a.dump_outputs:      # the outputs are files: the report's counts stand for them
+        write_dump(a.dump_outputs, {"report_counts": np.array([rep["reads_in"], rep["reads_out"], rep["reads_removed"], res["n_depleted_ids"]], dtype=np.float64)})
     out_bytes = os.path.getsize(o1) + os.path.getsize(o2)
     mean = lambda k: round(float(np.mean([r[1][k] for r in runs])), 1)
     out = {
@@ -709,7 +739,8 @@ def main_e2e(a, rank, world, local, dev):
         "reads_per_s_incl_index": round(n_rec * a.steps / dt, 1),
         "runs_ms": [{"total": round(r[0] * 1e3, 1), "index": round(r[1]["ms_index"], 1), "pass1": round(r[1]["ms_ingest"], 1), "pass2": round(r[1]["ms_write"], 1)} for r in runs],
         "result": {"reads_in": rep["reads_in"], "reads_out": rep["reads_out"], "reads_removed": rep["reads_removed"],
-                   "expected_removed (device flags, id union over mates)": 2 * expect_pairs, "identical": bool(ok)},
+                   "expected_removed (device flags, id union over mates)": None if expect_pairs is None else 2 * expect_pairs,
+                   "identical": ok},
         "setup_s": round(t_setup, 1),
     }
     if a.e2e_legacy:
@@ -723,7 +754,7 @@ def main_e2e(a, rank, world, local, dev):
     print(json.dumps(out), flush=True)
     if not a.e2e_dir:
         shutil.rmtree(work, ignore_errors=True)
-    assert ok, "end-to-end result differs from the device flags"
+    assert ok is not False, "end-to-end result differs from the device flags"
 
 
 def main_e2e_k2(a, rank, world, local, dev):
@@ -784,6 +815,8 @@ def main_e2e_k2(a, rank, world, local, dev):
     runs = [run() for _ in range(a.steps)]
     dt = sum(r[0] for r in runs)
     rep = json.load(open(js))
+    if a.dump_outputs:      # the outputs are files: the report's counts stand for them
+        write_dump(a.dump_outputs, {"report_counts": np.array([rep["reads_in"], rep["reads_out"], rep["reads_removed"]], dtype=np.float64)})
     out = {
         "metric": "reads/s end to end, taxid arm (FASTQ pairs + Kraken2-format database directory in -> kraken.reads / kraken.report + filtered FASTQ + JSON) - NOT the headline metric",
         "value": round(n_rec * a.steps / dt, 1), "unit": "reads/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
@@ -876,6 +909,60 @@ def diverge_reads(d_reads, n, L, r_lo, dev, slab=2_000_000):
 
 def ctx_chunk(a, n_rec):
     return min(a.chunk, n_rec)
+
+
+DUMP_SEED = 0x5C2B0050
+DUMP_BLOCK = 4096
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_dump(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy, float32 / float64 only, at most DUMP_MAX_BYTES in all."""
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
+def dump_pick(n, cap):
+    """Indices of the units a dump keeps: all n if n <= cap, else a fixed, seeded sample of cap of them (ascending)."""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False)).astype(np.int64)
+
+
+def block_sums(v):
+    """Sum of v over each DUMP_BLOCK consecutive entries: every entry of a larger output in a dump, summed."""
+    v = np.asarray(v)
+    return np.add.reduceat(v, np.arange(0, len(v), DUMP_BLOCK), dtype=np.int64).astype(np.float64) if len(v) else np.zeros(0, np.float64)
+
+
+def dump_flags(d, d_flags, cap=4_000_000):
+    """The per-record flags of the last timed step: `flags` of the records `flags_index` names (every record up to `cap`, else a
+    seeded sample), and `flags_block_sum` over every record of the batch."""
+    f = d_flags.cpu().numpy()
+    pick = dump_pick(len(f), cap)
+    write_dump(d, {"flags": f[pick].astype(np.float32), "flags_index": pick.astype(np.float64), "flags_block_sum": block_sums(f)})
+
+
+def dump_calls(d, fields, cap=1_000_000):
+    """The per-pair result of the Kraken2-style path of the last timed step (fields: name -> array over the job's pairs, `taxid` among
+    them): every pair up to `cap`, else a seeded sample (`pair_index`), and `classified_block_count` (pairs with a taxid) over every pair."""
+    taxid = np.asarray(fields["taxid"])
+    pick = dump_pick(len(taxid), cap)
+    arrays = {name: np.asarray(v)[pick].astype(np.float64) for name, v in fields.items()}
+    arrays["pair_index"] = pick.astype(np.float64)
+    arrays["classified_block_count"] = block_sums(taxid != 0)
+    write_dump(d, arrays)
+
+
+def flags_of_cuts(gathered, slice_bytes, cuts):
+    """The all-gathered bitmap slices (dist.union_depleted) back to one uint8 vector (1 = depleted) when rank r held records
+    [cuts[r], cuts[r + 1]) - the long reads' shards of equal bases, not dist.shard_range's."""
+    from scrubby_amd import dist as D
+    return torch.cat([D.unpack_flags(gathered[r * slice_bytes:(r + 1) * slice_bytes], cuts[r + 1] - cuts[r]) for r in range(len(cuts) - 1)])
 
 
 def long_read_lengths(seed, r0, n):

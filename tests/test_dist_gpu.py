@@ -56,26 +56,33 @@ def test_two_ranks_classify_their_shards_and_unite(tmp_path):
     assert res["counters"] == [20001, res["depleted"]] and 0 < res["depleted"] < 20001
 
 
+@pytest.mark.timeout(600)      # two bench runs of up to 280 s each
 def test_bench_spawns_its_ranks(tmp_path):
-    """`bench.py --gpus 2` starts two ranks itself and reports n_gpus 2 with the same records cut in two (strong scaling)."""
+    """`bench.py --gpus 2` starts two ranks itself and reports n_gpus 2 with the same records cut in two (strong scaling; --full: and the
+    weak-scaling figure)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--small", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--small", "--steps", "2", "--warmup", "1", "--no-cpu", "--full",
+                        "--dump-outputs", str(tmp_path / "d2")],
                        env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     j = json.loads(line)
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["config"]["records_total"] == 200_000 and j["config"]["records_rank0"] == 100_000
     assert j["weak_scaling"]["records_per_gpu"] == 200_000 and j["union_bytes_gathered"] == 2 * 12500
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--small", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary"],
-                         env=env, capture_output=True, text=True, timeout=280)
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--small", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary",
+                          "--dump-outputs", str(tmp_path / "d1")], env=env, capture_output=True, text=True, timeout=280)
     j1 = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][-1])
     assert j1["n_gpus"] == 1 and j1["result"]["reads_removed"] == j["result"]["reads_removed"]
+    # the dump of N = 2 is the united bitmap of the whole job: the flags of the one-rank run
+    f1, f2 = (np.load(tmp_path / d / "flags.npy") for d in ("d1", "d2"))
+    assert len(f2) == 200_000 and np.array_equal(f2, (f1 == 1).astype(np.float32))
 
 
+@pytest.mark.timeout(600)      # two bench runs of up to 280 s each
 def test_k2_bench_is_strong_scaled_over_its_ranks(tmp_path):
     """BASELINE configs[4] in miniature: `bench.py --workload k2 --gpus 2` cuts the SAME pairs in two (the ranks share device 0 here, so
     gloo carries the calls), gathers every pair's call inside the timed region and finds the human pairs the one-rank run finds."""
@@ -86,7 +93,8 @@ def test_k2_bench_is_strong_scaled_over_its_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     runs = {}
     for n in (1, 2):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "k2", "--gpus", str(n), "--small", "--steps", "2", "--warmup", "1", "--no-cpu"],
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "k2", "--gpus", str(n), "--small", "--steps", "2", "--warmup", "1", "--no-cpu",
+                            "--dump-outputs", str(tmp_path / str(n))],
                            env=env, capture_output=True, text=True, timeout=280)
         assert r.returncode == 0, r.stderr[-2000:]
         runs[n] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -94,3 +102,9 @@ def test_k2_bench_is_strong_scaled_over_its_ranks(tmp_path):
     assert j2["n_gpus"] == 2 and j2["scaling"] == "strong" and j2["config"]["records_total"] == 200_000 and j2["config"]["records_rank0"] == 100_000
     assert j2["calls_gathered_bytes"] == 2 * 50_000 * 4
     assert j1["result"]["pairs_human_total"] == j2["result"]["pairs_human_total"] > 10_000
+    # the dump of N = 2 holds the whole job's gathered calls, rank 1's half included (each run builds its own table with concurrent
+    # inserts, so a few non-human calls may differ between the two runs: the human ones are compared)
+    t1, t2 = (np.load(tmp_path / str(n) / "taxid.npy") for n in (1, 2))
+    assert len(t1) == len(t2) == 100_000 and int((t2 == 9606).sum()) == j2["result"]["pairs_human_total"] == int((t1 == 9606).sum())
+    assert int((t2[50_000:] == 9606).sum()) > 5_000
+    assert np.load(tmp_path / "2" / "classified_block_count.npy").sum() == int((t2 != 0).sum())
