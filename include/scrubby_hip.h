@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SH_VERSION 104   /* 0.1.3: sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
+#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, sh_k2_classify_*_q added; the old layouts are prefixes): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
 
 typedef int32_t sh_status;
 enum {
@@ -339,6 +339,10 @@ typedef struct sh_k2_opts {
     int32_t  value_bits;            /* low bits of a cell = internal taxid (set from hash.k2d on open) */
     int32_t  min_hit_groups;        /* --minimum-hit-groups, default 2 */
     double   confidence;            /* --confidence, default 0 (a double, as Kraken 2 parses it: ceil(c * kmers) decides) */
+    int32_t  min_base_quality;      /* --minimum-base-quality, default 0: a base whose Phred score is below it is ambiguous ('x');
+                                       needs the qualities of the _q entries */
+    int32_t  quick;                 /* --quick, default 0: the call is the first hit once min_hit_groups are seen, no ResolveTree
+                                       (unclassified when no k-mer gets there); total_kmers counts the k-mers before that hit */
 } sh_k2_opts;
 
 typedef struct sh_k2_taxnode {      /* taxo.k2d node: 7 x u64 */
@@ -360,6 +364,7 @@ typedef struct sh_k2_info {
 typedef struct sh_k2_stats {
     uint64_t n_units, n_classified, n_probes, n_kmers, n_overflow;
     float    ms_classify, ms_total;
+    uint64_t n_masked_bases;        /* bases of the batch masked by min_base_quality */
 } sh_k2_stats;
 
 sh_status sh_k2_default_opts(sh_k2_opts *out);
@@ -390,6 +395,14 @@ sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts *opts, cons
 /* the same from host memory */
 sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
                                uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats);
+/* both with Phred qualities for opts->min_base_quality: quals (nullable: nothing is masked) holds one byte per base at the
+ * offsets of bases, 0xFF = never masked (FASTA records).  The device form needs d_quals and d_bases at the same address
+ * modulo 8 and 8 readable bytes past the last quality.  With quals = NULL they are the two entries above. */
+sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
+                                  const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
+                                  sh_k2_stats *stats);
+sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
+                                 const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats);
 /* Kraken-style report (pct, clade reads, direct reads, rank code, taxid, indented name) from per-unit calls */
 sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, const char *path);
 
@@ -409,6 +422,8 @@ typedef struct sh_kraken_config {
     const char *json, *read_ids, *command;
     int32_t     device, threads;
     const char *classifier_args;    /* -C verbatim, nullable: echoed as settings.classifier_args in the JSON (report.rs:81) */
+    int32_t     min_base_quality;   /* from -C "--minimum-base-quality n"; <= 0: no masking (FASTQ records only) */
+    int32_t     quick;              /* from -C "--quick" */
 } sh_kraken_config;
 sh_status sh_kraken_run(const sh_kraken_config *cfg, sh_reads_result *out);
 

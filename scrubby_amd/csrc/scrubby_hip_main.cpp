@@ -2,6 +2,7 @@
 // (/root/reference/src/terminal.rs:57-157).  Only what the mm2 aligner path uses is implemented; options that
 // select other aligners / classifiers are accepted and rejected with the reason.
 #include "../../include/scrubby_hip.h"
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -147,6 +148,28 @@ int main(int argc, char **argv)
             if (p != std::string::npos) k.confidence = atof(cargs.c_str() + p + 12);
             p = cargs.find("--minimum-hit-groups");
             if (p != std::string::npos) k.min_hit_groups = atoi(cargs.c_str() + p + 20);
+        }
+        {   // --minimum-base-quality n (or =n) and --quick by tokens; any other token is named once on stderr
+            std::vector<std::string> tok, ignored;
+            for (size_t p = 0; (p = cargs.find_first_not_of(" \t", p)) != std::string::npos;) {
+                const size_t e = std::min(cargs.find_first_of(" \t", p), cargs.size());
+                tok.push_back(cargs.substr(p, e - p)); p = e;
+            }
+            for (size_t t = 0; t < tok.size(); ++t) {
+                const std::string &x = tok[t];
+                const bool has_next = t + 1 < tok.size();
+                if (x == "--quick") k.quick = 1;
+                else if (x == "--minimum-base-quality" && has_next) k.min_base_quality = atoi(tok[++t].c_str());
+                else if (x.rfind("--minimum-base-quality=", 0) == 0) k.min_base_quality = atoi(x.c_str() + 23);
+                else if ((x == "--confidence" || x == "--minimum-hit-groups") && has_next) ++t;      // read above
+                else if (x.rfind("--confidence", 0) == 0 || x.rfind("--minimum-hit-groups", 0) == 0) {}
+                else ignored.push_back(x);
+            }
+            if (!ignored.empty()) {
+                std::string l;
+                for (auto &x : ignored) l += " " + x;
+                fprintf(stderr, "[scrubby-hip] -C: ignored by the HIP backend's kraken2:%s\n", l.c_str());
+            }
         }
         k.json = json.empty() ? nullptr : json.c_str(); k.read_ids = ids.empty() ? nullptr : ids.c_str();
         k.command = command.c_str(); k.device = 0; k.threads = threads;

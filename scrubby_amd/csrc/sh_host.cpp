@@ -621,11 +621,14 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
     sh_k2_db_opts(db, &opts);
     if (c->confidence >= 0.0) opts.confidence = c->confidence;           // -C "--confidence x"
     if (c->min_hit_groups > 0) opts.min_hit_groups = c->min_hit_groups;   // -C "--minimum-hit-groups n"
+    opts.min_base_quality = c->min_base_quality > 0 ? c->min_base_quality : 0;    // -C "--minimum-base-quality n"
+    opts.quick = c->quick != 0;                                            // -C "--quick"
+    const bool want_q = opts.min_base_quality > 0;        // qualities at the offsets of the bases; 0xFF: FASTA, never masked
     auto t1 = now();
 
     // ingest: mates interleaved (records 2i, 2i+1); the id Kraken 2 prints for a pair is mate 1's first token with a trailing /1 removed
     std::vector<std::string> ids;
-    std::vector<uint8_t> bases;
+    std::vector<uint8_t> bases, quals;
     std::vector<uint64_t> offsets(1, 0);
     std::vector<uint32_t> len1, len2;
     auto fail = [&](sh_status s) { sh_k2_free(db); return s; };
@@ -641,10 +644,12 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
                 if (!get_id(a.header, id)) { delete r2; sh_set_error("record without an id in %s", c->input[0]); return fail(SH_ERR_IO); }
                 if (paired && id.size() > 2 && id.compare(id.size() - 2, 2, "/1") == 0) id.resize(id.size() - 2);
                 ids.push_back(id);
+                if (want_q) { if (a.fastq) quals.insert(quals.end(), a.qual.begin(), a.qual.end()); else quals.resize(quals.size() + a.seq.size(), 0xff); }
                 bases.insert(bases.end(), a.seq.begin(), a.seq.end()); offsets.push_back(bases.size()); len1.push_back((uint32_t)a.seq.size());
                 if (paired) {
                     const int s2 = r2->next(b);
                     if (s2 != 1) { std::string e = s2 == 0 ? "fewer records than mate 1" : r2->error; delete r2; sh_set_error("%s: %s", c->input[1], e.c_str()); return fail(SH_ERR_IO); }
+                    if (want_q) { if (b.fastq) quals.insert(quals.end(), b.qual.begin(), b.qual.end()); else quals.resize(quals.size() + b.seq.size(), 0xff); }
                     bases.insert(bases.end(), b.seq.begin(), b.seq.end()); offsets.push_back(bases.size()); len2.push_back((uint32_t)b.seq.size());
                 }
             }
@@ -657,7 +662,8 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
 
     std::vector<sh_k2_result> results(std::max<size_t>(ids.size(), 1));
     bases.resize(bases.size() + 64, 'N');
-    st = sh_k2_classify_batch(db, &opts, bases.data(), offsets.data(), offsets.size() - 1, paired ? 1 : 0, results.data(), nullptr);
+    if (want_q) quals.resize(bases.size(), 0xff);
+    st = sh_k2_classify_batch_q(db, &opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), offsets.size() - 1, paired ? 1 : 0, results.data(), nullptr);
     if (st != SH_OK) return fail(st);
     auto t3 = now();
 

@@ -12,12 +12,19 @@
 //            per lane, so the random 4-B gathers overlap instead of stalling the scan one at a time;
 //   resolve  per-lane hit list in LDS (<= HCAP distinct taxa; the rare unit beyond that is redone by the same kernel
 //            with its list in HBM), ResolveTree over BFS-ordered parent links.
+// Two compile-time switches, off in the default instance (which compiles to the code it had before they existed):
+//   QMASK    kraken2 --minimum-base-quality: quality words ride beside the base words, a base whose Phred score is below
+//            the threshold enters the scanner as a non-ACGT code (kraken2 masks it to 'x'); quality byte 0xFF = never masked;
+//   QUICK    kraken2 --quick: pass 2 of the drain walks each lane's runs in read order and stops the unit at the first hit
+//            run that brings the hit groups to the threshold (its taxon is the call, no hit list, no ResolveTree); the wave
+//            leaves the character loop once every lane has stopped or read its last character.
 // The bound is the HBM gather rate: one 32-B sector per probe, ~40 probes per 150-bp read.
 #include "sh_common.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #define K2_QCAP 8           // pending runs per lane
@@ -121,12 +128,18 @@ struct K2Args {
     const uint32_t *unit_list; uint32_t n_list;        // BIG pass: units to redo
     uint32_t *big_tax, *big_cnt;                       // BIG pass: K2_BIG_CAP entries per listed unit
 };
+// the QMASK instances' arguments (the others keep the kernel arguments they had)
+struct K2QArgs : K2Args {
+    const uint8_t *quals; int32_t min_qual;            // one byte per base at the bases' offsets (same address mod 8)
+};
+template <bool QMASK> using K2ArgsOf = std::conditional_t<QMASK, K2QArgs, K2Args>;
 // ctr layout
 #define K2C_OVER 0
 #define K2C_PROBES 8
 #define K2C_KMERS 72
 #define K2C_CLASSIFIED 136
-#define K2C_WORDS 200
+#define K2C_MASKED 200
+#define K2C_WORDS 264
 
 // hit list of one lane: entry j at [j * STRIDE]
 template <int STRIDE, int CAP>
@@ -234,12 +247,19 @@ __device__ static inline uint32_t k2_probe_rest(const K2Table &T, uint64_t g, ui
     return 0;
 }
 
-template <int W, bool BIG>
-__global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
+// kraken2 --minimum-base-quality (MaskLowQualityBases): Phred score below the threshold; 0xFF = a FASTA record, never masked
+__host__ __device__ static inline bool k2_masked(uint32_t q, int32_t min_qual)
+{
+    return q != 0xffu && (int32_t)q - '!' < min_qual;
+}
+
+template <int W, bool BIG, bool QMASK, bool QUICK>
+__global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
 {
     __shared__ uint64_t s_qmin[(K2_QCAP + 1) * 64];       // slot n_pend is written unconditionally, so one spare
     __shared__ uint32_t s_qlen[(K2_QCAP + 1) * 64];
-    __shared__ uint32_t s_htax[BIG ? 1 : K2_HCAP * 64], s_hcnt[BIG ? 1 : K2_HCAP * 64];
+    __shared__ uint32_t s_qpos[QUICK ? (K2_QCAP + 1) * 64 : 1];      // QUICK: k-mers of the unit before the run's first one
+    __shared__ uint32_t s_htax[BIG || QUICK ? 1 : K2_HCAP * 64], s_hcnt[BIG || QUICK ? 1 : K2_HCAP * 64];
     const uint32_t lane = threadIdx.x;
     const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
     const int32_t wlim = a.k - a.l + 1;
@@ -254,6 +274,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
         else { H.tax = s_htax + lane; H.cnt = s_hcnt + lane; }
         H.n = 0; H.over = false;
         uint32_t total = 0, groups = 0, n_pend = 0, probes_unit = 0;
+        bool stopped = false; uint32_t q_call = 0, q_total = 0;      // QUICK: the unit's scan has stopped on q_call
         const int n_frag = a.paired ? 2 : 1;
         auto drain = [&]() {
             // pass 1: every lane gathers the home group of each pending run, eight 16-B loads in flight; the outcome goes
@@ -293,7 +314,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
 #pragma nounroll
             for (uint32_t e = 0; e < K2_QCAP; ++e) {
                 if (__ballot(e < n_pend) == 0) break;
-                if (e < n_pend) {
+                if (e < n_pend && !(QUICK && stopped)) {      // QUICK: no run after the stopping one is looked at
                     const uint64_t v = s_qmin[e * 64 + lane];
                     if (!((skipped >> e) & 1u)) {
                         ++probes_unit;
@@ -304,7 +325,12 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
                             const uint64_t idx = k2_mod(hc, a.T.capacity, a.T.inv_capacity);
                             taxon = (idx >> 3) < n_full ? k2_probe_rest(a.T, idx >> 3, comp) : k2_finish_probe(a.T, idx, a.T.cells[idx], comp);
                         }
-                        if (taxon) { ++groups; H.add(taxon, s_qlen[e * 64 + lane]); }
+                        if (taxon) {
+                            ++groups;
+                            if constexpr (QUICK) {
+                                if ((int32_t)groups >= a.min_hit_groups) { stopped = true; q_call = taxon; q_total = s_qpos[e * 64 + lane]; }
+                            } else H.add(taxon, s_qlen[e * 64 + lane]);
+                        }
                     }
                 }
             }
@@ -324,10 +350,10 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
         for (int o = 32; o > 0; o >>= 1) { int32_t t = __shfl_xor(max_len, o); max_len = t > max_len ? t : max_len; }
         const int32_t n_chunks = (max_len + 7) / 8;
         K2Scan<W> S; S.reset();
-        uint64_t last_min = ~0ull; uint32_t run = 0;
+        uint64_t last_min = ~0ull; uint32_t run = 0, run_pos = 0;
         int32_t my_len = 0, off8 = 0; uint32_t sh = 0;
-        const uint64_t *wp = nullptr;
-        uint64_t w_cur = 0, w_next = 0;
+        const uint64_t *wp = nullptr, *qp = nullptr;
+        uint64_t w_cur = 0, w_next = 0, q_cur = 0, q_next = 0, qw = 0;
         // ONE loop over the characters of both fragments with ONE call site of drain (the probe code is large): step s is
         // character (s & 7) of chunk (s >> 3); the step after the last one flushes the final run and empties the queues.
         const int32_t n_steps = n_chunks * n_frag * 8;
@@ -339,7 +365,8 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
             if ((s & 7) == 0) {
                 if (c == 0 || end) {       // (wave-uniform) fragment boundary: flush the last run, restart the scanner
                     s_qmin[n_pend * 64 + lane] = last_min; s_qlen[n_pend * 64 + lane] = run;
-                    n_pend += run != 0;
+                    if constexpr (QUICK) s_qpos[n_pend * 64 + lane] = run_pos;
+                    n_pend += run != 0 && !(QUICK && stopped);
                     S.reset(); last_min = ~0ull; run = 0;
                     if (!end) {
                         const int f = cc < n_chunks ? 0 : 1;
@@ -349,28 +376,49 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
                         // only the aligned words that overlap the read are ever loaded
                         w_cur = my_len > 0 ? wp[0] : 0;
                         w_next = my_len + off8 > 8 ? wp[1] : 0;
+                        if constexpr (QMASK) {      // the same words of the quality array (same offsets, same address mod 8)
+                            qp = (const uint64_t *)((uintptr_t)(a.quals + o_beg[f]) & ~(uintptr_t)7);
+                            q_cur = my_len > 0 ? qp[0] : 0;
+                            q_next = my_len + off8 > 8 ? qp[1] : 0;
+                        }
                     }
                 }
                 if (!end) {
                     w = sh ? (w_cur >> sh) | (w_next << (64 - sh)) : w_cur;
                     w_cur = w_next;
                     w_next = (c + 2) * 8 < my_len + off8 ? wp[c + 2] : 0;      // two words ahead: the load has a whole chunk to land
+                    if constexpr (QMASK) {
+                        qw = sh ? (q_cur >> sh) | (q_next << (64 - sh)) : q_cur;
+                        q_cur = q_next;
+                        q_next = (c + 2) * 8 < my_len + off8 ? qp[c + 2] : 0;
+                    }
                 }
             }
             if (__ballot(n_pend >= (end ? 1u : (uint32_t)K2_QCAP - 1)) != 0) drain();       // wave-uniform: every lane is here
+            if constexpr (QUICK) {
+                // (wave-uniform) every lane has stopped, or has read the last character of its last fragment: straight on to
+                // the final flush and drain
+                const bool last_frag = cc >= (n_frag - 1) * n_chunks;
+                if ((s & 7) == 0 && !end && __ballot(!(stopped || !active || (last_frag && c * 8 >= my_len))) == 0) { s = n_steps - 1; continue; }
+            }
             if (end) break;
             const int32_t i = c * 8 + (s & 7);
             uint64_t m;
-            int ev = S.step_w(sh_nt4((uint32_t)w & 0xffu), i + 1, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
+            uint32_t code = sh_nt4((uint32_t)w & 0xffu);
+            if constexpr (QMASK) { code = k2_masked((uint32_t)qw & 0xffu, a.min_qual) ? 4u : code; qw >>= 8; }
+            int ev = S.step_w(code, i + 1, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
             w >>= 8;
             ev = i < my_len ? ev : 0;
             total += ev != 0;
             const bool fresh = ev == 2 && m != last_min;
             s_qmin[n_pend * 64 + lane] = last_min; s_qlen[n_pend * 64 + lane] = run;      // kept only if the run just ended
-            n_pend += fresh && run != 0;
+            if constexpr (QUICK) s_qpos[n_pend * 64 + lane] = run_pos;
+            n_pend += fresh && run != 0 && !(QUICK && stopped);
             run = fresh ? 1u : run + (ev == 2);
             last_min = fresh ? m : last_min;
+            if constexpr (QUICK) run_pos = fresh ? total - 1 : run_pos;
         }
+        if (QUICK && stopped) total = q_total;      // kraken2 --quick: the k-mers before the stopping one
         if (active) {
             kmers_thr += total;
             if (BIG || !H.over) probes_thr += probes_unit;       // a unit redone by the overflow pass is counted there
@@ -378,8 +426,12 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
                 const uint32_t oi = (uint32_t)atomicAdd(&a.ctr[K2C_OVER], 1ull);
                 a.over_list[oi] = (uint32_t)u;
             } else {
-                uint32_t call = k2_resolve(H, a.parent, total, a.confidence);
-                if (call && groups < (uint32_t)a.min_hit_groups) call = 0;
+                uint32_t call;
+                if constexpr (QUICK) call = stopped ? q_call : 0u;       // no stop: unclassified, whatever ResolveTree would say
+                else {
+                    call = k2_resolve(H, a.parent, total, a.confidence);
+                    if (call && groups < (uint32_t)a.min_hit_groups) call = 0;
+                }
                 sh_k2_result r{call ? a.ext[call] : 0u, call, total, groups};
                 a.out[u] = r;
                 class_thr += call != 0;
@@ -399,6 +451,18 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2Args a)
         if (kmers_thr && !BIG) atomicAdd(&a.ctr[K2C_KMERS + sh], kmers_thr);
         if (class_thr) atomicAdd(&a.ctr[K2C_CLASSIFIED + sh], (unsigned long long)class_thr);
     }
+}
+
+// bases the QMASK instances mask, over the whole batch [offsets[0], offsets[n_records]): counted apart from the scan, which
+// with --quick leaves a read early
+__global__ void k_k2_count_masked(const uint8_t *quals, const uint64_t *offsets, uint64_t n_records, int32_t min_qual, unsigned long long *ctr)
+{
+    const uint64_t beg = offsets[0], end = offsets[n_records];
+    unsigned long long n = 0;
+    for (uint64_t i = beg + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (uint64_t)gridDim.x * blockDim.x) n += k2_masked(quals[i], min_qual);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += (unsigned long long)__shfl_xor((long long)n, o);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&ctr[K2C_MASKED + (blockIdx.x & 63)], n);
 }
 
 // ---- table construction ----------------------------------------------------------------------------------------------
@@ -487,6 +551,7 @@ extern "C" sh_status sh_k2_default_opts(sh_k2_opts *o)
     o->value_bits = 17;
     o->min_hit_groups = 2;
     o->confidence = 0.0;
+    o->min_base_quality = 0; o->quick = 0;
     return SH_OK;
 }
 
@@ -747,19 +812,32 @@ extern "C" sh_status sh_k2_open(const char *dir, int device, sh_k2_db **out)
 }
 
 // ---- classification ---------------------------------------------------------------------------------------------------
-template <int W, bool BIG>
-static void launch_classify(const K2Args &a, uint64_t n_work, hipStream_t s)
+template <int W, bool BIG, bool QMASK, bool QUICK>
+static void launch_classify(const K2QArgs &a, uint64_t n_work, hipStream_t s)
 {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_work + 63) / 64, 1), 256 * 32);
-    hipLaunchKernelGGL((k_k2_classify<W, BIG>), dim3(grid), dim3(64), 0, s, a);
+    const K2ArgsOf<QMASK> &ka = a;
+    hipLaunchKernelGGL((k_k2_classify<W, BIG, QMASK, QUICK>), dim3(grid), dim3(64), 0, s, ka);
 }
-template <bool BIG>
-static sh_status dispatch_classify(const K2Args &a, uint64_t n_work, hipStream_t s)
+template <bool BIG, bool QMASK, bool QUICK>
+static void dispatch_w(const K2QArgs &a, uint64_t n_work, hipStream_t s)
 {
     switch (a.k - a.l + 1) {
-    case 1: launch_classify<1, BIG>(a, n_work, s); break;
-    case 5: launch_classify<5, BIG>(a, n_work, s); break;
-    default: launch_classify<16, BIG>(a, n_work, s); break;
+    case 1: launch_classify<1, BIG, QMASK, QUICK>(a, n_work, s); break;
+    case 5: launch_classify<5, BIG, QMASK, QUICK>(a, n_work, s); break;
+    default: launch_classify<16, BIG, QMASK, QUICK>(a, n_work, s); break;
+    }
+}
+// only the instances that are needed: a QUICK unit keeps no hit list, so it never overflows into the BIG pass
+template <bool BIG>
+static sh_status dispatch_classify(const K2QArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool quick)
+{
+    if (BIG) {
+        if (qmask) dispatch_w<true, true, false>(a, n_work, s); else dispatch_w<true, false, false>(a, n_work, s);
+    } else if (quick) {
+        if (qmask) dispatch_w<false, true, true>(a, n_work, s); else dispatch_w<false, false, true>(a, n_work, s);
+    } else {
+        if (qmask) dispatch_w<false, true, false>(a, n_work, s); else dispatch_w<false, false, false>(a, n_work, s);
     }
     return SH_OK;
 }
@@ -767,12 +845,22 @@ static sh_status dispatch_classify(const K2Args &a, uint64_t n_work, hipStream_t
 extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
                                            uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats)
 {
+    return sh_k2_classify_device_q(db, opts, d_bases, nullptr, d_offsets, n_records, paired, d_out, stream, stats);
+}
+
+extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
+                                             const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
+                                             sh_k2_stats *stats)
+{
     SH_CHECK(db && d_offsets && d_out && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_classify_device: null argument");
     SH_CHECK(!paired || (n_records & 1) == 0, SH_ERR_BAD_ARG, "paired input needs an even number of records (got %llu)", (unsigned long long)n_records);
     SH_HIP(hipSetDevice(db->device));
     hipStream_t s = (hipStream_t)stream;
     const sh_k2_opts &o = opts ? *opts : db->opts;
     SH_CHECK(o.k == db->opts.k && o.l == db->opts.l, SH_ERR_BAD_ARG, "options disagree with the database (k, l)");
+    const bool qmask = d_quals && o.min_base_quality > 0, quick = o.quick != 0;
+    SH_CHECK(!qmask || ((uintptr_t)d_quals & 7) == ((uintptr_t)d_bases & 7), SH_ERR_BAD_ARG,
+             "sh_k2_classify_device_q: qualities and bases must lie at the same address modulo 8");
     const uint64_t n_units = paired ? n_records / 2 : n_records;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n_units == 0) return SH_OK;
@@ -783,14 +871,16 @@ extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts 
     SH_HIP(hipMalloc(&ctr, K2C_WORDS * 8));
     SH_HIP(hipMalloc(&over, n_units * 4));
     SH_HIP(hipMemsetAsync(ctr, 0, K2C_WORDS * 8, s));
-    K2Args a{};
+    K2QArgs a{};
     a.bases = d_bases; a.offsets = d_offsets; a.n_units = n_units; a.paired = paired;
     a.T = K2Table{db->d_cells, db->capacity, db->value_bits, 1.0 / (double)db->capacity}; a.parent = db->d_parent; a.ext = db->d_ext; a.n_nodes = (uint32_t)db->nodes.size();
     a.k = o.k; a.l = o.l; a.spaced = o.spaced_seed_mask; a.toggle = o.toggle_mask; a.min_hash = o.min_acceptable_hash;
     a.min_hit_groups = o.min_hit_groups; a.confidence = o.confidence;
     a.out = d_out; a.over_list = over; a.ctr = ctr;
+    a.quals = qmask ? d_quals : nullptr; a.min_qual = qmask ? o.min_base_quality : 0;
     SH_HIP(hipEventRecord(e0, s));
-    dispatch_classify<false>(a, n_units, s);
+    if (qmask) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
+    dispatch_classify<false>(a, n_units, s, qmask, quick);
     SH_HIP(hipEventRecord(e1, s));
     std::vector<unsigned long long> h(K2C_WORDS);
     SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
@@ -802,7 +892,7 @@ extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts 
         SH_HIP(hipMalloc(&big_tax, n_over * K2_BIG_CAP * 4));
         SH_HIP(hipMalloc(&big_cnt, n_over * K2_BIG_CAP * 4));
         a.unit_list = over; a.n_list = (uint32_t)n_over; a.big_tax = big_tax; a.big_cnt = big_cnt;
-        dispatch_classify<true>(a, n_over, s);
+        dispatch_classify<true>(a, n_over, s, qmask, quick);
         SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
         SH_HIP(hipStreamSynchronize(s));
         SH_HIP(hipGetLastError());
@@ -811,7 +901,10 @@ extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts 
     hipEventElapsedTime(&ms, e0, e1);
     if (stats) {
         stats->n_units = n_units; stats->n_overflow = n_over; stats->ms_classify = ms; stats->ms_total = ms;
-        for (int i = 0; i < 64; ++i) { stats->n_probes += h[K2C_PROBES + i]; stats->n_kmers += h[K2C_KMERS + i]; stats->n_classified += h[K2C_CLASSIFIED + i]; }
+        for (int i = 0; i < 64; ++i) {
+            stats->n_probes += h[K2C_PROBES + i]; stats->n_kmers += h[K2C_KMERS + i]; stats->n_classified += h[K2C_CLASSIFIED + i];
+            stats->n_masked_bases += h[K2C_MASKED + i];
+        }
     }
     hipFree(ctr); hipFree(over); hipFree(big_tax); hipFree(big_cnt);
     hipEventDestroy(e0); hipEventDestroy(e1);
@@ -821,13 +914,26 @@ extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts 
 extern "C" sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
                                           uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats)
 {
+    return sh_k2_classify_batch_q(db, opts, bases, nullptr, offsets, n_records, paired, out, stats);
+}
+
+extern "C" sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
+                                            const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats)
+{
     SH_CHECK(db && offsets && out, SH_ERR_BAD_ARG, "sh_k2_classify_batch: null argument");
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n_records == 0) return SH_OK;
     SH_HIP(hipSetDevice(db->device));
     const uint64_t o0 = offsets[0], n_bases = offsets[n_records] - o0;
     const uint64_t n_units = paired ? n_records / 2 : n_records;
-    uint8_t *d_bases = nullptr; uint64_t *d_off = nullptr; sh_k2_result *d_out = nullptr;
+    // qualities are staged only when they can mask something; both arrays come from hipMalloc, so they share the address mod 8
+    const bool want_q = quals && (opts ? *opts : db->opts).min_base_quality > 0;
+    uint8_t *d_bases = nullptr, *d_quals = nullptr; uint64_t *d_off = nullptr; sh_k2_result *d_out = nullptr;
+    if (want_q) {
+        SH_HIP(hipMalloc(&d_quals, n_bases + 64));
+        SH_HIP(hipMemcpy(d_quals, quals + o0, n_bases, hipMemcpyHostToDevice));
+        SH_HIP(hipMemset(d_quals + n_bases, 0xff, 64));
+    }
     SH_HIP(hipMalloc(&d_bases, n_bases + 64));
     SH_HIP(hipMalloc(&d_off, (n_records + 1) * 8));
     SH_HIP(hipMalloc(&d_out, std::max<uint64_t>(n_units, 1) * sizeof(sh_k2_result)));
@@ -836,9 +942,9 @@ extern "C" sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *
     SH_HIP(hipMemcpy(d_bases, bases + o0, n_bases, hipMemcpyHostToDevice));
     SH_HIP(hipMemset(d_bases + n_bases, 'N', 64));
     SH_HIP(hipMemcpy(d_off, rel.data(), (n_records + 1) * 8, hipMemcpyHostToDevice));
-    sh_status st = sh_k2_classify_device(db, opts, d_bases, d_off, n_records, paired, d_out, nullptr, stats);
+    sh_status st = sh_k2_classify_device_q(db, opts, d_bases, d_quals, d_off, n_records, paired, d_out, nullptr, stats);
     if (st == SH_OK && hipMemcpy(out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost) != hipSuccess) { sh_set_error("copy of the results failed"); st = SH_ERR_HIP; }
-    hipFree(d_bases); hipFree(d_off); hipFree(d_out);
+    hipFree(d_bases); hipFree(d_quals); hipFree(d_off); hipFree(d_out);
     return st;
 }
 

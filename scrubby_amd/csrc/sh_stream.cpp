@@ -1385,6 +1385,8 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     sh_k2_db_opts(db, &opts);
     if (c->confidence >= 0.0) opts.confidence = c->confidence;           // -C "--confidence x"
     if (c->min_hit_groups > 0) opts.min_hit_groups = c->min_hit_groups;   // -C "--minimum-hit-groups n"
+    opts.min_base_quality = c->min_base_quality > 0 ? c->min_base_quality : 0;    // -C "--minimum-base-quality n"
+    opts.quick = c->quick != 0;                                            // -C "--quick"
     const auto t1 = now();
 
     // ---- ingest: both files side by side, parsed in place ----
@@ -1416,16 +1418,24 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     if (bad_id.load()) { sh_set_error("record without an id in %s", c->input[0]); return SH_ERR_IO; }
     for (uint64_t i = 0; i < n_rec; ++i) offsets[i + 1] += offsets[i];
     std::vector<uint8_t> bases(offsets[n_rec] + 64, (uint8_t)'N');
+    // qualities beside the bases, at the same offsets, only when they can mask something (0xFF: a FASTA record, never masked)
+    const bool want_q = opts.min_base_quality > 0;
+    std::vector<uint8_t> quals(want_q ? offsets[n_rec] + 64 : 0, 0xff);
     for (uint32_t f = 0; f < c->n_files; ++f)
         parallel_ranges(n_units, threads, [&, f](int, uint64_t lo, uint64_t hi) {
-            pf[f].for_range(lo, hi, [&](uint64_t k, const Chunk &ch, const Rec &r) { memcpy(bases.data() + offsets[paired ? 2 * k + f : k], ch.data + r.seq, r.seq_len); });
+            pf[f].for_range(lo, hi, [&](uint64_t k, const Chunk &ch, const Rec &r) {
+                const uint64_t o = offsets[paired ? 2 * k + f : k];
+                memcpy(bases.data() + o, ch.data + r.seq, r.seq_len);
+                if (want_q && r.fastq) memcpy(quals.data() + o, ch.data + r.qual, r.seq_len);
+            });
         });
     const auto t2 = now();
 
     std::vector<sh_k2_result> results(std::max<uint64_t>(n_units, 1));
-    st = sh_k2_classify_batch(db, &opts, bases.data(), offsets.data(), n_rec, paired ? 1 : 0, results.data(), nullptr);
+    st = sh_k2_classify_batch_q(db, &opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), n_rec, paired ? 1 : 0, results.data(), nullptr);
     if (st != SH_OK) return st;
     std::vector<uint8_t>().swap(bases);
+    std::vector<uint8_t>().swap(quals);
     const auto t3 = now();
 
     // ---- kraken.reads and kraken.report in the workdir (cleaner.rs:291-297) ----

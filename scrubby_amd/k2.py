@@ -13,7 +13,7 @@ from . import lib as S
 class K2Opts(C.Structure):
     _fields_ = [("k", C.c_int32), ("l", C.c_int32), ("spaced_seed_mask", C.c_uint64), ("toggle_mask", C.c_uint64),
                 ("min_acceptable_hash", C.c_uint64), ("value_bits", C.c_int32), ("min_hit_groups", C.c_int32),
-                ("confidence", C.c_double)]
+                ("confidence", C.c_double), ("min_base_quality", C.c_int32), ("quick", C.c_int32)]
 
 
 class K2TaxNode(C.Structure):
@@ -27,7 +27,7 @@ class K2Info(C.Structure):
 
 class K2Stats(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("n_classified", C.c_uint64), ("n_probes", C.c_uint64), ("n_kmers", C.c_uint64),
-                ("n_overflow", C.c_uint64), ("ms_classify", C.c_float), ("ms_total", C.c_float)]
+                ("n_overflow", C.c_uint64), ("ms_classify", C.c_float), ("ms_total", C.c_float), ("n_masked_bases", C.c_uint64)]
 
 
 class KrakenConfig(C.Structure):
@@ -37,7 +37,8 @@ class KrakenConfig(C.Structure):
                 ("taxa_direct", C.POINTER(C.c_char_p)), ("n_taxa_direct", C.c_uint32),
                 ("confidence", C.c_double), ("min_hit_groups", C.c_int32),
                 ("json", C.c_char_p), ("read_ids", C.c_char_p), ("command", C.c_char_p),
-                ("device", C.c_int32), ("threads", C.c_int32), ("classifier_args", C.c_char_p)]
+                ("device", C.c_int32), ("threads", C.c_int32), ("classifier_args", C.c_char_p),
+                ("min_base_quality", C.c_int32), ("quick", C.c_int32)]
 
 
 RESULT_DTYPE = np.dtype([("taxid", "<u4"), ("call", "<u4"), ("total_kmers", "<u4"), ("hit_groups", "<u4")])
@@ -130,23 +131,29 @@ class K2Db:
         S.check(S.load().sh_k2_export(self.h, C.c_void_p(cells.ctypes.data), C.c_void_p(parent.ctypes.data), C.c_void_p(ext.ctypes.data)))
         return cells, parent, ext
 
-    def classify(self, bases, offsets, paired=False, opts=None):
+    def classify(self, bases, offsets, paired=False, opts=None, quals=None):
+        """quals (optional): Phred+33 bytes at the offsets of `bases` (0xFF = never masked), used when opts.min_base_quality > 0."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            assert len(quals) >= int(offsets[-1]), "one quality byte per base"
         n_rec = len(offsets) - 1
         n_units = n_rec // 2 if paired else n_rec
         out = np.zeros(max(n_units, 1), dtype=RESULT_DTYPE)
         st = K2Stats()
-        S.check(S.load().sh_k2_classify_batch(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(bases.ctypes.data),
-                                              C.c_void_p(offsets.ctypes.data), C.c_uint64(n_rec), 1 if paired else 0,
-                                              C.c_void_p(out.ctypes.data), C.byref(st)))
+        S.check(S.load().sh_k2_classify_batch_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(bases.ctypes.data),
+                                                C.c_void_p(quals.ctypes.data) if quals is not None else None,
+                                                C.c_void_p(offsets.ctypes.data), C.c_uint64(n_rec), 1 if paired else 0,
+                                                C.c_void_p(out.ctypes.data), C.byref(st)))
         return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
 
-    def classify_device(self, d_bases, d_offsets, n_records, paired, d_out, opts=None):
+    def classify_device(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None):
         st = K2Stats()
-        S.check(S.load().sh_k2_classify_device(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
-                                               C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
-                                               C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st)))
+        S.check(S.load().sh_k2_classify_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
+                                                 C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
+                                                 C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
+                                                 C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st)))
         return {n: getattr(st, n) for n, _ in K2Stats._fields_}
 
     def write_report(self, results, path):
@@ -166,7 +173,7 @@ class K2Db:
 
 
 def kraken_run(inputs, outputs, db, taxa=(), taxa_direct=(), workdir=None, confidence=-1.0, min_hit_groups=0, extract=False,
-               json=None, read_ids=None, command="", device=0, threads=4, classifier_args=None):
+               json=None, read_ids=None, command="", device=0, threads=4, classifier_args=None, min_base_quality=0, quick=False):
     c = KrakenConfig()
     for i, (a, b) in enumerate(zip(inputs, outputs)):
         c.input[i], c.output[i] = str(a).encode(), str(b).encode()
@@ -180,6 +187,7 @@ def kraken_run(inputs, outputs, db, taxa=(), taxa_direct=(), workdir=None, confi
     c.read_ids = str(read_ids).encode() if read_ids else None
     c.command, c.device, c.threads = command.encode(), device, threads
     c.classifier_args = classifier_args.encode() if classifier_args else None
+    c.min_base_quality, c.quick = min_base_quality, int(quick)
     r = S.ReadsResult()
     S.check(S.load().sh_kraken_run(C.byref(c), C.byref(r)))
     return {n: getattr(r, n) for n, _ in S.ReadsResult._fields_}
