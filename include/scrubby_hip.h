@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, sh_k2_classify_*_q added; the old layouts are prefixes): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
+#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, sh_k2_classify_*_q added; the old layouts are prefixes; + Kraken 2 hit lists: sh_k2_classify_hits_*, sh_k2_hits_*, sh_k2_format_hits added, nothing changed): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
 
 typedef int32_t sh_status;
 enum {
@@ -403,6 +403,38 @@ sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opts *opts, co
                                   sh_k2_stats *stats);
 sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
                                  const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats);
+/* Kraken 2's per-k-mer hit list (column 5 of its output): per unit, in read order, the run-length encoding of the k-mers'
+ * taxa.  code = internal taxid (0: not in the table, or not looked up in a down-sampled database), SH_K2_HIT_AMBIGUOUS
+ * (ambiguous k-mers, masked bases included) or SH_K2_HIT_BORDER (the mate border of a pair, count 0, never merged).
+ * Adjacent runs of one code merge; the counts without the border add up to the unit's total_kmers. */
+#define SH_K2_HIT_AMBIGUOUS 0xFFFFFFFFu
+#define SH_K2_HIT_BORDER    0xFFFFFFFEu
+typedef struct sh_k2_hit { uint32_t code, count; } sh_k2_hit;
+typedef struct sh_k2_hits sh_k2_hits;   /* the lists of one call, in HBM; freed with sh_k2_hits_free */
+/* the classify entries above plus the hit lists (results and stats are bit-identical to theirs); not with opts->quick */
+sh_status sh_k2_classify_hits_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
+                                     uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits);
+sh_status sh_k2_classify_hits_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
+                                       const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
+                                       sh_k2_stats *stats, sh_k2_hits **hits);
+sh_status sh_k2_classify_hits_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
+                                    uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits);
+sh_status sh_k2_classify_hits_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
+                                      const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats,
+                                      sh_k2_hits **hits);
+/* units, entries, and units whose lists were redone by the overflow pass (any pointer may be NULL) */
+sh_status sh_k2_hits_count(const sh_k2_hits *hits, uint64_t *n_units, uint64_t *n_entries, uint64_t *n_redone);
+/* unit i's entries are [offsets[i], offsets[i + 1]); device pointers owned by the handle, or host copies (offsets: n_units + 1,
+ * entries: n_entries) */
+sh_status sh_k2_hits_device(const sh_k2_hits *hits, const uint64_t **d_offsets, const sh_k2_hit **d_entries);
+sh_status sh_k2_hits_copy(const sh_k2_hits *hits, uint64_t *offsets, sh_k2_hit *entries);
+sh_status sh_k2_hits_free(sh_k2_hits *hits);
+/* host only: column 5 of kraken.reads for one unit: "<taxid>:<n>", "A:<n>", "|:|" separated by single spaces (external ids
+ * from external[n_nodes]); "0:0" for a unit without entries; with quick != 0, "<quick_taxid>:Q" whatever the entries.
+ * Writes at most cap bytes including the terminating NUL; *len (nullable) = the full length without it.  A code outside the
+ * taxonomy is SH_ERR_BAD_ARG. */
+sh_status sh_k2_format_hits(const sh_k2_hit *entries, uint64_t n_entries, const uint32_t *external, uint64_t n_nodes, int32_t quick,
+                            uint32_t quick_taxid, char *buf, uint64_t cap, uint64_t *len);
 /* Kraken-style report (pct, clade reads, direct reads, rank code, taxid, indented name) from per-unit calls */
 sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, const char *path);
 

@@ -595,11 +595,64 @@ void shi_mkdir_p(const std::string &dir)
         if (i == dir.size() || dir[i] == '/') mkdir(dir.substr(0, i).c_str(), 0777);
 }
 
+// ---- Kraken 2's hit list (column 5 of kraken.reads; ClassifySequence / AddHitlistString in its classify.cc) -------------
+bool shi_k2_hitlist(std::string &o, const sh_k2_hit *e, uint64_t n, const uint32_t *external, uint64_t n_nodes, bool quick, uint32_t quick_taxid)
+{
+    char num[32];
+    if (quick) { o.append(num, (size_t)snprintf(num, sizeof num, "%u:Q", quick_taxid)); return true; }
+    if (n == 0) { o += "0:0"; return true; }           // a single read without k-mers
+    bool ok = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (i) o += ' ';
+        const uint32_t c = e[i].code;
+        if (c == SH_K2_HIT_BORDER) o += "|:|";
+        else if (c == SH_K2_HIT_AMBIGUOUS) o.append(num, (size_t)snprintf(num, sizeof num, "A:%u", e[i].count));
+        else {
+            ok = ok && c < n_nodes;
+            o.append(num, (size_t)snprintf(num, sizeof num, "%u:%u", c < n_nodes ? external[c] : 0u, e[i].count));
+        }
+    }
+    return ok;
+}
+
+extern "C" sh_status sh_k2_format_hits(const sh_k2_hit *entries, uint64_t n_entries, const uint32_t *external, uint64_t n_nodes, int32_t quick,
+                                       uint32_t quick_taxid, char *buf, uint64_t cap, uint64_t *len)
+{
+    SH_CHECK((entries || n_entries == 0 || quick) && (external || n_nodes == 0) && (buf || cap == 0), SH_ERR_BAD_ARG, "sh_k2_format_hits: null argument");
+    std::string o;
+    const bool ok = shi_k2_hitlist(o, entries, quick ? 0 : n_entries, external, n_nodes, quick != 0, quick_taxid);
+    if (len) *len = o.size();
+    if (cap) { const size_t m = std::min<size_t>(o.size(), (size_t)cap - 1); memcpy(buf, o.data(), m); buf[m] = 0; }
+    SH_CHECK(ok, SH_ERR_BAD_ARG, "sh_k2_format_hits: a taxon code outside the taxonomy of %llu nodes", (unsigned long long)n_nodes);
+    return SH_OK;
+}
+
+sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
+                              bool paired, sh_k2_result *results, ShiKrakenHits &hits)
+{
+    hits.quick = opts.quick != 0;
+    if (hits.quick) return sh_k2_classify_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr);       // "<taxid>:Q"
+    sh_k2_info info;
+    sh_status st = sh_k2_info_get(db, &info);
+    if (st != SH_OK) return st;
+    hits.ext.assign(info.n_nodes, 0);
+    st = sh_k2_export(db, nullptr, nullptr, hits.ext.data());
+    if (st != SH_OK) return st;
+    sh_k2_hits *h = nullptr;
+    st = sh_k2_classify_hits_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr, &h);
+    if (st != SH_OK) return st;
+    uint64_t n_units = 0, n_ent = 0;
+    sh_k2_hits_count(h, &n_units, &n_ent, nullptr);
+    hits.off.assign(n_units + 1, 0); hits.ent.resize(n_ent);
+    st = sh_k2_hits_copy(h, hits.off.data(), hits.ent.data());
+    sh_k2_hits_free(h);
+    return st;
+}
+
 // ---- Cleaner::run_kraken (cleaner.rs:288-330) in process: GPU classification instead of the external kraken2 ---------
 // kraken.reads / kraken.report are written into the workdir exactly where the reference expects them (:296-297), then
-// the same parse_classifier_output + clean_reads steps run on those files.  Divergence: column 5 of
-// kraken.reads carries the k-mer and hit-group totals, not Kraken2's positional hit list (the reference only stores it,
-// classifier.rs:401-419).
+// the same parse_classifier_output + clean_reads steps run on those files.  Column 5 of kraken.reads is Kraken 2's hit
+// list (with --quick, "<taxid>:Q"); the reference only stores it (classifier.rs:401-419).
 // collect-then-classify form; sh_kraken_run (sh_stream.cpp) hands over for empty inputs and as the A/B baseline
 sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
 {
@@ -663,7 +716,8 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
     std::vector<sh_k2_result> results(std::max<size_t>(ids.size(), 1));
     bases.resize(bases.size() + 64, 'N');
     if (want_q) quals.resize(bases.size(), 0xff);
-    st = sh_k2_classify_batch_q(db, &opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), offsets.size() - 1, paired ? 1 : 0, results.data(), nullptr);
+    ShiKrakenHits hits;
+    st = shi_kraken_classify(db, opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), offsets.size() - 1, paired, results.data(), hits);
     if (st != SH_OK) return fail(st);
     auto t3 = now();
 
@@ -674,10 +728,12 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
     {
         FILE *f = fopen(reads_path.c_str(), "w");
         if (!f) { sh_set_error("cannot write %s", reads_path.c_str()); return fail(SH_ERR_IO); }
+        std::string col5;
         for (size_t i = 0; i < ids.size(); ++i) {
             const sh_k2_result &r = results[i];
-            if (paired) fprintf(f, "%c\t%s\t%u\t%u|%u\tkmers=%u groups=%u\n", r.call ? 'C' : 'U', ids[i].c_str(), r.taxid, len1[i], len2[i], r.total_kmers, r.hit_groups);
-            else fprintf(f, "%c\t%s\t%u\t%u\tkmers=%u groups=%u\n", r.call ? 'C' : 'U', ids[i].c_str(), r.taxid, len1[i], r.total_kmers, r.hit_groups);
+            col5.clear(); hits.append(col5, i, r);
+            if (paired) fprintf(f, "%c\t%s\t%u\t%u|%u\t%s\n", r.call ? 'C' : 'U', ids[i].c_str(), r.taxid, len1[i], len2[i], col5.c_str());
+            else fprintf(f, "%c\t%s\t%u\t%u\t%s\n", r.call ? 'C' : 'U', ids[i].c_str(), r.taxid, len1[i], col5.c_str());
         }
         if (fclose(f) != 0) { sh_set_error("short write to %s", reads_path.c_str()); return fail(SH_ERR_IO); }
     }

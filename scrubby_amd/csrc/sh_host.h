@@ -29,3 +29,19 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
 sh_status shi_taxids_from_report(const char *report, const std::vector<std::string> &taxa_in, const std::vector<std::string> &direct_in,
                                  std::unordered_set<std::string> &out);
 void shi_mkdir_p(const std::string &dir);
+// column 5 of kraken.reads for one unit (sh_k2_format_hits), appended to o; false = a code outside the taxonomy
+bool shi_k2_hitlist(std::string &o, const sh_k2_hit *e, uint64_t n, const uint32_t *external, uint64_t n_nodes, bool quick, uint32_t quick_taxid);
+// the Kraken arm's classification of one host batch for both writers: the results and, unless opts.quick, every unit's hit list
+struct ShiKrakenHits {
+    bool quick = false;
+    std::vector<uint64_t> off;          // n_units + 1
+    std::vector<sh_k2_hit> ent;
+    std::vector<uint32_t> ext;          // external ids of the taxonomy
+    // column 5 of unit i (r: its result) appended to o
+    void append(std::string &o, uint64_t i, const sh_k2_result &r) const
+    {
+        shi_k2_hitlist(o, quick ? nullptr : ent.data() + off[i], quick ? 0 : off[i + 1] - off[i], ext.data(), ext.size(), quick, r.taxid);
+    }
+};
+sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
+                              bool paired, sh_k2_result *results, ShiKrakenHits &hits);

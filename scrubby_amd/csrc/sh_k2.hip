@@ -12,14 +12,21 @@
 //            per lane, so the random 4-B gathers overlap instead of stalling the scan one at a time;
 //   resolve  per-lane hit list in LDS (<= HCAP distinct taxa; the rare unit beyond that is redone by the same kernel
 //            with its list in HBM), ResolveTree over BFS-ordered parent links.
-// Two compile-time switches, off in the default instance (which compiles to the code it had before they existed):
+// Three compile-time switches, off in the default instance (which compiles to the code it had before they existed):
 //   QMASK    kraken2 --minimum-base-quality: quality words ride beside the base words, a base whose Phred score is below
 //            the threshold enters the scanner as a non-ACGT code (kraken2 masks it to 'x'); quality byte 0xFF = never masked;
 //   QUICK    kraken2 --quick: pass 2 of the drain walks each lane's runs in read order and stops the unit at the first hit
 //            run that brings the hit groups to the threshold (its taxon is the call, no hit list, no ResolveTree); the wave
-//            leaves the character loop once every lane has stopped or read its last character.
+//            leaves the character loop once every lane has stopped or read its last character;
+//   HITS     kraken2's per-k-mer hit list (column 5 of its output), run-length encoded over taxa: a queue entry also carries
+//            the ambiguous k-mers before it, a run that resumes after such a span is cut there (the piece after it reuses
+//            the run's taxon: no probe, no hit group), and the fragment's trailing ambiguous k-mers and the mate border go
+//            in an entry without k-mers.  Pass 2 of the drain emits each lane's entries in read order into an RLE state
+//            held in registers.  HITS 1 writes K2_HIT_INLINE entries per unit and counts them all (a longer unit goes on a
+//            list); HITS 2 redoes the listed units and writes their whole lists at their final offsets, nothing else.
 // The bound is the HBM gather rate: one 32-B sector per probe, ~40 probes per 150-bp read.
 #include "sh_common.h"
+#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -30,6 +37,12 @@
 #define K2_QCAP 8           // pending runs per lane
 #define K2_HCAP 8           // distinct taxa per unit kept in LDS (10 KiB of LDS per wave with the queue: 16 waves per CU)
 #define K2_BIG_CAP 4096     // ... in HBM for the overflow pass
+#define K2_HIT_INLINE 16    // hit-list entries per unit written in place by the HITS 1 instances (8 B each)
+#define K2_HIT_NONE 0xfffffffdu          // RLE state before the unit's first entry (never a code)
+// HITS queue entry word (s_qamb): the entry starts a run (probe it), the mate border follows it, ambiguous k-mers before it
+#define K2Q_PROBE 0x80000000u
+#define K2Q_BORDER 0x40000000u
+#define K2Q_AMB 0x3fffffffu
 
 struct sh_k2_db {
     int device = 0;
@@ -132,9 +145,17 @@ struct K2Args {
 struct K2QArgs : K2Args {
     const uint8_t *quals; int32_t min_qual;            // one byte per base at the bases' offsets (same address mod 8)
 };
-template <bool QMASK> using K2ArgsOf = std::conditional_t<QMASK, K2QArgs, K2Args>;
+// ... and the HITS instances' (with or without qualities)
+struct K2HArgs : K2QArgs {
+    uint2 *hits;                                       // HITS 1: K2_HIT_INLINE (code, count) per unit; HITS 2: the compacted lists
+    uint32_t *n_hits;                                  // HITS 1: entries of each unit
+    uint32_t *hit_over;                                // HITS 1: units with more than K2_HIT_INLINE entries
+    const uint64_t *hit_off;                           // HITS 2: first entry of each unit in `hits` (n_units + 1)
+};
+template <bool QMASK, int HITS = 0> using K2ArgsOf = std::conditional_t<HITS != 0, K2HArgs, std::conditional_t<QMASK, K2QArgs, K2Args>>;
 // ctr layout
 #define K2C_OVER 0
+#define K2C_HOVER 1
 #define K2C_PROBES 8
 #define K2C_KMERS 72
 #define K2C_CLASSIFIED 136
@@ -247,28 +268,61 @@ __device__ static inline uint32_t k2_probe_rest(const K2Table &T, uint64_t g, ui
     return 0;
 }
 
+// the whole probe of minimizer v whose home group did not decide it (HITS instances; the others keep this code inline)
+__device__ static inline uint32_t k2_probe_long(const K2Table &T, uint64_t v, uint64_t n_full)
+{
+    const uint64_t hc = k2_fmix64(v);
+    const uint32_t comp = (uint32_t)(hc >> (32 + T.value_bits));
+    const uint64_t idx = k2_mod(hc, T.capacity, T.inv_capacity);
+    return (idx >> 3) < n_full ? k2_probe_rest(T, idx >> 3, comp) : k2_finish_probe(T, idx, T.cells[idx], comp);
+}
+
 // kraken2 --minimum-base-quality (MaskLowQualityBases): Phred score below the threshold; 0xFF = a FASTA record, never masked
 __host__ __device__ static inline bool k2_masked(uint32_t q, int32_t min_qual)
 {
     return q != 0xffu && (int32_t)q - '!' < min_qual;
 }
 
-template <int W, bool BIG, bool QMASK, bool QUICK>
-__global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
+// HITS: one lane's hit-list state, kept in registers across drains: the open piece (ambiguous k-mers before it, K2Q_PROBE
+// if it starts a run), the ambiguous k-mers after its last k-mer, the taxon of the run the drain last looked up, and the RLE
+// state (the code and count not yet written, the entries so far, where they go and how many fit)
+struct K2HitState {
+    uint32_t pamb = 0, namb = 0, pflag = 0, run_taxon = 0;
+    uint32_t code = K2_HIT_NONE, cnt = 0, n = 0, cap = 0;
+    uint2 *out = nullptr;
+    __device__ inline void put(uint32_t c, uint32_t k)
+    {
+        if (n < cap) out[n] = make_uint2(c, k);
+        ++n;
+    }
+    __device__ inline void emit(uint32_t c, uint32_t k)
+    {   // runs of one code merge; the border never does
+        if (c == code && c != SH_K2_HIT_BORDER) { cnt += k; return; }
+        if (code != K2_HIT_NONE) put(code, cnt);
+        code = c; cnt = k;
+    }
+};
+struct K2NoHits {};
+
+template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0>
+__global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
 {
+    static_assert(HITS == 0 || !(BIG || QUICK), "the hit list is complete after pass 1 and has no --quick form");
+    constexpr bool LIST = BIG || HITS == 2;                // the work is a list of units to redo
     __shared__ uint64_t s_qmin[(K2_QCAP + 1) * 64];       // slot n_pend is written unconditionally, so one spare
     __shared__ uint32_t s_qlen[(K2_QCAP + 1) * 64];
     __shared__ uint32_t s_qpos[QUICK ? (K2_QCAP + 1) * 64 : 1];      // QUICK: k-mers of the unit before the run's first one
-    __shared__ uint32_t s_htax[BIG || QUICK ? 1 : K2_HCAP * 64], s_hcnt[BIG || QUICK ? 1 : K2_HCAP * 64];
+    __shared__ uint32_t s_qamb[HITS ? (K2_QCAP + 1) * 64 : 1];       // HITS: K2Q_* word of the entry
+    __shared__ uint32_t s_htax[BIG || QUICK || HITS == 2 ? 1 : K2_HCAP * 64], s_hcnt[BIG || QUICK || HITS == 2 ? 1 : K2_HCAP * 64];
     const uint32_t lane = threadIdx.x;
     const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
     const int32_t wlim = a.k - a.l + 1;
-    const uint64_t n_work = BIG ? a.n_list : a.n_units;
+    const uint64_t n_work = LIST ? a.n_list : a.n_units;
     unsigned long long probes_thr = 0, kmers_thr = 0; uint32_t class_thr = 0;
     for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_work; base += (uint64_t)gridDim.x * 64) {
         const uint64_t wi = base + lane;
         const bool active = wi < n_work;
-        const uint64_t u = active ? (BIG ? (uint64_t)a.unit_list[wi] : wi) : 0;
+        const uint64_t u = active ? (LIST ? (uint64_t)a.unit_list[wi] : wi) : 0;
         K2Hits<BIG ? 1 : 64, BIG ? K2_BIG_CAP : K2_HCAP> H;
         if (BIG) { H.tax = a.big_tax + (active ? wi : 0) * K2_BIG_CAP; H.cnt = a.big_cnt + (active ? wi : 0) * K2_BIG_CAP; }
         else { H.tax = s_htax + lane; H.cnt = s_hcnt + lane; }
@@ -276,6 +330,9 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
         uint32_t total = 0, groups = 0, n_pend = 0, probes_unit = 0;
         bool stopped = false; uint32_t q_call = 0, q_total = 0;      // QUICK: the unit's scan has stopped on q_call
         const int n_frag = a.paired ? 2 : 1;
+        std::conditional_t<HITS != 0, K2HitState, K2NoHits> R{};       // (an empty object in the other instances)
+        if constexpr (HITS == 1) { R.out = a.hits + u * K2_HIT_INLINE; R.cap = active ? K2_HIT_INLINE : 0; }
+        if constexpr (HITS == 2) { if (active) { R.out = a.hits + a.hit_off[u]; R.cap = (uint32_t)(a.hit_off[u + 1] - a.hit_off[u]); } }
         auto drain = [&]() {
             // pass 1: every lane gathers the home group of each pending run, eight 16-B loads in flight; the outcome goes
             // back into the queue slot: the taxon, or (undecided | truncated key | group) for the rare longer chain
@@ -288,6 +345,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     go[q] = e0 + q < n_pend;
+                    if constexpr (HITS) go[q] = go[q] && (s_qamb[(e0 + q) * 64 + lane] & K2Q_PROBE);      // a resumed run, a tail: no probe
                     idx[q] = 0; comp[q] = 0;
                     if (go[q]) {
                         const uint64_t hc = k2_fmix64(s_qmin[(e0 + q) * 64 + lane]);
@@ -312,9 +370,29 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
             }
             // pass 2: one copy of the long-chain code and of the hit-list update
 #pragma nounroll
-            for (uint32_t e = 0; e < K2_QCAP; ++e) {
+            for (uint32_t e = 0; e < K2_QCAP + (HITS ? 1 : 0); ++e) {      // HITS: a fragment's flush may queue a ninth entry (a tail)
                 if (__ballot(e < n_pend) == 0) break;
-                if (e < n_pend && !(QUICK && stopped)) {      // QUICK: no run after the stopping one is looked at
+                if constexpr (HITS) {
+                    if (e < n_pend) {
+                        const uint32_t qa = s_qamb[e * 64 + lane], len = s_qlen[e * 64 + lane];
+                        if (qa & K2Q_PROBE) {               // the entry starts a run: looked up as in the other instances
+                            R.run_taxon = 0;                // not looked up: taxon 0
+                            if (!((skipped >> e) & 1u)) {
+                                ++probes_unit;
+                                const uint64_t v = s_qmin[e * 64 + lane];
+                                R.run_taxon = (undecided >> e) & 1u ? k2_probe_long(a.T, v, n_full) : (uint32_t)v;
+                                if (R.run_taxon) {
+                                    ++groups;
+                                    if constexpr (HITS == 1) H.add(R.run_taxon, len);
+                                }
+                            }
+                        } else if (HITS == 1 && R.run_taxon && len) H.add(R.run_taxon, len);      // the rest of a run after ambiguous k-mers
+                        // read order: the ambiguous k-mers, the piece's k-mers, the border
+                        if (qa & K2Q_AMB) R.emit(SH_K2_HIT_AMBIGUOUS, qa & K2Q_AMB);
+                        if (len) R.emit(R.run_taxon, len);
+                        if (qa & K2Q_BORDER) R.emit(SH_K2_HIT_BORDER, 0);
+                    }
+                } else if (e < n_pend && !(QUICK && stopped)) {      // QUICK: no run after the stopping one is looked at
                     const uint64_t v = s_qmin[e * 64 + lane];
                     if (!((skipped >> e) & 1u)) {
                         ++probes_unit;
@@ -366,7 +444,15 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
                 if (c == 0 || end) {       // (wave-uniform) fragment boundary: flush the last run, restart the scanner
                     s_qmin[n_pend * 64 + lane] = last_min; s_qlen[n_pend * 64 + lane] = run;
                     if constexpr (QUICK) s_qpos[n_pend * 64 + lane] = run_pos;
+                    if constexpr (HITS) s_qamb[n_pend * 64 + lane] = R.pamb | R.pflag;
                     n_pend += run != 0 && !(QUICK && stopped);
+                    if constexpr (HITS) {
+                        // the fragment's trailing ambiguous k-mers and, after mate 1 (even one without k-mers), the border
+                        const bool border = a.paired && s == n_chunks * 8;
+                        s_qlen[n_pend * 64 + lane] = 0; s_qamb[n_pend * 64 + lane] = R.namb | (border ? K2Q_BORDER : 0u);
+                        n_pend += R.namb != 0 || border;
+                        R.pamb = 0; R.namb = 0; R.pflag = 0;
+                    }
                     S.reset(); last_min = ~0ull; run = 0;
                     if (!end) {
                         const int f = cc < n_chunks ? 0 : 1;
@@ -413,13 +499,34 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK> a)
             const bool fresh = ev == 2 && m != last_min;
             s_qmin[n_pend * 64 + lane] = last_min; s_qlen[n_pend * 64 + lane] = run;      // kept only if the run just ended
             if constexpr (QUICK) s_qpos[n_pend * 64 + lane] = run_pos;
-            n_pend += fresh && run != 0 && !(QUICK && stopped);
-            run = fresh ? 1u : run + (ev == 2);
+            if constexpr (HITS) {
+                // a new minimizer, or the same one back after ambiguous k-mers, closes the open piece
+                const bool cut = ev == 2 && (fresh || R.namb != 0);
+                s_qamb[n_pend * 64 + lane] = R.pamb | R.pflag;
+                n_pend += cut && run != 0;
+                R.pflag = fresh ? K2Q_PROBE : (cut ? 0u : R.pflag);
+                R.pamb = cut ? R.namb : R.pamb;
+                R.namb = cut ? 0u : R.namb + (ev == 1);
+                run = cut ? 1u : run + (ev == 2);
+            } else {
+                n_pend += fresh && run != 0 && !(QUICK && stopped);
+                run = fresh ? 1u : run + (ev == 2);
+            }
             last_min = fresh ? m : last_min;
             if constexpr (QUICK) run_pos = fresh ? total - 1 : run_pos;
         }
         if (QUICK && stopped) total = q_total;      // kraken2 --quick: the k-mers before the stopping one
-        if (active) {
+        if constexpr (HITS) {
+            if (R.code != K2_HIT_NONE) R.put(R.code, R.cnt);
+            if (HITS == 1 && active) {
+                a.n_hits[u] = R.n;
+                if (R.n > K2_HIT_INLINE) {
+                    const uint32_t oi = (uint32_t)atomicAdd(&a.ctr[K2C_HOVER], 1ull);
+                    a.hit_over[oi] = (uint32_t)u;
+                }
+            }
+        }
+        if (HITS != 2 && active) {       // HITS 2 redoes units whose results the first pass wrote
             kmers_thr += total;
             if (BIG || !H.over) probes_thr += probes_unit;       // a unit redone by the overflow pass is counted there
             if (!BIG && H.over) {
@@ -812,35 +919,61 @@ extern "C" sh_status sh_k2_open(const char *dir, int device, sh_k2_db **out)
 }
 
 // ---- classification ---------------------------------------------------------------------------------------------------
-template <int W, bool BIG, bool QMASK, bool QUICK>
-static void launch_classify(const K2QArgs &a, uint64_t n_work, hipStream_t s)
+template <int W, bool BIG, bool QMASK, bool QUICK, int HITS>
+static void launch_classify(const K2HArgs &a, uint64_t n_work, hipStream_t s)
 {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_work + 63) / 64, 1), 256 * 32);
-    const K2ArgsOf<QMASK> &ka = a;
-    hipLaunchKernelGGL((k_k2_classify<W, BIG, QMASK, QUICK>), dim3(grid), dim3(64), 0, s, ka);
+    const K2ArgsOf<QMASK, HITS> &ka = a;
+    hipLaunchKernelGGL((k_k2_classify<W, BIG, QMASK, QUICK, HITS>), dim3(grid), dim3(64), 0, s, ka);
 }
-template <bool BIG, bool QMASK, bool QUICK>
-static void dispatch_w(const K2QArgs &a, uint64_t n_work, hipStream_t s)
+template <bool BIG, bool QMASK, bool QUICK, int HITS = 0>
+static void dispatch_w(const K2HArgs &a, uint64_t n_work, hipStream_t s)
 {
     switch (a.k - a.l + 1) {
-    case 1: launch_classify<1, BIG, QMASK, QUICK>(a, n_work, s); break;
-    case 5: launch_classify<5, BIG, QMASK, QUICK>(a, n_work, s); break;
-    default: launch_classify<16, BIG, QMASK, QUICK>(a, n_work, s); break;
+    case 1: launch_classify<1, BIG, QMASK, QUICK, HITS>(a, n_work, s); break;
+    case 5: launch_classify<5, BIG, QMASK, QUICK, HITS>(a, n_work, s); break;
+    default: launch_classify<16, BIG, QMASK, QUICK, HITS>(a, n_work, s); break;
     }
 }
-// only the instances that are needed: a QUICK unit keeps no hit list, so it never overflows into the BIG pass
+// only the instances that are needed: a QUICK unit keeps no hit list, so it never overflows into the BIG pass; the BIG pass
+// needs no HITS instance (pass 1 already emitted the whole list of a unit with many taxa)
 template <bool BIG>
-static sh_status dispatch_classify(const K2QArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool quick)
+static sh_status dispatch_classify(const K2HArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool quick, int hits = 0)
 {
     if (BIG) {
         if (qmask) dispatch_w<true, true, false>(a, n_work, s); else dispatch_w<true, false, false>(a, n_work, s);
     } else if (quick) {
         if (qmask) dispatch_w<false, true, true>(a, n_work, s); else dispatch_w<false, false, true>(a, n_work, s);
+    } else if (hits == 1) {
+        if (qmask) dispatch_w<false, true, false, 1>(a, n_work, s); else dispatch_w<false, false, false, 1>(a, n_work, s);
+    } else if (hits == 2) {
+        if (qmask) dispatch_w<false, true, false, 2>(a, n_work, s); else dispatch_w<false, false, false, 2>(a, n_work, s);
     } else {
         if (qmask) dispatch_w<false, true, false>(a, n_work, s); else dispatch_w<false, false, false>(a, n_work, s);
     }
     return SH_OK;
 }
+
+// the hit lists of one call (sh_k2_classify_hits_*): per-unit offsets and the entries, compacted, in HBM
+struct sh_k2_hits {
+    int device = 0;
+    uint64_t n_units = 0, n_entries = 0, n_redone = 0;
+    uint64_t *d_off = nullptr;           // n_units + 1
+    sh_k2_hit *d_ent = nullptr;          // n_entries
+};
+
+// units whose list fits inline: their entries to the final offsets (the others were written there by the HITS 2 pass)
+__global__ void k_k2_hits_compact(const uint2 *inl, const uint32_t *n_hits, const uint64_t *off, uint64_t n_units, uint2 *out)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_units * K2_HIT_INLINE; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t u = i / K2_HIT_INLINE; const uint32_t j = (uint32_t)(i % K2_HIT_INLINE);
+        const uint32_t n = n_hits[u];
+        if (n <= K2_HIT_INLINE && j < n) out[off[u] + j] = inl[i];
+    }
+}
+
+static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
+                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out);
 
 extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
                                            uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats)
@@ -851,6 +984,66 @@ extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts 
 extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
                                              const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
                                              sh_k2_stats *stats)
+{
+    return k2_classify(db, opts, d_bases, d_quals, d_offsets, n_records, paired, d_out, stream, stats, nullptr);
+}
+
+extern "C" sh_status sh_k2_classify_hits_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
+                                                uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits)
+{
+    return sh_k2_classify_hits_device_q(db, opts, d_bases, nullptr, d_offsets, n_records, paired, d_out, stream, stats, hits);
+}
+
+extern "C" sh_status sh_k2_classify_hits_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
+                                                  const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
+                                                  sh_k2_stats *stats, sh_k2_hits **hits)
+{
+    SH_CHECK(hits, SH_ERR_BAD_ARG, "sh_k2_classify_hits_device: null argument");
+    *hits = nullptr;
+    SH_CHECK(!(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: use sh_k2_classify_device_q");
+    sh_status st = k2_classify(db, opts, d_bases, d_quals, d_offsets, n_records, paired, d_out, stream, stats, hits);
+    if (st != SH_OK) { sh_k2_hits_free(*hits); *hits = nullptr; }
+    return st;
+}
+
+extern "C" sh_status sh_k2_hits_count(const sh_k2_hits *h, uint64_t *n_units, uint64_t *n_entries, uint64_t *n_redone)
+{
+    SH_CHECK(h, SH_ERR_BAD_ARG, "sh_k2_hits_count: null argument");
+    if (n_units) *n_units = h->n_units;
+    if (n_entries) *n_entries = h->n_entries;
+    if (n_redone) *n_redone = h->n_redone;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_hits_device(const sh_k2_hits *h, const uint64_t **d_offsets, const sh_k2_hit **d_entries)
+{
+    SH_CHECK(h, SH_ERR_BAD_ARG, "sh_k2_hits_device: null argument");
+    if (d_offsets) *d_offsets = h->d_off;
+    if (d_entries) *d_entries = h->d_ent;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_hits_copy(const sh_k2_hits *h, uint64_t *offsets, sh_k2_hit *entries)
+{
+    SH_CHECK(h, SH_ERR_BAD_ARG, "sh_k2_hits_copy: null argument");
+    SH_HIP(hipSetDevice(h->device));
+    if (offsets && h->d_off) SH_HIP(hipMemcpy(offsets, h->d_off, (h->n_units + 1) * 8, hipMemcpyDeviceToHost));
+    else if (offsets) offsets[0] = 0;
+    if (entries && h->n_entries) SH_HIP(hipMemcpy(entries, h->d_ent, h->n_entries * sizeof(sh_k2_hit), hipMemcpyDeviceToHost));
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_hits_free(sh_k2_hits *h)
+{
+    if (!h) return SH_OK;
+    hipSetDevice(h->device);
+    hipFree(h->d_off); hipFree(h->d_ent);
+    delete h;
+    return SH_OK;
+}
+
+static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
+                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out)
 {
     SH_CHECK(db && d_offsets && d_out && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_classify_device: null argument");
     SH_CHECK(!paired || (n_records & 1) == 0, SH_ERR_BAD_ARG, "paired input needs an even number of records (got %llu)", (unsigned long long)n_records);
@@ -863,6 +1056,7 @@ extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opt
              "sh_k2_classify_device_q: qualities and bases must lie at the same address modulo 8");
     const uint64_t n_units = paired ? n_records / 2 : n_records;
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (hits_out) { *hits_out = new sh_k2_hits; (*hits_out)->device = db->device; }
     if (n_units == 0) return SH_OK;
     SH_CHECK(n_units <= 0xffffffffull, SH_ERR_BAD_ARG, "at most 2^32 - 1 units per call");
     hipEvent_t e0, e1;
@@ -871,7 +1065,15 @@ extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opt
     SH_HIP(hipMalloc(&ctr, K2C_WORDS * 8));
     SH_HIP(hipMalloc(&over, n_units * 4));
     SH_HIP(hipMemsetAsync(ctr, 0, K2C_WORDS * 8, s));
-    K2QArgs a{};
+    K2HArgs a{};
+    uint2 *hit_inl = nullptr; uint32_t *n_hits = nullptr, *hit_over = nullptr;
+    if (hits_out) {       // pass 1: K2_HIT_INLINE entries per unit in place, every unit's count (one spare: the scan's total)
+        SH_HIP(hipMalloc(&hit_inl, n_units * K2_HIT_INLINE * sizeof(uint2)));
+        SH_HIP(hipMalloc(&n_hits, (n_units + 1) * 4));
+        SH_HIP(hipMalloc(&hit_over, n_units * 4));
+        SH_HIP(hipMemsetAsync(n_hits + n_units, 0, 4, s));
+        a.hits = hit_inl; a.n_hits = n_hits; a.hit_over = hit_over;
+    }
     a.bases = d_bases; a.offsets = d_offsets; a.n_units = n_units; a.paired = paired;
     a.T = K2Table{db->d_cells, db->capacity, db->value_bits, 1.0 / (double)db->capacity}; a.parent = db->d_parent; a.ext = db->d_ext; a.n_nodes = (uint32_t)db->nodes.size();
     a.k = o.k; a.l = o.l; a.spaced = o.spaced_seed_mask; a.toggle = o.toggle_mask; a.min_hash = o.min_acceptable_hash;
@@ -880,7 +1082,7 @@ extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opt
     a.quals = qmask ? d_quals : nullptr; a.min_qual = qmask ? o.min_base_quality : 0;
     SH_HIP(hipEventRecord(e0, s));
     if (qmask) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
-    dispatch_classify<false>(a, n_units, s, qmask, quick);
+    dispatch_classify<false>(a, n_units, s, qmask, quick, hits_out ? 1 : 0);
     SH_HIP(hipEventRecord(e1, s));
     std::vector<unsigned long long> h(K2C_WORDS);
     SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
@@ -896,6 +1098,32 @@ extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opt
         SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
         SH_HIP(hipStreamSynchronize(s));
         SH_HIP(hipGetLastError());
+    }
+    if (hits_out) {
+        // exact offsets from the counts, the units with longer lists redone straight into place, the rest compacted
+        sh_k2_hits *hl = *hits_out;
+        hl->n_units = n_units;
+        SH_HIP(hipMalloc(&hl->d_off, (n_units + 1) * 8));
+        size_t tmp_bytes = 0; void *tmp = nullptr;
+        SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, n_hits, hl->d_off, (uint64_t)0, n_units + 1, rocprim::plus<uint64_t>(), s));
+        SH_HIP(hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 1)));
+        SH_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, n_hits, hl->d_off, (uint64_t)0, n_units + 1, rocprim::plus<uint64_t>(), s));
+        SH_HIP(hipMemcpyAsync(&hl->n_entries, hl->d_off + n_units, 8, hipMemcpyDeviceToHost, s));
+        SH_HIP(hipStreamSynchronize(s));
+        hipFree(tmp);
+        SH_HIP(hipMalloc(&hl->d_ent, std::max<uint64_t>(hl->n_entries, 1) * sizeof(sh_k2_hit)));
+        const uint64_t n_hover = h[K2C_HOVER];
+        if (n_hover) {
+            a.unit_list = hit_over; a.n_list = (uint32_t)n_hover; a.hits = (uint2 *)hl->d_ent; a.hit_off = hl->d_off;
+            dispatch_classify<false>(a, n_hover, s, qmask, quick, 2);
+        }
+        const uint64_t n_cp = n_units * K2_HIT_INLINE;
+        hipLaunchKernelGGL(k_k2_hits_compact, dim3((uint32_t)std::min<uint64_t>((n_cp + 255) / 256, 65536)), dim3(256), 0, s, hit_inl, n_hits, hl->d_off, n_units,
+                           (uint2 *)hl->d_ent);
+        SH_HIP(hipStreamSynchronize(s));
+        SH_HIP(hipGetLastError());
+        hl->n_redone = n_hover;
+        hipFree(hit_inl); hipFree(n_hits); hipFree(hit_over);
     }
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);
@@ -917,11 +1145,39 @@ extern "C" sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *
     return sh_k2_classify_batch_q(db, opts, bases, nullptr, offsets, n_records, paired, out, stats);
 }
 
+static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
+                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits);
+
 extern "C" sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
                                             const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats)
 {
+    return k2_classify_batch(db, opts, bases, quals, offsets, n_records, paired, out, stats, nullptr);
+}
+
+extern "C" sh_status sh_k2_classify_hits_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
+                                               uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits)
+{
+    return sh_k2_classify_hits_batch_q(db, opts, bases, nullptr, offsets, n_records, paired, out, stats, hits);
+}
+
+extern "C" sh_status sh_k2_classify_hits_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
+                                                 const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats,
+                                                 sh_k2_hits **hits)
+{
+    SH_CHECK(hits, SH_ERR_BAD_ARG, "sh_k2_classify_hits_batch: null argument");
+    *hits = nullptr;
+    SH_CHECK(!(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: use sh_k2_classify_batch_q");
+    sh_status st = k2_classify_batch(db, opts, bases, quals, offsets, n_records, paired, out, stats, hits);
+    if (st != SH_OK) { sh_k2_hits_free(*hits); *hits = nullptr; }
+    return st;
+}
+
+static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
+                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits)
+{
     SH_CHECK(db && offsets && out, SH_ERR_BAD_ARG, "sh_k2_classify_batch: null argument");
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (hits && n_records == 0) { *hits = new sh_k2_hits; (*hits)->device = db->device; }
     if (n_records == 0) return SH_OK;
     SH_HIP(hipSetDevice(db->device));
     const uint64_t o0 = offsets[0], n_bases = offsets[n_records] - o0;
@@ -942,7 +1198,7 @@ extern "C" sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts
     SH_HIP(hipMemcpy(d_bases, bases + o0, n_bases, hipMemcpyHostToDevice));
     SH_HIP(hipMemset(d_bases + n_bases, 'N', 64));
     SH_HIP(hipMemcpy(d_off, rel.data(), (n_records + 1) * 8, hipMemcpyHostToDevice));
-    sh_status st = sh_k2_classify_device_q(db, opts, d_bases, d_quals, d_off, n_records, paired, d_out, nullptr, stats);
+    sh_status st = k2_classify(db, opts, d_bases, d_quals, d_off, n_records, paired, d_out, nullptr, stats, hits);
     if (st == SH_OK && hipMemcpy(out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost) != hipSuccess) { sh_set_error("copy of the results failed"); st = SH_ERR_HIP; }
     hipFree(d_bases); hipFree(d_quals); hipFree(d_off); hipFree(d_out);
     return st;

@@ -1432,7 +1432,8 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     const auto t2 = now();
 
     std::vector<sh_k2_result> results(std::max<uint64_t>(n_units, 1));
-    st = sh_k2_classify_batch_q(db, &opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), n_rec, paired ? 1 : 0, results.data(), nullptr);
+    ShiKrakenHits hits;             // column 5: the hit lists (with --quick, "<taxid>:Q")
+    st = shi_kraken_classify(db, opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), n_rec, paired, results.data(), hits);
     if (st != SH_OK) return st;
     std::vector<uint8_t>().swap(bases);
     std::vector<uint8_t>().swap(quals);
@@ -1462,9 +1463,11 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
                 unit_id(ch, r, &id, &il);
                 o += x.call ? 'C' : 'U'; o += '\t'; o.append(id, il);
                 int m;
-                if (paired) m = snprintf(num, sizeof num, "\t%u\t%u|%u\tkmers=%u groups=%u\n", x.taxid, r.seq_len, (uint32_t)(offsets[2 * k + 2] - offsets[2 * k + 1]), x.total_kmers, x.hit_groups);
-                else m = snprintf(num, sizeof num, "\t%u\t%u\tkmers=%u groups=%u\n", x.taxid, r.seq_len, x.total_kmers, x.hit_groups);
+                if (paired) m = snprintf(num, sizeof num, "\t%u\t%u|%u\t", x.taxid, r.seq_len, (uint32_t)(offsets[2 * k + 2] - offsets[2 * k + 1]));
+                else m = snprintf(num, sizeof num, "\t%u\t%u\t", x.taxid, r.seq_len);
                 o.append(num, (size_t)m);
+                hits.append(o, k, x);
+                o += '\n';
             });
         });
         bool ok = true;

@@ -42,6 +42,38 @@ class KrakenConfig(C.Structure):
 
 
 RESULT_DTYPE = np.dtype([("taxid", "<u4"), ("call", "<u4"), ("total_kmers", "<u4"), ("hit_groups", "<u4")])
+# one hit-list entry: internal taxid (0 = not in the table / not looked up), HIT_AMBIGUOUS or HIT_BORDER, and its k-mer count
+HIT_DTYPE = np.dtype([("code", "<u4"), ("count", "<u4")])
+HIT_AMBIGUOUS, HIT_BORDER = 0xFFFFFFFF, 0xFFFFFFFE
+
+
+def format_hits(entries, external, quick=False, quick_taxid=0):
+    """Column 5 of kraken.reads for one unit (sh_k2_format_hits; host only, no GPU needed): entries = HIT_DTYPE array or
+    (code, count) pairs, external = the taxonomy's external ids by internal id."""
+    e = np.ascontiguousarray(np.array([tuple(x) for x in entries], dtype=HIT_DTYPE) if not isinstance(entries, np.ndarray) else entries, dtype=HIT_DTYPE)
+    ext = np.ascontiguousarray(external, dtype=np.uint32)
+    n = C.c_uint64()
+    L = S.load()
+    args = (C.c_void_p(e.ctypes.data), C.c_uint64(len(e)), C.c_void_p(ext.ctypes.data), C.c_uint64(len(ext)), int(bool(quick)), C.c_uint32(quick_taxid))
+    S.check(L.sh_k2_format_hits(*args, None, C.c_uint64(0), C.byref(n)))
+    buf = C.create_string_buffer(n.value + 1)
+    S.check(L.sh_k2_format_hits(*args, buf, C.c_uint64(n.value + 1), C.byref(n)))
+    return buf.value.decode()
+
+
+def _take_hits(h):
+    """offsets (n_units + 1) and entries of a sh_k2_hits handle copied to the host, and the units its overflow pass redid;
+    the handle is freed"""
+    L = S.load()
+    try:
+        nu, ne, nr = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        S.check(L.sh_k2_hits_count(h, C.byref(nu), C.byref(ne), C.byref(nr)))
+        offs = np.zeros(nu.value + 1, dtype=np.uint64)
+        ent = np.zeros(max(ne.value, 1), dtype=HIT_DTYPE)
+        S.check(L.sh_k2_hits_copy(h, C.c_void_p(offs.ctypes.data), C.c_void_p(ent.ctypes.data)))
+        return offs, ent[: ne.value], nr.value
+    finally:
+        L.sh_k2_hits_free(h)
 
 
 def default_opts():
@@ -131,8 +163,10 @@ class K2Db:
         S.check(S.load().sh_k2_export(self.h, C.c_void_p(cells.ctypes.data), C.c_void_p(parent.ctypes.data), C.c_void_p(ext.ctypes.data)))
         return cells, parent, ext
 
-    def classify(self, bases, offsets, paired=False, opts=None, quals=None):
-        """quals (optional): Phred+33 bytes at the offsets of `bases` (0xFF = never masked), used when opts.min_base_quality > 0."""
+    def classify(self, bases, offsets, paired=False, opts=None, quals=None, hits=False):
+        """quals (optional): Phred+33 bytes at the offsets of `bases` (0xFF = never masked), used when opts.min_base_quality > 0.
+        hits=True: also Kraken 2's hit lists (sh_k2_classify_hits_batch_q), returned third as (offsets, entries): unit i's
+        entries (HIT_DTYPE) are entries[offsets[i]:offsets[i + 1]]."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         if quals is not None:
@@ -142,11 +176,55 @@ class K2Db:
         n_units = n_rec // 2 if paired else n_rec
         out = np.zeros(max(n_units, 1), dtype=RESULT_DTYPE)
         st = K2Stats()
-        S.check(S.load().sh_k2_classify_batch_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(bases.ctypes.data),
-                                                C.c_void_p(quals.ctypes.data) if quals is not None else None,
-                                                C.c_void_p(offsets.ctypes.data), C.c_uint64(n_rec), 1 if paired else 0,
-                                                C.c_void_p(out.ctypes.data), C.byref(st)))
-        return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
+        args = (self.h, C.byref(opts) if opts is not None else None, C.c_void_p(bases.ctypes.data),
+                C.c_void_p(quals.ctypes.data) if quals is not None else None, C.c_void_p(offsets.ctypes.data), C.c_uint64(n_rec),
+                1 if paired else 0, C.c_void_p(out.ctypes.data), C.byref(st))
+        if not hits:
+            S.check(S.load().sh_k2_classify_batch_q(*args))
+            return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
+        h = C.c_void_p()
+        S.check(S.load().sh_k2_classify_hits_batch_q(*args, C.byref(h)))
+        offs, ent, redone = _take_hits(h)
+        return out[:n_units], dict({n: getattr(st, n) for n, _ in K2Stats._fields_}, n_hits_redone=redone), (offs, ent)
+
+    def classify_hit_strings(self, bases, offsets, paired=False, opts=None, quals=None):
+        """results, stats and column 5 of kraken.reads for every unit (strings, external taxids)"""
+        out, st, (offs, ent) = self.classify(bases, offsets, paired=paired, opts=opts, quals=quals, hits=True)
+        ext = self.export_external()
+        return out, st, [format_hits(ent[int(offs[i]): int(offs[i + 1])], ext) for i in range(len(out))]
+
+    def export_external(self):
+        ext = np.zeros(self.info()["n_nodes"], dtype=np.uint32)
+        S.check(S.load().sh_k2_export(self.h, None, None, C.c_void_p(ext.ctypes.data)))
+        return ext
+
+    def classify_device_hits(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None, to_host=True):
+        """sh_k2_classify_hits_device_q: results into d_out; returns (stats, (offsets, entries)) copied to the host, or with
+        to_host=False (stats, (d_offsets_ptr, d_entries_ptr, n_units, n_entries, handle)) - free the handle with free_hits."""
+        st = K2Stats()
+        h = C.c_void_p()
+        S.check(S.load().sh_k2_classify_hits_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
+                                                      C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
+                                                      C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
+                                                      C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st), C.byref(h)))
+        stats = {n: getattr(st, n) for n, _ in K2Stats._fields_}
+        if to_host:
+            offs, ent, stats["n_hits_redone"] = _take_hits(h)
+            return stats, (offs, ent)
+        nu, ne, po, pe = C.c_uint64(), C.c_uint64(), C.c_void_p(), C.c_void_p()
+        S.check(S.load().sh_k2_hits_count(h, C.byref(nu), C.byref(ne), None))
+        S.check(S.load().sh_k2_hits_device(h, C.byref(po), C.byref(pe)))
+        return stats, (po.value, pe.value, nu.value, ne.value, h)
+
+    @staticmethod
+    def free_hits(h):
+        S.load().sh_k2_hits_free(h)
+
+    @staticmethod
+    def hits_redone(h):
+        r = C.c_uint64()
+        S.check(S.load().sh_k2_hits_count(h, None, None, C.byref(r)))
+        return r.value
 
     def classify_device(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None):
         st = K2Stats()

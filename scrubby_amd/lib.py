@@ -134,6 +134,8 @@ EXPORTS = [
     "sh_k2_default_opts", "sh_k2_open", "sh_k2_create", "sh_k2_insert_device", "sh_k2_insert_sequence_device",
     "sh_k2_insert_random", "sh_k2_save", "sh_k2_info_get", "sh_k2_db_opts", "sh_k2_export", "sh_k2_free",
     "sh_k2_classify_device", "sh_k2_classify_batch", "sh_k2_classify_device_q", "sh_k2_classify_batch_q", "sh_k2_write_report", "sh_kraken_run",
+    "sh_k2_classify_hits_device", "sh_k2_classify_hits_device_q", "sh_k2_classify_hits_batch", "sh_k2_classify_hits_batch_q",
+    "sh_k2_hits_count", "sh_k2_hits_device", "sh_k2_hits_copy", "sh_k2_hits_free", "sh_k2_format_hits",
 ]
 
 _LIB = None
