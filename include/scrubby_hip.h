@@ -459,6 +459,88 @@ typedef struct sh_kraken_config {
 } sh_kraken_config;
 sh_status sh_kraken_run(const sh_kraken_config *cfg, sh_reads_result *out);
 
+/* ---- Kraken arm: database build (DESIGN.md §7 "Database build").  Kraken 2's build rules as recalled from build_db.cc,
+ * taxonomy.cc, estimate_capacity.cc and kraken2-build: PARITY UNPINNED, like the rest of the arm. ------------------------------ */
+/* Host only (no GPU): an NCBI taxonomy reduced to the taxa a library uses, in taxo.k2d's layout. */
+typedef struct sh_k2_taxonomy sh_k2_taxonomy;
+typedef struct sh_k2_taxonomy_info {
+    uint64_t n_nodes, names_len, ranks_len;
+    int32_t  value_bits;            /* smallest b with 2^b >= n_nodes (>= 1), or the larger value the caller asked for */
+    int32_t  pad;
+    uint64_t n_map_entries;         /* sequence ids of the id map whose taxon is in nodes.dmp */
+    uint64_t n_missing_taxa;        /* distinct taxids of the map (and of extra_taxids) that nodes.dmp lacks */
+} sh_k2_taxonomy_info;
+/* nodes.dmp + names.dmp (scientific names only) + seqid2taxid.map (nullable) + further taxids in use (nullable: those of
+ * `kraken:taxid|n` headers).  Every used taxon and its ancestors up to the root (taxid 1) are kept, the rest dropped; internal
+ * ids are breadth-first (0 the empty node, 1 the root), siblings in ascending external taxid.  A taxid that nodes.dmp lacks is
+ * named once on stderr and its sequences are skipped. */
+sh_status sh_k2_taxonomy_from_ncbi(const char *nodes_dmp, const char *names_dmp, const char *seqid2taxid_map,
+                                   const uint64_t *extra_taxids, uint64_t n_extra, int32_t value_bits, sh_k2_taxonomy **out);
+/* the host-depletion case: root -> one taxon (name NULL: "taxid <n>", rank NULL: "species"); every header maps to it */
+sh_status sh_k2_taxonomy_single(uint64_t taxid, const char *name, const char *rank, int32_t value_bits, sh_k2_taxonomy **out);
+sh_status sh_k2_taxonomy_info_get(const sh_k2_taxonomy *t, sh_k2_taxonomy_info *out);
+/* nodes[n_nodes], names[names_len], ranks[ranks_len]; any of them may be NULL */
+sh_status sh_k2_taxonomy_copy(const sh_k2_taxonomy *t, sh_k2_taxnode *nodes, char *names, char *ranks);
+/* external -> internal id; 0 = not in the reduced taxonomy */
+sh_status sh_k2_taxonomy_internal(const sh_k2_taxonomy *t, uint64_t external_id, uint32_t *internal_id);
+/* FASTA header (without '>') -> internal taxon of its record: the id is the first whitespace-delimited token; a token holding
+ * `kraken:taxid|<n>` takes <n>; ids joined by \x01 give the LCA of their taxa; 0 = no taxon, the record is skipped */
+sh_status sh_k2_taxonomy_header_taxon(const sh_k2_taxonomy *t, const char *header, uint64_t len, uint32_t *internal_id);
+sh_status sh_k2_taxonomy_free(sh_k2_taxonomy *t);
+
+/* capacity = ceil(256 * n_sampled / load_factor) (load_factor <= 0: 0.7); then kraken2-build --max-db-size B (0: none): when
+ * 4 * capacity > B, capacity = B / 4 and min_acceptable_hash = (uint64)((1 - B / (4 * needed)) * 2^64).  Host only. */
+sh_status sh_k2_capacity_plan(uint64_t n_sampled, double load_factor, uint64_t max_db_size, uint64_t *estimate, uint64_t *capacity,
+                              uint64_t *min_acceptable_hash);
+/* the --max-db-size rule alone, on a capacity that is already known */
+sh_status sh_k2_max_db_size(uint64_t needed_capacity, uint64_t max_db_size, uint64_t *capacity, uint64_t *min_acceptable_hash);
+/* the database's down-sampling threshold (set before the first insert; written to opts.k2d, honoured by the classifier) */
+sh_status sh_k2_set_min_acceptable_hash(sh_k2_db *db, uint64_t min_acceptable_hash);
+
+typedef struct sh_k2_build_stats {
+    uint64_t n_records;
+    uint64_t n_segments;            /* (record, segment) work items of the launch */
+    uint64_t n_runs;                /* minimizer runs handed to the table (a run that spans a segment border counts in both) */
+    uint64_t size;                  /* distinct keys in the table after the call */
+    float    ms;
+} sh_k2_build_stats;
+/* One launch over a batch of records in HBM: record r = d_bases[d_offsets[r], d_offsets[r + 1]) under internal taxon d_taxa[r]
+ * (0, or one outside the taxonomy = skip; so is a record shorter than k).  d_bases must be readable up to the 8-byte boundary behind its last base.  One synchronisation per call.
+ * SH_ERR_OOM when the table is full. */
+sh_status sh_k2_insert_library_device(sh_k2_db *db, const uint8_t *d_bases, const uint64_t *d_offsets, const uint32_t *d_taxa,
+                                      uint64_t n_records, void *stream, sh_k2_build_stats *stats);
+/* Kraken 2's capacity estimator: the distinct minimizers m with (fmix64(m) & 1023) < 4, accumulated over every batch given to
+ * one estimator; *n_sampled = their number so far (estimate = 256 * n_sampled: sh_k2_capacity_plan). */
+typedef struct sh_k2_estimator sh_k2_estimator;
+sh_status sh_k2_estimator_create(const sh_k2_opts *opts, int device, sh_k2_estimator **out);
+sh_status sh_k2_estimate_capacity_device(sh_k2_estimator *est, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_records,
+                                         void *stream, uint64_t *n_sampled);
+sh_status sh_k2_estimator_free(sh_k2_estimator *est);
+
+/* `scrubby-hip k2-build`: library FASTA files (plain, gzip, bzip2, xz) + taxonomy -> hash.k2d / opts.k2d / taxo.k2d */
+typedef struct sh_k2_build_config {
+    const char *const *input;  uint32_t n_input;
+    const char *taxonomy_dir;       /* holds nodes.dmp and names.dmp; NULL: single-taxon mode */
+    const char *seqid2taxid;        /* nullable (headers may carry kraken:taxid|n) */
+    uint64_t    taxid;              /* single-taxon mode: every record's taxon */
+    const char *name, *rank;        /* single-taxon mode, nullable */
+    const char *output_dir;
+    int32_t     k, l, minimizer_spaces;     /* 0: 35, 31, 7; minimizer_spaces < 0: no spaced seed */
+    int32_t     value_bits;         /* 0: the minimum for the taxonomy */
+    uint64_t    capacity;           /* 0: estimate it (a pass of its own over the input) */
+    double      load_factor;        /* <= 0: 0.7 */
+    uint64_t    max_db_size;        /* bytes, 0: unlimited */
+    uint64_t    chunk_bytes;        /* bases per batch, 0: 256 MiB; a longer record is cut (k - 1 bases repeated) */
+    int32_t     device, pad;
+} sh_k2_build_config;
+typedef struct sh_k2_build_result {
+    uint64_t n_records, n_skipped, n_bases, n_batches, n_cuts;
+    uint64_t n_runs, size, capacity, n_nodes, n_sampled, estimate, min_acceptable_hash;
+    int32_t  value_bits, pad;
+    double   s_taxonomy, s_estimate, s_fill, s_save, s_read, s_total;   /* s_read: reading + parsing + upload inside the two passes */
+} sh_k2_build_result;
+sh_status sh_k2_build_run(const sh_k2_build_config *cfg, sh_k2_build_result *out);
+
 /* ---- multi-GPU: the one exchange of the read-sharded path (HashSet union of cleaner.rs:564-570) --------------
  * d_flags[n] (1 = host) -> d_bits[(n + 7) / 8], bit i of byte j = record 8j + i; each rank packs its own slice and the disjoint
  * slices are all-gathered over RCCL (scrubby_amd/dist.py). */

@@ -16,7 +16,10 @@ static void usage()
             "scrubby-hip reads -i <R1> [R2] -o <O1> [O2] -c kraken2 -I <kraken2 db dir> [-T taxa..] [-D taxa..] [-w workdir]\n"
             "                  [-C \"--confidence x --minimum-hit-groups n\"] [-e] [-j report.json] [-r read_ids.tsv[.gz]]\n"
             "scrubby-hip classifier -i <R1> [R2] -o <O1> [O2] -k <report> -j <reads> -c kraken2|metabuli [-T taxa..] [-D taxa..]\n"
-            "                  [-e] [--json report.json] [-r read_ids.tsv]\n");
+            "                  [-e] [--json report.json] [-r read_ids.tsv]\n"
+            "scrubby-hip k2-build -i <library.fna[.gz]>.. -o <db dir> (-n <taxonomy dir> [-m <seqid2taxid.map>] | --taxid N [--name S] [--rank S])\n"
+            "                  [--kmer-len 35] [--minimizer-len 31] [--minimizer-spaces 7] [--capacity N] [--load-factor 0.7]\n"
+            "                  [--max-db-size BYTES] [--value-bits N] [--chunk-bytes N]\n");
 }
 
 // `scrubby classifier` (/root/reference/src/terminal.rs:204-279): clean reads from precomputed Kraken2 / Metabuli outputs
@@ -60,6 +63,54 @@ static int main_classifier(int argc, char **argv, const std::string &command)
     return 0;
 }
 
+// `scrubby-hip k2-build`: a Kraken 2 database directory from a FASTA library and a taxonomy (no counterpart in the reference, which
+// takes a finished database; kraken2-build's options)
+static int main_k2_build(int argc, char **argv)
+{
+    std::vector<std::string> in;
+    std::string out, taxdir, map, name, rank;
+    sh_k2_build_config c{};
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
+        auto multi = [&](std::vector<std::string> &v) { while (i + 1 < argc && argv[i + 1][0] != '-') v.push_back(argv[++i]); };
+        if (a == "-i" || a == "--input") multi(in);
+        else if (a == "-o" || a == "--output") out = val();
+        else if (a == "-n" || a == "--taxonomy") taxdir = val();
+        else if (a == "-m" || a == "--seqid2taxid") map = val();
+        else if (a == "--taxid") c.taxid = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "--name") name = val();
+        else if (a == "--rank") rank = val();
+        else if (a == "--kmer-len") c.k = atoi(val().c_str());
+        else if (a == "--minimizer-len") c.l = atoi(val().c_str());
+        else if (a == "--minimizer-spaces") { c.minimizer_spaces = atoi(val().c_str()); if (c.minimizer_spaces == 0) c.minimizer_spaces = -1; }
+        else if (a == "--capacity") c.capacity = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "--load-factor") c.load_factor = atof(val().c_str());
+        else if (a == "--max-db-size") c.max_db_size = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "--value-bits") c.value_bits = atoi(val().c_str());
+        else if (a == "--chunk-bytes") c.chunk_bytes = strtoull(val().c_str(), nullptr, 10);
+        else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+    }
+    if (in.empty() || out.empty()) { fprintf(stderr, "error: library files (-i) and an output directory (-o) are required\n"); return 2; }
+    if (taxdir.empty() == (c.taxid == 0)) { fprintf(stderr, "error: either -n <taxonomy dir> or --taxid N\n"); return 2; }
+    std::vector<const char *> ip;
+    for (auto &x : in) ip.push_back(x.c_str());
+    c.input = ip.data(); c.n_input = (uint32_t)ip.size(); c.output_dir = out.c_str();
+    c.taxonomy_dir = taxdir.empty() ? nullptr : taxdir.c_str(); c.seqid2taxid = map.empty() ? nullptr : map.c_str();
+    c.name = name.empty() ? nullptr : name.c_str(); c.rank = rank.empty() ? nullptr : rank.c_str();
+    sh_k2_build_result r{};
+    sh_status st = sh_k2_build_run(&c, &r);
+    if (st != SH_OK) { fprintf(stderr, "error (%d): %s\n", st, sh_last_error()); return 1; }
+    printf("{\"records\": %llu, \"records_skipped\": %llu, \"bases\": %llu, \"batches\": %llu, \"cuts\": %llu, \"runs_inserted\": %llu, \"size\": %llu, "
+           "\"capacity\": %llu, \"nodes\": %llu, \"value_bits\": %d, \"n_sampled\": %llu, \"estimate\": %llu, \"min_acceptable_hash\": %llu, "
+           "\"s_estimate\": %.3f, \"s_taxonomy\": %.3f, \"s_fill\": %.3f, \"s_save\": %.3f, \"s_read\": %.3f, \"s_total\": %.3f}\n",
+           (unsigned long long)r.n_records, (unsigned long long)r.n_skipped, (unsigned long long)r.n_bases, (unsigned long long)r.n_batches,
+           (unsigned long long)r.n_cuts, (unsigned long long)r.n_runs, (unsigned long long)r.size, (unsigned long long)r.capacity, (unsigned long long)r.n_nodes,
+           r.value_bits, (unsigned long long)r.n_sampled, (unsigned long long)r.estimate, (unsigned long long)r.min_acceptable_hash, r.s_estimate, r.s_taxonomy,
+           r.s_fill, r.s_save, r.s_read, r.s_total);
+    return 0;
+}
+
 // `scrubby alignment` (/root/reference/src/terminal.rs:281-360)
 static int main_alignment(int argc, char **argv, const std::string &command)
 {
@@ -99,6 +150,7 @@ static int main_alignment(int argc, char **argv, const std::string &command)
 
 int main(int argc, char **argv)
 {
+    if (argc >= 2 && std::string(argv[1]) == "k2-build") return main_k2_build(argc, argv);
     if (argc >= 2 && (std::string(argv[1]) == "classifier" || std::string(argv[1]) == "alignment")) {
         std::string command;
         for (int i = 0; i < argc; ++i) { if (i) command += ' '; command += argv[i]; }

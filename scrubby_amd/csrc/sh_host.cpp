@@ -18,7 +18,9 @@
 #include <thread>
 #include <ctime>
 #include <unordered_set>
+#include <unordered_map>
 #include <algorithm>
+#include <cmath>
 #include "sh_codec.h"
 
 namespace {
@@ -832,4 +834,295 @@ extern "C" sh_status sh_alignment_run(const sh_alignment_config *c, sh_reads_res
     ReportSettings st;
     st.alignment = c->alignment; st.min_len = c->min_len; st.min_cov = c->min_cov; st.min_mapq = c->min_mapq; st.extract = c->extract != 0;
     return finish_report(c->input, c->output, c->n_files, c->extract != 0, c->json, c->read_ids, c->command, st, res);
+}
+
+// ---- Kraken arm: taxonomy of a database build (DESIGN.md §7 "Database build") ------------------------------------------------
+// Kraken 2's rules as recalled from taxonomy.cc (NCBITaxonomy, ConvertToKrakenTaxonomyAndWriteToDisk) and build_db.cc
+// (ExtractNCBISequenceIDs, the id map): parity unpinned.  Host only: nothing here touches the GPU.
+struct sh_k2_taxonomy {
+    std::vector<sh_k2_taxnode> nodes;
+    std::vector<uint32_t> parent;
+    std::string names, ranks;
+    std::unordered_map<uint64_t, uint32_t> ext2int;
+    std::unordered_map<std::string, uint32_t> seq2int;
+    int32_t value_bits = 1;
+    uint64_t n_missing = 0;
+    uint32_t single = 0;         // single-taxon mode: every header's taxon
+};
+
+namespace {
+
+// one `a \t|\t b \t|\t c \t|` row of an NCBI dump: its fields without the padding tabs
+void dmp_fields(const char *line, std::vector<std::string> &f)
+{
+    f.clear();
+    const char *p = line;
+    for (;;) {
+        const char *bar = strchr(p, '|');
+        const char *e = bar ? bar : p + strlen(p);
+        const char *b = p;
+        while (b < e && (*b == '\t' || *b == ' ')) ++b;
+        while (e > b && (e[-1] == '\t' || e[-1] == ' ' || e[-1] == '\n' || e[-1] == '\r')) --e;
+        if (bar || e > b) f.emplace_back(b, e);
+        if (!bar) break;
+        p = bar + 1;
+    }
+}
+
+int32_t k2_min_value_bits(uint64_t n_nodes)
+{
+    int32_t b = 1;
+    while ((1ull << b) < n_nodes) ++b;
+    return b;
+}
+
+sh_status k2_taxonomy_bits(sh_k2_taxonomy *t, int32_t asked)
+{
+    const int32_t need = k2_min_value_bits(t->nodes.size());
+    SH_CHECK(asked == 0 || (asked >= need && asked <= 31), SH_ERR_BAD_ARG, "%zu taxonomy nodes need %d value bits (asked for %d)", t->nodes.size(), need, asked);
+    t->value_bits = asked ? asked : need;
+    return SH_OK;
+}
+
+uint32_t k2_tax_lca(const std::vector<uint32_t> &parent, uint32_t a, uint32_t b)
+{   // breadth-first ids: a parent's id is smaller than its child's
+    if (!a || !b) return a ? a : b;
+    while (a != b) { if (a > b) a = parent[a]; else b = parent[b]; }
+    return a;
+}
+
+}  // namespace
+
+extern "C" sh_status sh_k2_taxonomy_free(sh_k2_taxonomy *t) { delete t; return SH_OK; }
+
+extern "C" sh_status sh_k2_taxonomy_from_ncbi(const char *nodes_dmp, const char *names_dmp, const char *seqid2taxid_map, const uint64_t *extra_taxids,
+                                              uint64_t n_extra, int32_t value_bits, sh_k2_taxonomy **out)
+{
+    SH_CHECK(nodes_dmp && names_dmp && out && (extra_taxids || n_extra == 0), SH_ERR_BAD_ARG, "sh_k2_taxonomy_from_ncbi: null argument");
+    struct Raw { uint64_t parent; std::string rank; };
+    std::unordered_map<uint64_t, Raw> raw;
+    std::vector<std::string> f;
+    char *line = nullptr; size_t cap = 0;
+    {
+        FILE *fp = fopen(nodes_dmp, "r");
+        SH_CHECK(fp, SH_ERR_IO, "cannot open %s", nodes_dmp);
+        while (getline(&line, &cap, fp) > 0) {
+            dmp_fields(line, f);
+            if (f.size() < 3 || f[0].empty()) continue;
+            raw[strtoull(f[0].c_str(), nullptr, 10)] = Raw{strtoull(f[1].c_str(), nullptr, 10), f[2]};
+        }
+        fclose(fp);
+    }
+    if (!raw.count(1)) { free(line); sh_set_error("%s has no root (taxid 1)", nodes_dmp); return SH_ERR_IO; }
+    // the id map: two tab- or space-separated columns
+    std::vector<std::pair<std::string, uint64_t>> map_rows;
+    if (seqid2taxid_map) {
+        FILE *fp = fopen(seqid2taxid_map, "r");
+        if (!fp) { free(line); sh_set_error("cannot open %s", seqid2taxid_map); return SH_ERR_IO; }
+        while (getline(&line, &cap, fp) > 0) {
+            const char *b = line;
+            while (*b == ' ' || *b == '\t') ++b;
+            const char *e = b;
+            while (*e && *e != ' ' && *e != '\t' && *e != '\n' && *e != '\r') ++e;
+            if (e == b) continue;
+            const char *v = e;
+            while (*v == ' ' || *v == '\t') ++v;
+            if (*v < '0' || *v > '9') continue;
+            map_rows.emplace_back(std::string(b, e), strtoull(v, nullptr, 10));
+        }
+        fclose(fp);
+    }
+    // mark every used taxon and its ancestors up to the root; the others are dropped
+    std::unordered_set<uint64_t> marked{1}, missing;
+    auto use = [&](uint64_t t) {
+        if (!raw.count(t)) {
+            if (missing.insert(t).second) fprintf(stderr, "[scrubby-hip] k2-build: taxid %llu is not in nodes.dmp: its sequences are skipped\n", (unsigned long long)t);
+            return;
+        }
+        for (size_t guard = 0; t != 1 && guard < 1000 && marked.insert(t).second; ++guard) {
+            auto it = raw.find(t);
+            t = it == raw.end() || !raw.count(it->second.parent) ? 1 : it->second.parent;      // a broken chain hangs under the root
+        }
+    };
+    for (auto &r : map_rows) use(r.second);
+    for (uint64_t i = 0; i < n_extra; ++i) use(extra_taxids[i]);
+    std::unordered_map<uint64_t, std::vector<uint64_t>> kids;
+    for (uint64_t t : marked) {
+        if (t == 1) continue;
+        uint64_t p = raw[t].parent;
+        if (!marked.count(p) || p == t) p = 1;
+        kids[p].push_back(t);
+    }
+    // scientific names of the kept taxa
+    std::unordered_map<uint64_t, std::string> sci;
+    {
+        FILE *fp = fopen(names_dmp, "r");
+        if (!fp) { free(line); sh_set_error("cannot open %s", names_dmp); return SH_ERR_IO; }
+        while (getline(&line, &cap, fp) > 0) {
+            dmp_fields(line, f);
+            if (f.size() < 4 || f[3] != "scientific name") continue;
+            const uint64_t t = strtoull(f[0].c_str(), nullptr, 10);
+            if (marked.count(t)) sci.emplace(t, f[1]);
+        }
+        fclose(fp);
+    }
+    free(line);
+    // breadth-first internal ids: 0 the empty node, 1 the root, the children of a node consecutive and in ascending external
+    // taxid; names in id order, each rank string stored once
+    sh_k2_taxonomy *t = new sh_k2_taxonomy;
+    std::vector<uint64_t> order{0, 1};
+    t->nodes.assign(2, sh_k2_taxnode{});
+    t->parent.assign(2, 0);
+    std::unordered_map<std::string, uint64_t> rank_off;
+    for (size_t i = 1; i < order.size(); ++i) {
+        const uint64_t ext = order[i];
+        t->nodes[i].external_id = ext;
+        t->ext2int[ext] = (uint32_t)i;
+        t->nodes[i].name_offset = t->names.size();
+        t->names += sci.count(ext) ? sci[ext] : std::string();
+        t->names.push_back('\0');
+        const std::string &rk = raw[ext].rank;
+        auto ro = rank_off.find(rk);
+        if (ro == rank_off.end()) { ro = rank_off.emplace(rk, t->ranks.size()).first; t->ranks += rk; t->ranks.push_back('\0'); }
+        t->nodes[i].rank_offset = ro->second;
+        auto k = kids.find(ext);
+        if (k == kids.end()) continue;
+        std::sort(k->second.begin(), k->second.end());
+        t->nodes[i].first_child = order.size();
+        t->nodes[i].child_count = k->second.size();
+        for (uint64_t c : k->second) {
+            order.push_back(c);
+            sh_k2_taxnode nd{};
+            nd.parent = i;
+            t->nodes.push_back(nd);
+            t->parent.push_back((uint32_t)i);
+        }
+    }
+    for (auto &r : map_rows) {
+        auto it = t->ext2int.find(r.second);
+        if (it != t->ext2int.end()) t->seq2int[r.first] = it->second;
+    }
+    t->n_missing = missing.size();
+    sh_status st = k2_taxonomy_bits(t, value_bits);
+    if (st != SH_OK) { delete t; return st; }
+    *out = t;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_taxonomy_single(uint64_t taxid, const char *name, const char *rank, int32_t value_bits, sh_k2_taxonomy **out)
+{
+    SH_CHECK(out && taxid > 1, SH_ERR_BAD_ARG, "sh_k2_taxonomy_single: a taxid above 1 is required");
+    sh_k2_taxonomy *t = new sh_k2_taxonomy;
+    t->nodes.assign(3, sh_k2_taxnode{});
+    t->parent = {0, 0, 1};
+    t->nodes[1].external_id = 1; t->nodes[1].first_child = 2; t->nodes[1].child_count = 1;
+    t->nodes[2].external_id = taxid; t->nodes[2].parent = 1;
+    t->names = std::string("root"); t->names.push_back('\0');
+    t->nodes[2].name_offset = t->names.size();
+    t->names += name && *name ? std::string(name) : "taxid " + std::to_string(taxid); t->names.push_back('\0');
+    t->ranks = std::string("no rank"); t->ranks.push_back('\0');
+    t->nodes[2].rank_offset = t->ranks.size();
+    t->ranks += rank && *rank ? rank : "species"; t->ranks.push_back('\0');
+    t->ext2int[1] = 1; t->ext2int[taxid] = 2;
+    t->single = 2;
+    sh_status st = k2_taxonomy_bits(t, value_bits);
+    if (st != SH_OK) { delete t; return st; }
+    *out = t;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_taxonomy_info_get(const sh_k2_taxonomy *t, sh_k2_taxonomy_info *o)
+{
+    SH_CHECK(t && o, SH_ERR_BAD_ARG, "sh_k2_taxonomy_info_get: null argument");
+    memset(o, 0, sizeof(*o));
+    o->n_nodes = t->nodes.size(); o->names_len = t->names.size(); o->ranks_len = t->ranks.size(); o->value_bits = t->value_bits;
+    o->n_map_entries = t->seq2int.size(); o->n_missing_taxa = t->n_missing;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_taxonomy_copy(const sh_k2_taxonomy *t, sh_k2_taxnode *nodes, char *names, char *ranks)
+{
+    SH_CHECK(t, SH_ERR_BAD_ARG, "sh_k2_taxonomy_copy: null argument");
+    if (nodes) memcpy(nodes, t->nodes.data(), t->nodes.size() * sizeof(sh_k2_taxnode));
+    if (names) memcpy(names, t->names.data(), t->names.size());
+    if (ranks) memcpy(ranks, t->ranks.data(), t->ranks.size());
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_taxonomy_internal(const sh_k2_taxonomy *t, uint64_t external_id, uint32_t *internal_id)
+{
+    SH_CHECK(t && internal_id, SH_ERR_BAD_ARG, "sh_k2_taxonomy_internal: null argument");
+    auto it = t->ext2int.find(external_id);
+    *internal_id = it == t->ext2int.end() ? 0u : it->second;
+    return SH_OK;
+}
+
+// the `kraken:taxid|<n>` of an id, if it has one
+bool shi_k2_header_taxid(const char *id, size_t len, uint64_t *taxid)
+{
+    static const char tag[] = "kraken:taxid|";
+    const size_t tl = sizeof(tag) - 1;
+    for (size_t p = 0; p + tl < len; ++p) {
+        if (memcmp(id + p, tag, tl) != 0) continue;
+        size_t q = p + tl; uint64_t v = 0;
+        if (id[q] < '0' || id[q] > '9') return false;
+        for (; q < len && id[q] >= '0' && id[q] <= '9'; ++q) v = v * 10 + (uint64_t)(id[q] - '0');
+        *taxid = v;
+        return true;
+    }
+    return false;
+}
+
+extern "C" sh_status sh_k2_taxonomy_header_taxon(const sh_k2_taxonomy *t, const char *header, uint64_t len, uint32_t *internal_id)
+{
+    SH_CHECK(t && header && internal_id, SH_ERR_BAD_ARG, "sh_k2_taxonomy_header_taxon: null argument");
+    if (t->single) { *internal_id = t->single; return SH_OK; }
+    // every \x01-separated piece starts with an id (its first whitespace-delimited token): the record gets the LCA of their taxa
+    uint32_t taxon = 0;
+    auto sp = [](unsigned char ch) { return ch == ' ' || (ch >= '\t' && ch <= '\r'); };
+    for (uint64_t p = 0; p <= len;) {
+        uint64_t e = p;
+        while (e < len && header[e] != '\x01') ++e;
+        uint64_t b = p;
+        while (b < e && sp((unsigned char)header[b])) ++b;
+        uint64_t ie = b;
+        while (ie < e && !sp((unsigned char)header[ie])) ++ie;
+        if (ie > b) {
+            uint64_t ext = 0; uint32_t one = 0;
+            if (shi_k2_header_taxid(header + b, ie - b, &ext)) {
+                auto it = t->ext2int.find(ext);
+                one = it == t->ext2int.end() ? 0u : it->second;
+            } else {
+                auto it = t->seq2int.find(std::string(header + b, ie - b));
+                one = it == t->seq2int.end() ? 0u : it->second;
+            }
+            taxon = k2_tax_lca(t->parent, taxon, one);
+        }
+        p = e + 1;
+    }
+    *internal_id = taxon;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_max_db_size(uint64_t needed, uint64_t max_db_size, uint64_t *capacity, uint64_t *min_hash)
+{
+    SH_CHECK(capacity && min_hash && needed > 0, SH_ERR_BAD_ARG, "sh_k2_max_db_size: bad argument");
+    *capacity = needed; *min_hash = 0;
+    if (max_db_size && 4 * needed > max_db_size) {      // kraken2-build --max-db-size: a smaller table that keeps the upper part of the hash range
+        SH_CHECK(max_db_size >= 4, SH_ERR_BAD_ARG, "--max-db-size %llu holds no cell", (unsigned long long)max_db_size);
+        *capacity = max_db_size / 4;
+        const double keep = (double)max_db_size / (4.0 * (double)needed);
+        *min_hash = (uint64_t)ldexp(1.0 - keep, 64);
+    }
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_capacity_plan(uint64_t n_sampled, double load_factor, uint64_t max_db_size, uint64_t *estimate, uint64_t *capacity, uint64_t *min_hash)
+{
+    SH_CHECK(capacity && min_hash && load_factor <= 1.0, SH_ERR_BAD_ARG, "sh_k2_capacity_plan: bad argument");
+    // estimate_capacity.cc: 4 of 1024 hash residues are sampled, so each distinct sampled minimizer stands for 256
+    const uint64_t est = 256 * n_sampled;
+    if (estimate) *estimate = est;
+    const uint64_t needed = std::max<uint64_t>((uint64_t)ceil((double)est / (load_factor > 0 ? load_factor : 0.7)), 1);
+    return sh_k2_max_db_size(needed, max_db_size, capacity, min_hash);
 }

@@ -45,3 +45,5 @@ struct ShiKrakenHits {
 };
 sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
                               bool paired, sh_k2_result *results, ShiKrakenHits &hits);
+// database build: the <n> of a `kraken:taxid|<n>` sequence id (sh_host.cpp)
+bool shi_k2_header_taxid(const char *id, size_t len, uint64_t *taxid);

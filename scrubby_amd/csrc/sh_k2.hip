@@ -647,6 +647,116 @@ __global__ void k_k2_insert_seq(K2Build B, const uint8_t *bases, uint64_t n, uin
     if (runs) atomicAdd(n_runs, runs);
 }
 
+// ---- library build: a batch of records per launch (DESIGN.md §7 "Database build") ---------------------------------------
+// Work item = (record, segment of `seg` bases).  seg_off is the exclusive prefix sum of the records' segment counts, so a lane
+// finds its record by binary search and 10^5 short records fill the machine like one chromosome does.  A segment reads its own
+// record only: the k - 1 warm-up bases before it (none at the record's start), then its bases; minimizers are reported from the
+// first k-mer that ENDS inside the segment, as k_k2_insert_seq does.  The bases come in aligned 8-byte words (two in flight, as in
+// k_k2_classify) instead of one byte load per base.  The character loop has one trip count per wave, so `emit` is called by
+// all 64 lanes together and may use wave operations.
+#define K2_LIB_SEG 1024u      // measured choice: DESIGN.md §7
+struct K2LibArgs {
+    const uint8_t *bases; const uint64_t *offsets; const uint32_t *taxa;     // taxa == nullptr: every record counts (estimator)
+    uint64_t n_records; uint64_t *seg_off;                                   // n_records + 1
+    uint32_t n_nodes;                                                        // a taxon at or above it is skipped like taxon 0
+    uint32_t seg; int32_t k, l; uint64_t spaced, toggle, min_hash;
+};
+
+__global__ void k_k2_lib_segcount(K2LibArgs a)
+{
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= a.n_records; r += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t n = 0;
+        if (r < a.n_records && (!a.taxa || (a.taxa[r] && a.taxa[r] < a.n_nodes))) {
+            const uint64_t len = a.offsets[r + 1] - a.offsets[r];
+            n = len >= (uint64_t)a.k ? (len + a.seg - 1) / a.seg : 0;
+        }
+        a.seg_off[r] = n;
+    }
+}
+
+template <int W, typename Emit>
+__device__ static inline void k2_lib_scan(const K2LibArgs &a, Emit emit)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
+    const int32_t wlim = a.k - a.l + 1;
+    const uint64_t n_items = a.seg_off[a.n_records];
+    for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_items; base += (uint64_t)gridDim.x * 64) {
+        const uint64_t item = base + lane;
+        const bool active = item < n_items;
+        uint32_t taxon = 0; int32_t n = 0, lead = 0;
+        const uint8_t *p = a.bases;
+        if (active) {
+            uint64_t lo = 0, hi = a.n_records;       // the last record r with seg_off[r] <= item (records without segments are passed over)
+            while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (a.seg_off[mid] <= item) lo = mid; else hi = mid; }
+            const uint64_t r0 = a.offsets[lo], len = a.offsets[lo + 1] - r0;
+            const uint64_t s0 = (item - a.seg_off[lo]) * a.seg, s1 = s0 + a.seg < len ? s0 + a.seg : len;
+            const uint64_t from = s0 >= (uint64_t)(a.k - 1) ? s0 - (uint64_t)(a.k - 1) : 0;
+            p = a.bases + r0 + from; n = (int32_t)(s1 - from); lead = (int32_t)(s0 - from);
+            taxon = a.taxa ? a.taxa[lo] : 1u;
+        }
+        int32_t n_max = n;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const int32_t t = __shfl_xor(n_max, o); n_max = t > n_max ? t : n_max; }
+        const uint64_t *wp = (const uint64_t *)((uintptr_t)p & ~(uintptr_t)7);
+        const int32_t off8 = (int32_t)((uintptr_t)p & 7); const uint32_t sh = (uint32_t)off8 * 8;
+        // only the aligned words that overlap the segment are ever loaded
+        uint64_t w_cur = n > 0 ? wp[0] : 0, w_next = n + off8 > 8 ? wp[1] : 0;
+        K2Scan<W> S; S.reset();
+        uint64_t last = ~0ull;
+        const int32_t n_chunks = (n_max + 7) / 8;
+#pragma nounroll
+        for (int32_t c = 0; c < n_chunks; ++c) {
+            uint64_t w = sh ? (w_cur >> sh) | (w_next << (64 - sh)) : w_cur;
+            w_cur = w_next;
+            w_next = (c + 2) * 8 < n + off8 ? wp[c + 2] : 0;
+#pragma unroll
+            for (int32_t j = 0; j < 8; ++j) {
+                const int32_t i = c * 8 + j;
+                uint64_t m;
+                // `pos` only gates "a full k-mer has been read": counted from the warm-up start, never above k
+                const int ev = S.step_w(sh_nt4((uint32_t)w & 0xffu), i + 1 < a.k ? i + 1 : a.k, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
+                w >>= 8;
+                const bool fresh = ev == 2 && i < n && i >= lead && m != last;
+                last = fresh ? m : last;
+                emit(fresh && !(a.min_hash && k2_fmix64(m) < a.min_hash), m, taxon);
+            }
+        }
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(64) void k_k2_insert_lib(K2Build B, K2LibArgs a, unsigned long long *n_runs)
+{
+    unsigned long long runs = 0;
+    k2_lib_scan<W>(a, [&](bool go, uint64_t m, uint32_t taxon) {
+        if (go) { k2_insert(B, m, taxon); ++runs; }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) runs += (unsigned long long)__shfl_xor((long long)runs, o);
+    if (threadIdx.x == 0 && runs) atomicAdd(n_runs, runs);
+}
+
+// estimate_capacity.cc as recalled: minimizers whose hash falls in 4 of 1024 residues are collected; the distinct ones are
+// counted on the host side of the call (sort + unique).  One atomic per wave and step that samples anything; ctr[0] counts
+// every sampled run, also those that no longer fit `cap` (the caller grows the buffer and repeats the batch).
+template <int W>
+__global__ __launch_bounds__(64) void k_k2_estimate_lib(K2LibArgs a, uint64_t *buf, uint64_t cap, unsigned long long *ctr)
+{
+    const uint32_t lane = threadIdx.x;
+    k2_lib_scan<W>(a, [&](bool go, uint64_t m, uint32_t) {
+        const bool take = go && (k2_fmix64(m) & 1023u) < 4u;
+        const unsigned long long mask = __ballot(take);
+        if (!mask) return;
+        unsigned long long at = 0;
+        const int leader = __ffsll((long long)mask) - 1;
+        if ((int)lane == leader) at = atomicAdd(ctr, (unsigned long long)__popcll(mask));
+        at = (unsigned long long)__shfl((long long)at, leader);
+        at += (unsigned long long)__popcll(mask & ((1ull << lane) - 1));
+        if (take && at < cap) buf[at] = m;
+    });
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 extern "C" sh_status sh_k2_default_opts(sh_k2_opts *o)
 {
@@ -719,7 +829,7 @@ static sh_status k2_sync_counts(sh_k2_db *db, hipStream_t s)
     SH_HIP(hipMemcpyAsync(c, db->d_ctr, 16, hipMemcpyDeviceToHost, s));
     SH_HIP(hipStreamSynchronize(s));
     SH_HIP(hipGetLastError());
-    SH_CHECK(c[1] == 0, SH_ERR_OOM, "k2 table of %llu cells is full", (unsigned long long)db->capacity);
+    SH_CHECK(c[1] == 0, SH_ERR_OOM, "k2 table of %llu cells is full: build with a larger --capacity", (unsigned long long)db->capacity);
     db->size = c[0];
     return SH_OK;
 }
@@ -771,6 +881,170 @@ extern "C" sh_status sh_k2_insert_sequence_device(sh_k2_db *db, const uint8_t *d
     sh_status st = k2_sync_counts(db, s);
     if (n_inserted) *n_inserted = r;
     return st;
+}
+
+// ---- library build: host side of the two kernels above -------------------------------------------------------------------
+static uint32_t k2_lib_seg()
+{   // the segment length is a measured choice (scripts/k2_build_speed.py sweeps it through this switch)
+    const char *e = getenv("SCRUBBY_HIP_K2_SEG");
+    const long v = e && *e ? atol(e) : 0;
+    return v >= 64 && v <= (1 << 20) ? (uint32_t)v : K2_LIB_SEG;
+}
+
+// segment counts and their prefix sum in d_seg (n_records + 1 words, caller-owned); everything on stream s, no synchronisation
+static sh_status k2_lib_prepare(K2LibArgs &a, const sh_k2_opts &o, const uint8_t *d_bases, const uint64_t *d_offsets, const uint32_t *d_taxa, uint64_t n_records,
+                                uint64_t *d_seg, void **d_tmp, hipStream_t s)
+{
+    a.bases = d_bases; a.offsets = d_offsets; a.taxa = d_taxa; a.n_records = n_records; a.seg_off = d_seg;
+    a.seg = k2_lib_seg(); a.k = o.k; a.l = o.l; a.spaced = o.spaced_seed_mask; a.toggle = o.toggle_mask; a.min_hash = o.min_acceptable_hash;
+    hipLaunchKernelGGL(k_k2_lib_segcount, dim3((uint32_t)std::min<uint64_t>((n_records + 256) / 256, 4096)), dim3(256), 0, s, a);
+    size_t tmp_bytes = 0;
+    SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_seg, d_seg, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
+    SH_HIP(hipMalloc(d_tmp, std::max<size_t>(tmp_bytes, 1)));
+    SH_HIP(rocprim::exclusive_scan(*d_tmp, tmp_bytes, d_seg, d_seg, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
+    return SH_OK;
+}
+#define K2_LIB_GRID (256 * 32)      // one-wave blocks, grid-stride over the work items (their number stays on the device)
+
+extern "C" sh_status sh_k2_set_min_acceptable_hash(sh_k2_db *db, uint64_t min_acceptable_hash)
+{
+    SH_CHECK(db, SH_ERR_BAD_ARG, "sh_k2_set_min_acceptable_hash: null argument");
+    db->opts.min_acceptable_hash = min_acceptable_hash;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_insert_library_device(sh_k2_db *db, const uint8_t *d_bases, const uint64_t *d_offsets, const uint32_t *d_taxa, uint64_t n_records,
+                                                 void *stream, sh_k2_build_stats *stats)
+{
+    SH_CHECK(db && d_offsets && d_taxa && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_insert_library_device: null argument");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    SH_HIP(hipSetDevice(db->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_records == 0) return k2_sync_counts(db, s);
+    uint64_t *d_seg = nullptr; void *d_tmp = nullptr;
+    SH_HIP(hipMalloc(&d_seg, (n_records + 1) * 8));
+    hipEvent_t e0, e1;
+    SH_HIP(hipEventCreate(&e0)); SH_HIP(hipEventCreate(&e1));
+    unsigned long long *d_runs = db->d_ctr + 2;
+    SH_HIP(hipMemsetAsync(d_runs, 0, 8, s));
+    SH_HIP(hipEventRecord(e0, s));
+    K2LibArgs a{};
+    a.n_nodes = (uint32_t)db->nodes.size();
+    sh_status st = k2_lib_prepare(a, db->opts, d_bases, d_offsets, d_taxa, n_records, d_seg, &d_tmp, s);
+    if (st == SH_OK) {
+        switch (db->opts.k - db->opts.l + 1) {
+        case 1: hipLaunchKernelGGL(k_k2_insert_lib<1>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs); break;
+        case 5: hipLaunchKernelGGL(k_k2_insert_lib<5>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs); break;
+        default: hipLaunchKernelGGL(k_k2_insert_lib<16>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs); break;
+        }
+        hipEventRecord(e1, s);
+        unsigned long long r = 0, n_seg = 0;
+        hipMemcpyAsync(&r, d_runs, 8, hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(&n_seg, d_seg + n_records, 8, hipMemcpyDeviceToHost, s);
+        st = k2_sync_counts(db, s);        // the one synchronisation of the batch
+        if (stats) {
+            stats->n_records = n_records; stats->n_segments = n_seg; stats->n_runs = r; stats->size = db->size;
+            hipEventElapsedTime(&stats->ms, e0, e1);
+        }
+    }
+    hipFree(d_seg); hipFree(d_tmp);
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return st;
+}
+
+struct sh_k2_estimator {
+    int device = 0;
+    sh_k2_opts opts{};
+    uint64_t *d_buf = nullptr, *d_alt = nullptr;      // [0, n_have) distinct and sorted; a batch appends behind them
+    uint64_t cap = 0, n_have = 0;
+    unsigned long long *d_ctr = nullptr;              // [0] appended entries (n_have included), [1] distinct after the batch
+};
+
+extern "C" sh_status sh_k2_estimator_free(sh_k2_estimator *e)
+{
+    if (!e) return SH_OK;
+    hipSetDevice(e->device);
+    hipFree(e->d_buf); hipFree(e->d_alt); hipFree(e->d_ctr);
+    delete e;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_estimator_create(const sh_k2_opts *opts, int device, sh_k2_estimator **out)
+{
+    SH_CHECK(opts && out, SH_ERR_BAD_ARG, "sh_k2_estimator_create: null argument");
+    SH_CHECK(opts->l >= 1 && opts->l <= 31 && opts->k >= opts->l && opts->k - opts->l + 1 <= 16, SH_ERR_BAD_ARG, "sh_k2_estimator_create: unsupported k=%d l=%d", opts->k, opts->l);
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= device) { sh_set_error("no HIP device %d", device); return SH_ERR_NO_DEVICE; }
+    SH_HIP(hipSetDevice(device));
+    sh_k2_estimator *e = new sh_k2_estimator;
+    e->device = device; e->opts = *opts;
+    e->opts.min_acceptable_hash = 0;       // the estimate is of the whole library; --max-db-size is applied to it afterwards
+    if (hipMalloc(&e->d_ctr, 16) != hipSuccess) { delete e; sh_set_error("sh_k2_estimator_create: out of device memory"); return SH_ERR_OOM; }
+    *out = e;
+    return SH_OK;
+}
+
+static sh_status k2_estimator_grow(sh_k2_estimator *e, uint64_t cap, hipStream_t s)
+{
+    uint64_t *nb = nullptr, *na = nullptr;
+    SH_HIP(hipMalloc(&nb, cap * 8));
+    SH_HIP(hipMalloc(&na, cap * 8));
+    if (e->n_have) SH_HIP(hipMemcpyAsync(nb, e->d_buf, e->n_have * 8, hipMemcpyDeviceToDevice, s));
+    SH_HIP(hipStreamSynchronize(s));
+    hipFree(e->d_buf); hipFree(e->d_alt);
+    e->d_buf = nb; e->d_alt = na; e->cap = cap;
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_estimate_capacity_device(sh_k2_estimator *e, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_records, void *stream,
+                                                    uint64_t *n_sampled)
+{
+    SH_CHECK(e && d_offsets && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_estimate_capacity_device: null argument");
+    SH_HIP(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_sampled) *n_sampled = e->n_have;
+    if (n_records == 0) return SH_OK;
+    uint64_t *d_seg = nullptr; void *d_tmp = nullptr, *d_tmp2 = nullptr;
+    SH_HIP(hipMalloc(&d_seg, (n_records + 1) * 8));
+    K2LibArgs a{};
+    sh_status st = k2_lib_prepare(a, e->opts, d_bases, d_offsets, nullptr, n_records, d_seg, &d_tmp, s);
+    auto done = [&](sh_status r) { hipFree(d_seg); hipFree(d_tmp); hipFree(d_tmp2); return r; };
+    if (st != SH_OK) return done(st);
+    if (e->cap < e->n_have + (1u << 16)) { st = k2_estimator_grow(e, e->n_have * 2 + (1u << 20), s); if (st != SH_OK) return done(st); }
+    for (int attempt = 0;; ++attempt) {
+        unsigned long long c0 = e->n_have, total = 0;
+        if (hipMemcpyAsync(e->d_ctr, &c0, 8, hipMemcpyHostToDevice, s) != hipSuccess) { sh_set_error("estimator: copy failed"); return done(SH_ERR_HIP); }
+        switch (e->opts.k - e->opts.l + 1) {
+        case 1: hipLaunchKernelGGL(k_k2_estimate_lib<1>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr); break;
+        case 5: hipLaunchKernelGGL(k_k2_estimate_lib<5>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr); break;
+        default: hipLaunchKernelGGL(k_k2_estimate_lib<16>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr); break;
+        }
+        if (hipMemcpyAsync(&total, e->d_ctr, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+            sh_set_error("estimator: the scan failed"); return done(SH_ERR_HIP);
+        }
+        if (total > e->cap) {           // more sampled runs than the buffer holds: a larger one, and the batch again
+            if (attempt) { sh_set_error("estimator: sample buffer overflow"); return done(SH_ERR_HIP); }
+            st = k2_estimator_grow(e, total + (1u << 16), s);
+            if (st != SH_OK) return done(st);
+            continue;
+        }
+        if (total > e->n_have) {        // sort everything, keep the distinct keys
+            size_t b1 = 0, b2 = 0;
+            if (rocprim::radix_sort_keys(nullptr, b1, e->d_buf, e->d_alt, total, 0, 64, s) != hipSuccess ||
+                rocprim::unique(nullptr, b2, e->d_alt, e->d_buf, e->d_ctr + 1, total, rocprim::equal_to<uint64_t>(), s) != hipSuccess ||
+                hipMalloc(&d_tmp2, std::max<size_t>(std::max(b1, b2), 1)) != hipSuccess) { sh_set_error("estimator: scratch allocation failed"); return done(SH_ERR_OOM); }
+            unsigned long long uniq = 0;
+            if (rocprim::radix_sort_keys(d_tmp2, b1, e->d_buf, e->d_alt, total, 0, 64, s) != hipSuccess ||
+                rocprim::unique(d_tmp2, b2, e->d_alt, e->d_buf, e->d_ctr + 1, total, rocprim::equal_to<uint64_t>(), s) != hipSuccess ||
+                hipMemcpyAsync(&uniq, e->d_ctr + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+                sh_set_error("estimator: sort failed"); return done(SH_ERR_HIP);
+            }
+            e->n_have = uniq;
+        }
+        break;
+    }
+    if (n_sampled) *n_sampled = e->n_have;
+    return done(SH_OK);
 }
 
 extern "C" sh_status sh_k2_info_get(const sh_k2_db *db, sh_k2_info *o)

@@ -1555,3 +1555,255 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     res->ms_index = ms(t0, t1); res->ms_ingest = ms(t1, t2); res->ms_classify = ms(t2, t3); res->ms_write = ms(t3, t4);
     return SH_OK;
 }
+
+// ---- `scrubby-hip k2-build` (DESIGN.md §7 "Database build") --------------------------------------------------------------
+namespace {
+
+struct K2Batch {
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> taxa;
+    void clear() { bases.clear(); off.assign(1, 0); taxa.clear(); }
+};
+struct K2LibCounts { uint64_t n_records = 0, n_skipped = 0, n_bases = 0, n_batches = 0, n_cuts = 0; };
+
+// Streams the records of FASTA files (any container of sh_codec.h) as batches of at most `chunk` bases: host memory is bounded
+// by the chunk, not by the library.  The ChunkReader above cuts at record borders only and grows its buffer for a longer record;
+// a chromosome is one record, so this reader cuts INSIDE a record when the batch is full and starts the next batch with the
+// record's last k - 1 bases under the same taxon: every k-mer across the cut is in the second piece, none is invented, and
+// inserting or sampling a minimizer twice changes nothing.  taxon_of(header) = 0 skips the record (its bases are not kept).
+template <class TaxonOf, class OnBatch>
+sh_status k2_stream_library(const char *const *input, uint32_t n_input, uint64_t chunk, int32_t k, bool keep_bases, TaxonOf taxon_of, OnBatch on_batch,
+                            K2LibCounts &cn)
+{
+    K2Batch b;
+    b.clear();
+    b.bases.reserve(keep_bases ? chunk + 64 : 0);
+    std::vector<char> buf(4u << 20);
+    std::string hdr;
+    uint32_t taxon = 0;
+    uint64_t rec_start = 0;       // where the open record's piece begins in b.bases
+    bool open = false;
+    auto close_rec = [&] {
+        if (open && b.bases.size() > rec_start) { b.off.push_back(b.bases.size()); b.taxa.push_back(taxon); }
+        open = false;
+    };
+    auto flush = [&]() -> sh_status {
+        if (b.taxa.empty()) return SH_OK;
+        ++cn.n_batches;
+        return on_batch(b);
+    };
+    for (uint32_t fi = 0; fi < n_input; ++fi) {
+        shc::In in;
+        SH_CHECK(in.open(input[fi]), SH_ERR_IO, "%s", in.error.c_str());
+        bool line_start = true, in_hdr = false;
+        for (;;) {
+            const long got = in.read(buf.data(), buf.size());
+            SH_CHECK(got >= 0, SH_ERR_IO, "%s: %s", input[fi], in.error.c_str());
+            const char *p = buf.data(), *end = p + got;
+            while (p < end) {
+                const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
+                const char *le = nl ? nl : end;
+                if (line_start && !in_hdr && *p == '>') { close_rec(); in_hdr = true; hdr.clear(); ++p; }
+                else if (line_start && !in_hdr && *p == ';') { in_hdr = true; hdr.assign(1, ';'); }      // an old-style comment line: dropped below
+                if (in_hdr) {
+                    hdr.append(p, le);
+                    if (nl) {
+                        in_hdr = false;
+                        if (hdr.empty() || hdr[0] != ';') {
+                            while (!hdr.empty() && hdr.back() == '\r') hdr.pop_back();
+                            taxon = taxon_of(hdr);
+                            ++cn.n_records;
+                            cn.n_skipped += taxon == 0;
+                            open = taxon != 0 && keep_bases;
+                            rec_start = b.bases.size();
+                        }
+                    }
+                } else if (open) {
+                    const char *q = p;
+                    while (q < le) {
+                        if (b.bases.size() >= chunk) {        // the batch is full: cut the record here
+                            const uint64_t have = b.bases.size() - rec_start, keep = std::min<uint64_t>(have, (uint64_t)(k - 1));
+                            std::vector<uint8_t> tail(b.bases.end() - (ptrdiff_t)keep, b.bases.end());
+                            close_rec();
+                            sh_status st = flush();
+                            if (st != SH_OK) return st;
+                            b.clear();
+                            b.bases.insert(b.bases.end(), tail.begin(), tail.end());
+                            rec_start = 0; open = true; cn.n_cuts += have != 0;
+                        }
+                        size_t n = std::min<size_t>((size_t)(le - q), (size_t)(chunk - b.bases.size()));
+                        while (n && (q[n - 1] == '\r' || q[n - 1] == ' ') && q + n == le) --n, --le;       // CRLF, trailing blanks
+                        b.bases.insert(b.bases.end(), (const uint8_t *)q, (const uint8_t *)q + n);
+                        cn.n_bases += n;
+                        q += n;
+                    }
+                }
+                line_start = nl != nullptr;
+                p = nl ? nl + 1 : end;
+            }
+            if ((size_t)got < buf.size()) break;
+        }
+        if (in_hdr && (hdr.empty() || hdr[0] != ';')) { taxon = taxon_of(hdr); ++cn.n_records; cn.n_skipped += taxon == 0; }      // a header without a newline or bases
+        close_rec();
+        // a batch that is nearly full goes out between files too; otherwise the next file adds to it
+    }
+    close_rec();
+    return flush();
+}
+
+// kraken2-build's construct_seed_template + build_db's two bits per position: l - 2s ones, then s times "01", each doubled
+uint64_t k2_spaced_mask(int32_t l, int32_t spaces)
+{
+    uint64_t m = 0;
+    for (int32_t i = 0; i < l; ++i) {
+        const int32_t from_end = l - 1 - i;
+        const bool one = from_end >= 2 * spaces || (from_end & 1) == 0;
+        m = m << 2 | (one ? 3u : 0u);
+    }
+    return m;
+}
+
+struct K2DevBatch {
+    uint8_t *bases = nullptr; uint64_t *off = nullptr; uint32_t *taxa = nullptr;
+    uint64_t cap_bases = 0, cap_rec = 0;
+    ~K2DevBatch() { hipFree(bases); hipFree(off); hipFree(taxa); }
+    sh_status upload(const K2Batch &b)
+    {
+        const uint64_t nb = b.bases.size(), nr = b.taxa.size();
+        if (nb + 64 > cap_bases) { hipFree(bases); bases = nullptr; cap_bases = nb + 64 + nb / 8; SH_HIP(hipMalloc(&bases, cap_bases)); }
+        if (nr + 1 > cap_rec) {
+            hipFree(off); hipFree(taxa); off = nullptr; taxa = nullptr; cap_rec = (nr + 1) * 2;
+            SH_HIP(hipMalloc(&off, cap_rec * 8)); SH_HIP(hipMalloc(&taxa, cap_rec * 4));
+        }
+        SH_HIP(hipMemcpy(bases, b.bases.data(), nb, hipMemcpyHostToDevice));
+        SH_HIP(hipMemset(bases + nb, 'N', 64));
+        SH_HIP(hipMemcpy(off, b.off.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
+        SH_HIP(hipMemcpy(taxa, b.taxa.data(), nr * 4, hipMemcpyHostToDevice));
+        return SH_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_result *res)
+{
+    SH_CHECK(c && res, SH_ERR_BAD_ARG, "sh_k2_build_run: null argument");
+    SH_CHECK(c->input && c->n_input >= 1 && c->output_dir, SH_ERR_BAD_ARG, "k2-build: library files (-i) and an output directory (-o) are required");
+    for (uint32_t i = 0; i < c->n_input; ++i) SH_CHECK(c->input[i], SH_ERR_BAD_ARG, "k2-build: input %u missing", i);
+    SH_CHECK((c->taxonomy_dir != nullptr) != (c->taxid != 0), SH_ERR_BAD_ARG, "k2-build: either a taxonomy directory (with an id map or kraken:taxid headers) or --taxid");
+    memset(res, 0, sizeof(*res));
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto sec = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t_begin = now();
+    sh_k2_opts opts;
+    sh_k2_default_opts(&opts);
+    if (c->k > 0) opts.k = c->k;
+    if (c->l > 0) opts.l = c->l;
+    SH_CHECK(opts.l >= 1 && opts.l <= 31 && opts.k >= opts.l && opts.k - opts.l + 1 <= 16, SH_ERR_BAD_ARG, "k2-build: unsupported k=%d l=%d", opts.k, opts.l);
+    const int32_t spaces = c->minimizer_spaces == 0 ? 7 : std::max(c->minimizer_spaces, 0);
+    SH_CHECK(spaces <= opts.l / 4, SH_ERR_BAD_ARG, "k2-build: at most l / 4 = %d minimizer spaces", opts.l / 4);
+    opts.spaced_seed_mask = k2_spaced_mask(opts.l, spaces);
+    const uint64_t chunk = std::max<uint64_t>(c->chunk_bytes ? c->chunk_bytes : env_mb("SCRUBBY_HIP_K2_BUILD_CHUNK_MB", 256ull << 20), (uint64_t)(4 * opts.k));
+    SH_CHECK(chunk < (1ull << 31), SH_ERR_BAD_ARG, "k2-build: batches of at most 2 GiB");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= c->device) { sh_set_error("no HIP device %d", c->device); return SH_ERR_NO_DEVICE; }
+    SH_HIP(hipSetDevice(c->device));
+
+    K2DevBatch dev;
+    double s_gpu = 0;
+    // ---- pass 1 (only when something needs it): the capacity estimate over every record, and the taxids of kraken:taxid headers
+    uint64_t capacity = c->capacity, min_hash = 0;
+    std::vector<uint64_t> header_taxids;
+    const bool estimate = c->capacity == 0;
+    const auto t0 = now();
+    if (estimate || c->taxonomy_dir) {
+        sh_k2_estimator *est = nullptr;
+        if (estimate) { sh_status st = sh_k2_estimator_create(&opts, c->device, &est); if (st != SH_OK) return st; }
+        struct EG { sh_k2_estimator *e; ~EG() { sh_k2_estimator_free(e); } } eg{est};
+        std::unordered_set<uint64_t> seen;
+        K2LibCounts cn;
+        sh_status st = k2_stream_library(c->input, c->n_input, chunk, opts.k, estimate,
+            [&](const std::string &h) -> uint32_t {
+                if (c->taxonomy_dir)
+                    for (size_t p = 0; p <= h.size();) {        // each \x01-separated piece: its id is its first token
+                        size_t e = h.find('\x01', p); if (e == std::string::npos) e = h.size();
+                        const char *id; uint32_t il; uint64_t t;
+                        if (id_of(h.data() + p, (uint32_t)(e - p), &id, &il) && shi_k2_header_taxid(id, il, &t) && seen.insert(t).second) header_taxids.push_back(t);
+                        p = e + 1;
+                    }
+                return 1;
+            },
+            [&](const K2Batch &b) -> sh_status {
+                sh_status u = dev.upload(b);
+                if (u != SH_OK) return u;
+                const auto g0 = now();
+                u = sh_k2_estimate_capacity_device(est, dev.bases, dev.off, b.taxa.size(), nullptr, &res->n_sampled);
+                s_gpu += sec(g0, now());
+                return u;
+            }, cn);
+        if (st != SH_OK) return st;
+        if (estimate) {
+            st = sh_k2_capacity_plan(res->n_sampled, c->load_factor, c->max_db_size, &res->estimate, &capacity, &min_hash);
+            if (st != SH_OK) return st;
+        }
+    }
+    if (!estimate) { sh_status st = sh_k2_max_db_size(c->capacity, c->max_db_size, &capacity, &min_hash); if (st != SH_OK) return st; }
+    const auto t1 = now();
+    res->s_estimate = sec(t0, t1);
+    double s_read = res->s_estimate - s_gpu;
+
+    // ---- taxonomy (host)
+    sh_k2_taxonomy *tax = nullptr;
+    sh_status st;
+    if (c->taxonomy_dir) {
+        const std::string d = c->taxonomy_dir;
+        st = sh_k2_taxonomy_from_ncbi((d + "/nodes.dmp").c_str(), (d + "/names.dmp").c_str(), c->seqid2taxid, header_taxids.data(), header_taxids.size(), c->value_bits, &tax);
+    } else st = sh_k2_taxonomy_single(c->taxid, c->name, c->rank, c->value_bits, &tax);
+    if (st != SH_OK) return st;
+    struct TG { sh_k2_taxonomy *t; ~TG() { sh_k2_taxonomy_free(t); } } tg{tax};
+    sh_k2_taxonomy_info ti;
+    sh_k2_taxonomy_info_get(tax, &ti);
+    std::vector<sh_k2_taxnode> nodes(ti.n_nodes);
+    std::string names(ti.names_len, '\0'), ranks(ti.ranks_len, '\0');
+    sh_k2_taxonomy_copy(tax, nodes.data(), &names[0], &ranks[0]);
+    opts.value_bits = ti.value_bits;
+    const auto t2 = now();
+    res->s_taxonomy = sec(t1, t2);
+
+    // ---- pass 2: fill
+    sh_k2_db *db = nullptr;
+    st = sh_k2_create(&opts, capacity, nodes.data(), nodes.size(), names.data(), names.size(), ranks.data(), ranks.size(), c->device, &db);
+    if (st != SH_OK) return st;
+    struct DbGuard { sh_k2_db *d; ~DbGuard() { sh_k2_free(d); } } guard{db};
+    sh_k2_set_min_acceptable_hash(db, min_hash);
+    K2LibCounts cn;
+    s_gpu = 0;
+    st = k2_stream_library(c->input, c->n_input, chunk, opts.k, true,
+        [&](const std::string &h) -> uint32_t { uint32_t t = 0; sh_k2_taxonomy_header_taxon(tax, h.data(), h.size(), &t); return t; },
+        [&](const K2Batch &b) -> sh_status {
+            sh_status u = dev.upload(b);
+            if (u != SH_OK) return u;
+            const auto g0 = now();
+            sh_k2_build_stats bs;
+            u = sh_k2_insert_library_device(db, dev.bases, dev.off, dev.taxa, b.taxa.size(), nullptr, &bs);
+            s_gpu += sec(g0, now());
+            res->n_runs += bs.n_runs;
+            return u;
+        }, cn);
+    if (st != SH_OK) return st;
+    const auto t3 = now();
+    res->s_fill = sec(t2, t3);
+    s_read += res->s_fill - s_gpu;
+
+    shi_mkdir_p(c->output_dir);
+    st = sh_k2_save(db, c->output_dir);
+    if (st != SH_OK) return st;
+    const auto t4 = now();
+    sh_k2_info info;
+    sh_k2_info_get(db, &info);
+    res->n_records = cn.n_records; res->n_skipped = cn.n_skipped; res->n_bases = cn.n_bases; res->n_batches = cn.n_batches; res->n_cuts = cn.n_cuts;
+    res->size = info.size; res->capacity = capacity; res->n_nodes = ti.n_nodes; res->min_acceptable_hash = min_hash; res->value_bits = ti.value_bits;
+    res->s_save = sec(t3, t4); res->s_read = s_read; res->s_total = sec(t_begin, t4);
+    return SH_OK;
+}

@@ -41,6 +41,30 @@ class KrakenConfig(C.Structure):
                 ("min_base_quality", C.c_int32), ("quick", C.c_int32)]
 
 
+class K2TaxonomyInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint64), ("names_len", C.c_uint64), ("ranks_len", C.c_uint64), ("value_bits", C.c_int32), ("pad", C.c_int32),
+                ("n_map_entries", C.c_uint64), ("n_missing_taxa", C.c_uint64)]
+
+
+class K2BuildStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_segments", C.c_uint64), ("n_runs", C.c_uint64), ("size", C.c_uint64), ("ms", C.c_float)]
+
+
+class K2BuildConfig(C.Structure):
+    _fields_ = [("input", C.POINTER(C.c_char_p)), ("n_input", C.c_uint32), ("taxonomy_dir", C.c_char_p), ("seqid2taxid", C.c_char_p),
+                ("taxid", C.c_uint64), ("name", C.c_char_p), ("rank", C.c_char_p), ("output_dir", C.c_char_p),
+                ("k", C.c_int32), ("l", C.c_int32), ("minimizer_spaces", C.c_int32), ("value_bits", C.c_int32),
+                ("capacity", C.c_uint64), ("load_factor", C.c_double), ("max_db_size", C.c_uint64), ("chunk_bytes", C.c_uint64),
+                ("device", C.c_int32), ("pad", C.c_int32)]
+
+
+class K2BuildResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_skipped", "n_bases", "n_batches", "n_cuts", "n_runs", "size", "capacity", "n_nodes",
+                                           "n_sampled", "estimate", "min_acceptable_hash")] + \
+               [("value_bits", C.c_int32), ("pad", C.c_int32)] + \
+               [(n, C.c_double) for n in ("s_taxonomy", "s_estimate", "s_fill", "s_save", "s_read", "s_total")]
+
+
 RESULT_DTYPE = np.dtype([("taxid", "<u4"), ("call", "<u4"), ("total_kmers", "<u4"), ("hit_groups", "<u4")])
 # one hit-list entry: internal taxid (0 = not in the table / not looked up), HIT_AMBIGUOUS or HIT_BORDER, and its k-mer count
 HIT_DTYPE = np.dtype([("code", "<u4"), ("count", "<u4")])
@@ -102,6 +126,128 @@ def make_taxonomy(parents, externals, names, ranks):
     return nodes, bytes(name_pool), bytes(rank_pool)
 
 
+class Taxonomy:
+    """An NCBI taxonomy reduced to the taxa a library uses, in taxo.k2d's layout (sh_k2_taxonomy_*; host only, no GPU needed)."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def info(self):
+        i = K2TaxonomyInfo()
+        S.check(S.load().sh_k2_taxonomy_info_get(self.h, C.byref(i)))
+        return {n: getattr(i, n) for n, _ in K2TaxonomyInfo._fields_ if n != "pad"}
+
+    def arrays(self):
+        """(nodes, names, ranks): a K2TaxNode array and the two string pools"""
+        i = self.info()
+        nodes = (K2TaxNode * i["n_nodes"])()
+        names, ranks = C.create_string_buffer(max(i["names_len"], 1)), C.create_string_buffer(max(i["ranks_len"], 1))
+        S.check(S.load().sh_k2_taxonomy_copy(self.h, nodes, names, ranks))
+        return nodes, names.raw[: i["names_len"]], ranks.raw[: i["ranks_len"]]
+
+    def internal(self, external_id):
+        r = C.c_uint32()
+        S.check(S.load().sh_k2_taxonomy_internal(self.h, C.c_uint64(external_id), C.byref(r)))
+        return r.value
+
+    def header_taxon(self, header):
+        """internal taxon of the record with this FASTA header (without '>'); 0 = the record is skipped"""
+        hb = header if isinstance(header, bytes) else header.encode()
+        r = C.c_uint32()
+        S.check(S.load().sh_k2_taxonomy_header_taxon(self.h, hb, C.c_uint64(len(hb)), C.byref(r)))
+        return r.value
+
+    def close(self):
+        if self.h:
+            S.load().sh_k2_taxonomy_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def taxonomy_from_ncbi(nodes_dmp, names_dmp, seqid2taxid=None, extra_taxids=(), value_bits=0):
+    ex = (C.c_uint64 * max(len(extra_taxids), 1))(*extra_taxids)
+    h = C.c_void_p()
+    S.check(S.load().sh_k2_taxonomy_from_ncbi(str(nodes_dmp).encode(), str(names_dmp).encode(), str(seqid2taxid).encode() if seqid2taxid else None,
+                                              ex, C.c_uint64(len(extra_taxids)), value_bits, C.byref(h)))
+    return Taxonomy(h)
+
+
+def taxonomy_single(taxid, name=None, rank=None, value_bits=0):
+    h = C.c_void_p()
+    S.check(S.load().sh_k2_taxonomy_single(C.c_uint64(taxid), name.encode() if name else None, rank.encode() if rank else None, value_bits, C.byref(h)))
+    return Taxonomy(h)
+
+
+def capacity_plan(n_sampled, load_factor=0.7, max_db_size=0):
+    """(estimate, capacity, min_acceptable_hash) from the estimator's distinct sample count"""
+    e, c, m = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    S.check(S.load().sh_k2_capacity_plan(C.c_uint64(n_sampled), C.c_double(load_factor), C.c_uint64(max_db_size), C.byref(e), C.byref(c), C.byref(m)))
+    return e.value, c.value, m.value
+
+
+def max_db_size(needed_capacity, max_bytes):
+    """kraken2-build --max-db-size on a known capacity: (capacity, min_acceptable_hash)"""
+    c, m = C.c_uint64(), C.c_uint64()
+    S.check(S.load().sh_k2_max_db_size(C.c_uint64(needed_capacity), C.c_uint64(max_bytes), C.byref(c), C.byref(m)))
+    return c.value, m.value
+
+
+def _library_to_device(records):
+    """records: byte strings / uint8 arrays -> (d_bases with 64 bytes of padding, d_offsets, n_records) as torch tensors"""
+    import torch
+    arrs = [np.frombuffer(bytes(r), dtype=np.uint8) if not isinstance(r, np.ndarray) else r for r in records]
+    off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    if arrs:
+        off[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+    flat = np.concatenate(arrs + [np.full(64, ord("N"), np.uint8)])
+    return torch.from_numpy(flat).cuda(), torch.from_numpy(off.view(np.int64)).cuda(), len(arrs)
+
+
+def estimate_capacity(records, opts=None, batches=1, load_factor=0.7, max_db_size=0, device=0):
+    """Kraken 2's capacity estimate of a library given as a list of sequences, fed to one estimator in `batches` calls:
+    dict with n_sampled, estimate, capacity, min_acceptable_hash."""
+    S.require_gpu()
+    L = S.load()
+    o = opts if opts is not None else default_opts()
+    h = C.c_void_p()
+    S.check(L.sh_k2_estimator_create(C.byref(o), device, C.byref(h)))
+    try:
+        n = C.c_uint64()
+        step = max((len(records) + batches - 1) // batches, 1)
+        for b in range(0, len(records), step):
+            d_bases, d_off, nr = _library_to_device(records[b: b + step])
+            S.check(L.sh_k2_estimate_capacity_device(h, C.c_void_p(d_bases.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_uint64(nr), None, C.byref(n)))
+    finally:
+        L.sh_k2_estimator_free(h)
+    est, cap, mh = capacity_plan(n.value, load_factor, max_db_size)
+    return {"n_sampled": n.value, "estimate": est, "capacity": cap, "min_acceptable_hash": mh}
+
+
+def build_database(inputs, output_dir, taxonomy_dir=None, seqid2taxid=None, taxid=0, name=None, rank=None, k=0, l=0, minimizer_spaces=0,
+                   capacity=0, load_factor=0.0, max_db_size=0, value_bits=0, chunk_bytes=0, device=0):
+    """`scrubby-hip k2-build` (sh_k2_build_run): FASTA library files + (taxonomy directory [+ id map] | one taxid) -> a database
+    directory.  minimizer_spaces: 0 = Kraken 2's 7, negative = none.  Returns the result fields as a dict."""
+    S.require_gpu()
+    c = K2BuildConfig()
+    files = [inputs] if isinstance(inputs, (str, bytes)) or hasattr(inputs, "__fspath__") else list(inputs)
+    arr = (C.c_char_p * len(files))(*[str(f).encode() for f in files])
+    c.input, c.n_input = arr, len(files)
+    c.taxonomy_dir = str(taxonomy_dir).encode() if taxonomy_dir else None
+    c.seqid2taxid = str(seqid2taxid).encode() if seqid2taxid else None
+    c.taxid, c.name, c.rank = taxid, name.encode() if name else None, rank.encode() if rank else None
+    c.output_dir = str(output_dir).encode()
+    c.k, c.l, c.minimizer_spaces, c.value_bits = k, l, minimizer_spaces, value_bits
+    c.capacity, c.load_factor, c.max_db_size, c.chunk_bytes, c.device = capacity, load_factor, max_db_size, chunk_bytes, device
+    r = K2BuildResult()
+    S.check(S.load().sh_k2_build_run(C.byref(c), C.byref(r)))
+    return {n: getattr(r, n) for n, _ in K2BuildResult._fields_ if n != "pad"}
+
+
 class K2Db:
     def __init__(self, handle):
         self.h = handle
@@ -138,6 +284,35 @@ class K2Db:
         a = np.frombuffer(bytes(seq), dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
         d = torch.from_numpy(np.concatenate([a, np.full(64, ord("N"), np.uint8)])).cuda()
         return self.insert_sequence_device(d, len(a), taxon)
+
+    @classmethod
+    def create_from_taxonomy(cls, opts, capacity, taxonomy, device=0):
+        """an empty table over a Taxonomy; opts.value_bits is set from it"""
+        S.require_gpu()
+        nodes, npool, rpool = taxonomy.arrays()
+        opts.value_bits = taxonomy.info()["value_bits"]
+        h = C.c_void_p()
+        S.check(S.load().sh_k2_create(C.byref(opts), C.c_uint64(capacity), nodes, C.c_uint64(len(nodes)), npool, C.c_uint64(len(npool)),
+                                      rpool, C.c_uint64(len(rpool)), device, C.byref(h)))
+        return cls(h)
+
+    def set_min_acceptable_hash(self, v):
+        S.check(S.load().sh_k2_set_min_acceptable_hash(self.h, C.c_uint64(v)))
+
+    def insert_library_device(self, d_bases, d_offsets, d_taxa, n_records):
+        """sh_k2_insert_library_device on torch tensors (uint8 bases readable 8 bytes past the end, int64 offsets, int32 taxa)"""
+        st = K2BuildStats()
+        S.check(S.load().sh_k2_insert_library_device(self.h, C.c_void_p(d_bases.data_ptr()), C.c_void_p(d_offsets.data_ptr()),
+                                                     C.c_void_p(d_taxa.data_ptr()), C.c_uint64(n_records), S._stream_ptr(), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in K2BuildStats._fields_}
+
+    def insert_library(self, records, taxa):
+        """One launch over a list of sequences, record i under internal taxon taxa[i] (0 = skip)."""
+        import torch
+        assert len(records) == len(taxa)
+        d_bases, d_off, n = _library_to_device(records)
+        d_taxa = torch.from_numpy(np.ascontiguousarray(taxa, dtype=np.uint32).view(np.int32).copy()).cuda() if n else torch.zeros(1, dtype=torch.int32).cuda()
+        return self.insert_library_device(d_bases, d_off, d_taxa, n)
 
     def insert_random(self, seed, n, taxon_lo, taxon_hi):
         S.check(S.load().sh_k2_insert_random(self.h, C.c_uint64(seed), C.c_uint64(n), C.c_uint32(taxon_lo), C.c_uint32(taxon_hi), None))
