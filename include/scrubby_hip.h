@@ -532,14 +532,57 @@ typedef struct sh_k2_build_config {
     uint64_t    max_db_size;        /* bytes, 0: unlimited */
     uint64_t    chunk_bytes;        /* bases per batch, 0: 256 MiB; a longer record is cut (k - 1 bases repeated) */
     int32_t     device, pad;
+    int32_t     mask_low_complexity;        /* 1: both passes mask every batch on the GPU first (sh_k2_mask_device, masked bases
+                                             * become 'x'); 0: the library is taken as given */
+    int32_t     mask_window, mask_threshold;        /* 0: 64, 20 */
+    int32_t     pad2;
 } sh_k2_build_config;
 typedef struct sh_k2_build_result {
     uint64_t n_records, n_skipped, n_bases, n_batches, n_cuts;
     uint64_t n_runs, size, capacity, n_nodes, n_sampled, estimate, min_acceptable_hash;
     int32_t  value_bits, pad;
     double   s_taxonomy, s_estimate, s_fill, s_save, s_read, s_total;   /* s_read: reading + parsing + upload inside the two passes */
+    uint64_t n_masked_bases;        /* bases of the library the fill pass masked (each once, whatever the cuts) */
+    double   s_mask;                /* the mask calls of both passes (inside s_estimate and s_fill) */
 } sh_k2_build_result;
 sh_status sh_k2_build_run(const sh_k2_build_config *cfg, sh_k2_build_result *out);
+
+/* ---- low-complexity masking before the build (DESIGN.md §7 "Low-complexity masking"): kraken2-build's k2mask / dustmasker step.
+ * Symmetric DUST as recalled (Morgulis et al. 2006), in integers: PARITY WITH k2mask UNPINNED, like the rest of the section.
+ * Inside a maximal run of ACGTacgt (any other byte and a record border end it), an interval of triplets [i, j], i < j, of at most
+ * window - 2 triplets has the score r / l, r = sum over triplet codes of c (c - 1) / 2, l = j - i; it is perfect when
+ * 10 r > threshold * l and no interval inside it scores strictly higher; the bases of every perfect interval are masked. */
+typedef struct sh_k2_mask_stats {
+    uint64_t n_bases, n_masked;
+    uint64_t n_items;               /* (record, tile) work items of the launch */
+    float    ms;
+    int32_t  pad;
+} sh_k2_mask_stats;
+/* Masks a batch in HBM in place: record r = d_bases[d_offsets[r], d_offsets[r + 1]).  window 0 = 64 (allowed: 8 .. 64),
+ * threshold 0 = 20 (>= 1).  replacement = the byte masked bases become ('x' is what kraken2-build uses: not a nucleotide, so the
+ * minimizer scan restarts behind it), or 0 = soft masking (lower case).  d_bases must be readable up to the 8-byte boundary
+ * behind its last base, as for sh_k2_insert_library_device.  One synchronisation per call. */
+sh_status sh_k2_mask_device(uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_records, int32_t window, int32_t threshold,
+                            int32_t replacement, void *stream, sh_k2_mask_stats *stats);
+/* The same result on the CPU (no GPU), written as the streaming sdust programme is: the mirror the tests call; the GPU paths
+ * never do.  stats may be NULL (ms = 0, n_items = 0). */
+sh_status sh_k2_mask_host(uint8_t *bases, const uint64_t *offsets, uint64_t n_records, int32_t window, int32_t threshold,
+                          int32_t replacement, sh_k2_mask_stats *stats);
+/* `scrubby-hip k2-mask`: FASTA in (plain, gzip, bzip2, xz), masked FASTA out (container by extension), headers untouched */
+typedef struct sh_k2_mask_config {
+    const char *input, *output;
+    int32_t     window, threshold;  /* 0: 64, 20 */
+    int32_t     replacement;        /* 0: 'x' */
+    int32_t     soft;               /* 1: lower case instead of the replacement byte */
+    int32_t     line_width;         /* bases per output line (the CLI's default is 60); 0: a record's sequence on one line */
+    int32_t     device;
+    uint64_t    chunk_bytes;        /* bases per batch, 0: 256 MiB; the output does not depend on it */
+} sh_k2_mask_config;
+typedef struct sh_k2_mask_result {
+    uint64_t n_records, n_bases, n_masked_bases, n_batches, n_cuts;
+    double   s_mask, s_total;
+} sh_k2_mask_result;
+sh_status sh_k2_mask_run(const sh_k2_mask_config *cfg, sh_k2_mask_result *out);
 
 /* ---- multi-GPU: the one exchange of the read-sharded path (HashSet union of cleaner.rs:564-570) --------------
  * d_flags[n] (1 = host) -> d_bits[(n + 7) / 8], bit i of byte j = record 8j + i; each rank packs its own slice and the disjoint

@@ -19,7 +19,10 @@ static void usage()
             "                  [-e] [--json report.json] [-r read_ids.tsv]\n"
             "scrubby-hip k2-build -i <library.fna[.gz]>.. -o <db dir> (-n <taxonomy dir> [-m <seqid2taxid.map>] | --taxid N [--name S] [--rank S])\n"
             "                  [--kmer-len 35] [--minimizer-len 31] [--minimizer-spaces 7] [--capacity N] [--load-factor 0.7]\n"
-            "                  [--max-db-size BYTES] [--value-bits N] [--chunk-bytes N]\n");
+            "                  [--max-db-size BYTES] [--value-bits N] [--chunk-bytes N]\n"
+            "                  [--mask-low-complexity [--mask-window 64] [--mask-threshold 20]]\n"
+            "scrubby-hip k2-mask -i <in.fa[.gz|.bz2|.xz]> -o <out.fa[.gz|.bz2|.xz]> [-W 64] [-T 20] [-r x | --soft] [--line-width 60]\n"
+            "                  [--chunk-bytes N]\n");
 }
 
 // `scrubby classifier` (/root/reference/src/terminal.rs:204-279): clean reads from precomputed Kraken2 / Metabuli outputs
@@ -89,6 +92,9 @@ static int main_k2_build(int argc, char **argv)
         else if (a == "--max-db-size") c.max_db_size = strtoull(val().c_str(), nullptr, 10);
         else if (a == "--value-bits") c.value_bits = atoi(val().c_str());
         else if (a == "--chunk-bytes") c.chunk_bytes = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "--mask-low-complexity") c.mask_low_complexity = 1;
+        else if (a == "--mask-window") c.mask_window = atoi(val().c_str());
+        else if (a == "--mask-threshold") c.mask_threshold = atoi(val().c_str());
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
     }
     if (in.empty() || out.empty()) { fprintf(stderr, "error: library files (-i) and an output directory (-o) are required\n"); return 2; }
@@ -103,11 +109,44 @@ static int main_k2_build(int argc, char **argv)
     if (st != SH_OK) { fprintf(stderr, "error (%d): %s\n", st, sh_last_error()); return 1; }
     printf("{\"records\": %llu, \"records_skipped\": %llu, \"bases\": %llu, \"batches\": %llu, \"cuts\": %llu, \"runs_inserted\": %llu, \"size\": %llu, "
            "\"capacity\": %llu, \"nodes\": %llu, \"value_bits\": %d, \"n_sampled\": %llu, \"estimate\": %llu, \"min_acceptable_hash\": %llu, "
-           "\"s_estimate\": %.3f, \"s_taxonomy\": %.3f, \"s_fill\": %.3f, \"s_save\": %.3f, \"s_read\": %.3f, \"s_total\": %.3f}\n",
+           "\"s_estimate\": %.3f, \"s_taxonomy\": %.3f, \"s_fill\": %.3f, \"s_save\": %.3f, \"s_read\": %.3f, \"s_total\": %.3f",
            (unsigned long long)r.n_records, (unsigned long long)r.n_skipped, (unsigned long long)r.n_bases, (unsigned long long)r.n_batches,
            (unsigned long long)r.n_cuts, (unsigned long long)r.n_runs, (unsigned long long)r.size, (unsigned long long)r.capacity, (unsigned long long)r.n_nodes,
            r.value_bits, (unsigned long long)r.n_sampled, (unsigned long long)r.estimate, (unsigned long long)r.min_acceptable_hash, r.s_estimate, r.s_taxonomy,
            r.s_fill, r.s_save, r.s_read, r.s_total);
+    if (c.mask_low_complexity) printf(", \"masked_bases\": %llu, \"s_mask\": %.3f", (unsigned long long)r.n_masked_bases, r.s_mask);      // only with the flag
+    printf("}\n");
+    return 0;
+}
+
+// `scrubby-hip k2-mask`: the masking step of a build on its own, FASTA to FASTA (what running k2mask by hand gives kraken2-build)
+static int main_k2_mask(int argc, char **argv)
+{
+    std::string in, out;
+    sh_k2_mask_config c{};
+    c.line_width = 60;
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
+        if (a == "-i" || a == "--input") in = val();
+        else if (a == "-o" || a == "--output") out = val();
+        else if (a == "-W" || a == "--window") c.window = atoi(val().c_str());
+        else if (a == "-T" || a == "--threshold") c.threshold = atoi(val().c_str());
+        else if (a == "-r" || a == "--replacement") { const std::string v = val(); if (v.size() != 1) { fprintf(stderr, "error: -r takes one character\n"); return 2; } c.replacement = (unsigned char)v[0]; }
+        else if (a == "--soft") c.soft = 1;
+        else if (a == "--line-width") c.line_width = atoi(val().c_str());
+        else if (a == "--chunk-bytes") c.chunk_bytes = strtoull(val().c_str(), nullptr, 10);
+        else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+    }
+    if (in.empty() || out.empty()) { fprintf(stderr, "error: an input (-i) and an output (-o) FASTA file are required\n"); return 2; }
+    if (c.soft && c.replacement) { fprintf(stderr, "error: either -r or --soft\n"); return 2; }
+    c.input = in.c_str(); c.output = out.c_str();
+    sh_k2_mask_result r{};
+    sh_status st = sh_k2_mask_run(&c, &r);
+    if (st != SH_OK) { fprintf(stderr, "error (%d): %s\n", st, sh_last_error()); return 1; }
+    printf("{\"records\": %llu, \"bases\": %llu, \"masked_bases\": %llu, \"batches\": %llu, \"cuts\": %llu, \"s_mask\": %.3f, \"s_total\": %.3f}\n",
+           (unsigned long long)r.n_records, (unsigned long long)r.n_bases, (unsigned long long)r.n_masked_bases, (unsigned long long)r.n_batches,
+           (unsigned long long)r.n_cuts, r.s_mask, r.s_total);
     return 0;
 }
 
@@ -151,6 +190,7 @@ static int main_alignment(int argc, char **argv, const std::string &command)
 int main(int argc, char **argv)
 {
     if (argc >= 2 && std::string(argv[1]) == "k2-build") return main_k2_build(argc, argv);
+    if (argc >= 2 && std::string(argv[1]) == "k2-mask") return main_k2_mask(argc, argv);
     if (argc >= 2 && (std::string(argv[1]) == "classifier" || std::string(argv[1]) == "alignment")) {
         std::string command;
         for (int i = 0; i < argc; ++i) { if (i) command += ' '; command += argv[i]; }

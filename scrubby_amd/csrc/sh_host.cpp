@@ -12,6 +12,7 @@
 // a corrupt FASTQ is an error instead of a logged partial id set.
 #include "sh_common.h"
 #include "sh_host.h"
+#include "sh_k2_mask.h"
 #include <zlib.h>
 #include <sys/stat.h>
 #include <chrono>
@@ -1125,4 +1126,118 @@ extern "C" sh_status sh_k2_capacity_plan(uint64_t n_sampled, double load_factor,
     if (estimate) *estimate = est;
     const uint64_t needed = std::max<uint64_t>((uint64_t)ceil((double)est / (load_factor > 0 ? load_factor : 0.7)), 1);
     return sh_k2_max_db_size(needed, max_db_size, capacity, min_hash);
+}
+
+// ---- low-complexity masking, host mirror (DESIGN.md §7 "Low-complexity masking") -------------------------------------------------
+// Symmetric DUST in the shape of the published streaming programme: a sliding window of at most W - 2 triplets, the triplet
+// counts of the whole window (cw) and of its longest suffix in which no count exceeds 2 T / 10 (cv, L triplets: no interval
+// inside that suffix can score above T / 10, so starts inside it are never tried), and the list of the window's perfect
+// intervals, ordered by start from high to low; an interval is written out when its start leaves the window.  The device path
+// (sh_k2_mask.hip) keeps one lane per start instead and shares nothing with this.
+namespace {
+
+struct K2DustInterval { int64_t start, finish; int32_t r, l; };       // triplets [start, ..], bases [start, finish) of the run
+
+struct K2Dust {
+    int32_t W, T;
+    std::vector<int32_t> w;          // the window's triplets; head = index of the oldest
+    size_t head = 0;
+    int64_t ws = 0;                  // run position of the oldest triplet in the window
+    int32_t cw[64], cv[64], rw = 0, rv = 0, L = 0;
+    std::vector<K2DustInterval> P;
+    uint8_t *mark = nullptr;         // one byte per base of the run
+
+    size_t size() const { return w.size() - head; }
+    int32_t at(size_t i) const { return w[head + i]; }
+    void begin(uint8_t *m) { w.clear(); head = 0; ws = 0; memset(cw, 0, sizeof cw); memset(cv, 0, sizeof cv); rw = rv = L = 0; P.clear(); mark = m; }
+    void emit(const K2DustInterval &p) { memset(mark + p.start, 1, (size_t)(p.finish - p.start)); }
+    void leave(int64_t new_ws)
+    {   // the longest of the intervals that start lowest stands for all that leave with it
+        if (P.empty() || P.back().start >= new_ws) return;
+        emit(P.back());
+        while (!P.empty() && P.back().start < new_ws) P.pop_back();
+    }
+    void shift(int32_t t)
+    {
+        if ((int32_t)size() >= W - 2) {
+            const int32_t s = at(0);
+            ++head; ++ws;
+            rw -= --cw[s];
+            if (L > (int32_t)size()) { --L; rv -= --cv[s]; }
+            if (head >= 4096) { w.erase(w.begin(), w.begin() + (ptrdiff_t)head); head = 0; }
+        }
+        w.push_back(t);
+        ++L;
+        rw += cw[t]++;
+        rv += cv[t]++;
+        if (cv[t] * 10 > 2 * T) {
+            int32_t s;
+            do { s = at(size() - (size_t)L); rv -= --cv[s]; --L; } while (s != t);
+        }
+    }
+    void find_perfect()
+    {
+        int32_t c[64], r = rv, max_r = 0, max_l = 0;
+        memcpy(c, cv, sizeof c);
+        for (int64_t i = (int64_t)size() - L - 1; i >= 0; --i) {
+            const int32_t t = at((size_t)i);
+            r += c[t]++;
+            const int32_t new_r = r, new_l = (int32_t)((int64_t)size() - i - 1);
+            if (new_r * 10 <= T * new_l) continue;
+            size_t j = 0;
+            for (; j < P.size() && P[j].start >= ws + i; ++j)      // the perfect intervals inside [i, end]: their best score
+                if (max_r == 0 || P[j].r * max_l > max_r * P[j].l) { max_r = P[j].r; max_l = P[j].l; }
+            if (max_r == 0 || new_r * max_l >= max_r * new_l) {
+                max_r = new_r; max_l = new_l;
+                P.insert(P.begin() + (ptrdiff_t)j, K2DustInterval{ws + i, ws + (int64_t)size() - 1 + 3, new_r, new_l});
+            }
+        }
+    }
+    void push(int32_t t)
+    {
+        leave((int32_t)size() >= W - 2 ? ws + 1 : ws);
+        shift(t);
+        if ((int32_t)size() - L >= 1) find_perfect();
+    }
+    void end() { for (const K2DustInterval &p : P) emit(p); P.clear(); }
+};
+
+}  // namespace
+
+extern "C" sh_status sh_k2_mask_host(uint8_t *bases, const uint64_t *offsets, uint64_t n_records, int32_t window, int32_t threshold, int32_t replacement,
+                                     sh_k2_mask_stats *stats)
+{
+    SH_CHECK(offsets && (bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_mask_host: null argument");
+    sh_status st = shi_k2_mask_params(&window, &threshold, replacement, "sh_k2_mask_host");
+    if (st != SH_OK) return st;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    K2Dust D; D.W = window; D.T = threshold;
+    std::vector<uint8_t> mark;
+    uint64_t n_masked = 0;
+    for (uint64_t r = 0; r < n_records; ++r) {
+        SH_CHECK(offsets[r + 1] >= offsets[r], SH_ERR_BAD_ARG, "sh_k2_mask_host: offsets decrease");
+        uint8_t *seq = bases + offsets[r];
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        for (uint64_t i = 0; i < len;) {
+            if (sh_nt4(seq[i]) > 3) { ++i; continue; }
+            uint64_t e = i;
+            while (e < len && sh_nt4(seq[e]) <= 3) ++e;
+            const uint64_t n = e - i;                       // one run of nucleotides
+            if (n >= 4) {
+                mark.assign(n, 0);
+                D.begin(mark.data());
+                int32_t t = 0;
+                for (uint64_t p = 0; p < n; ++p) {
+                    t = (int32_t)(((uint32_t)t << 2 | sh_nt4(seq[i + p])) & 63u);
+                    if (p >= 2) D.push(t);
+                }
+                D.end();
+                for (uint64_t p = 0; p < n; ++p)
+                    if (mark[p]) { seq[i + p] = replacement ? (uint8_t)replacement : (uint8_t)(seq[i + p] | 0x20u); ++n_masked; }
+            }
+            i = e;
+        }
+    }
+    if (stats) { stats->n_bases = n_records ? offsets[n_records] - offsets[0] : 0; stats->n_masked = n_masked; }
+    return SH_OK;
 }

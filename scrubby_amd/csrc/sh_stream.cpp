@@ -20,6 +20,7 @@
 // An empty input file (App. C Q6: warning, output not created, counts from whatever the output path holds) is the one
 // case handed to the collect-then-map form in sh_host.cpp.
 #include "sh_host.h"
+#include "sh_k2_mask.h"
 #include <zlib.h>
 #include "sh_codec.h"
 #include <fcntl.h>
@@ -1563,7 +1564,8 @@ struct K2Batch {
     std::vector<uint8_t> bases;
     std::vector<uint64_t> off;
     std::vector<uint32_t> taxa;
-    void clear() { bases.clear(); off.assign(1, 0); taxa.clear(); }
+    bool head_cont = false, tail_cut = false;     // the first record continues a record cut in the batch before; the last one is cut
+    void clear() { bases.clear(); off.assign(1, 0); taxa.clear(); head_cont = tail_cut = false; }
 };
 struct K2LibCounts { uint64_t n_records = 0, n_skipped = 0, n_bases = 0, n_batches = 0, n_cuts = 0; };
 
@@ -1572,9 +1574,12 @@ struct K2LibCounts { uint64_t n_records = 0, n_skipped = 0, n_bases = 0, n_batch
 // a chromosome is one record, so this reader cuts INSIDE a record when the batch is full and starts the next batch with the
 // record's last k - 1 bases under the same taxon: every k-mer across the cut is in the second piece, none is invented, and
 // inserting or sampling a minimizer twice changes nothing.  taxon_of(header) = 0 skips the record (its bases are not kept).
+// `context` > 0 (low-complexity masking): the next piece repeats k - 1 + context bases, so that after masking both pieces can give
+// up the margin next to the cut whose mask lacked its context (DESIGN.md §7 "Low-complexity masking": the cut).  Both pieces must
+// then be at least that long: a record that has fewer bases in a full batch is not cut, it moves to the next batch whole.
 template <class TaxonOf, class OnBatch>
 sh_status k2_stream_library(const char *const *input, uint32_t n_input, uint64_t chunk, int32_t k, bool keep_bases, TaxonOf taxon_of, OnBatch on_batch,
-                            K2LibCounts &cn)
+                            K2LibCounts &cn, uint64_t context = 0)
 {
     K2Batch b;
     b.clear();
@@ -1623,14 +1628,19 @@ sh_status k2_stream_library(const char *const *input, uint32_t n_input, uint64_t
                     const char *q = p;
                     while (q < le) {
                         if (b.bases.size() >= chunk) {        // the batch is full: cut the record here
-                            const uint64_t have = b.bases.size() - rec_start, keep = std::min<uint64_t>(have, (uint64_t)(k - 1));
+                            const uint64_t have = b.bases.size() - rec_start;
+                            const bool move = context && rec_start > 0 && have < (uint64_t)(k - 1) + context;
+                            const uint64_t keep = move ? have : std::min<uint64_t>(have, (uint64_t)(k - 1) + context);
                             std::vector<uint8_t> tail(b.bases.end() - (ptrdiff_t)keep, b.bases.end());
+                            if (move) b.bases.resize(rec_start);
                             close_rec();
+                            b.tail_cut = context && !move && have != 0;
                             sh_status st = flush();
                             if (st != SH_OK) return st;
                             b.clear();
                             b.bases.insert(b.bases.end(), tail.begin(), tail.end());
-                            rec_start = 0; open = true; cn.n_cuts += have != 0;
+                            b.head_cont = context && !move && have != 0;
+                            rec_start = 0; open = true; cn.n_cuts += have != 0 && !move;
                         }
                         size_t n = std::min<size_t>((size_t)(le - q), (size_t)(chunk - b.bases.size()));
                         while (n && (q[n - 1] == '\r' || q[n - 1] == ' ') && q + n == le) --n, --le;       // CRLF, trailing blanks
@@ -1706,6 +1716,33 @@ extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_re
     opts.spaced_seed_mask = k2_spaced_mask(opts.l, spaces);
     const uint64_t chunk = std::max<uint64_t>(c->chunk_bytes ? c->chunk_bytes : env_mb("SCRUBBY_HIP_K2_BUILD_CHUNK_MB", 256ull << 20), (uint64_t)(4 * opts.k));
     SH_CHECK(chunk < (1ull << 31), SH_ERR_BAD_ARG, "k2-build: batches of at most 2 GiB");
+    // low-complexity masking (off: the library is taken as given, byte for byte what it was)
+    const bool masking = c->mask_low_complexity != 0;
+    int32_t mask_w = c->mask_window, mask_t = c->mask_threshold;
+    if (masking) { sh_status ms = shi_k2_mask_params(&mask_w, &mask_t, 'x', "k2-build"); if (ms != SH_OK) return ms; }
+    else SH_CHECK(mask_w == 0 && mask_t == 0, SH_ERR_BAD_ARG, "k2-build: --mask-window / --mask-threshold need --mask-low-complexity");
+    const uint64_t mask_ctx = masking ? 2 * (uint64_t)(mask_w - 1) : 0;
+    SH_CHECK(!masking || chunk >= 4 * ((uint64_t)(opts.k - 1) + mask_ctx), SH_ERR_BAD_ARG, "k2-build: with masking a batch holds at least %llu bases",
+             (unsigned long long)(4 * ((uint64_t)(opts.k - 1) + mask_ctx)));
+    double s_mask = 0;
+    uint64_t n_masked = 0;
+    // masks the uploaded batch in place.  A piece next to a cut then gives up its W - 1 bases there (they were context only: their
+    // own mask lacked its context) by moving the record's border in the offsets the scan kernels get, and the k - 1 bases it
+    // shares with the piece before the cut are counted there.
+    auto mask_batch = [&](const K2Batch &b, uint8_t *d_bases, uint64_t *d_off, bool count) -> sh_status {
+        if (!masking) return SH_OK;
+        const auto m0 = std::chrono::steady_clock::now();
+        sh_k2_mask_stats ms;
+        const uint64_t margin = (uint64_t)(mask_w - 1), nr = b.taxa.size();
+        sh_status u = shi_k2_mask_device(d_bases, d_off, nr, mask_w, mask_t, 'x', b.head_cont ? margin + (uint64_t)(opts.k - 1) : 0, b.tail_cut ? margin : 0, nullptr, &ms);
+        if (u != SH_OK) return u;
+        const uint64_t first = b.off[0] + margin, last = b.off[nr] - margin;
+        if (b.head_cont) SH_HIP(hipMemcpy(d_off, &first, 8, hipMemcpyHostToDevice));
+        if (b.tail_cut) SH_HIP(hipMemcpy(d_off + nr, &last, 8, hipMemcpyHostToDevice));
+        s_mask += std::chrono::duration<double>(std::chrono::steady_clock::now() - m0).count();
+        if (count) n_masked += ms.n_masked;
+        return SH_OK;
+    };
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= c->device) { sh_set_error("no HIP device %d", c->device); return SH_ERR_NO_DEVICE; }
     SH_HIP(hipSetDevice(c->device));
@@ -1738,10 +1775,11 @@ extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_re
                 sh_status u = dev.upload(b);
                 if (u != SH_OK) return u;
                 const auto g0 = now();
-                u = sh_k2_estimate_capacity_device(est, dev.bases, dev.off, b.taxa.size(), nullptr, &res->n_sampled);
+                u = mask_batch(b, dev.bases, dev.off, false);
+                if (u == SH_OK) u = sh_k2_estimate_capacity_device(est, dev.bases, dev.off, b.taxa.size(), nullptr, &res->n_sampled);
                 s_gpu += sec(g0, now());
                 return u;
-            }, cn);
+            }, cn, mask_ctx);
         if (st != SH_OK) return st;
         if (estimate) {
             st = sh_k2_capacity_plan(res->n_sampled, c->load_factor, c->max_db_size, &res->estimate, &capacity, &min_hash);
@@ -1785,12 +1823,13 @@ extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_re
             sh_status u = dev.upload(b);
             if (u != SH_OK) return u;
             const auto g0 = now();
-            sh_k2_build_stats bs;
-            u = sh_k2_insert_library_device(db, dev.bases, dev.off, dev.taxa, b.taxa.size(), nullptr, &bs);
+            sh_k2_build_stats bs{};
+            u = mask_batch(b, dev.bases, dev.off, true);
+            if (u == SH_OK) u = sh_k2_insert_library_device(db, dev.bases, dev.off, dev.taxa, b.taxa.size(), nullptr, &bs);
             s_gpu += sec(g0, now());
             res->n_runs += bs.n_runs;
             return u;
-        }, cn);
+        }, cn, mask_ctx);
     if (st != SH_OK) return st;
     const auto t3 = now();
     res->s_fill = sec(t2, t3);
@@ -1805,5 +1844,83 @@ extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_re
     res->n_records = cn.n_records; res->n_skipped = cn.n_skipped; res->n_bases = cn.n_bases; res->n_batches = cn.n_batches; res->n_cuts = cn.n_cuts;
     res->size = info.size; res->capacity = capacity; res->n_nodes = ti.n_nodes; res->min_acceptable_hash = min_hash; res->value_bits = ti.value_bits;
     res->s_save = sec(t3, t4); res->s_read = s_read; res->s_total = sec(t_begin, t4);
+    res->n_masked_bases = n_masked; res->s_mask = s_mask;
+    return SH_OK;
+}
+
+// ---- `scrubby-hip k2-mask`: what a masked build would see, as a FASTA file ------------------------------------------------------
+extern "C" sh_status sh_k2_mask_run(const sh_k2_mask_config *c, sh_k2_mask_result *res)
+{
+    SH_CHECK(c && res, SH_ERR_BAD_ARG, "sh_k2_mask_run: null argument");
+    SH_CHECK(c->input && c->output, SH_ERR_BAD_ARG, "k2-mask: an input (-i) and an output (-o) FASTA file are required");
+    memset(res, 0, sizeof(*res));
+    const auto t_begin = std::chrono::steady_clock::now();
+    int32_t W = c->window, T = c->threshold;
+    const int32_t repl = c->soft ? 0 : (c->replacement ? c->replacement : 'x');
+    sh_status st = shi_k2_mask_params(&W, &T, repl, "k2-mask");
+    if (st != SH_OK) return st;
+    SH_CHECK(c->line_width >= 0, SH_ERR_BAD_ARG, "k2-mask: negative line width");
+    SH_CHECK(repl != '>' && repl != '\n' && repl != '\r' && (c->soft || repl > ' '), SH_ERR_BAD_ARG, "k2-mask: the replacement must be a printable character other than '>'");
+    const uint64_t margin = (uint64_t)(W - 1), ctx = 2 * margin;
+    const uint64_t chunk = std::max<uint64_t>(c->chunk_bytes ? c->chunk_bytes : env_mb("SCRUBBY_HIP_K2_BUILD_CHUNK_MB", 256ull << 20), 4 * ctx);
+    SH_CHECK(chunk < (1ull << 31), SH_ERR_BAD_ARG, "k2-mask: batches of at most 2 GiB");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= c->device) { sh_set_error("no HIP device %d", c->device); return SH_ERR_NO_DEVICE; }
+    SH_HIP(hipSetDevice(c->device));
+    shc::Out out;
+    SH_CHECK(out.open(c->output), SH_ERR_IO, "%s", out.error.c_str());
+    std::vector<std::string> headers;          // record i's header; a piece carries i + 1 where the build carries a taxon
+    uint64_t written = 0;                      // headers [0, written) are in the output
+    uint64_t col = 0;                          // bases on the open output line
+    std::string text;
+    std::vector<uint8_t> host;
+    K2DevBatch dev;
+    K2LibCounts cn;
+    double s_mask = 0;
+    auto header_up_to = [&](uint64_t n) {      // the headers of the records before record n, and record n's own
+        if (written > n) return;
+        if (col) { text += '\n'; col = 0; }
+        for (; written <= n; ++written) { text += '>'; text += headers[written]; text += '\n'; }
+    };
+    const char *in_files[1] = {c->input};
+    st = k2_stream_library(in_files, 1, chunk, 1, true,
+        [&](const std::string &h) -> uint32_t { headers.push_back(h); return (uint32_t)headers.size(); },
+        [&](const K2Batch &b) -> sh_status {
+            sh_status u = dev.upload(b);
+            if (u != SH_OK) return u;
+            const auto m0 = std::chrono::steady_clock::now();
+            sh_k2_mask_stats ms;
+            // the margins next to a cut are neither counted nor written below: the neighbouring piece has those bases
+            u = shi_k2_mask_device(dev.bases, dev.off, b.taxa.size(), W, T, repl, b.head_cont ? margin : 0, b.tail_cut ? margin : 0, nullptr, &ms);
+            if (u != SH_OK) return u;
+            s_mask += std::chrono::duration<double>(std::chrono::steady_clock::now() - m0).count();
+            res->n_masked_bases += ms.n_masked;
+            host.resize(b.bases.size());
+            SH_HIP(hipMemcpy(host.data(), dev.bases, host.size(), hipMemcpyDeviceToHost));
+            text.clear();
+            const size_t nr = b.taxa.size();
+            for (size_t i = 0; i < nr; ++i) {
+                header_up_to((uint64_t)b.taxa[i] - 1);
+                uint64_t lo = b.off[i], hi = b.off[i + 1];
+                if (i == 0 && b.head_cont) lo += margin;
+                if (i + 1 == nr && b.tail_cut) hi -= margin;
+                while (lo < hi) {
+                    const uint64_t room = c->line_width ? (uint64_t)c->line_width - col : hi - lo, n = std::min<uint64_t>(room, hi - lo);
+                    text.append((const char *)host.data() + lo, (size_t)n);
+                    lo += n; col += n;
+                    if (c->line_width && col == (uint64_t)c->line_width) { text += '\n'; col = 0; }
+                }
+            }
+            SH_CHECK(out.write(text.data(), text.size()), SH_ERR_IO, "%s: %s", c->output, out.error.c_str());
+            return SH_OK;
+        }, cn, ctx);
+    if (st != SH_OK) return st;
+    text.clear();
+    if (col) { text += '\n'; col = 0; }
+    for (; written < headers.size(); ++written) { text += '>'; text += headers[written]; text += '\n'; }
+    SH_CHECK(out.write(text.data(), text.size()) && out.close(), SH_ERR_IO, "%s: %s", c->output, out.error.c_str());
+    res->n_records = cn.n_records; res->n_bases = cn.n_bases; res->n_batches = cn.n_batches; res->n_cuts = cn.n_cuts;
+    res->s_mask = s_mask;
+    res->s_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     return SH_OK;
 }

@@ -55,14 +55,30 @@ class K2BuildConfig(C.Structure):
                 ("taxid", C.c_uint64), ("name", C.c_char_p), ("rank", C.c_char_p), ("output_dir", C.c_char_p),
                 ("k", C.c_int32), ("l", C.c_int32), ("minimizer_spaces", C.c_int32), ("value_bits", C.c_int32),
                 ("capacity", C.c_uint64), ("load_factor", C.c_double), ("max_db_size", C.c_uint64), ("chunk_bytes", C.c_uint64),
-                ("device", C.c_int32), ("pad", C.c_int32)]
+                ("device", C.c_int32), ("pad", C.c_int32),
+                ("mask_low_complexity", C.c_int32), ("mask_window", C.c_int32), ("mask_threshold", C.c_int32), ("pad2", C.c_int32)]
 
 
 class K2BuildResult(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_skipped", "n_bases", "n_batches", "n_cuts", "n_runs", "size", "capacity", "n_nodes",
                                            "n_sampled", "estimate", "min_acceptable_hash")] + \
                [("value_bits", C.c_int32), ("pad", C.c_int32)] + \
-               [(n, C.c_double) for n in ("s_taxonomy", "s_estimate", "s_fill", "s_save", "s_read", "s_total")]
+               [(n, C.c_double) for n in ("s_taxonomy", "s_estimate", "s_fill", "s_save", "s_read", "s_total")] + \
+               [("n_masked_bases", C.c_uint64), ("s_mask", C.c_double)]
+
+
+class K2MaskStats(C.Structure):
+    _fields_ = [("n_bases", C.c_uint64), ("n_masked", C.c_uint64), ("n_items", C.c_uint64), ("ms", C.c_float), ("pad", C.c_int32)]
+
+
+class K2MaskConfig(C.Structure):
+    _fields_ = [("input", C.c_char_p), ("output", C.c_char_p), ("window", C.c_int32), ("threshold", C.c_int32), ("replacement", C.c_int32),
+                ("soft", C.c_int32), ("line_width", C.c_int32), ("device", C.c_int32), ("chunk_bytes", C.c_uint64)]
+
+
+class K2MaskResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_bases", "n_masked_bases", "n_batches", "n_cuts")] + \
+               [("s_mask", C.c_double), ("s_total", C.c_double)]
 
 
 RESULT_DTYPE = np.dtype([("taxid", "<u4"), ("call", "<u4"), ("total_kmers", "<u4"), ("hit_groups", "<u4")])
@@ -228,10 +244,67 @@ def estimate_capacity(records, opts=None, batches=1, load_factor=0.7, max_db_siz
     return {"n_sampled": n.value, "estimate": est, "capacity": cap, "min_acceptable_hash": mh}
 
 
+def _replacement_code(replacement):
+    """b"x" / "x" / 120 -> 120; None, b"" or 0 -> 0 (soft masking: lower case)"""
+    if not replacement:
+        return 0
+    if isinstance(replacement, int):
+        return replacement
+    r = replacement if isinstance(replacement, bytes) else str(replacement).encode()
+    assert len(r) == 1, "the replacement is one byte"
+    return r[0]
+
+
+def _mask_stats(st):
+    return {n: getattr(st, n) for n, _ in K2MaskStats._fields_ if n != "pad"}
+
+
+def mask_low_complexity(records, window=64, threshold=20, replacement=b"x", return_stats=False):
+    """Symmetric DUST on the GPU (sh_k2_mask_device) over a list of sequences; replacement None / 0 = soft masking (lower case).
+    Returns the masked sequences as bytes, in order (and the call's statistics with return_stats=True)."""
+    S.require_gpu()
+    d_bases, d_off, n = _library_to_device(records)
+    st = K2MaskStats()
+    S.check(S.load().sh_k2_mask_device(C.c_void_p(d_bases.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_uint64(n), window, threshold,
+                                       _replacement_code(replacement), S._stream_ptr(), C.byref(st)))
+    flat = d_bases.cpu().numpy()
+    off = d_off.cpu().numpy()
+    out = [flat[int(off[i]): int(off[i + 1])].tobytes() for i in range(n)]
+    return (out, _mask_stats(st)) if return_stats else out
+
+
+def mask_low_complexity_host(records, window=64, threshold=20, replacement=b"x", return_stats=False):
+    """The same on the CPU (sh_k2_mask_host, the streaming mirror; no GPU needed)."""
+    arrs = [np.frombuffer(bytes(r), dtype=np.uint8) for r in records]
+    off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    if arrs:
+        off[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+    flat = np.concatenate(arrs + [np.zeros(8, np.uint8)]).copy()
+    st = K2MaskStats()
+    S.check(S.load().sh_k2_mask_host(C.c_void_p(flat.ctypes.data), C.c_void_p(off.ctypes.data), C.c_uint64(len(arrs)), window, threshold,
+                                     _replacement_code(replacement), C.byref(st)))
+    out = [flat[int(off[i]): int(off[i + 1])].tobytes() for i in range(len(arrs))]
+    return (out, _mask_stats(st)) if return_stats else out
+
+
+def mask_file(input, output, window=0, threshold=0, replacement=b"x", soft=False, line_width=60, chunk_bytes=0, device=0):
+    """`scrubby-hip k2-mask` (sh_k2_mask_run): FASTA in, masked FASTA out; returns the result fields as a dict."""
+    S.require_gpu()
+    c = K2MaskConfig()
+    c.input, c.output = str(input).encode(), str(output).encode()
+    c.window, c.threshold, c.replacement, c.soft = window, threshold, _replacement_code(replacement), int(bool(soft))
+    c.line_width, c.device, c.chunk_bytes = line_width, device, chunk_bytes
+    r = K2MaskResult()
+    S.check(S.load().sh_k2_mask_run(C.byref(c), C.byref(r)))
+    return {n: getattr(r, n) for n, _ in K2MaskResult._fields_}
+
+
 def build_database(inputs, output_dir, taxonomy_dir=None, seqid2taxid=None, taxid=0, name=None, rank=None, k=0, l=0, minimizer_spaces=0,
-                   capacity=0, load_factor=0.0, max_db_size=0, value_bits=0, chunk_bytes=0, device=0):
+                   capacity=0, load_factor=0.0, max_db_size=0, value_bits=0, chunk_bytes=0, device=0, mask=False, mask_window=0,
+                   mask_threshold=0):
     """`scrubby-hip k2-build` (sh_k2_build_run): FASTA library files + (taxonomy directory [+ id map] | one taxid) -> a database
-    directory.  minimizer_spaces: 0 = Kraken 2's 7, negative = none.  Returns the result fields as a dict."""
+    directory.  minimizer_spaces: 0 = Kraken 2's 7, negative = none.  mask=True: low-complexity sequence is masked on the GPU
+    before both passes (kraken2-build's default; off here).  Returns the result fields as a dict."""
     S.require_gpu()
     c = K2BuildConfig()
     files = [inputs] if isinstance(inputs, (str, bytes)) or hasattr(inputs, "__fspath__") else list(inputs)
@@ -243,6 +316,7 @@ def build_database(inputs, output_dir, taxonomy_dir=None, seqid2taxid=None, taxi
     c.output_dir = str(output_dir).encode()
     c.k, c.l, c.minimizer_spaces, c.value_bits = k, l, minimizer_spaces, value_bits
     c.capacity, c.load_factor, c.max_db_size, c.chunk_bytes, c.device = capacity, load_factor, max_db_size, chunk_bytes, device
+    c.mask_low_complexity, c.mask_window, c.mask_threshold = int(bool(mask)), mask_window, mask_threshold
     r = K2BuildResult()
     S.check(S.load().sh_k2_build_run(C.byref(c), C.byref(r)))
     return {n: getattr(r, n) for n, _ in K2BuildResult._fields_ if n != "pad"}

@@ -139,6 +139,7 @@ EXPORTS = [
     "sh_k2_taxonomy_from_ncbi", "sh_k2_taxonomy_single", "sh_k2_taxonomy_info_get", "sh_k2_taxonomy_copy", "sh_k2_taxonomy_internal",
     "sh_k2_taxonomy_header_taxon", "sh_k2_taxonomy_free", "sh_k2_capacity_plan", "sh_k2_max_db_size", "sh_k2_set_min_acceptable_hash",
     "sh_k2_insert_library_device", "sh_k2_estimator_create", "sh_k2_estimate_capacity_device", "sh_k2_estimator_free", "sh_k2_build_run",
+    "sh_k2_mask_device", "sh_k2_mask_host", "sh_k2_mask_run",
 ]
 
 _LIB = None
