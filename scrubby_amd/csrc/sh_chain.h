@@ -229,11 +229,15 @@ __device__ inline int32_t comput_sc(uint32_t lo_i, uint32_t q_i, uint32_t lo_j, 
 
 // ---- stores -----------------------------------------------------------------------------------
 // LDS, lane-interleaved [i][64]; 11 B per anchor.  `aux` holds x>>32 while sorting, then
-// {f:16, p:8, t:8}; group ids (rank of x>>32 among the read's anchors) replace x>>32.
+// {f:16, p:8, t:8}; group ids (rank of x>>32 among the read's anchors) replace x>>32.  The x>>32 of the first NHI groups stay in
+// registers (ghi: constant indices only, selected by a compare chain - the kernel's LDS leaves it under 2 waves per SIMD, so
+// registers are free); a higher rank has to be recomputed from the seeds.
 template <int CAP>
 struct SmallStore {
     uint32_t *lo; uint32_t *aux; uint16_t *qv; uint8_t *gv;     // already offset by lane
     static constexpr int S = 64;
+    static constexpr int NHI = 8;
+    uint32_t ghi[NHI];
     __device__ inline void set_raw(int i, uint64_t x, uint32_t q) { lo[i * S] = (uint32_t)x; aux[i * S] = (uint32_t)(x >> 32); qv[i * S] = (uint16_t)q; }
     __device__ inline uint64_t raw_x(int i) const { return (uint64_t)aux[i * S] << 32 | lo[i * S]; }
     __device__ inline void sort_finalize(int n)
@@ -248,7 +252,25 @@ struct SmallStore {
         }
         uint32_t prev = n > 0 ? aux[0] : 0;
         uint8_t g = 0;
-        for (int i = 0; i < n; ++i) { uint32_t h = aux[i * S]; g += h != prev; prev = h; gv[i * S] = g; }
+#pragma unroll
+        for (int t = 0; t < NHI; ++t) ghi[t] = prev;
+        for (int i = 0; i < n; ++i) {
+            uint32_t h = aux[i * S];
+            if (h != prev) {
+                ++g;
+#pragma unroll
+                for (int t = 1; t < NHI; ++t) ghi[t] = g == t ? h : ghi[t];
+            }
+            prev = h; gv[i * S] = g;
+        }
+    }
+    // x>>32 of group g if it is one of the kept ones
+    __device__ inline bool group_hi(uint32_t g, uint32_t &h) const
+    {
+        h = ghi[0];
+#pragma unroll
+        for (int t = 1; t < NHI; ++t) h = g == (uint32_t)t ? ghi[t] : h;
+        return g < (uint32_t)NHI;
     }
     __device__ inline uint32_t grp(int i) const { return gv[i * S]; }
     __device__ inline uint32_t rlo(int i) const { return lo[i * S]; }

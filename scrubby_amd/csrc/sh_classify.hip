@@ -73,7 +73,7 @@ struct Counters {
     uint32_t n_small, n_resketch, n_big[2], n_big_defer[2], n_defer, n_small2;      // n_small2: LDS-path reads the pair pass left undecided
     uint32_t n_big_total, pad1;   // repeat-path reads before the pair pass took its share (0: no pair pass)
     uint32_t n_sort[N_SORT_CLS], n_giant_tiles, n_giant_rounds;
-    uint32_t expand_ticket, pad_t;         // k_expand: next read of the pass's list
+    uint32_t expand_ticket, lc_ticket;     // k_expand / k_local_cluster: next read of the pass's list
     uint32_t top_ticket[N_SORT_CLS];       // k_sort_top / k_giant_top: likewise
     uint32_t sort_ticket[N_SORT_CLS];      // k_sort_lds: next item of the class (blocks draw reads one by one: their costs differ a hundredfold)
     uint32_t n_long_segs, pad2;
@@ -87,6 +87,7 @@ struct Counters {
     unsigned long long lext_clk[LR_NCLK], lext_d[8], lext_slow, lext_kernel_sum;  // long-read extension stage (sh_long.h): reads for the large-scratch pass, RMQ re-chains, steps with tied priorities
     uint32_t n_cl[4], cl_ticket, cl_ticket3;      // global queue of big clusters (k_cluster_dp), by size class; tickets: classes 0-2 one by one, class 3 eight at a time
     uint32_t n_leg_reason[4];     // why reads left the long-read front end: 0 room/segments, 1 thinning screen, 2 anchors beyond the giant path, 3 unused
+    uint32_t pair_mid[4];         // SCRUBBY_HIP_DBG & 16: k_pair_pass mode 2, reads that meet every premise except unc <= ext_unc_max (0: LDS path's list, 2: repeat path's), and those of them the middle check decides (1, 3)
     unsigned long long arena_cursor, anchor_cursor;
     unsigned long long cl_tot[4], cl_anchor_tot[4], cl_dbg[10], pf_dbg[16];
     unsigned long long sort_tot[N_SORT_CLS + 1], sort_anchor_tot[N_SORT_CLS + 1];    // SCRUBBY_HIP_DBG & 16: reads / anchors per sort class (4 = chained inside k_expand)     // statistics of k_cluster_dp by size class (whole chunk)
@@ -726,10 +727,11 @@ struct K2Args {
     ChainSink sink; int32_t emit;                   // SH_F_CIGAR: every kept chain is handed to the extension stage; no flag-only shortcut in the DP
     BaseCtx BC;
     int32_t quiet;      // k_chain_large re-running reads that were counted before: no statistics
+    int32_t dbg, dbg_slot;      // SCRUBBY_HIP_DBG (k_pair_pass: bit 4 counts what the middle check is handed, in Counters::pair_mid[dbg_slot ..])
 };
 
-// hi word (strand | contig) of anchor group g of a read chained in a SmallStore: the store keeps group ranks only, so the
-// g-th smallest distinct x >> 32 is recomputed from the seeds (<= K2_CAP anchors)
+// hi word (strand | contig) of anchor group g of a read chained in a SmallStore, for the ranks beyond the store's register table
+// (SmallStore::group_hi): the g-th smallest distinct x >> 32 is recomputed from the seeds (<= K2_CAP anchors)
 __device__ inline uint32_t small_group_hi(SeedView sv, const uint64_t *__restrict__ positions, int32_t qlen, int32_t k, uint32_t g)
 {
     long long prev = -1;
@@ -797,7 +799,7 @@ __global__ __launch_bounds__(64) void k_chain_small(K2Args a)
             if (a.emit && a.trace == nullptr && a.P.ext_lemma) {      // flag-only: the top chain, vouched for by chain_lemma, decides without a hand-over
                 chain_dp_mask(S, (int)n_a, qlen, a.P);
                 BestChain bc{};
-                auto hi = [&](int32_t i) { return small_group_hi(sv, a.positions, qlen, a.P.k, S.grp(i)); };
+                auto hi = [&](int32_t i) { const uint32_t g = S.grp(i); uint32_t h; return S.group_hi(g, h) ? h : small_group_hi(sv, a.positions, qlen, a.P.k, g); };
                 const BestEmit<SmallStore<CAP>, decltype(hi)> be{&S, &bc, region_hash(qlen), a.P.k, 0u, hi, true, TandemQ{sv.base, sv.n, sv.stride, qlen, info >> 31}};
                 backtrack_mask(S, (int)n_a, a.P, n_u, best, false, be);
                 tried = true;
@@ -822,7 +824,9 @@ __global__ __launch_bounds__(64) void k_chain_small(K2Args a)
             else if (a.emit) {      // every chain goes to the extension stage, which decides the read
                 if (!tried) chain_dp_mask(S, (int)n_a, qlen, a.P);
                 auto emf = [&](int64_t zi, int64_t end_i, int32_t sc, int64_t cnt, int32_t zf) {
-                    const uint32_t hi = small_group_hi(sv, a.positions, qlen, a.P.k, S.grp((int)zi));
+                    const uint32_t g = S.grp((int)zi);
+                    uint32_t hi;
+                    if (!S.group_hi(g, hi)) hi = small_group_hi(sv, a.positions, qlen, a.P.k, g);
                     sink_emit(a.sink, r, (int32_t)zi, (int32_t)end_i, sc, (uint32_t)cnt, (uint32_t)zf, (uint32_t)zi, a.P.k, region_hash(qlen), qlen,
                               [&](int32_t i, uint64_t &x, uint32_t &q) { x = (uint64_t)hi << 32 | S.rlo(i); q = S.qp(i); },
                               [&](int32_t i) { return S.Pm(i); });
@@ -864,13 +868,14 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
     __shared__ uint32_t s_key[32 * 64];
     const uint32_t lane = threadIdx.x;
     const uint32_t n_work = *a.work_count;
-    uint32_t n_host_wave = 0;
+    uint32_t n_host_wave = 0, n_mid_wave = 0, n_mid_ok_wave = 0;
     unsigned long long anchors_wave = 0;
     for (uint32_t base = blockIdx.x * 64; base < n_work; base += gridDim.x * 64) {
         const uint32_t wi = base + lane;
         const bool valid = wi < n_work;
         uint32_t r = 0, info = 0, n_seed = 0, tot = 0;
-        bool found = false;
+        bool found = false, need_mid = false;
+        MidReq mid{0, 0, 0, 0, 0}; int32_t qlen_ = 0;
         if (valid && distinct == 2) {
             // SH_F_CIGAR (ChainParams::ext_*): the read is decided here only if the whole outcome of minimap2 is known from its seed
             // records - every seed a singleton (none is filtered, anchors = seeds), all anchors on ONE diagonal of one contig /
@@ -881,7 +886,11 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
             // no second pass runs; mlen >= covered = k + sum min(k, d) >= 2k >= min_chain_score (span >= k); one gap at most
             // can be left-aligned into the middle (mm_fix_cigar, from the right extension), so the first or the last k-mer stays a
             // run of k matches: dp_max >= a * k >= min_dp_max; max_clip_ratio >= 1 disables the clip test.  Host-checked premises
-            // in fill_chain_params.  Everything else goes through the full path.
+            // in fill_chain_params.  A read that meets every premise except U <= ext_unc_max (one substitution opens a gap of ~k bases) is the
+            // `fast` case of k_local_cluster with the read's seeds in place of K and u_out = 0 (every seed is a singleton, nothing lies
+            // outside): the licence written above that branch holds as it stands, so the lane raises the MidReq chain_lemma would raise for
+            // the single co-diagonal run (ext_lemma) and the wave checks it on the bases below.  No z-drop: mapped, as above; else the read
+            // stays undecided.  Everything else goes through the full path.
             r = a.work[wi];
             info = a.k1info[r];
             n_seed = info >> 16 & 0x7fffu;
@@ -895,11 +904,12 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
             if (mdy < a.P.bw) mdy = a.P.bw;
             const int32_t dmax = mdx < mdy ? mdx : mdy;
             bool ok = a.P.ext_s1 != 0 && n_seed >= 2 && (int32_t)n_seed >= a.P.min_cnt && n_seed <= a.seed_cap;
-            uint64_t w0 = 0; uint32_t q0 = 0, qp = 0; int32_t unc = 0;
+            uint64_t w0 = 0, wl = 0; uint32_t q0 = 0, ql = 0, qp = 0; int32_t unc = 0;
             for (uint32_t i = 0; ok && i < n_seed; ++i) {
                 const uint4 sd = rec[i];
                 const uint64_t w1 = (uint64_t)sd.y << 32 | sd.x;
                 if ((sd.z & SH_REC_OCC_MASK) != 1u) { ok = false; break; }
+                wl = w1; ql = sd.w;
                 if (i == 0) { w0 = w1; q0 = sd.w; qp = sd.w >> 1; continue; }
                 const bool fw0 = (uint32_t)(w0 & 1u) == (q0 & 1u), fwi = (uint32_t)(w1 & 1u) == (sd.w & 1u);
                 const int32_t D = (int32_t)(sd.w >> 1) - (int32_t)(q0 >> 1), d = (int32_t)(sd.w >> 1) - (int32_t)qp;
@@ -911,6 +921,18 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
             const int32_t span = (int32_t)qp - (int32_t)(q0 >> 1);
             found = ok && span >= a.P.k && unc <= a.P.ext_unc_max;
             tot = n_seed;
+            if (ok && span >= a.P.k && !found && a.P.ext_lemma) {
+                // the run's first and last anchor in x order: on the reverse strand the seeds (query order) run against x and q is flipped
+                uint64_t xa, xb; uint32_t qa, qb;
+                make_anchor(w0, q0, qlen, a.P.k, xa, qa);
+                make_anchor(wl, ql, qlen, a.P.k, xb, qb);
+                if (xb < xa) { xa = xb; const uint32_t t = qa; qa = qb; qb = t; }
+                const uint32_t hi = (uint32_t)(xa >> 32);
+                need_mid = true;
+                mid.rid = (int32_t)(hi & 0x7fffffffu); mid.rev = (int32_t)(hi >> 31);
+                mid.qs = (int32_t)qa + 1 - a.P.k; mid.qe = (int32_t)qb + 1; mid.rs = (int32_t)(uint32_t)xa + 1 - a.P.k;
+                qlen_ = qlen;
+            }
         } else if (valid) {
             r = a.work[wi];
             info = a.k1info[r];
@@ -938,6 +960,11 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
             }
             if (!distinct) found = found && tot <= (uint32_t)a.P.max_skip + 1u;
         }
+        if (distinct == 2 && a.P.ext_lemma) {      // wave-uniform: the stretches above, the wave on one lane's request at a time
+            const bool mid_ok = resolve_mid_wave(need_mid, mid, a.bases + a.offsets[r], qlen_, a.BC, a.P);
+            found = found || (need_mid && mid_ok);
+            if (a.dbg & 16) { n_mid_wave += (uint32_t)__popcll(__ballot(need_mid)); n_mid_ok_wave += (uint32_t)__popcll(__ballot(need_mid && mid_ok)); }
+        }
         if (distinct == 1 && __ballot(found) != 0) {
             uint32_t mx = found ? n_seed : 0u;
             mx = wave_all_max_u32(mx);
@@ -961,6 +988,7 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
     if (lane == 0 && n_host_wave) { atomicAdd(&a.ctr->sh_host[SHARD()], n_host_wave); atomicAdd(&a.ctr->sh_pair[SHARD()], n_host_wave); }
     anchors_wave = wave_all_add_u64(anchors_wave);
     if (lane == 0 && anchors_wave) atomicAdd(&a.ctr->sh_anchors[SHARD()], anchors_wave);
+    if (lane == 0 && n_mid_wave) { atomicAdd(&a.ctr->pair_mid[a.dbg_slot], n_mid_wave); atomicAdd(&a.ctr->pair_mid[a.dbg_slot + 1], n_mid_ok_wave); }
 }
 
 // after the pair pass over the repeat path's list: the survivors (collected in the deferral list) become the list
@@ -1010,7 +1038,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     const uint32_t n_work = *a.work_count;
     const ChainParams &P = a.P;
     uint32_t n_hit = 0;
-    for (uint32_t w = blockIdx.x; w < n_work; w += gridDim.x) {
+    // reads are drawn four at a time, not dealt out by block index: while k_chain_small's blocks hold wave slots beside this kernel a fifth of
+    // its blocks start only when the first ones end, and with a fixed share each they would repeat the whole kernel's time on an idle machine
+    uint32_t w_next = 0, w_stop = 0;
+    for (;;) {
+        if (w_next >= w_stop) {
+            uint32_t t = 0;
+            if (lane == 0) t = atomicAdd(&a.ctr->lc_ticket, 4u);
+            w_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+            w_stop = w_next + 4u < n_work ? w_next + 4u : n_work;
+            if (w_next >= n_work) break;
+        }
+        const uint32_t w = w_next++;
         const uint32_t r = a.work[w];
         const uint32_t info = a.k1info[r];
         const uint32_t n_seed = info >> 16 & 0x7fffu;
@@ -3930,6 +3969,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     b.P = c->P;
     b.sink = c->sink; b.emit = c->ext ? 1 : 0;
     b.BC = BaseCtx{idx->d_ref, idx->d_cstart, d_bases};
+    b.dbg = getenv("SCRUBBY_HIP_DBG") ? atoi(getenv("SCRUBBY_HIP_DBG")) : 0;
     if (c->ext && (d_trace != nullptr || c->ext_long)) { b.sink.best = nullptr; b.sink.tie = nullptr; }      // trace mode / long-read presets: every chain is handed over
     const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(n_tiles, 1), 256 * 8);
     // K2 only needs K1's output and nothing waits for it before the end of the call: it runs on a side stream, beside k_local_cluster /
@@ -3994,7 +4034,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     if (pair_pass) {      // the repeat path's list: reads two singleton seeds decide never reach k_expand; the rest moves to the other list
         K2Args pb = b;
         pb.work = c->d_big[0][0]; pb.work_count = &c->d_ctr->n_big[0];
-        pb.leftover = c->d_big[0][1]; pb.leftover_count = &c->d_ctr->n_big_defer[0];
+        pb.leftover = c->d_big[0][1]; pb.leftover_count = &c->d_ctr->n_big_defer[0]; pb.dbg_slot = 2;
         hipLaunchKernelGGL(k_pair_pass, dim3(grid * 2), dim3(64), 0, s, pb, pair_mode_big);
         hipLaunchKernelGGL(k_pair_swap, dim3(1), dim3(1), 0, s, c->d_ctr);
         cur0 = 1;
@@ -4037,6 +4077,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             if (k.dbg & 16) fprintf(stderr, "[dbg] iter %d resketch %u reasons %u %u %u pair tests between two singletons (dbg) %u segs %u big %u/%u defer %u/%u\n", iter, c->h_ctr->n_resketch, c->h_ctr->n_leg_reason[0], c->h_ctr->n_leg_reason[1], c->h_ctr->n_leg_reason[2], c->h_ctr->n_leg_reason[3], c->h_ctr->n_long_segs, c->h_ctr->n_big[0], c->h_ctr->n_big[1], c->h_ctr->n_big_defer[0], c->h_ctr->n_big_defer[1]);
             if (k.dbg & 16) fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", c->h_ctr->cl_tot[0], c->h_ctr->cl_tot[1], c->h_ctr->cl_tot[2], c->h_ctr->cl_tot[3], c->h_ctr->cl_anchor_tot[0], c->h_ctr->cl_anchor_tot[1], c->h_ctr->cl_anchor_tot[2], c->h_ctr->cl_anchor_tot[3]);
             if (k.dbg & 16) fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", c->h_ctr->sort_tot[6], c->h_ctr->sort_anchor_tot[6], c->h_ctr->sort_tot[0], c->h_ctr->sort_anchor_tot[0], c->h_ctr->sort_tot[1], c->h_ctr->sort_anchor_tot[1], c->h_ctr->sort_tot[2], c->h_ctr->sort_anchor_tot[2], c->h_ctr->sort_tot[3], c->h_ctr->sort_anchor_tot[3], c->h_ctr->sort_tot[4], c->h_ctr->sort_anchor_tot[4], c->h_ctr->sort_tot[5], c->h_ctr->sort_anchor_tot[5]);
+            if (k.dbg & 16) fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", c->h_ctr->pair_mid[0], c->h_ctr->pair_mid[1], c->h_ctr->pair_mid[2], c->h_ctr->pair_mid[3]);
             if (k.dbg & 16) fprintf(stderr, "[dbg] local-cluster shortcut: tried %u, no singleton / filtered %u, singletons apart %u, window %u, K size %u, no margin %u, decided %u\n", c->h_ctr->ext_s3[0], c->h_ctr->ext_s3[1], c->h_ctr->ext_s3[2], c->h_ctr->ext_s3[3], c->h_ctr->ext_s3[4], c->h_ctr->ext_s3[5], c->h_ctr->ext_s3[7]);
             if (k.dbg & 16) fprintf(stderr, "[dbg] ring DP: chunks in window %llu, beyond %llu, far rescans %llu; clusters %llu (anchors %llu), with a max_skip break %llu (anchors %llu), widest window %llu, anchors of clusters with a window > 64: %llu, > 128: %llu\n", c->h_ctr->cl_dbg[0], c->h_ctr->cl_dbg[1], c->h_ctr->cl_dbg[2], c->h_ctr->cl_dbg[3], c->h_ctr->cl_dbg[6], c->h_ctr->cl_dbg[4], c->h_ctr->cl_dbg[5], c->h_ctr->cl_dbg[7], c->h_ctr->cl_dbg[8], c->h_ctr->cl_dbg[9]);
             if (k.dbg & 16) fprintf(stderr, "[dbg] parallel fill: reads done %llu (anchors %llu), not applicable %llu (anchors %llu), dirty anchors %llu; k_cluster_dp clusters prefilled %llu, sequential %llu (anchors %llu); read-level backtracks tried %llu, candidates listed %llu, given up (too many) %llu, chains visited %llu\n", c->h_ctr->pf_dbg[0], c->h_ctr->pf_dbg[3], c->h_ctr->pf_dbg[1], c->h_ctr->pf_dbg[4], c->h_ctr->pf_dbg[2], c->h_ctr->pf_dbg[5], c->h_ctr->pf_dbg[6], c->h_ctr->pf_dbg[7], c->h_ctr->pf_dbg[8], c->h_ctr->pf_dbg[11], c->h_ctr->pf_dbg[12], c->h_ctr->pf_dbg[10]);
