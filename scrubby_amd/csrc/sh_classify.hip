@@ -42,6 +42,7 @@
 // Results are bit-identical to oracle/mm_oracle.c (tests/test_parity_gpu.py).
 #include "sh_common.h"
 #include "sh_wave.h"
+#include "sh_merge4.h"
 #include "sh_sketch.h"
 #include "sh_chain.h"
 #include "sh_long.h"
@@ -72,7 +73,7 @@ __device__ inline uint32_t lane_id() { return threadIdx.x & 63; }
 struct Counters {
     uint32_t n_small, n_resketch, n_big[2], n_big_defer[2], n_defer, n_small2;      // n_small2: LDS-path reads the pair pass left undecided
     uint32_t n_big_total, pad1;   // repeat-path reads before the pair pass took its share (0: no pair pass)
-    uint32_t n_sort[N_SORT_CLS], n_giant_tiles, n_giant_rounds;
+    uint32_t n_sort[N_SORT_CLS], n_giant_tiles, n_giant_passes;
     uint32_t expand_ticket, lc_ticket;     // k_expand / k_local_cluster: next read of the pass's list
     uint32_t top_ticket[N_SORT_CLS];       // k_sort_top / k_giant_top: likewise
     uint32_t sort_ticket[N_SORT_CLS];      // k_sort_lds: next item of the class (blocks draw reads one by one: their costs differ a hundredfold)
@@ -1528,6 +1529,7 @@ struct K3Args {
     uint64_t *stage_x; uint32_t *stage_q; unsigned long long stage_cap;      // where k_expand leaves those reads' anchors (generation order)
     int32_t locus_min_qlen;            // reads shorter than this are not thinned out (mm_map_frag's rescue test could depend on what is left out)
     int32_t cl_lds;                    // k_sort_lds queues its big clusters for k_cluster_dp (long-read presets handing over every chain)
+    uint32_t giant_fanin;              // runs a giant-read merge pass merges into one: 4, or 2 (SCRUBBY_HIP_GIANT_FANIN, A/B and tests); decides the passes a read takes and so the buffer it ends in
 };
 
 
@@ -1772,7 +1774,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // the count can exceed 31 bits only for absurd inputs; saturate (such a read never gets arena space)
         const uint32_t n_a = n_part > 0x7fffffffull ? 0x7fffffffu : (uint32_t)n_part;
 
-        if (n_a > (GT << 8)) {             // beyond the giant path's 8 merge rounds: legacy path (never for sr: <= 22 x 5000)
+        if (n_a > (GT << 8)) {             // beyond the giant path's 4 merge passes (8 two-way rounds): legacy path (never for sr: <= 22 x 5000)
             if (lane == 0) {
                 atomicAdd(&a.ctr->n_leg_reason[2], 1u);
                 BigMeta m{r, 0, 0, 2u};
@@ -2275,19 +2277,16 @@ __global__ __launch_bounds__(NTHR) void k_sort_lds(K3Args a)
 // Bandwidth-oriented merge sort over ALL giant reads of the pass at once:
 //   k_giant_scan       tile table: read i owns tiles [tile_base[i], tile_base[i+1]) of GT anchors
 //   k_giant_chunksort  one block per tile: load coalesced -> stable sort in LDS -> store coalesced
-//   per round (run width GT, 2GT, ...):
-//     k_giant_partition  one thread per output tile: merge-path split of its first output (independent binary searches)
-//     k_giant_merge      one block per output tile: the two input ranges staged coalesced through LDS, merged in LDS,
-//                        GT outputs stored coalesced into the other buffer
+//   per pass (run width GT, 4 GT, 16 GT, ...: groups of up to four runs become one, sh_merge4.h):
+//     k_giant_split      one thread per output tile: the four-way co-rank of its first output (nested merge path)
+//     k_giant_merge4     one block per output tile: its shares of the four runs staged coalesced through LDS, merged there as
+//                        (A + B) + (C + D), GT outputs stored coalesced into the other buffer
 //   k_giant_chain      one block per read: clusters chained over arena slices (chain_sorted)
-// A read needing r rounds ends in buffer (r & 1); reads that are done sit out the later rounds.
+// A read needing r passes ends in buffer (r & 1); reads that are done sit out the later passes.  The fan-in is K3Args::giant_fanin (4;
+// SCRUBBY_HIP_GIANT_FANIN=2 gives the two-way rounds through the same kernels): every place that asks where a read ended reads it there.
 
-__device__ inline uint32_t giant_rounds(uint32_t n)
-{
-    uint32_t r = 0;
-    for (uint32_t w = GT; w < n; w <<= 1) ++r;
-    return r;
-}
+__device__ inline uint32_t giant_lf(uint32_t fanin) { return fanin == 4 ? 2u : 1u; }
+__device__ inline uint32_t giant_passes(uint32_t n, uint32_t fanin) { return m4_passes(n, GT, giant_lf(fanin)); }
 
 // The dirty clusters par_fill_block left (PF_DIRTY at their first anchor): the sequential DP, p turned into indices into the read's array,
 // marks cleared.  One wave per cluster; every thread of the block calls.  A dirty cluster of more than max_len anchors is left as it is and
@@ -2401,7 +2400,7 @@ __global__ __launch_bounds__(512) void k_giant_top(K3Args a)
         const uint32_t n = si.n;
         if (n == 0) continue;
         const int32_t qlen = (int32_t)si.qlen;
-        const bool in_b = giant_rounds(n) & 1;
+        const bool in_b = giant_passes(n, a.giant_fanin) & 1;
         uint64_t *x = (in_b ? a.B.bx : a.B.ax) + si.off; uint32_t *q = (in_b ? a.B.bq : a.B.aq) + si.off;
         int32_t *f = a.B.af + si.off, *pt = (int32_t *)(a.B.az + si.off);
         const uint32_t mdx = chain_max_dist_x(P_l, qlen);
@@ -2451,7 +2450,7 @@ __global__ __launch_bounds__(1024) void k_giant_scan(K3Args a)
             run += wave_sum_u32(t);
         }
         max_n = wave_all_max_u32(max_n);
-        if (lane == 0) { a.B.tile_base[n_items] = run; a.ctr->n_giant_tiles = run; a.ctr->n_giant_rounds = giant_rounds(max_n); }
+        if (lane == 0) { a.B.tile_base[n_items] = run; a.ctr->n_giant_tiles = run; a.ctr->n_giant_passes = giant_passes(max_n, a.giant_fanin); }
     }
     // largest first: a read of 500 k anchors drawn last would run on alone after every other block has finished.  Counting sort by
     // floor(log2 n), falling (the whole block); the order inside a size class does not matter.
@@ -2488,88 +2487,79 @@ __global__ __launch_bounds__(256) void k_giant_chunksort(K3Args a)
     }
 }
 
-struct GiantTile { const uint64_t *sx; const uint32_t *sq; uint64_t *dx; uint32_t *dq; uint32_t L0, L1, R1, o0, o1; bool active; };
+struct GiantTile { const uint64_t *sx; const uint32_t *sq; uint64_t *dx; uint32_t *dq; M4Group g; uint32_t o0, o1; bool active; };
 
-__device__ inline GiantTile giant_tile(const K3Args &a, uint32_t t, uint32_t n_items, uint32_t round)
+__device__ inline GiantTile giant_tile(const K3Args &a, uint32_t t, uint32_t n_items, uint32_t pass)
 {
     GiantTile g;
     const uint32_t it = giant_item_of(a.B.tile_base, n_items, t);
     const SortItem si = a.B.sort_items[SORT_CLS_GIANT][it];
-    const uint32_t width = GT << round;
-    g.active = width < si.n;                       // this read still has runs to merge in this round
-    const bool src_b = round & 1;                  // after `round` rounds the data sits in buffer (round & 1)
+    const uint32_t width = GT << (giant_lf(a.giant_fanin) * pass);
+    g.active = width < si.n;                       // this read still has runs to merge in this pass
+    const bool src_b = pass & 1;                   // after `pass` passes the data sits in buffer (pass & 1)
     g.sx = (src_b ? a.B.bx : a.B.ax) + si.off; g.sq = (src_b ? a.B.bq : a.B.aq) + si.off;
     g.dx = (src_b ? a.B.ax : a.B.bx) + si.off; g.dq = (src_b ? a.B.aq : a.B.bq) + si.off;
     g.o0 = (t - a.B.tile_base[it]) * GT; g.o1 = g.o0 + GT < si.n ? g.o0 + GT : si.n;
-    const uint32_t pb = g.o0 / (2 * width) * (2 * width);
-    g.L0 = pb; g.L1 = pb + width < si.n ? pb + width : si.n; g.R1 = pb + 2 * width < si.n ? pb + 2 * width : si.n;
+    g.g = m4_group(g.o0, si.n, width, a.giant_fanin);
     return g;
 }
 
-// split[t] = number of elements the left run contributes before output o0 of tile t
-__global__ __launch_bounds__(256) void k_giant_partition(K3Args a, uint32_t round)
+// tile_split[3 t ..] = elements the group's runs A, B, C contribute before output o0 of tile t (D's share follows from o0)
+__global__ __launch_bounds__(256) void k_giant_split(K3Args a, uint32_t pass)
 {
-    if (round >= a.ctr->n_giant_rounds) return;
+    if (pass >= a.ctr->n_giant_passes) return;
     const uint32_t n_items = a.ctr->n_sort[SORT_CLS_GIANT], n_tiles = a.ctr->n_giant_tiles;
     for (uint32_t t = blockIdx.x * 256 + threadIdx.x; t < n_tiles; t += gridDim.x * 256) {
-        const GiantTile g = giant_tile(a, t, n_items, round);
+        const GiantTile g = giant_tile(a, t, n_items, pass);
         if (!g.active) continue;
-        const uint32_t lenL = g.L1 - g.L0, lenR = g.R1 - g.L1, d = g.o0 - g.L0;
-        uint32_t lo = d > lenR ? d - lenR : 0, hi = d < lenL ? d : lenL;
-        while (lo < hi) {
-            uint32_t mid = (lo + hi) >> 1;
-            if (g.sx[g.L0 + mid] <= g.sx[g.L1 + (d - 1 - mid)]) lo = mid + 1; else hi = mid;
-        }
-        a.B.tile_split[t] = lo;
+        uint32_t ca, cb, cc;
+        m4_corank4(g.sx, g.g, g.o0 - g.g.e[0], ca, cb, cc);
+        a.B.tile_split[3 * (size_t)t] = ca; a.B.tile_split[3 * (size_t)t + 1] = cb; a.B.tile_split[3 * (size_t)t + 2] = cc;
     }
 }
 
-__global__ __launch_bounds__(256) void k_giant_merge(K3Args a, uint32_t round)
+__global__ __launch_bounds__(256) void k_giant_merge4(K3Args a, uint32_t pass)
 {
-    __shared__ uint64_t s_x[GT];          // [0, la): left range, [la, la+lb): right range; la + lb <= GT
+    __shared__ uint64_t s_x[GT];          // the tile's shares of A, B, C, D one after the other: GT anchors at most
     __shared__ uint32_t s_q[GT];
-    if (round >= a.ctr->n_giant_rounds) return;
+    if (pass >= a.ctr->n_giant_passes) return;
     const uint32_t tid = threadIdx.x, n_items = a.ctr->n_sort[SORT_CLS_GIANT], n_tiles = a.ctr->n_giant_tiles;
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const GiantTile g = giant_tile(a, t, n_items, round);
+        const GiantTile g = giant_tile(a, t, n_items, pass);
         if (!g.active) continue;                               // uniform per block
-        const uint32_t d0 = g.o0 - g.L0, d1 = g.o1 - g.L0;
-        const uint32_t a0 = a.B.tile_split[t];
-        // the next tile of the same pair starts where this one ends; the pair's last tile ends at the run ends
-        const bool last_of_pair = g.o1 == g.R1;
-        const uint32_t a1 = last_of_pair ? g.L1 - g.L0 : a.B.tile_split[t + 1];
-        const uint32_t b0 = d0 - a0, b1 = d1 - a1;
-        const uint32_t la = a1 - a0, lb = b1 - b0;
-        for (uint32_t i = tid; i < la; i += 256) { s_x[i] = g.sx[g.L0 + a0 + i]; s_q[i] = g.sq[g.L0 + a0 + i]; }
-        for (uint32_t i = tid; i < lb; i += 256) { s_x[la + i] = g.sx[g.L1 + b0 + i]; s_q[la + i] = g.sq[g.L1 + b0 + i]; }
+        const uint32_t d0 = g.o0 - g.g.e[0], d1 = g.o1 - g.g.e[0];
+        const uint32_t a0 = a.B.tile_split[3 * (size_t)t], b0 = a.B.tile_split[3 * (size_t)t + 1], c0 = a.B.tile_split[3 * (size_t)t + 2];
+        // the next tile of the same group starts where this one ends; the group's last tile ends at the run ends
+        const bool last_of_group = g.o1 == g.g.e[4];
+        const uint32_t a1 = last_of_group ? g.g.e[1] - g.g.e[0] : a.B.tile_split[3 * (size_t)t + 3];
+        const uint32_t b1 = last_of_group ? g.g.e[2] - g.g.e[1] : a.B.tile_split[3 * (size_t)t + 4];
+        const uint32_t c1 = last_of_group ? g.g.e[3] - g.g.e[2] : a.B.tile_split[3 * (size_t)t + 5];
+        const uint32_t e0d = d0 - a0 - b0 - c0, e1d = d1 - a1 - b1 - c1;      // D's
+        const uint32_t p1 = a1 - a0, p2 = p1 + (b1 - b0), p3 = p2 + (c1 - c0), m = p3 + (e1d - e0d);      // m = o1 - o0 <= GT
+        const uint32_t sa = g.g.e[0] + a0, sb = g.g.e[1] + b0 - p1, sc = g.g.e[2] + c0 - p2, sd = g.g.e[3] + e0d - p3;      // LDS position i comes from s? + i (mod 2^32)
+        for (uint32_t i = tid; i < m; i += 256) {
+            const uint32_t src = (i < p1 ? sa : i < p2 ? sb : i < p3 ? sc : sd) + i;
+            s_x[i] = g.sx[src]; s_q[i] = g.sq[src];
+        }
         __syncthreads();
-        // merge in LDS: 8 outputs per thread, kept in registers until every thread has read its inputs, then through LDS again so that the
-        // stores are coalesced (a thread storing its own 8 outputs touched 64 sectors per instruction: a quarter of the kernel's time)
-        const uint32_t m = la + lb;
+        // two merge levels in LDS, 8 outputs per thread: kept in registers until every thread has read its inputs, then through LDS again -
+        // as the next level's input, and at the end so that the stores are coalesced (a thread storing its own 8 outputs touched 64 sectors
+        // per instruction: a quarter of the kernel's time)
         constexpr uint32_t C = 8;
         uint64_t ox[C]; uint32_t oq[C];
         const uint32_t e0 = tid * C, e1 = e0 + C < m ? e0 + C : m;      // GT = 256 * C outputs at most
-        if (e0 < m) {
-            uint32_t lo = e0 > lb ? e0 - lb : 0, hi = e0 < la ? e0 : la;
-            while (lo < hi) {
-                uint32_t mid = (lo + hi) >> 1;
-                if (s_x[mid] <= s_x[la + (e0 - 1 - mid)]) lo = mid + 1; else hi = mid;
-            }
-            uint32_t ia = lo, ib = e0 - lo;
-            uint64_t va = ia < la ? s_x[ia] : ~0ull, vb = ib < lb ? s_x[la + ib] : ~0ull;
-#pragma unroll
-            for (uint32_t u = 0; u < C; ++u) {
-                if (e0 + u < e1) {
-                    const bool takeL = ia < la && (ib >= lb || va <= vb);
-                    if (takeL) { ox[u] = va; oq[u] = s_q[ia]; ++ia; va = ia < la ? s_x[ia] : ~0ull; }
-                    else { ox[u] = vb; oq[u] = s_q[la + ib]; ++ib; vb = ib < lb ? s_x[la + ib] : ~0ull; }
-                }
-            }
-        }
+        m4_thread_merge<C>(s_x, s_q, p1, p2, p3, m, e0, ox, oq);
         __syncthreads();
 #pragma unroll
         for (uint32_t u = 0; u < C; ++u) if (e0 + u < e1) { s_x[e0 + u] = ox[u]; s_q[e0 + u] = oq[u]; }
         __syncthreads();
+        if (p2 != 0 && p2 != m) {      // uniform per block; with one side empty the first level gave the output
+            m4_thread_merge<C>(s_x, s_q, p2, m, m, m, e0, ox, oq);
+            __syncthreads();
+#pragma unroll
+            for (uint32_t u = 0; u < C; ++u) if (e0 + u < e1) { s_x[e0 + u] = ox[u]; s_q[e0 + u] = oq[u]; }
+            __syncthreads();
+        }
         for (uint32_t i = tid; i < m; i += 256) { g.dx[g.o0 + i] = s_x[i]; g.dq[g.o0 + i] = s_q[i]; }
         __syncthreads();
     }
@@ -2597,7 +2587,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (n == 0) continue;                 // decided by k_group_probe
         bool pre = (si.qlen >> 31) != 0;      // k_giant_top's par_fill_block applied: f, p and the dirty marks are there
         si.qlen &= 0x7fffffffu;
-        const bool in_b = giant_rounds(n) & 1;
+        const bool in_b = giant_passes(n, a.giant_fanin) & 1;
         uint64_t *sx = (in_b ? a.B.bx : a.B.ax) + si.off; uint32_t *sq = (in_b ? a.B.bq : a.B.aq) + si.off;
         if (tid == 0) s_found = 0;
         __syncthreads();
@@ -3524,7 +3514,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
         const uint64_t sort_cap[N_SORT_CLS] = {max_reads + 32 * waves, max_reads + 32 * waves, max_reads + 8 * waves, max_reads + 8 * waves, max_reads + waves, max_reads + waves};
         uint64_t sort_cap_sum = 0;
         for (int i = 0; i < N_SORT_CLS; ++i) sort_cap_sum += sort_cap[i];
-        uint64_t fixed = 4 * 64 * sizeof(SortItem) + 4096 + max_reads * (sizeof(BigMeta) + 8 + 8) + sort_cap_sum * sizeof(SortItem) + sort_cap[N_SORT_CLS - 1] * 4 + 16384;
+        uint64_t fixed = 4 * 64 * sizeof(SortItem) + 4096 + max_reads * (sizeof(BigMeta) + 8 + 16) + sort_cap_sum * sizeof(SortItem) + sort_cap[N_SORT_CLS - 1] * 4 + 16384;
         uint64_t per_anchor = 8 + 8 + 8 + 4 + 4 + 4 + 2 + (c->ext ? 8 + 3 : 0);   // ax bx az aq bq af (+ tile_split and cluster queue shares) (+ hz)
         uint64_t cap = left > fixed ? (left - fixed) / per_anchor : 0;
         cap &= ~15ull;
@@ -3541,7 +3531,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
         for (int i = 0; i < N_SORT_CLS; ++i) B.sort_items[i] = (SortItem *)take(sort_cap[i] * sizeof(SortItem));
         B.tile_base = (uint32_t *)take((max_reads + 1) * 4);
         B.giant_order = (uint32_t *)take(sort_cap[N_SORT_CLS - 1] * 4);
-        B.tile_split = (uint32_t *)take((cap / GT + max_reads + 2) * 4);
+        B.tile_split = (uint32_t *)take((cap / GT + max_reads + 2) * 12);      // three words per tile
         {   // a cluster of class c has more than {4096, 1024, 256, 64} anchors
             const uint64_t div[4] = {4096, 1024, 256, c->ext ? 8u : 64u};
             for (int i = 0; i < 4; ++i) { B.cl_cap[i] = (uint32_t)std::min<uint64_t>(cap / div[i] + 64, UINT32_MAX); B.cl_items[i] = (SortItem *)take((uint64_t)B.cl_cap[i] * sizeof(SortItem)); }
@@ -3881,9 +3871,9 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     hipLaunchKernelGGL((k_sort_lds<SORT_LDS_C, 4, 512>), dim3(256), dim3(512), 0, s1, k);
     hipLaunchKernelGGL(k_giant_scan, dim3(1), dim3(1024), 0, g, k);
     hipLaunchKernelGGL(k_giant_chunksort, dim3(256 * 3), dim3(256), 0, g, k);
-    for (uint32_t round = 0; round < 8; ++round) {      // run widths GT << round: up to 2^19 anchors per read
-        hipLaunchKernelGGL(k_giant_partition, dim3(256), dim3(256), 0, g, k, round);
-        hipLaunchKernelGGL(k_giant_merge, dim3(256 * 6), dim3(256), 0, g, k, round);      // 24 KB of LDS per block: six per CU
+    for (uint32_t pass = 0; pass < (k.giant_fanin == 4 ? 4u : 8u); ++pass) {      // run widths GT, 4 GT, ... (fan-in 2: GT << pass): up to 2^19 anchors per read
+        hipLaunchKernelGGL(k_giant_split, dim3(256), dim3(256), 0, g, k, pass);
+        hipLaunchKernelGGL(k_giant_merge4, dim3(256 * 6), dim3(256), 0, g, k, pass);      // 24 KB of LDS per block: six per CU
     }
     // flag-only hand-over (t_mode): the big clusters first (k_cluster_dp), then the small ones against the best score those gave
     const bool two_phase = k.t_mode && k.sink.best != nullptr;
@@ -4008,6 +3998,11 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     if (!getenv("SCRUBBY_HIP_AB_NOCHAIN")) k.dbg &= ~3;      // bits 0 / 1 switch the class kernels' chaining OFF (timing A/Bs: the answers are then wrong) - only with this second switch
     if (getenv("SCRUBBY_HIP_NO_PARFILL")) k.dbg |= 128;      // A/B: every cluster chained by the sequential DP
     k.top_max = TOPBT_MAX; k.pft_gmin = 32768u;
+    k.giant_fanin = 4u;
+    if (const char *env = getenv("SCRUBBY_HIP_GIANT_FANIN")) {      // A/B and tests: 2 = the two-way rounds
+        if (atoi(env) != 2 && atoi(env) != 4) { sh_set_error("SCRUBBY_HIP_GIANT_FANIN must be 2 or 4, not '%s'", env); return SH_ERR_BAD_ARG; }
+        k.giant_fanin = (uint32_t)atoi(env);
+    }
     if (const char *env = getenv("SCRUBBY_HIP_PFT_GMIN")) k.pft_gmin = (uint32_t)std::max(1, atoi(env));
     if (const char *env = getenv("SCRUBBY_HIP_TOPBT_MAX")) k.top_max = std::max(1, std::min(TOPBT_MAX, atoi(env)));
     if (getenv("SCRUBBY_HIP_NO_TOPBT")) k.dbg |= 512;        // A/B: clusters visited one by one even when the read's DP is done
