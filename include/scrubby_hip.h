@@ -601,6 +601,28 @@ sh_status sh_dbg_rmq_trace(int32_t device, uint64_t seed, int32_t n_ops, int32_t
  * results in the order of k_dbg_wave_ops (tests/test_wave_ops_gpu.py compares them with numpy) */
 sh_status sh_dbg_wave_ops(int32_t device, const int32_t *in32, const uint64_t *in64, int32_t bcast_lane, int32_t *out32, uint64_t *out64);
 
+/* ---- Kraken arm: database inspection (DESIGN.md §7 "Database inspection"): what kraken2-inspect prints, as recalled from
+ * dump_table.cc and CompactHashTable::GetValueCounts: PARITY WITH kraken2-inspect UNPINNED, like the rest of the arm.  One pass over
+ * the table in HBM: every non-empty cell (the whole cell is not 0) counts under its value, cell & ((1 << value_bits) - 1).  An
+ * occupied cell whose value is 0 or >= n_nodes is a bad value: counted in n_bad_values and nowhere else. */
+typedef struct sh_k2_inspect_stats { uint64_t n_cells, n_occupied, n_bad_values; float ms; int32_t pad; } sh_k2_inspect_stats;
+/* counts of the table as it is now (after any inserts).  d_counts: n_nodes uint64 in HBM, overwritten.  Asynchronous on stream unless stats != NULL. */
+sh_status sh_k2_value_counts_device(const sh_k2_db *db, uint64_t *d_counts, void *stream, sh_k2_inspect_stats *stats);
+sh_status sh_k2_value_counts(const sh_k2_db *db, uint64_t *counts /* host, n_nodes */, sh_k2_inspect_stats *stats);
+#define SH_K2_INSPECT_ZERO_COUNTS 1   /* kraken2-inspect --report-zero-counts: also the taxa whose clade count is 0 */
+#define SH_K2_INSPECT_MPA         2   /* kraken2-inspect --use-mpa-style: "d__A|p__B<tab>clade" per taxon of a lettered rank */
+/* host only, no GPU: the report over any taxonomy in taxo.k2d's layout.  flags: SH_K2_INSPECT_ZERO_COUNTS, SH_K2_INSPECT_MPA.  header (nullable) is written first, verbatim.  path NULL or "-" = stdout. */
+sh_status sh_k2_counts_report(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *names, uint64_t names_len, const char *ranks, uint64_t ranks_len,
+                              const uint64_t *counts, int32_t flags, const char *header, const char *path);
+/* the seven '#' lines of a database into buf (the cap / len convention of the hit-list formatter above) */
+sh_status sh_k2_inspect_header(const sh_k2_db *db, char *buf, uint64_t cap, uint64_t *len);
+/* `scrubby-hip k2-inspect`: open, count, write the header and the report.  skip_counts: the header only, nothing is launched.
+ * Bad values: SH_ERR_IO that names their number, no report.  A header size that differs from the occupied cells is named once on
+ * stderr; the header's value is printed all the same. */
+typedef struct sh_k2_inspect_config { const char *db, *output; int32_t skip_counts, report_zero_counts, use_mpa_style, device; } sh_k2_inspect_config;
+typedef struct sh_k2_inspect_result { uint64_t capacity, size_header, n_occupied, n_bad_values, n_nodes, n_taxa_with_minimizers; double s_open, s_count, s_report, s_total; } sh_k2_inspect_result;
+sh_status sh_k2_inspect_run(const sh_k2_inspect_config *cfg, sh_k2_inspect_result *out);
+
 #ifdef __cplusplus
 }
 #endif

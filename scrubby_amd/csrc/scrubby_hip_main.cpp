@@ -22,7 +22,8 @@ static void usage()
             "                  [--max-db-size BYTES] [--value-bits N] [--chunk-bytes N]\n"
             "                  [--mask-low-complexity [--mask-window 64] [--mask-threshold 20]]\n"
             "scrubby-hip k2-mask -i <in.fa[.gz|.bz2|.xz]> -o <out.fa[.gz|.bz2|.xz]> [-W 64] [-T 20] [-r x | --soft] [--line-width 60]\n"
-            "                  [--chunk-bytes N]\n");
+            "                  [--chunk-bytes N]\n"
+            "scrubby-hip k2-inspect -d <db dir> [-o report.txt] [--skip-counts] [--report-zero-counts] [--use-mpa-style] [--device N]\n");
 }
 
 // `scrubby classifier` (/root/reference/src/terminal.rs:204-279): clean reads from precomputed Kraken2 / Metabuli outputs
@@ -150,6 +151,34 @@ static int main_k2_mask(int argc, char **argv)
     return 0;
 }
 
+// `scrubby-hip k2-inspect`: the options a database was built with and its minimizers per taxon (kraken2-inspect's options)
+static int main_k2_inspect(int argc, char **argv)
+{
+    std::string db, out;
+    sh_k2_inspect_config c{};
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
+        if (a == "-d" || a == "--db") db = val();
+        else if (a == "-o" || a == "--output") out = val();
+        else if (a == "--skip-counts") c.skip_counts = 1;
+        else if (a == "--report-zero-counts") c.report_zero_counts = 1;
+        else if (a == "--use-mpa-style") c.use_mpa_style = 1;
+        else if (a == "--device") c.device = atoi(val().c_str());
+        else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+    }
+    if (db.empty()) { fprintf(stderr, "error: a database directory (-d) is required\n"); return 2; }
+    c.db = db.c_str(); c.output = out.empty() ? nullptr : out.c_str();
+    sh_k2_inspect_result r{};
+    sh_status st = sh_k2_inspect_run(&c, &r);
+    if (st != SH_OK) { fprintf(stderr, "error (%d): %s\n", st, sh_last_error()); return 1; }
+    // the report may be on stdout: the figures go to stderr
+    fprintf(stderr, "[scrubby-hip] capacity %llu, size %llu, occupied %llu, nodes %llu, taxa with minimizers %llu; open %.3f s, count %.3f s, report %.3f s, total %.3f s\n",
+            (unsigned long long)r.capacity, (unsigned long long)r.size_header, (unsigned long long)r.n_occupied, (unsigned long long)r.n_nodes,
+            (unsigned long long)r.n_taxa_with_minimizers, r.s_open, r.s_count, r.s_report, r.s_total);
+    return 0;
+}
+
 // `scrubby alignment` (/root/reference/src/terminal.rs:281-360)
 static int main_alignment(int argc, char **argv, const std::string &command)
 {
@@ -191,6 +220,7 @@ int main(int argc, char **argv)
 {
     if (argc >= 2 && std::string(argv[1]) == "k2-build") return main_k2_build(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "k2-mask") return main_k2_mask(argc, argv);
+    if (argc >= 2 && std::string(argv[1]) == "k2-inspect") return main_k2_inspect(argc, argv);
     if (argc >= 2 && (std::string(argv[1]) == "classifier" || std::string(argv[1]) == "alignment")) {
         std::string command;
         for (int i = 0; i < argc; ++i) { if (i) command += ' '; command += argv[i]; }

@@ -26,6 +26,8 @@
 //            list); HITS 2 redoes the listed units and writes their whole lists at their final offsets, nothing else.
 // The bound is the HBM gather rate: one 32-B sector per probe, ~40 probes per 150-bp read.
 #include "sh_common.h"
+#include "sh_k2_db.h"
+#include "sh_k2_inspect.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <cmath>
@@ -43,19 +45,6 @@
 #define K2Q_PROBE 0x80000000u
 #define K2Q_BORDER 0x40000000u
 #define K2Q_AMB 0x3fffffffu
-
-struct sh_k2_db {
-    int device = 0;
-    sh_k2_opts opts{};
-    uint64_t capacity = 0, size = 0;
-    int32_t key_bits = 0, value_bits = 0;
-    uint32_t *d_cells = nullptr, *d_parent = nullptr, *d_ext = nullptr;
-    unsigned long long *d_ctr = nullptr;         // [0] new cells claimed, [1] table full
-    std::vector<sh_k2_taxnode> nodes;
-    std::string names, ranks;
-    // opts.k2d fields carried through save/open
-    int32_t dna_db = 1, revcom_version = 1, db_version = 0, db_type = 0;
-};
 
 // ---- device helpers ----------------------------------------------------------------------------------------------
 __host__ __device__ static inline uint64_t k2_fmix64(uint64_t k)
@@ -1479,8 +1468,6 @@ static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, c
 }
 
 // ---- Kraken-style report (SURVEY.md App. B "Outputs consumed by Scrubby"; parsed by classifier.rs:449-466) -------------
-static const char *k2_pool(const std::string &pool, uint64_t off) { return off < pool.size() ? pool.c_str() + off : ""; }
-
 extern "C" sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *res, uint64_t n_units, const char *path)
 {
     SH_CHECK(db && path && (res || n_units == 0), SH_ERR_BAD_ARG, "sh_k2_write_report: null argument");
@@ -1494,32 +1481,8 @@ extern "C" sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *
     SH_CHECK(f, SH_ERR_IO, "cannot write %s", path);
     const double total = n_units ? (double)n_units : 1.0;
     if (unclassified) fprintf(f, "%6.2f\t%llu\t%llu\tU\t0\tunclassified\n", 100.0 * (double)unclassified / total, (unsigned long long)unclassified, (unsigned long long)unclassified);
-    // depth-first from the root, children by clade count (descending; ties by id), rank codes with a depth suffix
-    struct Frame { uint32_t id; std::string code; int code_depth; int depth; };
-    std::vector<Frame> stack;
-    if (clade[1]) stack.push_back(Frame{1, "R", 0, 0});
-    while (!stack.empty()) {
-        Frame fr = stack.back(); stack.pop_back();
-        const sh_k2_taxnode &nd = db->nodes[fr.id];
-        std::string code = fr.code; int cd = fr.code_depth;
-        if (fr.id != 1) {
-            const std::string rank = k2_pool(db->ranks, nd.rank_offset);
-            const char *letter = nullptr;
-            if (rank == "superkingdom") letter = "D"; else if (rank == "kingdom") letter = "K"; else if (rank == "phylum") letter = "P";
-            else if (rank == "class") letter = "C"; else if (rank == "order") letter = "O"; else if (rank == "family") letter = "F";
-            else if (rank == "genus") letter = "G"; else if (rank == "species") letter = "S";
-            if (letter) { code = letter; cd = 0; } else ++cd;
-        }
-        std::string rc = code; if (cd) rc += std::to_string(cd);
-        fprintf(f, "%6.2f\t%llu\t%llu\t%s\t%llu\t", 100.0 * (double)clade[fr.id] / total, (unsigned long long)clade[fr.id], (unsigned long long)direct[fr.id], rc.c_str(),
-                (unsigned long long)nd.external_id);
-        for (int i = 0; i < fr.depth; ++i) fputs("  ", f);
-        fprintf(f, "%s\n", k2_pool(db->names, nd.name_offset));
-        std::vector<uint32_t> kids;
-        for (uint64_t c = 0; c < nd.child_count; ++c) { const uint64_t id = nd.first_child + c; if (id < n && clade[id]) kids.push_back((uint32_t)id); }
-        std::sort(kids.begin(), kids.end(), [&](uint32_t x, uint32_t y) { return clade[x] != clade[y] ? clade[x] > clade[y] : x < y; });
-        for (size_t i = kids.size(); i-- > 0;) stack.push_back(Frame{kids[i], code, cd, fr.depth + 1});
-    }
+    // the rows are those of a database inspection (sh_k2_inspect.hip): one tree walk for both reports
+    shi_k2_report_rows(f, db->nodes.data(), n, db->names, db->ranks, clade.data(), direct.data(), total, 0);
     const bool ok = fclose(f) == 0;
     SH_CHECK(ok, SH_ERR_IO, "short write to %s", path);
     return SH_OK;

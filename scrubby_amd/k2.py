@@ -81,6 +81,22 @@ class K2MaskResult(C.Structure):
                [("s_mask", C.c_double), ("s_total", C.c_double)]
 
 
+class K2InspectStats(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_occupied", C.c_uint64), ("n_bad_values", C.c_uint64), ("ms", C.c_float), ("pad", C.c_int32)]
+
+
+class K2InspectConfig(C.Structure):
+    _fields_ = [("db", C.c_char_p), ("output", C.c_char_p), ("skip_counts", C.c_int32), ("report_zero_counts", C.c_int32),
+                ("use_mpa_style", C.c_int32), ("device", C.c_int32)]
+
+
+class K2InspectResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("capacity", "size_header", "n_occupied", "n_bad_values", "n_nodes", "n_taxa_with_minimizers")] + \
+               [(n, C.c_double) for n in ("s_open", "s_count", "s_report", "s_total")]
+
+
+INSPECT_ZERO_COUNTS, INSPECT_MPA = 1, 2
+
 RESULT_DTYPE = np.dtype([("taxid", "<u4"), ("call", "<u4"), ("total_kmers", "<u4"), ("hit_groups", "<u4")])
 # one hit-list entry: internal taxid (0 = not in the table / not looked up), HIT_AMBIGUOUS or HIT_BORDER, and its k-mer count
 HIT_DTYPE = np.dtype([("code", "<u4"), ("count", "<u4")])
@@ -259,6 +275,10 @@ def _mask_stats(st):
     return {n: getattr(st, n) for n, _ in K2MaskStats._fields_ if n != "pad"}
 
 
+def _inspect_stats(st):
+    return {n: getattr(st, n) for n, _ in K2InspectStats._fields_ if n != "pad"}
+
+
 def mask_low_complexity(records, window=64, threshold=20, replacement=b"x", return_stats=False):
     """Symmetric DUST on the GPU (sh_k2_mask_device) over a list of sequences; replacement None / 0 = soft masking (lower case).
     Returns the masked sequences as bytes, in order (and the call's statistics with return_stats=True)."""
@@ -320,6 +340,30 @@ def build_database(inputs, output_dir, taxonomy_dir=None, seqid2taxid=None, taxi
     r = K2BuildResult()
     S.check(S.load().sh_k2_build_run(C.byref(c), C.byref(r)))
     return {n: getattr(r, n) for n, _ in K2BuildResult._fields_ if n != "pad"}
+
+
+def counts_report(nodes, names, ranks, counts, path, zero_counts=False, mpa=False, header=None):
+    """kraken2-inspect's report (sh_k2_counts_report; host only, no GPU needed) over a taxonomy in taxo.k2d's layout (a K2TaxNode
+    array and the two string pools, as Taxonomy.arrays() gives them) and one count per node; header (optional) is written first,
+    verbatim; path None or "-" = stdout."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    assert len(c) == len(nodes), "one count per taxonomy node"
+    flags = (INSPECT_ZERO_COUNTS if zero_counts else 0) | (INSPECT_MPA if mpa else 0)
+    hb = None if header is None else (header if isinstance(header, bytes) else header.encode())
+    S.check(S.load().sh_k2_counts_report(nodes, C.c_uint64(len(nodes)), names, C.c_uint64(len(names)), ranks, C.c_uint64(len(ranks)),
+                                         C.c_void_p(c.ctypes.data), flags, hb, None if path is None else str(path).encode()))
+
+
+def inspect_database(db_dir, output=None, skip_counts=False, report_zero_counts=False, use_mpa_style=False, device=0):
+    """`scrubby-hip k2-inspect` (sh_k2_inspect_run): the header lines and the per-taxon minimizer report of a database directory,
+    to `output` or stdout; returns the result fields as a dict."""
+    S.require_gpu()
+    c = K2InspectConfig()
+    c.db, c.output = str(db_dir).encode(), str(output).encode() if output else None
+    c.skip_counts, c.report_zero_counts, c.use_mpa_style, c.device = int(bool(skip_counts)), int(bool(report_zero_counts)), int(bool(use_mpa_style)), device
+    r = K2InspectResult()
+    S.check(S.load().sh_k2_inspect_run(C.byref(c), C.byref(r)))
+    return {n: getattr(r, n) for n, _ in K2InspectResult._fields_}
 
 
 class K2Db:
@@ -482,6 +526,32 @@ class K2Db:
                                                  C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
                                                  C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st)))
         return {n: getattr(st, n) for n, _ in K2Stats._fields_}
+
+    def value_counts(self, return_stats=False):
+        """minimizers of the table per internal taxon (sh_k2_value_counts): uint64[n_nodes]; with return_stats=True also the
+        call's statistics (n_cells, n_occupied, n_bad_values, ms)"""
+        counts = np.zeros(self.info()["n_nodes"], dtype=np.uint64)
+        st = K2InspectStats()
+        S.check(S.load().sh_k2_value_counts(self.h, C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (counts, _inspect_stats(st)) if return_stats else counts
+
+    def value_counts_device(self, d_counts, stream=None, stats=False):
+        """sh_k2_value_counts_device into d_counts (a torch int64 tensor of n_nodes elements on the database's device, overwritten)
+        on `stream` (a torch stream; None: the current one).  Without stats the call only enqueues; with stats=True it waits and
+        returns the statistics."""
+        assert d_counts.numel() >= self.info()["n_nodes"] and d_counts.element_size() == 8 and d_counts.is_contiguous()
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else S._stream_ptr()
+        st = K2InspectStats() if stats else None
+        S.check(S.load().sh_k2_value_counts_device(self.h, C.c_void_p(d_counts.data_ptr()), sp, C.byref(st) if stats else None))
+        return _inspect_stats(st) if stats else None
+
+    def inspect_header(self):
+        """the seven '#' lines kraken2-inspect prints in front of its report (sh_k2_inspect_header)"""
+        n = C.c_uint64()
+        S.check(S.load().sh_k2_inspect_header(self.h, None, C.c_uint64(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value + 1)
+        S.check(S.load().sh_k2_inspect_header(self.h, buf, C.c_uint64(n.value + 1), C.byref(n)))
+        return buf.value.decode()
 
     def write_report(self, results, path):
         r = np.ascontiguousarray(results, dtype=RESULT_DTYPE)

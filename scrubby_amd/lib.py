@@ -140,6 +140,7 @@ EXPORTS = [
     "sh_k2_taxonomy_header_taxon", "sh_k2_taxonomy_free", "sh_k2_capacity_plan", "sh_k2_max_db_size", "sh_k2_set_min_acceptable_hash",
     "sh_k2_insert_library_device", "sh_k2_estimator_create", "sh_k2_estimate_capacity_device", "sh_k2_estimator_free", "sh_k2_build_run",
     "sh_k2_mask_device", "sh_k2_mask_host", "sh_k2_mask_run",
+    "sh_k2_value_counts_device", "sh_k2_value_counts", "sh_k2_counts_report", "sh_k2_inspect_header", "sh_k2_inspect_run",
 ]
 
 _LIB = None
