@@ -600,6 +600,30 @@ sh_status sh_dbg_rmq_trace(int32_t device, uint64_t seed, int32_t n_ops, int32_t
 /* test aid: the wave primitives of csrc/sh_wave.h (DPP scans / reductions / broadcasts) on one wave of inputs: 12 x 64 int32 and 9 x 64 uint64
  * results in the order of k_dbg_wave_ops (tests/test_wave_ops_gpu.py compares them with numpy) */
 sh_status sh_dbg_wave_ops(int32_t device, const int32_t *in32, const uint64_t *in64, int32_t bcast_lane, int32_t *out32, uint64_t *out64);
+/* Test aids: the two alignment kernels of the extension stage called directly (csrc/sh_dbg_align.hip; tests/test_ksw_gpu.py compares them
+ * with the oracle's mma_ksw_extd2 / mma_ksw_ll bit for bit).  A batch of cases runs in one launch, one 64-lane block per case.  The sequences are
+ * codes 0..4 at byte offsets of one host blob, so a case can start at any alignment.
+ * route 0: the case goes through ksw_extd2_wave as the short-read stage calls it (state and directions in LDS / directions in HBM / both in
+ * HBM); route 1: through lr_align_pair as the long-read stage calls it (never all in LDS).  Every wave's scratch is sized for the largest
+ * case of the batch that is not marked `unsized`; an unsized case must be one the code under test then turns away (else SH_ERR_BAD_ARG).
+ * Result: the eleven fields of ksw_extz_t, the storage form taken (0 / 1 / 2; route 1 turned away by lr_align_pair: -1 = direction bytes
+ * beyond the scratch, -2 = bases beyond it, fields as after a reset) and where the case's CIGAR words (len << 4 | op) start in out_cigar, which holds
+ * cigar_cap >= the sum of qlen + tlen over the batch words. */
+typedef struct sh_dbg_ksw_case {
+    uint64_t q_off, t_off;
+    int32_t qlen, tlen, a, b, sc_ambi, q, e, q2, e2, w, zdrop, end_bonus, flag, route, unsized, pad;
+} sh_dbg_ksw_case;
+typedef struct sh_dbg_ksw_result {
+    int32_t max, zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, reach_end, n_cigar, form;
+    uint64_t cigar_off;
+} sh_dbg_ksw_result;
+sh_status sh_dbg_ksw_extd2(int32_t device, const uint8_t *blob, uint64_t blob_len, const sh_dbg_ksw_case *cases, int32_t n_cases,
+                           sh_dbg_ksw_result *out, uint32_t *out_cigar, uint64_t cigar_cap);
+/* the local alignment behind the inversion test (lr_ksw_ll_wave), rows sized as the long-read working memory sizes them: the score and the
+ * end of the alignment in the query (qe) and the target (te) */
+typedef struct sh_dbg_ll_case { uint64_t q_off, t_off; int32_t qlen, tlen, a, b, sc_ambi, gapo, gape, pad; } sh_dbg_ll_case;
+typedef struct sh_dbg_ll_result { int32_t score, qe, te, pad; } sh_dbg_ll_result;
+sh_status sh_dbg_ksw_ll(int32_t device, const uint8_t *blob, uint64_t blob_len, const sh_dbg_ll_case *cases, int32_t n_cases, sh_dbg_ll_result *out);
 
 /* ---- Kraken arm: database inspection (DESIGN.md §7 "Database inspection"): what kraken2-inspect prints, as recalled from
  * dump_table.cc and CompactHashTable::GetValueCounts: PARITY WITH kraken2-inspect UNPINNED, like the rest of the arm.  One pass over

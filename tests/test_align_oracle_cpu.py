@@ -43,23 +43,44 @@ def cigar_score(cig, qs, ts, mat, q, e, q2, e2):
     return sc, i, j
 
 
+def _check_kat(L, c, w):
+    for flag in (0, 0x40, 0x40 | 0x02 | 0x80, 0x02):          # global; extension; extension, gaps right-aligned, CIGAR reversed; right-aligned
+        ez, cig, mat = extd2(L, c["query"], c["target"], c["a"], c["b"], c["sc_ambi"], c["q"], c["e"], c["q2"], c["e2"], w, -1, 10 if flag & 0x40 else -1, flag)
+        x = c["expect"]
+        assert (ez.score, ez.max, ez.mqe, ez.mte) == (x["score"], x["max"], x["mqe"], x["mte"]), (c, flag)
+        s2, i2, j2 = cigar_score(cig if not (flag & 0x80) else cig[::-1], c["query"], c["target"], mat, c["q"], c["e"], c["q2"], c["e2"])
+        if flag & 0x40:
+            end = (ez.mqe_t + 1, len(c["query"])) if ez.reach_end else (ez.max_t + 1, ez.max_q + 1)
+            want = ez.mqe if ez.reach_end else ez.max
+        else:
+            end, want = (len(c["target"]), len(c["query"])), ez.score
+        if cig:
+            assert (i2, j2) == end and s2 == want, (c, flag, cig)
+
+
 def test_ksw_against_the_independent_known_answers(oracle):
     L = oracle.lib()
     kat = json.load(open(os.path.join(HERE, "golden", "align_kat.json")))
     assert len(kat["cases"]) >= 100
     for c in kat["cases"]:
-        for flag in (0, 0x40, 0x40 | 0x02 | 0x80, 0x02):          # global; extension; extension, gaps right-aligned, CIGAR reversed; right-aligned
-            ez, cig, mat = extd2(L, c["query"], c["target"], c["a"], c["b"], c["sc_ambi"], c["q"], c["e"], c["q2"], c["e2"], 200, -1, 10 if flag & 0x40 else -1, flag)
-            x = c["expect"]
-            assert (ez.score, ez.max, ez.mqe, ez.mte) == (x["score"], x["max"], x["mqe"], x["mte"]), (c, flag)
-            s2, i2, j2 = cigar_score(cig if not (flag & 0x80) else cig[::-1], c["query"], c["target"], mat, c["q"], c["e"], c["q2"], c["e2"])
-            if flag & 0x40:
-                end = (ez.mqe_t + 1, len(c["query"])) if ez.reach_end else (ez.max_t + 1, ez.max_q + 1)
-                want = ez.mqe if ez.reach_end else ez.max
-            else:
-                end, want = (len(c["target"]), len(c["query"])), ez.score
-            if cig:
-                assert (i2, j2) == end and s2 == want, (c, flag, cig)
+        _check_kat(L, c, 200)
+
+
+def kat_wide():
+    """align_kat_wide.json with its sequences as code lists: the plain programme at the shapes where the device kernel changes path"""
+    kat = json.load(open(os.path.join(HERE, "golden", "align_kat_wide.json")))
+    for c in kat["cases"]:
+        c["query"], c["target"] = ["ACGTN".index(x) for x in c["query"]], ["ACGTN".index(x) for x in c["target"]]
+    return kat["cases"]
+
+
+def test_ksw_against_the_independent_known_answers_where_the_device_goes_wide(oracle):
+    L = oracle.lib()
+    cases = kat_wide()
+    assert len(cases) >= 24 and max(len(c["query"]) for c in cases) == 460
+    assert sum(min(len(c["query"]), len(c["target"])) > 256 for c in cases) >= 8      # diagonals of more than 256 cells
+    for c in cases:
+        _check_kat(L, c, -1)
 
 
 def test_ksw_zdrop_and_band(oracle):
