@@ -624,6 +624,29 @@ sh_status sh_dbg_ksw_extd2(int32_t device, const uint8_t *blob, uint64_t blob_le
 typedef struct sh_dbg_ll_case { uint64_t q_off, t_off; int32_t qlen, tlen, a, b, sc_ambi, gapo, gape, pad; } sh_dbg_ll_case;
 typedef struct sh_dbg_ll_result { int32_t score, qe, te, pad; } sh_dbg_ll_result;
 sh_status sh_dbg_ksw_ll(int32_t device, const uint8_t *blob, uint64_t blob_len, const sh_dbg_ll_case *cases, int32_t n_cases, sh_dbg_ll_result *out);
+/* Test aid: the variants of the chaining DP (mg_lchain_dp) and of the backtrack (mg_chain_backtrack) in csrc/sh_chain.h, called directly
+ * (csrc/sh_dbg_chain.hip; tests/test_chain_gpu.py compares them with the oracle's mmo_chain_arrays, integers only).  One launch per DP variant,
+ * one block per case, with the block size the product runs the variant with.
+ * x / q: n_total sorted anchors (x = strand<<63 | contig<<32 | ref pos, q = query pos; bit 31 of q marks the first anchor of a cluster where
+ * the variant expects it: 6, 7 and the backtrack 5); a case reads n of them from `off` (variant 3: in any order, it sorts them itself).
+ * dp: 0 = none, f / p are taken from f_in / p_in; 1 chain_dp (LargeStore); 2 chain_dp_mask (SliceStore); 3 chain_dp_mask over SmallStore<32>,
+ *     filled with set_raw + sort_finalize; 4 chain_dp_wave; 5 chain_dp_ring; 6 par_fill_block (256 threads); 7 par_fill_tiled (512 threads, g_min).
+ * bt: 0 = none; 1 backtrack_small; 2 backtrack_mask; 3 backtrack_heap; 4 backtrack_wave_top; 5 backtrack_block_top (a zeroed ChainSink, at most
+ *     top_cap candidates); 6 first_chain_quick.  bt 1..4 and 6 go with dp 0..5 (after dp 3 over the SmallStore: bt 2 only), bt 5 with dp 0, 6, 7 (dp 0 and 6: 256 threads).
+ * The outputs of case i start at o_i = the sum of n over the cases before it, in f_in, p_in, f, p, t (what the store holds at the end) and,
+ * times five, in chains: (zi, end_i, score, cnt, zf) per accepted chain in visit order, recorded by the test emitter (whose done() is false).
+ * ret: the DP's return value; bt_ret: backtrack 5's return value, 6's result.  A case its variant cannot take (n > 64 for the masks; n > 32,
+ * q > 65535 or k * n > 65535 for the SmallStore; max_iter > 8000 for the ring; unsorted anchors; a combination not listed) is SH_ERR_BAD_ARG
+ * before any launch. */
+typedef struct sh_dbg_chain_case {
+    uint64_t off;
+    int32_t n, qlen, dp, bt, g_min, first_only, top_cap, pad;
+    int32_t k, is_sr, min_cnt, min_sc, max_gap, max_gap_ref, max_frag_len, bw, max_skip, max_iter;
+    float chain_gap_scale, chain_skip_scale;
+} sh_dbg_chain_case;
+typedef struct sh_dbg_chain_result { int32_t ret, bt_ret, n_u, best, n_emit, pad; } sh_dbg_chain_result;
+sh_status sh_dbg_chain(int32_t device, const uint64_t *x, const uint32_t *q, uint64_t n_total, const sh_dbg_chain_case *cases, int32_t n_cases,
+                       const int32_t *f_in, const int32_t *p_in, sh_dbg_chain_result *out, int32_t *f, int32_t *p, int32_t *t, int32_t *chains);
 
 /* ---- Kraken arm: database inspection (DESIGN.md §7 "Database inspection"): what kraken2-inspect prints, as recalled from
  * dump_table.cc and CompactHashTable::GetValueCounts: PARITY WITH kraken2-inspect UNPINNED, like the rest of the arm.  One pass over

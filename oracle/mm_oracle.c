@@ -712,6 +712,49 @@ static int32_t chain_dp(const mmo_opts *o, scratch_t *s, int64_t n, int k_idx, i
     return chain_backtrack(o, s, n, max_drop, best_score);
 }
 
+/* mg_lchain_dp + mg_chain_backtrack over a caller's sorted anchors (x = strand<<63 | rid<<32 | ref pos, y = q_span<<32 | query pos): the DP
+ * arrays f / p (n each) and the chains in visit order, u[c] = score<<32 | cnt (at most n) with their anchors from the last one backwards in
+ * v (at most n).  For tests that compare the arrays themselves (tests/chain_ref.py, the device variants).  Returns the number of chains. */
+int32_t mmo_chain_arrays(const mmo_opts *o, int k, int qlen, const uint64_t *x, const uint64_t *y, int64_t n, int32_t *f, int64_t *p,
+                         uint64_t *u, int32_t *v, int32_t *n_u, int64_t *n_v)
+{
+    scratch_t s;
+    int32_t best = 0, nu;
+    int64_t i;
+    memset(&s, 0, sizeof(s));
+    *n_u = 0; *n_v = 0;
+    if (n <= 0) return 0;
+    s.a = (m128 *)malloc(sizeof(m128) * (size_t)n); s.cap_a = n;
+    for (i = 0; i < n; ++i) s.a[i].x = x[i], s.a[i].y = y[i];
+    nu = chain_dp(o, &s, n, k, qlen, &best);
+    memcpy(f, s.f, 4 * (size_t)n);
+    memcpy(p, s.p, 8 * (size_t)n);
+    if (nu > 0) memcpy(u, s.u, 8 * (size_t)nu);
+    if (s.n_v > 0) memcpy(v, s.v, 4 * (size_t)s.n_v);
+    *n_u = nu; *n_v = s.n_v;
+    scratch_free(&s);
+    return nu;
+}
+
+/* mg_chain_backtrack alone, over a caller's f / p (p[i] < i or -1): the chains as mmo_chain_arrays returns them */
+int32_t mmo_backtrack_arrays(const mmo_opts *o, int64_t n, const int32_t *f, const int64_t *p, uint64_t *u, int32_t *v, int32_t *n_u, int64_t *n_v)
+{
+    scratch_t s;
+    int32_t best = 0, nu;
+    memset(&s, 0, sizeof(s));
+    *n_u = 0; *n_v = 0;
+    if (n <= 0) return 0;
+    s.f = (int32_t *)malloc(4 * (size_t)n); s.t = (int32_t *)malloc(4 * (size_t)n); s.p = (int64_t *)malloc(8 * (size_t)n);
+    s.z = (m128 *)malloc(16 * (size_t)n * 2); s.cap_dp = n;
+    memcpy(s.f, f, 4 * (size_t)n); memcpy(s.p, p, 8 * (size_t)n);
+    nu = chain_backtrack(o, &s, n, o->bw, &best);
+    if (nu > 0) memcpy(u, s.u, 8 * (size_t)nu);
+    if (s.n_v > 0) memcpy(v, s.v, 4 * (size_t)s.n_v);
+    *n_u = nu; *n_v = s.n_v;
+    scratch_free(&s);
+    return nu;
+}
+
 /* compact_a of mg_lchain_dp: each chain's anchors in ascending order, chains re-ordered by the target position of their
  * first anchor (stable for equal keys); u[] follows.  Result in s->b. */
 static void compact_chains(scratch_t *s)

@@ -124,6 +124,13 @@ int32_t mmo_comput_sc(uint64_t ai_x, uint64_t ai_y, uint64_t aj_x, uint64_t aj_y
                       int32_t max_dist_y, int32_t bw, float chn_pen_gap, float chn_pen_skip);
 float mmo_log2(float x);
 
+/* mg_lchain_dp + mg_chain_backtrack over caller-supplied sorted anchors: f / p of every anchor, the chains in visit order (u = score<<32 | cnt,
+ * v = their anchors from the last one backwards); see mm_oracle.c */
+int32_t mmo_chain_arrays(const mmo_opts *o, int k, int qlen, const uint64_t *x, const uint64_t *y, int64_t n, int32_t *f, int64_t *p,
+                         uint64_t *u, int32_t *v, int32_t *n_u, int64_t *n_v);
+/* mg_chain_backtrack alone over caller-supplied f / p */
+int32_t mmo_backtrack_arrays(const mmo_opts *o, int64_t n, const int32_t *f, const int64_t *p, uint64_t *u, int32_t *v, int32_t *n_u, int64_t *n_v);
+
 #ifdef __cplusplus
 }
 #endif

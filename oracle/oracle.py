@@ -112,6 +112,11 @@ def lib():
     L.mmo_comput_sc.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_float, C.c_float]
     L.mmo_comput_sc.restype = C.c_int32
+    L.mmo_chain_arrays.argtypes = [C.POINTER(Opts), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.mmo_chain_arrays.restype = C.c_int32
+    L.mmo_backtrack_arrays.argtypes = [C.POINTER(Opts), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.mmo_backtrack_arrays.restype = C.c_int32
     L.mmo_log2.argtypes = [C.c_float]
     L.mmo_log2.restype = C.c_float
     L.syn_cpu_ref.argtypes = [C.POINTER(RefParams), C.c_uint64, C.c_uint64, C.c_void_p]
@@ -150,6 +155,41 @@ def preset(name):
     if rc != 0:
         raise ValueError(f"preset {name!r}: rc={rc}")
     return o
+
+
+def chain_arrays(o, k, qlen, x, q):
+    """mg_lchain_dp + mg_chain_backtrack over sorted anchors (x, q) with q_span = k: f, p and the chains in visit order as
+    (zi, end_i, score, cnt, zf) - the last anchor, the index the walk stopped at (-1 = root), the score, the anchors, f of zi."""
+    x = np.ascontiguousarray(x, np.uint64)
+    y = np.ascontiguousarray(q, np.uint64) | np.uint64(k << 32)
+    n = len(x)
+    f, p = np.zeros(n, np.int32), np.zeros(n, np.int64)
+    u, v = np.zeros(n, np.uint64), np.zeros(n, np.int32)
+    n_u, n_v = C.c_int32(0), C.c_int64(0)
+    lib().mmo_chain_arrays(C.byref(o), k, qlen, x.ctypes.data, y.ctypes.data, n, f.ctypes.data, p.ctypes.data, u.ctypes.data, v.ctypes.data,
+                           C.byref(n_u), C.byref(n_v))
+    return f, p.astype(np.int32), _chain_list(f, p, u, v, n_u.value, n_v.value)
+
+
+def _chain_list(f, p, u, v, n_u, n_v):
+    chains, at = [], 0
+    for c in range(n_u):
+        sc, cnt = int(u[c]) >> 32, int(u[c]) & 0xffffffff
+        zi, last = int(v[at]), int(v[at + cnt - 1])
+        chains.append((zi, int(p[last]), sc, cnt, int(f[zi])))
+        at += cnt
+    assert at == n_v
+    return chains
+
+
+def backtrack_arrays(o, f, p):
+    """mg_chain_backtrack alone over given f / p: the chains as chain_arrays returns them"""
+    f, p = np.ascontiguousarray(f, np.int32), np.ascontiguousarray(p, np.int64)
+    n = len(f)
+    u, v = np.zeros(n, np.uint64), np.zeros(n, np.int32)
+    n_u, n_v = C.c_int32(0), C.c_int64(0)
+    lib().mmo_backtrack_arrays(C.byref(o), n, f.ctypes.data, p.ctypes.data, u.ctypes.data, v.ctypes.data, C.byref(n_u), C.byref(n_v))
+    return _chain_list(f, p, u, v, n_u.value, n_v.value)
 
 
 def sketch(seq, w, k, rid=0):

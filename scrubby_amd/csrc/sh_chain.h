@@ -58,6 +58,9 @@ struct ChainParams {
     int32_t ext_a, ext_b, ext_amb, ext_zdrop;      // scores of the middle check (mm_test_zdrop over the ungapped stretch)
 };
 
+// chn_pen_gap / chn_pen_skip of mg_lchain_dp from an option's scale (host side: fill_chain_params, and the debug entry sh_dbg_chain)
+static inline float chain_pen_of(float scale, int32_t k) { return (float)(scale * 0.01 * k); }
+
 // what the middle check reads: the reference (4-bit codes) and the reads (ASCII)
 struct BaseCtx { const uint8_t *ref; const uint64_t *cstart; const uint8_t *bases; };
 

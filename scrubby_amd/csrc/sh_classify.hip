@@ -3358,8 +3358,8 @@ static void fill_chain_params(const sh_opts &o, int32_t mid_occ, ChainParams &P)
     P.min_cnt = o.min_cnt; P.min_sc = o.min_chain_score;
     P.max_gap = o.max_gap; P.max_gap_ref = o.max_gap_ref; P.max_frag_len = o.max_frag_len; P.bw = o.bw;
     P.max_skip = o.max_chain_skip; P.max_iter = o.max_chain_iter;
-    P.pen_gap = (float)(o.chain_gap_scale * 0.01 * o.k);
-    P.pen_skip = (float)(o.chain_skip_scale * 0.01 * o.k);
+    P.pen_gap = chain_pen_of(o.chain_gap_scale, o.k);
+    P.pen_skip = chain_pen_of(o.chain_skip_scale, o.k);
     P.q_occ_frac = o.q_occ_frac;
     const bool early_ok = o.k > 0 && (o.min_chain_score + o.k - 1) / o.k >= o.min_cnt && o.bw >= o.min_chain_score && o.bw / o.k + 1 >= o.min_cnt;
     P.flag_stop = early_ok && !getenv("SCRUBBY_HIP_NO_FLAG_STOP") ? o.min_chain_score : INT32_MAX;

@@ -7,6 +7,8 @@ its minimap2 dependency is not on this box, so these vectors are AUTHORED here:
                         pure Python (window minimum over canonical k-mer hashes, straight from the
                         published (w,k)-minimizer definition), NOT by the C state machine;
   * chain_kat.json    — hand-computable pair scores of the chaining recurrence;
+  * chain_dp_kat.json — f, p and the chains of about twenty small anchor sets at the edges of the chaining recurrence (ties, the max_skip
+                        break, the max_ii shortcut, the window, the backtrack's drop), from the plain model tests/chain_ref.py alone;
   * classify_kat.json — a 6 kb toy reference, reads cut from it (expected host) and unrelated
                         reads (expected retained), with the expected flags by construction.
 Run from the repo root:  python tests/golden/make_golden.py
@@ -17,6 +19,7 @@ import os
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
 CODE = {65: 0, 67: 1, 71: 2, 84: 3}
 
 
@@ -60,7 +63,32 @@ def brute_minimizers(seq, w, k):
     return sorted(out, key=lambda t: t[1])
 
 
+CHAIN_KAT = ("edge_dq0", "edge_dq1", "edge_dq_mdy_sr", "edge_dq_mdy1_sr", "edge_dr0", "edge_dd_bw", "edge_dd_bw1", "edge_dg_k", "edge_dg_k1",
+             "edge_win_mdx", "edge_win_mdx1", "edge_group", "edge_strand", "tie_dq_0", "tie_dq_3", "skip_dense_0", "skip_dense_1", "skip_dense_2",
+             "maxii_tie", "maxii_20", "iter_50", "clus_mixed", "tandem_0", "tandem_6", "groups_9x3")
+
+
+def chain_dp_kat():
+    """the chaining edges: the model's f, p and chains on small cases of tests/chain_cases.py (the first dozen have two to four anchors and
+    can be checked by hand with the pair scores of chain_kat.json).  The model asks the oracle for the pair score only."""
+    import sys
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from oracle import oracle as O
+    from tests import chain_cases as K, chain_ref as R
+    by_name = {c["name"]: c for c in K.table()}
+    out = []
+    for name in CHAIN_KAT:
+        c = by_name[name]
+        m = R.run(O.lib(), c["o"], c["qlen"], [int(v) for v in c["x"]], [int(v) for v in c["q"]])
+        out.append({"name": name, "opt": c["o"]._asdict(), "qlen": c["qlen"], "x": [int(v) for v in c["x"]], "q": [int(v) for v in c["q"]],
+                    "f": m.f, "p": m.p, "chains": [list(ch) for ch in m.chains]})
+    json.dump({"comment": "tests/chain_ref.py on cases of tests/chain_cases.py: f, p, chains as [zi, end_i, score, cnt, zf] in visit order", "cases": out},
+              open(os.path.join(HERE, "chain_dp_kat.json"), "w"), indent=None, separators=(",", ":"))
+
+
 def main():
+    chain_dp_kat()
     rng = np.random.default_rng(20261003)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
     sk = []
