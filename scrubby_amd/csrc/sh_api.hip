@@ -135,9 +135,7 @@ extern "C" sh_status sh_classify_batch(const sh_index *idx, const sh_opts *opts,
     for (uint64_t r = 0; r < n_reads; ++r) max_len = std::max<uint32_t>(max_len, (uint32_t)std::min<uint64_t>(offsets[r + 1] - offsets[r], UINT32_MAX));
     for (uint64_t r0 = 0; r0 < n_reads; r0 += CH) piece_bases = std::max(piece_bases, offsets[std::min(n_reads, r0 + CH)] - offsets[r0]);
     const uint64_t need_reads = std::min(CH, n_reads);
-    std::string env_sig;
-    for (const char *v : {"SCRUBBY_HIP_ARENA_MB", "SCRUBBY_HIP_NO_FLAG_STOP", "SCRUBBY_HIP_NO_PAIR", "SCRUBBY_HIP_PAIR_MIN", "SCRUBBY_HIP_NO_S1", "SCRUBBY_HIP_EXT_MB", "SCRUBBY_HIP_EXT_REGCAP", "SCRUBBY_HIP_NO_LEMMA",
-                          "SCRUBBY_HIP_LEXT_A", "SCRUBBY_HIP_LEXT_BIG_A", "SCRUBBY_HIP_LEXT_P_KB", "SCRUBBY_HIP_RMQ_EXACT_MAX", "SCRUBBY_HIP_RMQ_ONE_LANE", "SCRUBBY_HIP_COOP_MIN", "SCRUBBY_HIP_COOP_RUN", "SCRUBBY_HIP_E2_JOIN_MIN", "SCRUBBY_HIP_LEXT_BIG_P_KB", "SCRUBBY_HIP_STAGE_MB", "SCRUBBY_HIP_STREAMS"}) { const char *e = getenv(v); env_sig += e ? e : "-"; env_sig += '|'; }
+    const std::string env_sig = shi_switches_sig();      // what sh_ctx_create reads from the environment
     const bool no_pool = false;
 
     BatchScratch *B = nullptr;

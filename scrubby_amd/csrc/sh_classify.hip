@@ -728,7 +728,7 @@ struct K2Args {
     ChainSink sink; int32_t emit;                   // SH_F_CIGAR: every kept chain is handed to the extension stage; no flag-only shortcut in the DP
     BaseCtx BC;
     int32_t quiet;      // k_chain_large re-running reads that were counted before: no statistics
-    int32_t dbg, dbg_slot;      // SCRUBBY_HIP_DBG (k_pair_pass: bit 4 counts what the middle check is handed, in Counters::pair_mid[dbg_slot ..])
+    int32_t dbg, dbg_slot;      // CallSwitches::dbg (k_pair_pass: DBG_STATS counts what the middle check is handed, in Counters::pair_mid[dbg_slot ..])
 };
 
 // hi word (strand | contig) of anchor group g of a read chained in a SmallStore, for the ranks beyond the store's register table
@@ -964,7 +964,7 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
         if (distinct == 2 && a.P.ext_lemma) {      // wave-uniform: the stretches above, the wave on one lane's request at a time
             const bool mid_ok = resolve_mid_wave(need_mid, mid, a.bases + a.offsets[r], qlen_, a.BC, a.P);
             found = found || (need_mid && mid_ok);
-            if (a.dbg & 16) { n_mid_wave += (uint32_t)__popcll(__ballot(need_mid)); n_mid_ok_wave += (uint32_t)__popcll(__ballot(need_mid && mid_ok)); }
+            if (a.dbg & DBG_STATS) { n_mid_wave += (uint32_t)__popcll(__ballot(need_mid)); n_mid_ok_wave += (uint32_t)__popcll(__ballot(need_mid && mid_ok)); }
         }
         if (distinct == 1 && __ballot(found) != 0) {
             uint32_t mx = found ? n_seed : 0u;
@@ -1784,7 +1784,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
             continue;
         }
-        if (!LONG && a.flag_only && !a.emit && P.pair_dq_max > 0 && n_st == 1 && n_a > (uint32_t)P.pair_min_anchors && pair_decides(rec0, my_n0, n_seed, lane, a.positions, P, ((a.dbg & 16) && (!(a.dbg & 128) || n_a > 4096u)) ? &a.ctr->n_leg_reason[3] : nullptr)) {
+        if (!LONG && a.flag_only && !a.emit && P.pair_dq_max > 0 && n_st == 1 && n_a > (uint32_t)P.pair_min_anchors && pair_decides(rec0, my_n0, n_seed, lane, a.positions, P, ((a.dbg & DBG_STATS) && (!(a.dbg & DBG_NO_PARFILL) || n_a > 4096u)) ? &a.ctr->n_leg_reason[3] : nullptr)) {
             // decided without a single anchor: sh_stats.n_anchors still counts what the occurrence filter admitted
             if (lane == 0) { BigMeta m{r, n_a, rep_len, 0u}; a.B.meta[w] = m; a.B.acc_nu[w] = 1; a.B.acc_best[w] = P.min_sc; }
             anchors_wave += n_a; ++n_pair;
@@ -1903,7 +1903,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                                 nullptr, nullptr, a.emit ? &sink_l : nullptr, r, nullptr);      // <= 64 anchors: no cluster needs a heap
             n_u = wave_all_add(n_u); best = wave_all_max(best);
             if (lane == 0) { a.B.acc_nu[w] = n_u; a.B.acc_best[w] = best; }
-            if ((a.dbg & 16) && lane == 0) { atomicAdd(&a.ctr->sort_tot[N_SORT_CLS], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[N_SORT_CLS], (unsigned long long)n_a); }
+            if ((a.dbg & DBG_STATS) && lane == 0) { atomicAdd(&a.ctr->sort_tot[N_SORT_CLS], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[N_SORT_CLS], (unsigned long long)n_a); }
             __syncthreads();
         } else if (to_stage) {
             // the anchors are in the staging buffer; k_lr_locus decides which of them can matter, moves those to the arena and lists the read in a sort class
@@ -1916,7 +1916,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             SortItem *const items = a.B.tabs->sort_items[cls];
             for (uint32_t i = lo + lane; i < hi; i += 64) items[i].n = 0;
             if (lane == 0) { SortItem it{w, n_a, (uint32_t)qlen, 0, off}; items[si] = it; }
-            if ((a.dbg & 16) && lane == 0) { atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_a); }
+            if ((a.dbg & DBG_STATS) && lane == 0) { atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_a); }
         }
     }
     for (int cls = 0; cls < N_SORT_CLS; ++cls)
@@ -1993,7 +1993,7 @@ __global__ __launch_bounds__(256) void k_lr_locus(K3Args a, int lc)
         const uint32_t V3 = block_max(t1 < V2 ? t1 : (t2 < V2 ? t2 : t3), 2);
         uint32_t T = V3 < (V1 >> 4) ? V3 : (V1 >> 4);
         if ((int32_t)si.qlen < a.locus_min_qlen) T = 0;      // a short read: whether the long join runs can hinge on a chain left out (lr_chains_wave) - it keeps everything
-        if (a.dbg & 1024) T = V1;      // tests (SCRUBBY_HIP_LOCUS_TOP1): the largest run only - reads with a second locus must be caught and redone
+        if (a.dbg & DBG_LOCUS_TOP1) T = V1;      // tests (SCRUBBY_HIP_LOCUS_TOP1): the largest run only - reads with a second locus must be caught and redone
         if (T < min_cnt) T = min_cnt;
         // which anchors stay (one bit each), how many, the largest bound left out
         uint32_t kept_thr = 0, dmax = 0;
@@ -2041,7 +2041,7 @@ __global__ __launch_bounds__(256) void k_lr_locus(K3Args a, int lc)
                 const uint32_t oi = atomicAdd(&a.ctr->n_sort[cls], 1u);
                 SortItem o{si.w, n_keep, si.qlen, 0, doff};
                 a.B.tabs->sort_items[cls][oi] = o;
-                if (a.dbg & 16) { atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_keep); }
+                if (a.dbg & DBG_STATS) { atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_keep); }
             }
             st_in += n; st_kept += n_keep; st_reads += dmax != 0;
         }
@@ -2223,7 +2223,7 @@ __global__ __launch_bounds__(NTHR) void k_sort_lds(K3Args a)
     __shared__ union GpPf { struct { uint32_t key[GP_SLOTS], cnt[GP_SLOTS]; } g; ParFillLds pf; } s_u;      // group_probe's table (before the sort, flag-only) / par_fill_block's (after it)
     uint32_t *const s_gkey = s_u.g.key, *const s_gcnt = s_u.g.cnt;
     ParFillLds &s_pf = s_u.pf;
-    const bool use_pf = (a.emit || !a.flag_only) && !(a.dbg & 128);
+    const bool use_pf = (a.emit || !a.flag_only) && !(a.dbg & DBG_NO_PARFILL);
     const uint32_t tid = threadIdx.x;
     const uint32_t n_items = a.ctr->n_sort[CLS];
     __shared__ uint32_t s_it;
@@ -2242,7 +2242,7 @@ __global__ __launch_bounds__(NTHR) void k_sort_lds(K3Args a)
         for (uint32_t i = tid; i < n; i += NTHR) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
         if (tid == 0) s_found = 0;
         __syncthreads();
-        if (a.flag_only && !a.emit && a.P.flag_stop != INT32_MAX && n >= 96 && !(a.dbg & 64)) {
+        if (a.flag_only && !a.emit && a.P.flag_stop != INT32_MAX && n >= 96 && !(a.dbg & DBG_NO_GROUP_PROBE)) {
             // flag-only: the largest (strand, contig) group first (see k_group_probe); its sort ping-pongs over the loaded
             // anchors, so a miss reloads them for the full sort
             uint32_t n_cl0 = 0;
@@ -2261,12 +2261,12 @@ __global__ __launch_bounds__(NTHR) void k_sort_lds(K3Args a)
         // clusters of more than 256 anchors go to k_cluster_dp's queue instead (their sorted anchors to the arena's second buffer)
         const bool to_q = CLS >= 1 && a.cl_lds && n > 256u;
         const GlobalQ clq{a.B.tabs->cl_items, a.B.tabs->cl_cap, a.ctr->n_cl, si.w, 1u, si.off};
-        if (!(a.dbg & 1))
+        if (!(a.dbg & DBG_NO_CHAIN_LDS))
         chain_sorted<false>(rx, rq, f, pt, n, tid, NTHR, (int32_t)si.qlen, a.P, a.flag_only ? &s_found : nullptr,
                             BigList{s_bstart, s_blen, &s_bcount, NMAX / 7 + 1}, n_u, best, n_cl, to_q ? &clq : nullptr, nullptr,
                             a.emit ? &a.sink : nullptr, a.B.meta[si.w].r, a.emit ? a.B.hz + si.off : nullptr,
-                            nullptr, 0u, -1, TandemQ{nullptr, 0u, 1u, 0, 0u}, use_pf ? &s_pf : nullptr, nullptr, (a.dbg & 16) ? a.ctr->pf_dbg : nullptr,
-                            (a.quiet || (a.emit && a.sink.best && !(a.dbg & 512))) ? nullptr : a.ctr->sh_pf_reads,      // with ChainSink::best k_sort_top counted the read
+                            nullptr, 0u, -1, TandemQ{nullptr, 0u, 1u, 0, 0u}, use_pf ? &s_pf : nullptr, nullptr, (a.dbg & DBG_STATS) ? a.ctr->pf_dbg : nullptr,
+                            (a.quiet || (a.emit && a.sink.best && !(a.dbg & DBG_NO_TOPBT))) ? nullptr : a.ctr->sh_pf_reads,      // with ChainSink::best k_sort_top counted the read
                             to_q ? a.B.bx + si.off : nullptr, to_q ? a.B.bq + si.off : nullptr, 256u);
         store_read_result(a, si.w, n_u, best, n_cl, s_red);
         __syncthreads();
@@ -2334,7 +2334,7 @@ __global__ __launch_bounds__(NTHR) void k_sort_top(K3Args a)
     const ChainSink sink_l = a.sink; const ChainParams P_l = a.P;      // local copies: see k_giant_chain
     const uint32_t tid = threadIdx.x;
     const uint32_t n_items = a.ctr->n_sort[CLS];
-    unsigned long long *const dbg = (a.dbg & 16) ? a.ctr->pf_dbg : nullptr;
+    unsigned long long *const dbg = (a.dbg & DBG_STATS) ? a.ctr->pf_dbg : nullptr;
     for (;;) {
         if (tid == 0) s_it = atomicAdd(&a.ctr->top_ticket[CLS], 1u);
         __syncthreads();
@@ -2387,8 +2387,8 @@ __global__ __launch_bounds__(512) void k_giant_top(K3Args a)
     const ChainSink sink_l = a.sink; const ChainParams P_l = a.P;
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
     const uint32_t n_items = a.ctr->n_sort[SORT_CLS_GIANT];
-    unsigned long long *const dbg = (a.dbg & 16) ? a.ctr->pf_dbg : nullptr;
-    const bool top = a.emit && sink_l.best != nullptr && !(a.dbg & 512);
+    unsigned long long *const dbg = (a.dbg & DBG_STATS) ? a.ctr->pf_dbg : nullptr;
+    const bool top = a.emit && sink_l.best != nullptr && !(a.dbg & DBG_NO_TOPBT);
     for (;;) {
         if (tid == 0) s_it = atomicAdd(&a.ctr->top_ticket[SORT_CLS_GIANT], 1u);
         __syncthreads();
@@ -2593,7 +2593,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         __syncthreads();
         int32_t n_u = 0, best = 0; uint32_t n_cl = 0;
         const GlobalQ gq{a.B.tabs->cl_items, a.B.tabs->cl_cap, a.ctr->n_cl, si.w, in_b ? 1u : 0u, si.off};
-        if (!(a.dbg & 2))
+        if (!(a.dbg & DBG_NO_CHAIN_GIANT))
         chain_sorted<true>(sx, sq, a.B.af + si.off, (int32_t *)(a.B.az + si.off), n, tid, nthr, (int32_t)si.qlen, P_l,
                      a.flag_only ? &s_found : nullptr, BigList{s_bstart, s_blen, &s_bcount, 2048}, n_u, best, n_cl, &gq, s_nxt,
                      a.emit ? &sink_l : nullptr, a.B.meta[si.w].r, a.emit ? (in_b ? a.B.ax : a.B.bx) + si.off : nullptr,      // heap: the sort's other buffer
@@ -2649,17 +2649,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
         const uint32_t rd = a.emit ? a.B.meta[ci.w].r : 0u, cbase = ci.pad >> 1;
         int32_t n_u, best;
         const bool pre = (ci.qlen >> 31) != 0;      // f and p are par_fill_block's
-        if ((a.dbg & 16) && lane == 0) { atomicAdd(&a.ctr->pf_dbg[pre ? 5 : 6], 1ull); if (!pre) atomicAdd(&a.ctr->pf_dbg[7], (unsigned long long)ci.n); }
+        if ((a.dbg & DBG_STATS) && lane == 0) { atomicAdd(&a.ctr->pf_dbg[pre ? 5 : 6], 1ull); if (!pre) atomicAdd(&a.ctr->pf_dbg[7], (unsigned long long)ci.n); }
         const int32_t cqlen = (int32_t)(ci.qlen & 0x7fffffffu);
         if (a.P.max_iter <= RING_TMAX_ITER)
             chain_cluster_ring(gx, gq, a.B.af + ci.off, (int32_t *)(a.B.az + ci.off), (int32_t)ci.n, cqlen, a.P, n_u, best,
-                               a.flag_only != 0, lane, s_ring[wv], (a.dbg & 16) ? a.ctr->cl_dbg : nullptr, sk, a.emit ? rd : 0u, cbase, heap, pre);
+                               a.flag_only != 0, lane, s_ring[wv], (a.dbg & DBG_STATS) ? a.ctr->cl_dbg : nullptr, sk, a.emit ? rd : 0u, cbase, heap, pre);
         else {      // look-back windows beyond the LDS mark bitmap: DP state in the arena throughout
             SliceStore S{gx, gq, a.B.af + ci.off, (int32_t *)(a.B.az + ci.off), pre ? (int32_t)cbase : 0};
             chain_cluster_wave(S, (int32_t)ci.n, cqlen, a.P, heap, n_u, best, a.flag_only != 0, lane, sk, rd, cbase, pre);
         }
         ++n_cl;
-        if ((a.dbg & 16) && lane == 0) { atomicAdd(&a.ctr->cl_tot[c], 1ull); atomicAdd(&a.ctr->cl_anchor_tot[c], (unsigned long long)ci.n); }
+        if ((a.dbg & DBG_STATS) && lane == 0) { atomicAdd(&a.ctr->cl_tot[c], 1ull); atomicAdd(&a.ctr->cl_anchor_tot[c], (unsigned long long)ci.n); }
         if (lane == 0 && n_u > 0) { atomicAdd(&a.B.acc_nu[ci.w], n_u); atomicMax(&a.B.acc_best[ci.w], best); }
     }
     if (lane == 0 && n_cl) atomicAdd(&a.ctr->sh_clusters[(blockIdx.x * 4 + wv) & 63], n_cl);
@@ -3301,6 +3301,8 @@ struct sh_ctx {
     const sh_index *idx = nullptr;
     int idx_device = 0;
     sh_opts opts{};
+    CtxSwitches sw{};                // read when the context is created
+    CallSwitches cs{};               // read by every sh_classify_device call, before its first chunk
     ChainParams P{};
     uint64_t max_reads = 0, max_bases = 0;
     uint32_t max_read_len = 0, seed_cap = 192, lds_words = 0;
@@ -3347,11 +3349,11 @@ struct sh_ctx {
     hipStream_t sx[4] = {};          // side streams: K2 and the sort classes run beside the main stream
     int side_pick[2] = {0, 1};       // long reads: the side streams of the giants' launch and of the follower (pick_side_streams)
     hipStream_t side_probed = nullptr; bool side_probed_done = false;
-    int par = 1;                     // bit 0: K2 on a side stream (SCRUBBY_HIP_STREAMS=0: on the main stream)
+    int par = 1;                     // CtxSwitches::streams
     hipEvent_t evx[8] = {};
 };
 
-static void fill_chain_params(const sh_opts &o, int32_t mid_occ, ChainParams &P)
+static void fill_chain_params(const sh_opts &o, const CtxSwitches &sw, int32_t mid_occ, ChainParams &P)
 {
     P.k = o.k; P.is_sr = o.is_sr;
     P.mid_occ = mid_occ; P.max_occ = o.max_occ; P.max_max_occ = o.max_max_occ; P.occ_dist = o.occ_dist;
@@ -3362,23 +3364,23 @@ static void fill_chain_params(const sh_opts &o, int32_t mid_occ, ChainParams &P)
     P.pen_skip = chain_pen_of(o.chain_skip_scale, o.k);
     P.q_occ_frac = o.q_occ_frac;
     const bool early_ok = o.k > 0 && (o.min_chain_score + o.k - 1) / o.k >= o.min_cnt && o.bw >= o.min_chain_score && o.bw / o.k + 1 >= o.min_cnt;
-    P.flag_stop = early_ok && !getenv("SCRUBBY_HIP_NO_FLAG_STOP") ? o.min_chain_score : INT32_MAX;
+    P.flag_stop = early_ok && !sw.no_flag_stop ? o.min_chain_score : INT32_MAX;
     // pair test (ChainParams::pair_dq_*): needs flag_stop, two anchors enough (min_cnt, 2k >= min_sc), no skip penalty
-    const bool pair_ok = P.flag_stop != INT32_MAX && o.chain_skip_scale == 0.0f && o.min_cnt <= 2 && 2 * o.k >= o.min_chain_score && !getenv("SCRUBBY_HIP_NO_PAIR");
+    const bool pair_ok = P.flag_stop != INT32_MAX && o.chain_skip_scale == 0.0f && o.min_cnt <= 2 && 2 * o.k >= o.min_chain_score && !sw.no_pair;
     const int32_t dmin = std::max(1, o.min_chain_score - o.k);
     const int32_t dmax = std::min(std::min(std::min(24, o.max_chain_skip - 1), std::min(o.max_chain_iter - 1, o.bw)), o.max_gap);
     P.pair_dq_min = pair_ok && dmin <= dmax ? dmin : 0;
     P.pair_dq_max = pair_ok && dmin <= dmax ? dmax : 0;
-    P.pair_min_anchors = getenv("SCRUBBY_HIP_PAIR_MIN") ? atoi(getenv("SCRUBBY_HIP_PAIR_MIN")) : 32;
+    P.pair_min_anchors = (int32_t)sw.pair_min_anchors;
     // SH_F_CIGAR: the decision is taken by the extension stage from ALL chains of a read, so the DP shortcuts above are off; the one
     // shortcut left is k_pair_pass mode 2 (ChainParams::ext_*)
     P.ext_s1 = 0; P.ext_unc_max = 0; P.ext_lemma = 0; P.ext_a = P.ext_b = P.ext_amb = P.ext_zdrop = 0;
     if ((o.flags & SH_F_CIGAR) && o.is_sr) {
         P.flag_stop = INT32_MAX; P.pair_dq_min = P.pair_dq_max = 0;
         const bool s1 = o.a > 0 && o.b > 0 && o.a * o.k >= o.min_dp_max && 2 * o.k >= o.min_chain_score && o.max_clip_ratio >= 1.0f &&
-                        o.chain_skip_scale == 0.0f && o.min_cnt <= 2 && o.zdrop >= 0 && o.bw >= 0 && !getenv("SCRUBBY_HIP_NO_S1");
+                        o.chain_skip_scale == 0.0f && o.min_cnt <= 2 && o.zdrop >= 0 && o.bw >= 0 && !sw.no_s1;
         P.ext_s1 = s1 ? 1 : 0;
-        const bool lem = o.a > 0 && o.b > 0 && o.a * o.k >= o.min_dp_max && 2 * o.k >= o.min_chain_score && o.max_clip_ratio >= 1.0f && o.zdrop >= 0 && !getenv("SCRUBBY_HIP_NO_LEMMA");
+        const bool lem = o.a > 0 && o.b > 0 && o.a * o.k >= o.min_dp_max && 2 * o.k >= o.min_chain_score && o.max_clip_ratio >= 1.0f && o.zdrop >= 0 && !sw.no_lemma;
         P.ext_lemma = lem ? 1 : 0;
         P.ext_unc_max = (s1 || lem) ? o.zdrop / o.b : 0;
         P.ext_a = o.a; P.ext_b = -o.b; P.ext_amb = o.sc_ambi > 0 ? -o.sc_ambi : o.sc_ambi; P.ext_zdrop = o.zdrop;
@@ -3387,7 +3389,7 @@ static void fill_chain_params(const sh_opts &o, int32_t mid_occ, ChainParams &P)
     if ((o.flags & SH_F_CIGAR) && !o.is_sr) { P.flag_stop = INT32_MAX; P.pair_dq_min = P.pair_dq_max = 0; }
 }
 
-static void fill_long_params(const sh_opts &o, int32_t mid_occ, LongParams &L)
+static void fill_long_params(const sh_opts &o, const CtxSwitches &sw, int32_t mid_occ, LongParams &L)
 {
     L.k = o.k; L.min_cnt = o.min_cnt; L.min_sc = o.min_chain_score; L.max_gap = o.max_gap; L.bw = o.bw; L.bw_long = o.bw_long < o.bw ? o.bw : o.bw_long; L.min_ksw_len = o.min_ksw_len;
     L.a = o.a; L.b = o.b; L.q = o.q; L.e = o.e; L.q2 = o.q2; L.e2 = o.e2; L.sc_ambi = o.sc_ambi;
@@ -3398,18 +3400,14 @@ static void fill_long_params(const sh_opts &o, int32_t mid_occ, LongParams &L)
     L.mid_occ = mid_occ; L.max_max_occ = o.max_max_occ; L.occ_dist = o.occ_dist;
     // ties of the long join that matter: the literal tree for reads of up to this many chain anchors (4096 by default; a satellite read of 10^5 anchors would keep
     // one lane chasing pointers for seconds - DESIGN.md 3.2); SCRUBBY_HIP_RMQ_EXACT_MAX=-1 takes every such read to the tree, 0 none
-    L.rmq_exact_max = -1;      // every read that meets a tie that matters, or outgrows the rings, takes the literal tree (round 5: the tree lives in LDS)
-    if (const char *env = getenv("SCRUBBY_HIP_RMQ_EXACT_MAX")) L.rmq_exact_max = atoi(env);
+    L.rmq_exact_max = (int32_t)sw.rmq_exact_max;      // (default -1) every read that meets a tie that matters, or outgrows the rings, takes the literal tree (round 5: the tree lives in LDS)
     // A read whose inner RMQ window (1000 reference bases) holds more than the 4096-anchor ring (5-bp satellite lattices: 23 of the bench's 2 M
     // reads) can only be chained by the literal one-lane trees over node pools in HBM - 10 to 25 s of one wave per read, measured.  Off by
     // default: such reads are counted (sh_stats.n_ext_unresolved) and keep their chain-level answer; SCRUBBY_HIP_RMQ_ONE_LANE=1 chains them.
-    L.e2_join_min = INT32_MAX;      // (was 60 000 while the tree was kept for the whole read; with the join shared among waves the 1024-anchor ring's pass is the faster place: 8.35 -> 8.24 s per 2 M reads)
-    if (const char *env = getenv("SCRUBBY_HIP_E2_JOIN_MIN")) L.e2_join_min = atoi(env);
-    L.coop_min = LR_COOP_MIN; L.coop_run = LR_COOP_RUN; L.coop_check = getenv("SCRUBBY_HIP_COOP_CHECK") ? 1 : 0;
-    if (const char *env = getenv("SCRUBBY_HIP_COOP_MIN")) L.coop_min = std::max(1, atoi(env));
-    if (const char *env = getenv("SCRUBBY_HIP_COOP_RUN")) L.coop_run = std::max(2, atoi(env));
-    L.rmq_one_lane = 0;
-    if (const char *env = getenv("SCRUBBY_HIP_RMQ_ONE_LANE")) L.rmq_one_lane = atoi(env) != 0;
+    L.e2_join_min = (int32_t)sw.e2_join_min;      // (default: never; was 60 000 while the tree was kept for the whole read; with the join shared among waves the 1024-anchor ring's pass is the faster place: 8.35 -> 8.24 s per 2 M reads)
+    static_assert(SW_COOP_MIN == LR_COOP_MIN && SW_COOP_RUN == LR_COOP_RUN && SW_TOPBT_MAX == TOPBT_MAX, "sh_switches.h repeats these defaults");
+    L.coop_min = (int32_t)sw.coop_min; L.coop_run = (int32_t)sw.coop_run; L.coop_check = (int32_t)sw.coop_check;
+    L.rmq_one_lane = sw.rmq_one_lane != 0;
 }
 
 static void fill_align_params(const sh_opts &o, AlignParams &A)
@@ -3436,9 +3434,9 @@ sh_status shi_ctx_rebind(sh_ctx *c, const sh_index *idx)
              SH_ERR_BAD_ARG, "shi_ctx_rebind: the index resolved its occurrence threshold under other parameters");
     c->idx = idx;
     const int32_t mid_occ = c->opts.mid_occ > 0 ? c->opts.mid_occ : idx->mid_occ;
-    fill_chain_params(c->opts, mid_occ, c->P);
+    fill_chain_params(c->opts, c->sw, mid_occ, c->P);
     c->AP.lemma = c->P.ext_lemma; c->AP.unc_max = c->P.ext_unc_max;
-    fill_long_params(c->opts, mid_occ, c->LP);
+    fill_long_params(c->opts, c->sw, mid_occ, c->LP);
     return SH_OK;
 }
 uint64_t shi_ctx_max_reads(const sh_ctx *c) { return c->max_reads; }
@@ -3458,11 +3456,13 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
     SH_HIP(hipSetDevice(idx->device));
     sh_ctx *c = new sh_ctx();
     c->idx = idx; c->idx_device = idx->device; c->opts = *opts; c->max_reads = max_reads; c->max_bases = max_bases; c->max_read_len = max_read_len;
+    const CtxSwitches &sw = c->sw = shi_ctx_switches();
+    c->cs = shi_call_switches();      // for the [dbg] lines below: every call reads it afresh
     int32_t mid_occ = opts->mid_occ > 0 ? opts->mid_occ : idx->mid_occ;
-    fill_chain_params(*opts, mid_occ, c->P);
+    fill_chain_params(*opts, sw, mid_occ, c->P);
     fill_align_params(*opts, c->AP);
     c->AP.lemma = c->P.ext_lemma; c->AP.unc_max = c->P.ext_unc_max;
-    fill_long_params(*opts, mid_occ, c->LP);
+    fill_long_params(*opts, sw, mid_occ, c->LP);
     c->ext = (opts->flags & SH_F_CIGAR) != 0;
     c->ext_long = c->ext && !opts->is_sr;
     if (c->ext) {
@@ -3500,7 +3500,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
     c->arena_bytes = std::max<uint64_t>(4ull << 30, max_reads * 4096ull);      // floor: a small batch still meets reads with 10^5 anchors (4 MB each); a starved arena means deferral rounds of ~1.5 ms
     // without K1 every read takes the legacy path, whose sketch buffers and anchors live in the arena: ~48 B per base
     if (!c->use_k1) c->arena_bytes = std::max<uint64_t>(c->arena_bytes, std::min<uint64_t>(max_reads * (uint64_t)max_read_len * 48ull, (c->ext_long ? 32ull : 64ull) << 30));      // long-read presets with the extension filter: the raw anchors have their own buffer (d_stage_*)
-    if (const char *env = getenv("SCRUBBY_HIP_ARENA_MB")) c->arena_bytes = (uint64_t)atoll(env) << 20;
+    if (sw.arena_bytes != SW_UNSET) c->arena_bytes = (uint64_t)sw.arena_bytes;
     if ((e = hipMalloc(&c->d_arena, c->arena_bytes)) != hipSuccess) return fail(e, "arena");
     {
         const uint64_t big_min = (64ull << 20) + max_reads * 160;
@@ -3576,7 +3576,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
             cap_anch = std::max<uint64_t>(cap_anch, cb / 8);
             cap_recs = std::max<uint64_t>(cap_recs, std::min<uint64_t>(cb / 64, 1ull << 28) + 8 * max_reads);
         }
-        if (const char *env = getenv("SCRUBBY_HIP_EXT_MB")) { cap_anch = std::max<uint64_t>(1 << 16, ((uint64_t)atoll(env) << 20) / 16); cap_recs = std::max<uint64_t>(1 << 12, cap_anch / 16); }
+        if (sw.ext_bytes != SW_UNSET) { cap_anch = std::max<uint64_t>(1 << 16, (uint64_t)sw.ext_bytes / 16); cap_recs = std::max<uint64_t>(1 << 12, cap_anch / 16); }
         cap_recs = std::min<uint64_t>((cap_recs + SINK_SHARDS - 1) / SINK_SHARDS, 0xfffffff0ull / SINK_SHARDS);      // per shard
         cap_anch = (cap_anch + SINK_SHARDS - 1) / SINK_SHARDS;
         auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
@@ -3594,8 +3594,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
         c->sink.best = (unsigned long long *)take(max_reads * 8);
         c->sink.tie = (uint32_t *)take(max_reads * 4);
         c->sink.n_recs = c->d_ctr->ext_n_recs; c->sink.n_anch = c->d_ctr->ext_n_anch; c->sink.overflow = &c->d_ctr->ext_overflow;
-        c->ext_reg_cap = 16384;
-        if (const char *env = getenv("SCRUBBY_HIP_EXT_REGCAP")) c->ext_reg_cap = (uint32_t)std::max(65, atoi(env));      // tests: chains of a read the full procedure takes
+        c->ext_reg_cap = (uint32_t)sw.ext_reg_cap;
         if (!c->ext_long) {
             c->ext_scratch_per_wave = align_scratch_layout(max_read_len, c->ext_reg_cap, nullptr, nullptr, nullptr);
             const uint64_t budget = 4ull << 30;
@@ -3622,13 +3621,13 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
             // 2 MB of direction bytes in the first size (8 until the second size's launch ran beside the first: a read that needs more costs
             // nothing extra now, and the smaller slots are 1700 waves instead of 1100 within the same budget)
             z.cap_p = std::min<uint64_t>(2ull << 20, (uint64_t)(2 * z.cap_k) * (z.cap_k + 32));
-            if (const char *env = getenv("SCRUBBY_HIP_LEXT_P_KB")) z.cap_p = (uint64_t)atoll(env) << 10;
-            if (const char *env = getenv("SCRUBBY_HIP_LEXT_A")) { z.cap_a = (uint32_t)std::max(64, atoi(env)); z.cap_u = z.cap_r = std::max(16u, z.cap_a / 4); }      // tests
+            if (sw.lext_p_bytes != SW_UNSET) z.cap_p = (uint64_t)sw.lext_p_bytes;
+            if (sw.lext_a != SW_UNSET) { z.cap_a = (uint32_t)sw.lext_a; z.cap_u = z.cap_r = std::max(16u, z.cap_a / 4); }
             LongSizes zb = z;
             zb.cap_p = std::min<uint64_t>(32ull << 20, (uint64_t)(2 * z.cap_k) * (z.cap_k + 32));
             zb.cap_a = 1u << 18; zb.cap_u = zb.cap_r = 1u << 16; zb.cap_m = 65536;
-            if (const char *env = getenv("SCRUBBY_HIP_LEXT_BIG_P_KB")) zb.cap_p = (uint64_t)atoll(env) << 10;      // tests: alignments beyond the second size
-            if (const char *env = getenv("SCRUBBY_HIP_LEXT_BIG_A")) { zb.cap_a = (uint32_t)std::max(1024, atoi(env)); zb.cap_u = zb.cap_r = std::max(64u, zb.cap_a / 4); }      // tests: reads beyond the second size
+            if (sw.lext_big_p_bytes != SW_UNSET) zb.cap_p = (uint64_t)sw.lext_big_p_bytes;
+            if (sw.lext_big_a != SW_UNSET) { zb.cap_a = (uint32_t)sw.lext_big_a; zb.cap_u = zb.cap_r = std::max(64u, zb.cap_a / 4); }
             uint64_t budget[4] = {22ull << 30, 8ull << 30, 26ull << 30, 10ull << 30};
             const uint64_t wave_max[4] = {256 * 12, 256, 256 * 8, 256};      // LDS: 13 KB per wave in the chains kernel (twelve to a CU), 19 KB in the regions kernel
             {   // no more than a third of what the device has left (several contexts, ranks sharing a device, smaller GPUs)
@@ -3641,13 +3640,13 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
             for (int ph = 0; ph < 2; ++ph) for (int t = 0; t < 2; ++t) {
                 LongSizes q = t ? zb : z;
                 q.phase = ph;
-                if (ph == 0 && !t && !getenv("SCRUBBY_HIP_LEXT_A")) { q.cap_a = 65536; q.cap_u = 16384; }      // the chains kernel: 64 Ki anchors in every slot (the second size has 256 slots only, and a 40-kb read's join takes a second)
+                if (ph == 0 && !t && sw.lext_a == SW_UNSET) { q.cap_a = 65536; q.cap_u = 16384; }      // the chains kernel: 64 Ki anchors in every slot (the second size has 256 slots only, and a 40-kb read's join takes a second)
                 const int i = ph * 2 + t;
                 c->lext_sz[i] = q;
                 c->lext_per_wave[i] = long_ws_carve(nullptr, nullptr, q);
                 if (i == 0) { int dev = 0, ncu = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) c->n_cu = ncu; }
                 c->lext_waves[i] = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({wave_max[i], budget[i] / c->lext_per_wave[i], t ? std::max<uint64_t>(4, max_reads / 16) : max_reads}));
-                if (getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] long-read stage working memory %d: %u waves x %.2f MB\n", i, c->lext_waves[i], c->lext_per_wave[i] / 1048576.0);
+                if (c->cs.dbg_set) fprintf(stderr, "[dbg] long-read stage working memory %d: %u waves x %.2f MB\n", i, c->lext_waves[i], c->lext_per_wave[i] / 1048576.0);
                 if ((e = hipMalloc(&c->d_lext[i], (uint64_t)c->lext_waves[i] * c->lext_per_wave[i])) != hipSuccess) return fail(e, "long-read extension-stage scratch");
             }
             if ((e = hipMalloc(&c->d_lext_big, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
@@ -3682,7 +3681,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
                     size_t fr = 0, tot = 0;
                     if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->stage_cap = std::min<uint64_t>(c->stage_cap, std::max<uint64_t>(1ull << 20, (uint64_t)((double)fr * 0.45) / 12));
                 }
-                if (const char *env = getenv("SCRUBBY_HIP_STAGE_MB")) c->stage_cap = std::max<uint64_t>(1ull << 16, ((uint64_t)atoll(env) << 20) / 12);
+                if (sw.stage_bytes != SW_UNSET) c->stage_cap = std::max<uint64_t>(1ull << 16, (uint64_t)sw.stage_bytes / 12);
                 if ((e = hipMalloc(&c->d_stage_x, c->stage_cap * 8)) != hipSuccess) return fail(e, "long-read anchor staging");
                 if ((e = hipMalloc(&c->d_stage_q, c->stage_cap * 4)) != hipSuccess) return fail(e, "long-read anchor staging");
             }
@@ -3699,7 +3698,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
     for (auto &ev : c->evx) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
     // (the side streams are created when a call first needs one: HIP deals its hardware queues - four by default - out to the streams that
     // exist, and a side stream that shares the caller's queue runs after it, not beside it)
-    if (const char *env = getenv("SCRUBBY_HIP_STREAMS")) c->par = atoi(env);
+    c->par = (int)sw.streams;
     *out = c;
     return SH_OK;
 }
@@ -3784,10 +3783,7 @@ static sh_status pick_side_streams(sh_ctx *c, hipStream_t s)
     sh_status es = ensure_side_streams(c, 0, 2);
     if (es != SH_OK) return es;
     // SCRUBBY_HIP_SIDE_PICK=g,f pins the two streams (giants' launch, follower) and skips the probe
-    if (const char *pin = getenv("SCRUBBY_HIP_SIDE_PICK")) {
-        int g = 0, f = 1;
-        if (sscanf(pin, "%d,%d", &g, &f) == 2 && g >= 0 && g < 3 && f >= 0 && f < 3) { c->side_pick[0] = g; c->side_pick[1] = f; c->side_probed = s; c->side_probed_done = true; return SH_OK; }
-    }
+    if (c->cs.side_pick >= 0) { c->side_pick[0] = (int)c->cs.side_pick & 255; c->side_pick[1] = (int)c->cs.side_pick >> 8; c->side_probed = s; c->side_probed_done = true; return SH_OK; }
     struct Events {      // destroyed on every way out
         hipEvent_t t0 = nullptr, t1 = nullptr, e = nullptr;
         ~Events() { if (t0) hipEventDestroy(t0); if (t1) hipEventDestroy(t1); if (e) hipEventDestroy(e); }
@@ -3815,7 +3811,7 @@ static sh_status pick_side_streams(sh_ctx *c, hipStream_t s)
     std::sort(ord, ord + 3, [&](int a, int b) { return ms[a] < ms[b]; });
     c->side_pick[0] = ord[0]; c->side_pick[1] = ord[1];
     c->side_probed = s; c->side_probed_done = true;
-    if (getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] side streams beside the caller's: %.2f %.2f %.2f ms for two 0.2-ms kernels; giants on %d, follower on %d\n", ms[0], ms[1], ms[2], c->side_pick[0], c->side_pick[1]);
+    if (c->cs.dbg_set) fprintf(stderr, "[dbg] side streams beside the caller's: %.2f %.2f %.2f ms for two 0.2-ms kernels; giants on %d, follower on %d\n", ms[0], ms[1], ms[2], c->side_pick[0], c->side_pick[1]);
     return SH_OK;
 }
 
@@ -3840,15 +3836,15 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     }
     // the sort classes run one after the other.  Side by side (streams sx[0..2]) measured 9 % slower when they carried the whole repeat
     // path (they fight for LDS); that mode predates k_group_probe, which the class-4 and giant kernels must follow: it stays off.
-    static const int side_env = getenv("SCRUBBY_HIP_SIDE") ? atoi(getenv("SCRUBBY_HIP_SIDE")) : -1;
+    const int64_t side_env = c->cs.side;
     // small batches (an eighth of the bench's records on each of 8 GPUs): every class kernel is mostly tail, side by side they overlap:
     // 39.3 -> 36.6 ms at 2.5 M records; at 20 M it costs 2 % (SCRUBBY_HIP_SIDE=0 / 1 forces either)
-    const bool gp = k.flag_only && k.P.flag_stop != INT32_MAX && !(k.dbg & 64);      // k_group_probe runs (chain-level decision): the class-4 and giant kernels must follow it
+    const bool gp = k.flag_only && k.P.flag_stop != INT32_MAX && !(k.dbg & DBG_NO_GROUP_PROBE);      // k_group_probe runs (chain-level decision): the class-4 and giant kernels must follow it
     const bool side = side_env > 0 || (side_env < 0 && !gp && c->cur_reads <= 3000000ull);
     if (side) { sh_status es = ensure_side_streams(c, 0, 2); if (es != SH_OK) return es; }
     hipStream_t s0 = side ? c->sx[0] : s, s1 = side ? c->sx[1] : s, g = side ? c->sx[2] : s;
-    const bool use_pf = (k.emit || !k.flag_only) && !(k.dbg & 128);
-    const bool use_top = use_pf && k.emit && k.sink.best != nullptr && !(k.dbg & 512);
+    const bool use_pf = (k.emit || !k.flag_only) && !(k.dbg & DBG_NO_PARFILL);
+    const bool use_top = use_pf && k.emit && k.sink.best != nullptr && !(k.dbg & DBG_NO_TOPBT);
     if (use_pf) SH_HIP(hipMemsetAsync(&ctr->top_ticket[0], 0, 4 * N_SORT_CLS, s));
     if (side) {
         SH_HIP(hipEventRecord(c->evx[0], s));
@@ -3884,7 +3880,7 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
         SH_HIP(hipEventRecord(c->evx[2], c->sx[1])); SH_HIP(hipStreamWaitEvent(g, c->evx[2], 0));
         SH_HIP(hipEventRecord(c->evx[6], s)); SH_HIP(hipStreamWaitEvent(g, c->evx[6], 0));
     }
-    if (!(k.dbg & 32)) hipLaunchKernelGGL(k_cluster_dp, dim3(256 * 7), dim3(256), 0, g, k);      // 72 VGPRs: 7 waves per SIMD (4: 74 ms, 6: 60, 8 with spills: 57)
+    if (!(k.dbg & DBG_NO_CLUSTER_DP)) hipLaunchKernelGGL(k_cluster_dp, dim3(256 * 7), dim3(256), 0, g, k);      // 72 VGPRs: 7 waves per SIMD (4: 74 ms, 6: 60, 8 with spills: 57)
     if (two_phase) {
         SH_HIP(hipMemsetAsync(&ctr->sort_ticket[SORT_CLS_GIANT], 0, 4, g));
         hipLaunchKernelGGL(k_giant_chain, dim3(1024), dim3(512), 0, g, k, 1);
@@ -3959,15 +3955,15 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     b.P = c->P;
     b.sink = c->sink; b.emit = c->ext ? 1 : 0;
     b.BC = BaseCtx{idx->d_ref, idx->d_cstart, d_bases};
-    b.dbg = getenv("SCRUBBY_HIP_DBG") ? atoi(getenv("SCRUBBY_HIP_DBG")) : 0;
+    const CallSwitches &cs = c->cs;
+    b.dbg = (int32_t)cs.dbg;
     if (c->ext && (d_trace != nullptr || c->ext_long)) { b.sink.best = nullptr; b.sink.tie = nullptr; }      // trace mode / long-read presets: every chain is handed over
     const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(n_tiles, 1), 256 * 8);
     // K2 only needs K1's output and nothing waits for it before the end of the call: it runs on a side stream, beside k_local_cluster /
     // k_expand / the sort classes.  Starting it late instead, beside the giant reads' DP kernels of the second pass (SCRUBBY_HIP_K2_LATE=1),
     // was measured with the extension filter on: K2 itself 64 -> 22 ms, but the step 408 -> 428 ms - it does not find room beside those
     // persistent grids and ends up serialised.
-    static const int k2_late_env = getenv("SCRUBBY_HIP_K2_LATE") ? atoi(getenv("SCRUBBY_HIP_K2_LATE")) : -1;
-    const bool k2_late = c->use_k1 && (c->par & 1) && k2_late_env > 0;
+    const bool k2_late = c->use_k1 && (c->par & 1) && cs.k2_late > 0;
     K2Args kb = b;
     auto launch_k2 = [&]() -> sh_status {
         if (c->par & 1) { sh_status es = ensure_side_streams(c, 3, 3); if (es != SH_OK) return es; }
@@ -3994,31 +3990,22 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     k.k1info = c->d_k1info; k.flags = d_flags; k.trace = d_trace; k.ctr = c->d_ctr; k.B = c->B; k.P = c->P;
     k.flag_only = d_trace == nullptr && !c->ext;      // SH_F_CIGAR: every chain is needed, no early exit
     k.sink = b.sink; k.emit = c->ext ? 1 : 0; k.BC = b.BC; k.t_mode = (c->ext && !c->ext_long && d_trace == nullptr) ? 1 : 0;
-    k.dbg = getenv("SCRUBBY_HIP_DBG") ? atoi(getenv("SCRUBBY_HIP_DBG")) : 0;
-    if (!getenv("SCRUBBY_HIP_AB_NOCHAIN")) k.dbg &= ~3;      // bits 0 / 1 switch the class kernels' chaining OFF (timing A/Bs: the answers are then wrong) - only with this second switch
-    if (getenv("SCRUBBY_HIP_NO_PARFILL")) k.dbg |= 128;      // A/B: every cluster chained by the sequential DP
-    k.top_max = TOPBT_MAX; k.pft_gmin = 32768u;
-    k.giant_fanin = 4u;
-    if (const char *env = getenv("SCRUBBY_HIP_GIANT_FANIN")) {      // A/B and tests: 2 = the two-way rounds
-        if (atoi(env) != 2 && atoi(env) != 4) { sh_set_error("SCRUBBY_HIP_GIANT_FANIN must be 2 or 4, not '%s'", env); return SH_ERR_BAD_ARG; }
-        k.giant_fanin = (uint32_t)atoi(env);
-    }
-    if (const char *env = getenv("SCRUBBY_HIP_PFT_GMIN")) k.pft_gmin = (uint32_t)std::max(1, atoi(env));
-    if (const char *env = getenv("SCRUBBY_HIP_TOPBT_MAX")) k.top_max = std::max(1, std::min(TOPBT_MAX, atoi(env)));
-    if (getenv("SCRUBBY_HIP_NO_TOPBT")) k.dbg |= 512;        // A/B: clusters visited one by one even when the read's DP is done
-    if (getenv("SCRUBBY_HIP_LOCUS_TOP1")) k.dbg |= 1024;     // tests: k_lr_locus keeps the largest run of windows only
+    k.dbg = (int32_t)cs.dbg;
+    k.top_max = (int32_t)cs.top_max; k.pft_gmin = (uint32_t)cs.pft_gmin;
+    SH_CHECK(cs.giant_fanin != 0, SH_ERR_BAD_ARG, "SCRUBBY_HIP_GIANT_FANIN must be 2 or 4, not '%s'", shi_call_switch_text(&CallSwitches::giant_fanin));
+    k.giant_fanin = (uint32_t)cs.giant_fanin;
     k.resketch_list = c->d_work_resketch;
     // long-read presets, flag-only: the anchors that cannot hold regs[0] never reach the sort classes (k_lr_locus).  Needs the probe (a read
     // with anchors left out is only ever proven mapped by it), a single chaining pass (max_occ <= mid_occ: whether mm_map_frag chains again
     // must not hinge on chains left out) and windows narrow enough to tell loci apart
-    k.locus = c->ext_long && c->use_long && d_trace == nullptr && !getenv("SCRUBBY_HIP_NO_LOCUS") && !getenv("SCRUBBY_HIP_NO_PROBE") &&
+    k.locus = c->ext_long && c->use_long && d_trace == nullptr && !cs.no_locus && !cs.no_probe &&
               c->opts.max_clip_ratio >= 1.0f && c->P.max_occ <= c->P.mid_occ && c->locus_shift <= 20 && c->opts.min_cnt >= 1;
     {   // the shortest read for which `qlen - span > rmq_rescue_size || span > qlen * rmq_rescue_ratio` holds whatever the span (lr_chains_wave)
         int32_t q = 1;
         while (q < (1 << 30) && !((float)(q - c->LP.rmq_rescue_size) > (float)q * c->LP.rmq_rescue_ratio)) q = q < 64 ? q + 1 : q + q / 64;
         k.locus_min_qlen = c->LP.bw_long > c->LP.bw ? q : 0;
     }
-    k.cl_lds = c->ext_long && c->P.max_iter <= RING_TMAX_ITER && !getenv("SCRUBBY_HIP_NO_CL_LDS");
+    k.cl_lds = c->ext_long && c->P.max_iter <= RING_TMAX_ITER && !cs.no_cl_lds;
     k.locus_shift = c->locus_shift; k.lr_drop = c->d_lr_drop; k.stage_x = c->d_stage_x; k.stage_q = c->d_stage_q; k.stage_cap = c->stage_cap;
     for (int i = 0; i < 3; ++i) k.locus_items[i] = c->d_locus[i];
     if (c->ext_long) SH_HIP(hipMemsetAsync(c->d_lr_drop, 0, n_reads * 4, s));
@@ -4034,7 +4021,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         hipLaunchKernelGGL(k_pair_swap, dim3(1), dim3(1), 0, s, c->d_ctr);
         cur0 = 1;
     }
-    if (k.t_mode && c->P.ext_lemma && c->use_k1 && !c->use_long && !(k.dbg & 256)) {      // reads whose singleton seeds' locus settles them
+    if (k.t_mode && c->P.ext_lemma && c->use_k1 && !c->use_long && !(k.dbg & DBG_NO_LOCAL_CLUSTER)) {      // reads whose singleton seeds' locus settles them
         K2Args pb = b;
         pb.work = c->d_big[0][cur0]; pb.work_count = &c->d_ctr->n_big[0];
         pb.leftover = c->d_big[0][cur0 ^ 1]; pb.leftover_count = &c->d_ctr->n_big_defer[0];
@@ -4069,13 +4056,13 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             SH_HIP(hipStreamSynchronize(s));
             SH_HIP(hipGetLastError());
             if (first) { snap = *c->h_ctr; first = false; c->dbg_ptr[0] = c->d_big[1][cur1]; c->dbg_n[0] = snap.n_big[1]; c->dbg_ptr[1] = c->dbg_ptr[2] = nullptr; c->dbg_n[1] = c->dbg_n[2] = 0; }
-            if (k.dbg & 16) fprintf(stderr, "[dbg] iter %d resketch %u reasons %u %u %u pair tests between two singletons (dbg) %u segs %u big %u/%u defer %u/%u\n", iter, c->h_ctr->n_resketch, c->h_ctr->n_leg_reason[0], c->h_ctr->n_leg_reason[1], c->h_ctr->n_leg_reason[2], c->h_ctr->n_leg_reason[3], c->h_ctr->n_long_segs, c->h_ctr->n_big[0], c->h_ctr->n_big[1], c->h_ctr->n_big_defer[0], c->h_ctr->n_big_defer[1]);
-            if (k.dbg & 16) fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", c->h_ctr->cl_tot[0], c->h_ctr->cl_tot[1], c->h_ctr->cl_tot[2], c->h_ctr->cl_tot[3], c->h_ctr->cl_anchor_tot[0], c->h_ctr->cl_anchor_tot[1], c->h_ctr->cl_anchor_tot[2], c->h_ctr->cl_anchor_tot[3]);
-            if (k.dbg & 16) fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", c->h_ctr->sort_tot[6], c->h_ctr->sort_anchor_tot[6], c->h_ctr->sort_tot[0], c->h_ctr->sort_anchor_tot[0], c->h_ctr->sort_tot[1], c->h_ctr->sort_anchor_tot[1], c->h_ctr->sort_tot[2], c->h_ctr->sort_anchor_tot[2], c->h_ctr->sort_tot[3], c->h_ctr->sort_anchor_tot[3], c->h_ctr->sort_tot[4], c->h_ctr->sort_anchor_tot[4], c->h_ctr->sort_tot[5], c->h_ctr->sort_anchor_tot[5]);
-            if (k.dbg & 16) fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", c->h_ctr->pair_mid[0], c->h_ctr->pair_mid[1], c->h_ctr->pair_mid[2], c->h_ctr->pair_mid[3]);
-            if (k.dbg & 16) fprintf(stderr, "[dbg] local-cluster shortcut: tried %u, no singleton / filtered %u, singletons apart %u, window %u, K size %u, no margin %u, decided %u\n", c->h_ctr->ext_s3[0], c->h_ctr->ext_s3[1], c->h_ctr->ext_s3[2], c->h_ctr->ext_s3[3], c->h_ctr->ext_s3[4], c->h_ctr->ext_s3[5], c->h_ctr->ext_s3[7]);
-            if (k.dbg & 16) fprintf(stderr, "[dbg] ring DP: chunks in window %llu, beyond %llu, far rescans %llu; clusters %llu (anchors %llu), with a max_skip break %llu (anchors %llu), widest window %llu, anchors of clusters with a window > 64: %llu, > 128: %llu\n", c->h_ctr->cl_dbg[0], c->h_ctr->cl_dbg[1], c->h_ctr->cl_dbg[2], c->h_ctr->cl_dbg[3], c->h_ctr->cl_dbg[6], c->h_ctr->cl_dbg[4], c->h_ctr->cl_dbg[5], c->h_ctr->cl_dbg[7], c->h_ctr->cl_dbg[8], c->h_ctr->cl_dbg[9]);
-            if (k.dbg & 16) fprintf(stderr, "[dbg] parallel fill: reads done %llu (anchors %llu), not applicable %llu (anchors %llu), dirty anchors %llu; k_cluster_dp clusters prefilled %llu, sequential %llu (anchors %llu); read-level backtracks tried %llu, candidates listed %llu, given up (too many) %llu, chains visited %llu\n", c->h_ctr->pf_dbg[0], c->h_ctr->pf_dbg[3], c->h_ctr->pf_dbg[1], c->h_ctr->pf_dbg[4], c->h_ctr->pf_dbg[2], c->h_ctr->pf_dbg[5], c->h_ctr->pf_dbg[6], c->h_ctr->pf_dbg[7], c->h_ctr->pf_dbg[8], c->h_ctr->pf_dbg[11], c->h_ctr->pf_dbg[12], c->h_ctr->pf_dbg[10]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] iter %d resketch %u reasons %u %u %u pair tests between two singletons (dbg) %u segs %u big %u/%u defer %u/%u\n", iter, c->h_ctr->n_resketch, c->h_ctr->n_leg_reason[0], c->h_ctr->n_leg_reason[1], c->h_ctr->n_leg_reason[2], c->h_ctr->n_leg_reason[3], c->h_ctr->n_long_segs, c->h_ctr->n_big[0], c->h_ctr->n_big[1], c->h_ctr->n_big_defer[0], c->h_ctr->n_big_defer[1]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", c->h_ctr->cl_tot[0], c->h_ctr->cl_tot[1], c->h_ctr->cl_tot[2], c->h_ctr->cl_tot[3], c->h_ctr->cl_anchor_tot[0], c->h_ctr->cl_anchor_tot[1], c->h_ctr->cl_anchor_tot[2], c->h_ctr->cl_anchor_tot[3]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", c->h_ctr->sort_tot[6], c->h_ctr->sort_anchor_tot[6], c->h_ctr->sort_tot[0], c->h_ctr->sort_anchor_tot[0], c->h_ctr->sort_tot[1], c->h_ctr->sort_anchor_tot[1], c->h_ctr->sort_tot[2], c->h_ctr->sort_anchor_tot[2], c->h_ctr->sort_tot[3], c->h_ctr->sort_anchor_tot[3], c->h_ctr->sort_tot[4], c->h_ctr->sort_anchor_tot[4], c->h_ctr->sort_tot[5], c->h_ctr->sort_anchor_tot[5]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", c->h_ctr->pair_mid[0], c->h_ctr->pair_mid[1], c->h_ctr->pair_mid[2], c->h_ctr->pair_mid[3]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] local-cluster shortcut: tried %u, no singleton / filtered %u, singletons apart %u, window %u, K size %u, no margin %u, decided %u\n", c->h_ctr->ext_s3[0], c->h_ctr->ext_s3[1], c->h_ctr->ext_s3[2], c->h_ctr->ext_s3[3], c->h_ctr->ext_s3[4], c->h_ctr->ext_s3[5], c->h_ctr->ext_s3[7]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] ring DP: chunks in window %llu, beyond %llu, far rescans %llu; clusters %llu (anchors %llu), with a max_skip break %llu (anchors %llu), widest window %llu, anchors of clusters with a window > 64: %llu, > 128: %llu\n", c->h_ctr->cl_dbg[0], c->h_ctr->cl_dbg[1], c->h_ctr->cl_dbg[2], c->h_ctr->cl_dbg[3], c->h_ctr->cl_dbg[6], c->h_ctr->cl_dbg[4], c->h_ctr->cl_dbg[5], c->h_ctr->cl_dbg[7], c->h_ctr->cl_dbg[8], c->h_ctr->cl_dbg[9]);
+            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] parallel fill: reads done %llu (anchors %llu), not applicable %llu (anchors %llu), dirty anchors %llu; k_cluster_dp clusters prefilled %llu, sequential %llu (anchors %llu); read-level backtracks tried %llu, candidates listed %llu, given up (too many) %llu, chains visited %llu\n", c->h_ctr->pf_dbg[0], c->h_ctr->pf_dbg[3], c->h_ctr->pf_dbg[1], c->h_ctr->pf_dbg[4], c->h_ctr->pf_dbg[2], c->h_ctr->pf_dbg[5], c->h_ctr->pf_dbg[6], c->h_ctr->pf_dbg[7], c->h_ctr->pf_dbg[8], c->h_ctr->pf_dbg[11], c->h_ctr->pf_dbg[12], c->h_ctr->pf_dbg[10]);
             resk_done = c->h_ctr->n_resketch;
             const uint32_t d0 = c->h_ctr->n_big_defer[0], d1 = c->h_ctr->n_big_defer[1];
             if (d0 == 0 && d1 == 0) break;
@@ -4123,7 +4110,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         x.P = c->LP; x.AP = c->AP; x.CP = c->P;
         x.AR.base = c->d_larena; x.AR.cap = c->larena_bytes; x.AR.cursor = &c->d_ctr->arena_cursor; x.AR.hdr = c->d_lhdr;
         x.list = c->d_ext_list; x.n_list = &c->d_ctr->ext_n_list; x.ctr = c->d_ctr; x.flags = d_flags; x.trace = d_trace; x.flag_only = d_trace == nullptr;
-        x.clk = getenv("SCRUBBY_HIP_DBG") ? (getenv("SCRUBBY_HIP_DBG_EXACT") ? 3 : 1) : 0; x.probe = getenv("SCRUBBY_HIP_NO_PROBE") ? 0 : 1;
+        x.clk = cs.dbg_set ? (cs.dbg_exact ? 3 : 1) : 0; x.probe = cs.no_probe ? 0 : 1;
         x.drop = k.locus ? c->d_lr_drop : nullptr; x.fb_list = c->d_lr_fb; x.n_fb = &c->d_ctr->lr_n_fb;
         x.exact_list = c->d_lext_exact_list; x.n_exact = &c->d_ctr->lext_n_exact;
         x.exact_list2 = c->d_lext_exact_list2; x.n_exact2 = &c->d_ctr->lext_n_exact2;
@@ -4181,7 +4168,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         // reads whose answer could depend on what was left out, after the repeat path has chained them again with every anchor
         // lr_coop_fill's queue, counters and descriptors for one launch of an EXACT instance (three regions: the giants, E2a, E1 - launches that
         // may run side by side); zeroed on the launch's stream
-        static const bool coop = !getenv("SCRUBBY_HIP_GIANTS_PLAIN") && !getenv("SCRUBBY_HIP_NO_COOP");
+        const bool coop = !cs.giants_plain && !cs.no_coop;
         auto coop_setup = [&](ExtLongArgs &xx, int which, hipStream_t st, uint32_t n_blocks) -> sh_status {
             constexpr uint32_t QCAP = 65536, NDESC = 512;
             constexpr size_t off_desc = 256, off_ready = off_desc + NDESC * sizeof(LongCoopDesc), off_items = off_ready + QCAP * 4, region = off_items + QCAP * 16;
@@ -4215,7 +4202,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                 // reads whose chain anchors outgrow the first size go straight to the large working memory, on a side stream beside the rest
                 int bin_cut = 0;
                 while (bin_cut < 31 && (2ull << bin_cut) <= c->lext_sz[0].cap_a) ++bin_cut;      // bin b holds totals in [2^b, 2^(b+1))
-                if (const char *env = getenv("SCRUBBY_HIP_GIANT_BINS_DOWN")) bin_cut = std::max(1, bin_cut - atoi(env));
+                bin_cut = std::max(1, bin_cut - (int)cs.giant_bins_down);
                 xa.hist = c->d_ctr->lext_hist; xa.bin_cut = bin_cut; xa.part = 1;
                 ExtLongArgs xg = xa;
                 xg.scratch = c->d_lext[1]; xg.scratch_per_wave = c->lext_per_wave[1]; xg.sz = c->lext_sz[1];
@@ -4226,7 +4213,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                 // behind it), and because a CU the main grid has filled has no such room left, the main grid is held back until the giants'
                 // blocks have begun (k_wait_started: bounded, ~2 ms at most).  The main grid's blocks (13 KB) fit beside them.
                 uint32_t g_waves = std::min<uint32_t>(c->lext_waves[1], 64u);
-                if (const char *env = getenv("SCRUBBY_HIP_GIANT_WAVES")) g_waves = std::min<uint32_t>(c->lext_waves[1], (uint32_t)std::max(1, atoi(env)));
+                if (cs.giant_waves != SW_UNSET) g_waves = std::min<uint32_t>(c->lext_waves[1], (uint32_t)cs.giant_waves);
                 xg.started = &c->d_ctr->lext_started;
                 SH_HIP(hipMemsetAsync(&c->d_ctr->lext_started, 0, 4, s));
                 SH_HIP(hipEventRecord(c->evx[0], s));
@@ -4235,7 +4222,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                 const uint32_t m_waves = c->lext_waves[0];
                 // (the giants on the EXACT instance at once: the tree is only kept over the stretches that ask it, lr_rmq_fill - a giant with a tie
                 // is not chained twice, and the exact passes lose their longest reads)
-                static const bool giants_exact = !getenv("SCRUBBY_HIP_GIANTS_PLAIN");
+                const bool giants_exact = !cs.giants_plain;
                 if (coop) { sh_status cs = coop_setup(xg, 0, sg, g_waves); if (cs != SH_OK) return cs; }      // the giants' waves share the long join of the launch's largest reads (lr_coop_fill, sh_long.h)
                 if (giants_exact) hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(g_waves), dim3(64), 0, sg, xg);
                 else hipLaunchKernelGGL((k_long_chains<4096, false, false>), dim3(g_waves), dim3(64), 0, sg, xg);
@@ -4244,7 +4231,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                 hipLaunchKernelGGL((k_long_chains<512, false, false>), dim3(m_waves), dim3(64), 0, s, xa);
                 SH_HIP(hipStreamWaitEvent(s, c->evx[1], 0));
                 sh_status st = sync_ctr(); if (st != SH_OK) return st;
-                if (coop && getenv("SCRUBBY_HIP_DBG")) {
+                if (coop && cs.dbg_set) {
                     uint32_t h[64] = {};
                     SH_HIP(hipMemcpy(h, c->d_coop, sizeof(h), hipMemcpyDeviceToHost));
                     fprintf(stderr, "[dbg] long join shared among the giants' waves: %u reads in %u runs (%u taken off the queue)\n", h[48], h[0], h[16]);
@@ -4331,7 +4318,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                     if (c->h_ctr->lext_n_unres > 0) { st = on_demand(2, xe); if (st != SH_OK) return st; }
                 }
                 SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big2, 0, 8, s));
-                if (getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] exact long join: %u reads on the 1024-anchor ring beside %u on the 4096-anchor ring (%u with tied priorities so far), %u more on the large ring afterwards, %u beyond it, %.1f ms\n", n_e1, n_e2a, c->h_ctr->lext_rmq_tie, n_e2b, n_e3,
+                if (cs.dbg_set) fprintf(stderr, "[dbg] exact long join: %u reads on the 1024-anchor ring beside %u on the 4096-anchor ring (%u with tied priorities so far), %u more on the large ring afterwards, %u beyond it, %.1f ms\n", n_e1, n_e2a, c->h_ctr->lext_rmq_tie, n_e2b, n_e3,
                                                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ex).count());
             }
             SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "long-read extension stage: internal overflow code %u", c->h_ctr->ext_overflow);
@@ -4345,11 +4332,10 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                 // there: the pass used to begin when the first had ended, and it is one alignment of ~4 * 10^8 cells on one wave - a third of a
                 // second during which nothing else ran.  Both grids are resident together (two waves per SIMD each: 8 per CU); what the
                 // follower leaves (it gives up after a bounded number of looks) the launch after the first one takes, as before.
-                static const bool no_follow = getenv("SCRUBBY_HIP_NO_FOLLOW") != nullptr;
                 // (both grids must be RESIDENT together - a follower that holds the slot a block of the first launch waits for would wait for that
                 // launch to end: the first launch gives up the slots the follower needs; its reads are drawn by ticket, so fewer blocks lose nothing)
                 const uint32_t slots = 8u * (uint32_t)c->n_cu;
-                const bool follow = !no_follow && c->lext_waves[3] <= slots / 4;
+                const bool follow = !cs.no_follow && c->lext_waves[3] <= slots / 4;
                 const uint32_t w_first = follow ? std::min<uint32_t>(c->lext_waves[2], slots - c->lext_waves[3]) : c->lext_waves[2];
                 if (follow) {
                     SH_HIP(hipMemsetAsync(c->d_lext_big2, 0xff, (size_t)n_reads * 4, s));
@@ -4386,9 +4372,9 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         };
         { sh_status st = ext_round(0); if (st != SH_OK) return st; }
         const uint32_t n_fb = c->h_ctr->lr_n_fb;
-        if (k.locus && getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] anchors by locus: %u reads thinned out (%llu of %llu anchors kept); %u reads redone with every anchor (one chain and more possible %u, short read %u, top score within reach of what was left out %u, no chain after the join %u, probe undecided %u, no probe %u, no chain among the anchors kept %u)\n",
+        if (k.locus && cs.dbg_set) fprintf(stderr, "[dbg] anchors by locus: %u reads thinned out (%llu of %llu anchors kept); %u reads redone with every anchor (one chain and more possible %u, short read %u, top score within reach of what was left out %u, no chain after the join %u, probe undecided %u, no probe %u, no chain among the anchors kept %u)\n",
                                                         c->h_ctr->lr_locus_reads, c->h_ctr->lr_locus_kept, c->h_ctr->lr_locus_in, n_fb, c->h_ctr->lr_fb_why[0], c->h_ctr->lr_fb_why[1], c->h_ctr->lr_fb_why[2], c->h_ctr->lr_fb_why[3], c->h_ctr->lr_fb_why[4], c->h_ctr->lr_fb_why[5], c->h_ctr->lr_fb_why[6]);
-        if (getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] probes that gave up (first round): region %u, window %u, filling over 4 M cells %u, direction bytes %u, z-drop / empty %u, CIGAR room %u, no proof within six fillings %u\n",
+        if (cs.dbg_set) fprintf(stderr, "[dbg] probes that gave up (first round): region %u, window %u, filling over 4 M cells %u, direction bytes %u, z-drop / empty %u, CIGAR room %u, no proof within six fillings %u\n",
                                                c->h_ctr->lr_probe_why[1], c->h_ctr->lr_probe_why[2], c->h_ctr->lr_probe_why[3], c->h_ctr->lr_probe_why[4], c->h_ctr->lr_probe_why[5], c->h_ctr->lr_probe_why[6], c->h_ctr->lr_probe_why[7]);
         if (stats && k.locus) { stats->n_locus_reads += c->h_ctr->lr_locus_reads; stats->n_locus_redone += n_fb; }
         if (n_fb > 0) {
@@ -4415,9 +4401,9 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             static bool warned = false;
             if (!warned) { warned = true; fprintf(stderr, "[scrubby-hip] WARNING: %u read(s) outgrew the extension stage's largest working memory (e.g. read %u of its batch, code %u: 18 chains, 20 read length, 21 chain anchors, 22 RMQ window, 23 seeds, 24 regions, 27-30 alignment window, 32 direction bytes); they keep their chain-level answer (mapped)\n", c->h_ctr->lext_unresolved, c->h_ctr->lext_err_read, c->h_ctr->lext_err_code); }
         }
-        if (getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] long-read extension stage: %u reads with chains, %u re-chained (RMQ), %u with tied RMQ priorities, %u needed the large scratch, %u regions aligned, %u reads dropped\n",
+        if (cs.dbg_set) fprintf(stderr, "[dbg] long-read extension stage: %u reads with chains, %u re-chained (RMQ), %u with tied RMQ priorities, %u needed the large scratch, %u regions aligned, %u reads dropped\n",
                                                ext_list, c->h_ctr->lext_rechained, c->h_ctr->lext_rmq_tie, n_big_a, c->h_ctr->ext_regions, c->h_ctr->ext_dropped);
-        if (getenv("SCRUBBY_HIP_DBG")) {
+        if (cs.dbg_set) {
             unsigned long long tot = 0, mr = 0, ma = 0, sr = 0, sa = 0;
             for (int i = 0; i < LR_NCLK; ++i) tot += c->h_ctr->lext_clk[i];
             fprintf(stderr, "[dbg] long-read extension stage, share of wave time: gather %.1f  rmq-sort %.1f  rmq-fill %.1f  backtrack+compact %.1f  gen_regs %.1f  parent/select %.1f  squeeze %.1f  region set-up %.1f  ksw %.1f  z-drop test %.1f  update_extra %.1f  staging %.1f %%  (total %.1f wave-s at 100 MHz)\n",
@@ -4510,7 +4496,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         if (d_trace != nullptr && c->h_ctr->ext_n_unres > 0) { const uint32_t keep = ext_list; sh_status st = sr_on_demand(x); if (st != SH_OK) return st; ext_list = keep; }
         const uint32_t n_redo = c->h_ctr->ext_n_redo;
         if (d_trace == nullptr) { c->dbg_ptr[1] = c->d_ext_redo; c->dbg_n[1] = n_redo; }
-        if (getenv("SCRUBBY_HIP_DBG")) fprintf(stderr, "[dbg] extension stage: %u reads handed over chains, %u not settled by their top chain (tie %u, missing %u, short stretch %u, z-drop %u)\n", ext_list, n_redo, c->h_ctr->ext_reason[1], c->h_ctr->ext_reason[2], c->h_ctr->ext_reason[3], c->h_ctr->ext_reason[4]);
+        if (cs.dbg_set) fprintf(stderr, "[dbg] extension stage: %u reads handed over chains, %u not settled by their top chain (tie %u, missing %u, short stretch %u, z-drop %u)\n", ext_list, n_redo, c->h_ctr->ext_reason[1], c->h_ctr->ext_reason[2], c->h_ctr->ext_reason[3], c->h_ctr->ext_reason[4]);
         uint32_t n_redo2 = 0;
         if (d_trace == nullptr && n_redo > 0) {
             // second pass: regs[0] of the reads its max stretch could not vouch for goes through mm_align1 (one wave per read)
@@ -4616,6 +4602,7 @@ extern "C" sh_status sh_classify_device(sh_ctx *c, const uint8_t *d_bases, const
     SH_CHECK(c && d_offsets && d_flags && (d_bases || n_bases == 0), SH_ERR_BAD_ARG, "sh_classify_device: null argument");
     SH_HIP(hipSetDevice(c->idx->device));
     hipStream_t s = (hipStream_t)stream;
+    c->cs = shi_call_switches();
     if (stats) memset(stats, 0, sizeof(*stats));
     if (c->ext_long) {      // the stage's per-read path record of this call
         if (n_reads > c->lkind_cap) {

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include "../../include/scrubby_hip.h"
+#include "sh_switches.h"      // the SCRUBBY_HIP_* switches of the classify path and the DBG_* bits the kernels test
 
 // ---- HBM index layout ---------------------------------------------------------
 // slot = 16 B {w0, w1}; w0 = ~0 (empty) | key (2k bits <= 56) | multi << 63

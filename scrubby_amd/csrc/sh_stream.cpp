@@ -745,22 +745,14 @@ struct CtxCache {
     std::mutex mu;
     sh_ctx *ctx = nullptr;
     sh_opts opts{};
-    std::string env;          // the environment switches a context captures when it is created
-    static std::string env_sig()
-    {
-        std::string e;
-        for (const char *v : {"SCRUBBY_HIP_ARENA_MB", "SCRUBBY_HIP_NO_FLAG_STOP", "SCRUBBY_HIP_NO_PAIR", "SCRUBBY_HIP_PAIR_MIN", "SCRUBBY_HIP_NO_S1", "SCRUBBY_HIP_NO_LEMMA", "SCRUBBY_HIP_EXT_MB", "SCRUBBY_HIP_DBG", "SCRUBBY_HIP_LEXT_P_KB", "SCRUBBY_HIP_RMQ_EXACT_MAX", "SCRUBBY_HIP_RMQ_ONE_LANE"}) {
-            const char *x = getenv(v); e += x ? x : "-"; e += '|';
-        }
-        return e;
-    }
+    std::string env;          // the environment switches a context captures when it is created (shi_switches_sig)
     sh_ctx *take(const sh_opts &o, const sh_index *idx)
     {
         std::lock_guard<std::mutex> lk(mu);
         if (!ctx) return nullptr;
         sh_ctx *c = ctx;
         ctx = nullptr;
-        if (memcmp(&opts, &o, sizeof(o)) != 0 || env != env_sig() || shi_ctx_rebind(c, idx) != SH_OK) { sh_ctx_destroy(c); return nullptr; }
+        if (memcmp(&opts, &o, sizeof(o)) != 0 || env != shi_switches_sig() || shi_ctx_rebind(c, idx) != SH_OK) { sh_ctx_destroy(c); return nullptr; }
         return c;
     }
     void give(sh_ctx *c, const sh_opts &o)
@@ -770,7 +762,7 @@ struct CtxCache {
         ctx = nullptr;
         const char *off = getenv("SCRUBBY_HIP_CTX_CACHE");
         if (off && atoi(off) == 0) { sh_ctx_destroy(c); return; }
-        ctx = c; opts = o; env = env_sig();
+        ctx = c; opts = o; env = shi_switches_sig();
     }
     void release()
     {
