@@ -355,58 +355,121 @@ __device__ inline void gen_anchors(Store &S, SeedView sv, const uint64_t *__rest
     S.sort_finalize(na);
 }
 
-// mg_lchain_dp: fills f/p; t is scratch
-template <class Store, class Idx>
-__device__ inline bool chain_dp(Store &S, Idx n, int32_t qlen, const ChainParams &P, int32_t stop_at = INT32_MAX)
+// mg_lchain_dp's look-back window: the largest reference (x) and query (y) distance of a link
+__device__ inline uint32_t chain_max_dist_x(const ChainParams &P, int32_t qlen)
 {
-    int32_t max_dist_y = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap;
-    int32_t max_dist_x;
-    if (P.max_gap_ref > 0) max_dist_x = P.max_gap_ref;
-    else if (P.max_frag_len > 0) { max_dist_x = P.max_frag_len - qlen; if (max_dist_x < P.max_gap) max_dist_x = P.max_gap; }
-    else max_dist_x = P.max_gap;
-    if (max_dist_x < P.bw) max_dist_x = P.bw;
-    if (max_dist_y < P.bw) max_dist_y = P.bw;
+    int32_t m;
+    if (P.max_gap_ref > 0) m = P.max_gap_ref;
+    else if (P.max_frag_len > 0) { m = P.max_frag_len - qlen; if (m < P.max_gap) m = P.max_gap; }
+    else m = P.max_gap;
+    if (m < P.bw) m = P.bw;
+    return (uint32_t)m;
+}
+__device__ inline int32_t chain_max_dist_y(const ChainParams &P, int32_t qlen)
+{
+    int32_t m = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap;
+    return m < P.bw ? P.bw : m;
+}
 
-    S.clearAux(n);
+// ---- mg_lchain_dp's max_ii shortcut ---------------------------------------------------------------------------------
+// max_ii = the anchor with the largest f inside the window: found by a scan of [st, i) when it is unset or has left the window
+// (each DP below has its own scan), scored against anchor i when the look-back scan ended before reaching it (max_ii < end_j),
+// and moved to i when i is in reach of it and scores higher.  `at` says how grp / rlo / qp / F of an index are fetched: a Store,
+// or whatever the DP keeps of its anchors (the ring DP holds anchor max_ii in registers).
+template <class At, class Idx>
+__device__ __forceinline__ bool max_ii_in_reach(const At &at, Idx max_ii, uint32_t gi, uint32_t li, int32_t max_dist_x)
+{
+    return max_ii >= 0 && gi == at.grp(max_ii) && (uint64_t)(li - at.rlo(max_ii)) <= (uint64_t)max_dist_x;
+}
+template <class At, class Idx>
+__device__ __forceinline__ void max_ii_apply(const At &at, Idx max_ii, Idx end_j, uint32_t li, uint32_t qi, int32_t max_dist_x, int32_t max_dist_y,
+                                             const ChainParams &P, int32_t &max_f, Idx &max_j)
+{
+    if (max_ii < 0 || max_ii >= end_j) return;
+    const int32_t tmp = comput_sc(li, qi, at.rlo(max_ii), at.qp(max_ii), max_dist_x, max_dist_y, P);
+    if (tmp == SH_SC_NONE) return;
+    const int32_t c = tmp + at.F(max_ii);
+    if (max_f < c) { max_f = c; max_j = max_ii; }
+}
+template <class At, class Idx>
+__device__ __forceinline__ bool max_ii_moves(const At &at, Idx max_ii, uint32_t gi, uint32_t li, int32_t max_dist_x, int32_t max_f)
+{
+    return max_ii < 0 || (max_ii_in_reach(at, max_ii, gi, li, max_dist_x) && at.F(max_ii) < max_f);
+}
+
+// ---- the sequential mg_lchain_dp: fills f/p --------------------------------------------------------------------------
+// Where the t[] marks of the look-back scan live is a policy.  MarksInStore: the store's t slots, as mg_lchain_dp has them (t[j] == i).
+struct MarksInStore {
+    static constexpr bool LOADS_AHEAD = false;
+    static constexpr int UNROLL = 1;
+    template <class Store, class Idx> __device__ inline void init(Store &S, Idx n) { S.clearAux(n); }
+    __device__ inline void begin() {}
+    template <class Store, class Idx> __device__ inline bool marked(const Store &S, Idx j, Idx i) const { return S.T(j) == (int32_t)i; }
+    template <class Store, class Idx> __device__ inline void mark(Store &S, int32_t pj, Idx i) { S.setT(pj, (int32_t)i); }
+};
+// MarksInReg, n <= 64: one 64-bit register.  t[j] == i only asks "was j the predecessor of an anchor already visited in THIS scan", so
+// a mask reset for every i is equivalent, and t is left untouched.  Without the LDS store -> load dependency through t[] the j loop's
+// loads are independent and pipeline: F(j) / Pm(j) are loaded ahead of comput_sc and the loop is unrolled by two.
+struct MarksInReg {
+    static constexpr bool LOADS_AHEAD = true;
+    static constexpr int UNROLL = 2;
+    uint64_t m;
+    template <class Store, class Idx> __device__ inline void init(Store &, Idx) {}
+    __device__ inline void begin() { m = 0; }
+    template <class Store, class Idx> __device__ inline bool marked(const Store &, Idx j, Idx) const { return (m >> j) & 1; }
+    template <class Store, class Idx> __device__ inline void mark(Store &, int32_t pj, Idx) { m |= 1ULL << pj; }
+};
+
+template <class Marks, class Store, class Idx>
+__device__ inline bool chain_dp_seq(Store &S, Idx n, int32_t qlen, const ChainParams &P, int32_t stop_at)
+{
+    const int32_t max_dist_x = (int32_t)chain_max_dist_x(P, qlen), max_dist_y = chain_max_dist_y(P, qlen);
+    Marks marks;
+    marks.init(S, n);
     Idx st = 0, max_ii = -1;
     for (Idx i = 0; i < n; ++i) {
         Idx max_j = -1, j;
         const uint32_t gi = S.grp(i), li = S.rlo(i), qi = S.qp(i);
         int32_t max_f = P.k, n_skip = 0;
+        marks.begin();
         while (st < i && (gi != S.grp(st) || (uint64_t)li > (uint64_t)S.rlo(st) + (uint64_t)max_dist_x)) ++st;
         if (i - st > (Idx)P.max_iter) st = i - (Idx)P.max_iter;
+#pragma unroll Marks::UNROLL
         for (j = i - 1; j >= st; --j) {
+            int32_t fj = 0, pj = -1;
+            if (Marks::LOADS_AHEAD) { fj = S.F(j); pj = S.Pm(j); }
             int32_t sc = comput_sc(li, qi, S.rlo(j), S.qp(j), max_dist_x, max_dist_y, P);
             if (sc == SH_SC_NONE) continue;
-            sc += S.F(j);
+            if (!Marks::LOADS_AHEAD) fj = S.F(j);
+            sc += fj;
             if (sc > max_f) {
                 max_f = sc; max_j = j;
                 if (n_skip > 0) --n_skip;
-            } else if (S.T(j) == (int32_t)i) {
+            } else if (marks.marked(S, j, i)) {
                 if (++n_skip > P.max_skip) break;
             }
-            int32_t pj = S.Pm(j);
-            if (pj >= 0) S.setT(pj, (int32_t)i);
+            if (!Marks::LOADS_AHEAD) pj = S.Pm(j);
+            if (pj >= 0) marks.mark(S, pj, i);
         }
-        Idx end_j = j;
-        bool far = true;
-        if (max_ii >= 0) far = (gi != S.grp(max_ii)) || ((uint64_t)(li - S.rlo(max_ii)) > (uint64_t)max_dist_x);
-        if (max_ii < 0 || far) {
+        const Idx end_j = j;
+        if (!max_ii_in_reach(S, max_ii, gi, li, max_dist_x)) {
             int32_t mx = INT32_MIN;
             max_ii = -1;
             for (j = i - 1; j >= st; --j) { int32_t fj = S.F(j); if (mx < fj) { mx = fj; max_ii = j; } }
         }
-        if (max_ii >= 0 && max_ii < end_j) {
-            int32_t tmp = comput_sc(li, qi, S.rlo(max_ii), S.qp(max_ii), max_dist_x, max_dist_y, P);
-            if (tmp != SH_SC_NONE && max_f < tmp + S.F(max_ii)) { max_f = tmp + S.F(max_ii); max_j = max_ii; }
-        }
+        max_ii_apply(S, max_ii, end_j, li, qi, max_dist_x, max_dist_y, P, max_f, max_j);
         S.setFP(i, max_f, (int32_t)max_j);
         if (max_f >= stop_at) return true;
-        bool near = false;
-        if (max_ii >= 0) near = (gi == S.grp(max_ii)) && ((uint64_t)(li - S.rlo(max_ii)) <= (uint64_t)max_dist_x);
-        if (max_ii < 0 || (near && S.F(max_ii) < max_f)) max_ii = i;
+        if (max_ii_moves(S, max_ii, gi, li, max_dist_x, max_f)) max_ii = i;
     }
     return false;
+}
+
+// mg_lchain_dp; t is scratch (it is left holding the scan's marks)
+template <class Store, class Idx>
+__device__ inline bool chain_dp(Store &S, Idx n, int32_t qlen, const ChainParams &P, int32_t stop_at = INT32_MAX)
+{
+    return chain_dp_seq<MarksInStore, Store, Idx>(S, n, qlen, P, stop_at);
 }
 
 // mg_chain_bk_end
@@ -467,77 +530,12 @@ __device__ inline void backtrack_small(Store &S, int n, const ChainParams &P, in
 }
 
 // ---- n <= 64: the t[] array of mg_lchain_dp / mg_chain_backtrack lives in one 64-bit register ---------------
-// In the DP, t[j] == i only asks "was j the predecessor of an anchor already visited in THIS scan", so a mask
-// reset for every i is equivalent.  In the backtrack the transient value 2 never survives a call of
+// The DP: MarksInReg above.  In the backtrack the transient value 2 never survives a call of
 // mg_chain_bk_end (it is set and cleared on the same path), so only t == 1 persists: one mask again.
-// Without the LDS store -> load dependency through t[] the j loop's loads are independent and pipeline.
 template <class Store>
 __device__ inline bool chain_dp_mask(Store &S, int n, int32_t qlen, const ChainParams &P, int32_t stop_at = INT32_MAX)
 {
-    int32_t max_dist_y = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap;
-    int32_t max_dist_x;
-    if (P.max_gap_ref > 0) max_dist_x = P.max_gap_ref;
-    else if (P.max_frag_len > 0) { max_dist_x = P.max_frag_len - qlen; if (max_dist_x < P.max_gap) max_dist_x = P.max_gap; }
-    else max_dist_x = P.max_gap;
-    if (max_dist_x < P.bw) max_dist_x = P.bw;
-    if (max_dist_y < P.bw) max_dist_y = P.bw;
-
-    int st = 0, max_ii = -1;
-    for (int i = 0; i < n; ++i) {
-        int max_j = -1, j;
-        const uint32_t gi = S.grp(i), li = S.rlo(i), qi = S.qp(i);
-        int32_t max_f = P.k, n_skip = 0;
-        uint64_t marked = 0;
-        while (st < i && (gi != S.grp(st) || (uint64_t)li > (uint64_t)S.rlo(st) + (uint64_t)max_dist_x)) ++st;
-        if (i - st > P.max_iter) st = i - P.max_iter;
-#pragma unroll 2
-        for (j = i - 1; j >= st; --j) {
-            const int32_t fj = S.F(j), pj = S.Pm(j);
-            int32_t sc = comput_sc(li, qi, S.rlo(j), S.qp(j), max_dist_x, max_dist_y, P);
-            if (sc == SH_SC_NONE) continue;
-            sc += fj;
-            if (sc > max_f) {
-                max_f = sc; max_j = j;
-                if (n_skip > 0) --n_skip;
-            } else if ((marked >> j) & 1) {
-                if (++n_skip > P.max_skip) break;
-            }
-            if (pj >= 0) marked |= 1ULL << pj;
-        }
-        const int end_j = j;
-        bool far = true;
-        if (max_ii >= 0) far = (gi != S.grp(max_ii)) || ((uint64_t)(li - S.rlo(max_ii)) > (uint64_t)max_dist_x);
-        if (max_ii < 0 || far) {
-            int32_t mx = INT32_MIN;
-            max_ii = -1;
-            for (j = i - 1; j >= st; --j) { int32_t fj = S.F(j); if (mx < fj) { mx = fj; max_ii = j; } }
-        }
-        if (max_ii >= 0 && max_ii < end_j) {
-            int32_t tmp = comput_sc(li, qi, S.rlo(max_ii), S.qp(max_ii), max_dist_x, max_dist_y, P);
-            if (tmp != SH_SC_NONE && max_f < tmp + S.F(max_ii)) { max_f = tmp + S.F(max_ii); max_j = max_ii; }
-        }
-        S.setFP(i, max_f, max_j);
-        if (max_f >= stop_at) return true;
-        bool near = false;
-        if (max_ii >= 0) near = (gi == S.grp(max_ii)) && ((uint64_t)(li - S.rlo(max_ii)) <= (uint64_t)max_dist_x);
-        if (max_ii < 0 || (near && S.F(max_ii) < max_f)) max_ii = i;
-    }
-    return false;
-}
-
-__device__ inline uint32_t chain_max_dist_x(const ChainParams &P, int32_t qlen)
-{
-    int32_t m;
-    if (P.max_gap_ref > 0) m = P.max_gap_ref;
-    else if (P.max_frag_len > 0) { m = P.max_frag_len - qlen; if (m < P.max_gap) m = P.max_gap; }
-    else m = P.max_gap;
-    if (m < P.bw) m = P.bw;
-    return (uint32_t)m;
-}
-__device__ inline int32_t chain_max_dist_y(const ChainParams &P, int32_t qlen)
-{
-    int32_t m = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap;
-    return m < P.bw ? P.bw : m;
+    return chain_dp_seq<MarksInReg, Store, int>(S, n, qlen, P, stop_at);
 }
 
 // ---- mg_lchain_dp without its sequential state: all anchors of a read at once ---------------------------------------------------------
@@ -560,6 +558,49 @@ __device__ inline int32_t chain_max_dist_y(const ChainParams &P, int32_t qlen)
 #define PF_DEAD 0x7ffffff2
 struct ParFillLds { unsigned long long qmask[PF_MAX_Q / 64]; uint32_t qpre[PF_MAX_Q / 64 + 1]; uint32_t start[PF_MAX_RANK + 1], cur[PF_MAX_RANK]; int32_t n_dirty; uint32_t dirty[PF_DIRTY_CAP]; };
 
+// The counting sort of par-fill: elements k < n, with query position q_of(k) <= PF_MAX_Q, ordered by the rank of their query position.
+// Leaves the rank table in L (qmask / qpre: the distinct positions; start[r] .. start[r + 1]: the slots of rank r) and calls put(slot, k)
+// once per element.  Returns the number of ranks R; above PF_MAX_RANK nothing but qmask / qpre was written.  All threads of the block
+// call it; R is read after a barrier, so the caller's test on it is uniform.
+__device__ inline uint32_t pf_rank_of(const ParFillLds &L, uint32_t qq) { return L.qpre[qq >> 6] + (uint32_t)__popcll(L.qmask[qq >> 6] & ((1ull << (qq & 63)) - 1ull)); }
+template <class QOf, class Put>
+__device__ __forceinline__ uint32_t pf_rank_sort(ParFillLds &L, uint32_t n, uint32_t tid, uint32_t nthr, QOf q_of, Put put)
+{
+    for (uint32_t t = tid; t < PF_MAX_Q / 64; t += nthr) L.qmask[t] = 0;
+    __syncthreads();
+    for (uint32_t k = tid; k < n; k += nthr) {
+        const uint32_t qq = q_of(k);
+        if (!((L.qmask[qq >> 6] >> (qq & 63)) & 1ull)) atomicOr(&L.qmask[qq >> 6], 1ull << (qq & 63));
+    }
+    __syncthreads();
+    if (tid == 0) { uint32_t acc = 0; for (int w = 0; w < PF_MAX_Q / 64; ++w) { L.qpre[w] = acc; acc += (uint32_t)__popcll(L.qmask[w]); } L.qpre[PF_MAX_Q / 64] = acc; }
+    __syncthreads();
+    const uint32_t R = L.qpre[PF_MAX_Q / 64];
+    if (R > PF_MAX_RANK) return R;
+    for (uint32_t t = tid; t <= R; t += nthr) L.start[t] = 0;
+    __syncthreads();
+    for (uint32_t k = tid; k < n; k += nthr) atomicAdd(&L.start[pf_rank_of(L, q_of(k)) + 1], 1u);
+    __syncthreads();
+    if (tid == 0) { uint32_t acc = 0; for (uint32_t r = 0; r < R; ++r) { acc += L.start[r + 1]; L.start[r + 1] = acc; } }
+    __syncthreads();
+    for (uint32_t t = tid; t < R; t += nthr) L.cur[t] = L.start[t];
+    __syncthreads();
+    for (uint32_t k = tid; k < n; k += nthr) put(atomicAdd(&L.cur[pf_rank_of(L, q_of(k))], 1u), k);
+    __syncthreads();
+    return R;
+}
+
+// Folds predecessor j, scoring sc against the anchor, into the anchor's maximum.  false: more than max_skip valid predecessors - the
+// anchor is dirty, no need to see the rest.
+__device__ __forceinline__ bool pf_fold(int32_t sc, const int32_t *f, int32_t j, int32_t max_skip, int32_t &max_f, int32_t &max_j, int32_t &nv)
+{
+    if (sc == SH_SC_NONE) return true;
+    if (++nv > max_skip) return false;
+    const int32_t c = sc + f[j];
+    if (c > max_f) { max_f = c; max_j = j; }
+    return true;
+}
+
 // x, q: the read's sorted anchors with the cluster starts marked in bit 31 of q; f, pt: DP state (pt = p, t interleaved).  All threads of the
 // block call it.  false: not applicable (query positions beyond PF_MAX_Q, more than PF_MAX_RANK of them, too many dirty anchors) - nothing usable
 // was written.  true: f and p hold mg_lchain_dp's values for every clean cluster, t = 0 except PF_DIRTY at the first anchor of a dirty one.
@@ -568,29 +609,10 @@ __device__ inline bool par_fill_block(PX x, PQ q, int32_t *f, int32_t *pt, uint3
 {
     if (qlen > PF_MAX_Q || n >= 0x7ffffff0u) return false;
     const int32_t mdy = chain_max_dist_y(P, qlen), mdx = (int32_t)chain_max_dist_x(P, qlen);
-    for (uint32_t t = tid; t < PF_MAX_Q / 64; t += nthr) L.qmask[t] = 0;
     if (tid == 0) L.n_dirty = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) {
-        const uint32_t qq = (uint32_t)q[i] & 0x7fffffffu;
-        if (!((L.qmask[qq >> 6] >> (qq & 63)) & 1ull)) atomicOr(&L.qmask[qq >> 6], 1ull << (qq & 63));
-    }
-    __syncthreads();
-    if (tid == 0) { uint32_t acc = 0; for (int w = 0; w < PF_MAX_Q / 64; ++w) { L.qpre[w] = acc; acc += (uint32_t)__popcll(L.qmask[w]); } L.qpre[PF_MAX_Q / 64] = acc; }
-    __syncthreads();
-    const uint32_t R = L.qpre[PF_MAX_Q / 64];
+    const uint32_t R = pf_rank_sort(L, n, tid, nthr, [&](uint32_t i) { return (uint32_t)q[i] & 0x7fffffffu; },
+                                    [&](uint32_t slot, uint32_t i) { pt[2 * (size_t)slot + 1] = (int32_t)i; });
     if (R > PF_MAX_RANK) return false;
-    for (uint32_t t = tid; t <= R; t += nthr) L.start[t] = 0;
-    __syncthreads();
-    auto rank_of = [&](uint32_t qq) { return L.qpre[qq >> 6] + (uint32_t)__popcll(L.qmask[qq >> 6] & ((1ull << (qq & 63)) - 1ull)); };
-    for (uint32_t i = tid; i < n; i += nthr) atomicAdd(&L.start[rank_of((uint32_t)q[i] & 0x7fffffffu) + 1], 1u);
-    __syncthreads();
-    if (tid == 0) { uint32_t acc = 0; for (uint32_t r = 0; r < R; ++r) { acc += L.start[r + 1]; L.start[r + 1] = acc; } }
-    __syncthreads();
-    for (uint32_t t = tid; t < R; t += nthr) L.cur[t] = L.start[t];
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) { const uint32_t slot = atomicAdd(&L.cur[rank_of((uint32_t)q[i] & 0x7fffffffu)], 1u); pt[2 * (size_t)slot + 1] = (int32_t)i; }
-    __syncthreads();
     for (uint32_t r = 0; r < R; ++r) {
         const uint32_t e = L.start[r + 1];
         for (uint32_t idx = L.start[r] + tid; idx < e; idx += nthr) {
@@ -607,7 +629,7 @@ __device__ inline bool par_fill_block(PX x, PQ q, int32_t *f, int32_t *pt, uint3
                     const uint32_t qj = (uint32_t)q[j], xj = (uint32_t)x[j];
                     if (xi - xj > lim) break;
                     const int32_t sc = comput_sc(xi, qi, xj, qj & 0x7fffffffu, mdx, mdy, P);
-                    if (sc != SH_SC_NONE) { if (++nv > P.max_skip) break; const int32_t c = sc + f[j]; if (c > max_f) { max_f = c; max_j = (int32_t)j; } }      // dirty: no need to see the rest
+                    if (!pf_fold(sc, f, (int32_t)j, P.max_skip, max_f, max_j, nv)) break;
                     if (qj >> 31) break;
                 }
             }
@@ -631,7 +653,6 @@ __device__ inline bool par_fill_block(PX x, PQ q, int32_t *f, int32_t *pt, uint3
 // completely in LDS (its own rank table, all rounds), with the last PFT_H anchors of the tile before it as a halo; f and (p, t = 0) go
 // out once, coalesced.  An anchor whose window is not inside tile + halo is dirty (so is one with PFT_H anchors within max_dist_x behind
 // it: the max_iter cut is not looked at any closer than that; needs max_iter >= PFT_H).  Same contract as par_fill_block.
-__device__ inline int32_t wave_scan_max_incl(int32_t v);      // below, with the other DPP scans
 #define PFT_T 4096
 #define PFT_H 256
 struct PfTile { uint32_t x[PFT_H + PFT_T], q[PFT_H + PFT_T]; int32_t f[PFT_H + PFT_T]; uint16_t p[PFT_T], perm[PFT_T], dcs[PFT_H + PFT_T]; int32_t wtot[16], carry; };
@@ -651,17 +672,10 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
     uint32_t h = 0;
     for (uint32_t t0 = 0; t0 < n; t0 += PFT_T) {
         const uint32_t tn = n - t0 < PFT_T ? n - t0 : PFT_T;
-        for (uint32_t t = tid; t < PF_MAX_Q / 64; t += nthr) L.qmask[t] = 0;
         if (tid == 0) T.carry = -1;
-        __syncthreads();
-        for (uint32_t k = tid; k < tn; k += nthr) {
-            const uint32_t qr = q[t0 + k], qq = qr & 0x7fffffffu;
-            T.x[h + k] = (uint32_t)x[t0 + k]; T.q[h + k] = qr;
-            if (!((L.qmask[qq >> 6] >> (qq & 63)) & 1ull)) atomicOr(&L.qmask[qq >> 6], 1ull << (qq & 63));
-        }
-        __syncthreads();
-        if (tid == 0) { uint32_t acc = 0; for (int w = 0; w < PF_MAX_Q / 64; ++w) { L.qpre[w] = acc; acc += (uint32_t)__popcll(L.qmask[w]); } L.qpre[PF_MAX_Q / 64] = acc; }
+        for (uint32_t k = tid; k < tn; k += nthr) { T.x[h + k] = (uint32_t)x[t0 + k]; T.q[h + k] = q[t0 + k]; }
         if (G > 1) {      // dcs over halo + tile (an anchor whose cluster starts before the halo counts from index 0: the scan then runs out of halo)
+            __syncthreads();
             for (uint32_t c0 = 0; c0 < h + tn; c0 += nthr) {
                 const uint32_t k = c0 + tid;
                 const int32_t v = k < h + tn && (T.q[k] >> 31) ? (int32_t)k : -1;
@@ -676,20 +690,8 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
                 if (tid == nthr - 1) T.carry = inc;
             }
         }
-        __syncthreads();
-        const uint32_t R = L.qpre[PF_MAX_Q / 64];
+        const uint32_t R = pf_rank_sort(L, tn, tid, nthr, [&](uint32_t k) { return T.q[h + k] & 0x7fffffffu; }, [&](uint32_t slot, uint32_t k) { T.perm[slot] = (uint16_t)k; });
         if (R > PF_MAX_RANK) return false;
-        for (uint32_t t = tid; t <= R; t += nthr) L.start[t] = 0;
-        __syncthreads();
-        auto rank_of = [&](uint32_t qq) { return L.qpre[qq >> 6] + (uint32_t)__popcll(L.qmask[qq >> 6] & ((1ull << (qq & 63)) - 1ull)); };
-        for (uint32_t k = tid; k < tn; k += nthr) atomicAdd(&L.start[rank_of(T.q[h + k] & 0x7fffffffu) + 1], 1u);
-        __syncthreads();
-        if (tid == 0) { uint32_t acc = 0; for (uint32_t r = 0; r < R; ++r) { acc += L.start[r + 1]; L.start[r + 1] = acc; } }
-        __syncthreads();
-        for (uint32_t t = tid; t < R; t += nthr) L.cur[t] = L.start[t];
-        __syncthreads();
-        for (uint32_t k = tid; k < tn; k += nthr) T.perm[atomicAdd(&L.cur[rank_of(T.q[h + k] & 0x7fffffffu)], 1u)] = (uint16_t)k;
-        __syncthreads();
         for (uint32_t r = 0; r < R; ++r) {
             const uint32_t e = L.start[r + 1];
             for (uint32_t base = L.start[r]; base < e; base += n_grp) {
@@ -708,7 +710,7 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
                             const uint32_t qj = T.q[j], xj = T.x[j];
                             if (xi - xj > lim) { stop = true; break; }
                             const int32_t sc = comput_sc(xi, qi, xj, qj & 0x7fffffffu, mdx, mdy, P);
-                            if (sc != SH_SC_NONE) { if (++nv > P.max_skip) { stop = true; break; } const int32_t c = sc + T.f[j]; if (c > max_f) { max_f = c; max_j = j; } }
+                            if (!pf_fold(sc, T.f, j, P.max_skip, max_f, max_j, nv)) { stop = true; break; }
                             if (qj >> 31) { stop = true; break; }
                         }
                         if (!stop && t0 > h) bad = true;      // ran out of halo
@@ -719,7 +721,7 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
                             const uint32_t xj = T.x[j];
                             if (xi - xj > lim) { stop = true; break; }
                             const int32_t sc = comput_sc(xi, qi, xj, T.q[j] & 0x7fffffffu, mdx, mdy, P);
-                            if (sc != SH_SC_NONE) { if (++nv > P.max_skip) { stop = true; break; } const int32_t c = sc + T.f[j]; if (c > max_f) { max_f = c; max_j = j; } }
+                            if (!pf_fold(sc, T.f, j, P.max_skip, max_f, max_j, nv)) { stop = true; break; }
                         }
                         // the cluster starts before the halo and this lane never met the distance limit
                         if (!stop && jmin == 0 && t0 > h && !(T.q[0] >> 31)) bad = true;
@@ -761,6 +763,17 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
     return true;
 }
 
+// what mg_chain_bk_end sees of a store when the t == 1 marks are the bits of `done`; its own transient marks (2, then 0 again)
+// are never looked at, so writing them is nothing
+template <class Store>
+struct DoneMaskView {
+    const Store &S; uint64_t done;
+    __device__ inline int32_t F(int i) const { return S.F(i); }
+    __device__ inline int32_t Pm(int i) const { return S.Pm(i); }
+    __device__ inline int32_t T(int i) const { return (int32_t)((done >> i) & 1); }
+    __device__ inline void setT(int, int32_t) const {}
+};
+
 template <class Store, class EM = NoEmit>
 __device__ inline void backtrack_mask(Store &S, int n, const ChainParams &P, int32_t &n_u, int32_t &best, bool first_only, const EM &em = EM())
 {
@@ -780,17 +793,10 @@ __device__ inline void backtrack_mask(Store &S, int n, const ChainParams &P, int
         const int32_t zf = (int32_t)(cur >> 32);
         const int zi = (int)(cur & 0xffffffff);
         if (em.done(zf)) break;
-        // mg_chain_bk_end
-        int i = zi, end_i = -1, max_i = zi;
-        int32_t max_s = 0;
-        do {
-            end_i = i = S.Pm(i);
-            int32_t sc = i < 0 ? zf : zf - S.F(i);
-            if (sc > max_s) { max_s = sc; max_i = i; }
-            else if (max_s - sc > P.bw) break;
-        } while (i >= 0 && !((done >> i) & 1));
-        (void)end_i;
+        const DoneMaskView<Store> V{S, done};
+        const int max_i = chain_bk_end<const DoneMaskView<Store>, int>(V, P.bw, zf, zi);
         const int64_t n_v0 = n_v;
+        int i;
         for (i = zi; i != max_i; i = S.Pm(i)) { ++n_v; done |= 1ULL << i; }
         const int32_t sc = i < 0 ? zf : zf - S.F(i);
         if (sc >= P.min_sc && n_v > n_v0 && n_v - n_v0 >= P.min_cnt) { ++n_u; if (sc > best) best = sc; em((int64_t)zi, (int64_t)max_i, sc, n_v - n_v0, zf); }
@@ -924,15 +930,6 @@ __device__ inline uint32_t prefix_popc64(uint64_t mask)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// inclusive prefix composition (lane order) of the functions x -> max(x + a, b)
-#define SH_COMP_STEP(CTRL, ROWS) { const int32_t pa = dpp_mov<CTRL, ROWS>(0, a), pb = dpp_mov<CTRL, ROWS>(-(1 << 29), b); \
-                                   const int32_t nb = pb + a > b ? pb + a : b; a = pa + a; b = nb; }
-__device__ inline void wave_scan_compose(int32_t &a, int32_t &b)
-{
-    SH_COMP_STEP(0x111, 0xf) SH_COMP_STEP(0x112, 0xf) SH_COMP_STEP(0x114, 0xf) SH_COMP_STEP(0x118, 0xf)
-    SH_COMP_STEP(0x142, 0xa) SH_COMP_STEP(0x143, 0xc)
-}
-
 // ---- wave-cooperative DP: all 64 lanes work on ONE cluster ---------------------------------------------------------
 // mg_lchain_dp scans the predecessors j = i-1 .. st of anchor i sequentially, with a running maximum, the
 // max_skip counter and the t[] marks.  Here the 64 lanes evaluate 64 predecessors at once and the sequential
@@ -942,21 +939,57 @@ __device__ inline void wave_scan_compose(int32_t &a, int32_t &b)
 //                           first, then read; a mark written by a lane past the break point can only concern
 //                           anchors that are themselves past the break point, so over-marking is harmless;
 //   * n_skip (saturating decrement on a new maximum, increment on a marked non-maximum, break above max_skip)
-//                         = prefix composition of functions x -> max(x + a, b), which is closed under composition.
+//                         = a walk reflected at zero, from two ballots and a prefix minimum (chain_wave_scan_step).
 // The critical path of a 20-anchor cluster drops from ~190 dependent pair evaluations to 20 wave steps.
 __device__ inline void wave_mem_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
+// One chunk of up to 64 predecessors in scan order (lane 0 first; lanes 0 .. last hold the chunk).  sc: the lane's candidate score
+// f[j] + comput_sc, INT32_MIN without one (has = false); is_t: the lane's predecessor is marked (t[j] == i).  Continues the scan from
+// the running max_f / n_skip and says where the sequential scan would stand after the chunk: max_lane = the lane that raised max_f
+// last (-1: none did), brk_lane = the lane at which n_skip went above max_skip (-1: the scan goes on) - nothing after it counts.
+struct WaveScanStep { int32_t max_f, n_skip; int max_lane, brk_lane; };
+__device__ __forceinline__ WaveScanStep chain_wave_scan_step(uint32_t lane, int32_t sc, bool has, bool is_t, int last, int32_t max_skip, int32_t max_f, int32_t n_skip)
+{
+    // exclusive prefix maximum in scan order, seeded with the running max_f
+    const int32_t incl = wave_scan_max_incl(sc);
+    int32_t excl = wave_shr1(incl, INT32_MIN);
+    if (excl < max_f) excl = max_f;
+    const bool new_max = has && sc > excl;
+    const bool inc_ev = has && !new_max && is_t;
+    // n_skip is a walk reflected at zero (new maximum: max(x - 1, 0); marked non-maximum: x + 1):
+    // x_l = Y_l - min(0, min_{m <= l} Y_m) with the free walk Y_l = n_skip + #inc(<= l) - #new_max(<= l)
+    const uint64_t inc_m = __ballot(inc_ev), nm_m = __ballot(new_max);
+    const int32_t yl = n_skip + (int32_t)prefix_popc64(inc_m) + (inc_ev ? 1 : 0) - (int32_t)prefix_popc64(nm_m) - (new_max ? 1 : 0);
+    const int32_t mn = wave_scan_min_incl(yl);
+    const int32_t val = yl - (mn < 0 ? mn : 0);
+    const uint64_t brk = __ballot(inc_ev && val > max_skip);
+    WaveScanStep r{max_f, 0, -1, brk ? __ffsll((unsigned long long)brk) - 1 : -1};
+    if (r.brk_lane > last) r.brk_lane = -1;
+    const int L = r.brk_lane >= 0 ? r.brk_lane : last;
+    const int32_t mm = __builtin_amdgcn_readlane(incl, L);      // max over the lanes up to the break point
+    if (mm > max_f) {
+        r.max_f = mm;
+        const uint64_t eq = __ballot((int)lane <= L && sc == mm);
+        r.max_lane = __ffsll((unsigned long long)eq) - 1;
+    }
+    r.n_skip = __builtin_amdgcn_readlane(val, L);
+    return r;
+}
+
+// how the max_ii helpers reach a cluster's anchors through chain_dp_wave's volatile views (one cluster: grp is constant)
+struct SliceAtV {
+    volatile const uint64_t *x; volatile const uint32_t *q; volatile const int32_t *f;
+    __device__ inline uint32_t grp(int) const { return 0; }
+    __device__ inline uint32_t rlo(int i) const { return (uint32_t)x[i]; }
+    __device__ inline uint32_t qp(int i) const { return q[i] & 0x7fffffffu; }
+    __device__ inline int32_t F(int i) const { return f[i]; }
+};
+
 __device__ inline bool chain_dp_wave(const SliceStore &S, int n, int32_t qlen, const ChainParams &P, uint32_t lane, int32_t stop_at = INT32_MAX)
 {
-    int32_t max_dist_y = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap;
-    int32_t max_dist_x;
-    if (P.max_gap_ref > 0) max_dist_x = P.max_gap_ref;
-    else if (P.max_frag_len > 0) { max_dist_x = P.max_frag_len - qlen; if (max_dist_x < P.max_gap) max_dist_x = P.max_gap; }
-    else max_dist_x = P.max_gap;
-    if (max_dist_x < P.bw) max_dist_x = P.bw;
-    if (max_dist_y < P.bw) max_dist_y = P.bw;
+    const int32_t max_dist_x = (int32_t)chain_max_dist_x(P, qlen), max_dist_y = chain_max_dist_y(P, qlen);
     volatile const uint64_t *x = S.x; volatile const uint32_t *q = S.q; volatile int32_t *f = S.f; volatile int32_t *pt = S.pt;
-    const int NEG = -(1 << 28);
+    const SliceAtV at{x, q, f};
 
     for (int i = (int)lane; i < n; i += 64) pt[2 * i + 1] = 0;
     wave_mem_sync();
@@ -979,33 +1012,13 @@ __device__ inline bool chain_dp_wave(const SliceStore &S, int n, int32_t qlen, c
             if (has && pj >= 0) pt[2 * pj + 1] = i;
             wave_mem_sync();
             const bool is_t = has && pt[2 * j + 1] == i;
-            // exclusive prefix maximum in scan order (lane 0 = j = jb first), seeded with the running max_f
-            const int32_t scv = has ? sc : INT32_MIN;
-            const int32_t incl = wave_scan_max_incl(scv);
-            int32_t excl = wave_shr1(incl, INT32_MIN);
-            if (excl < max_f) excl = max_f;
-            const bool new_max = has && sc > excl;
-            const bool inc_ev = has && !new_max && is_t;
-            // n_skip is a walk reflected at zero (see chain_dp_ring)
-            const uint64_t inc_m = __ballot(inc_ev), nm_m = __ballot(new_max);
-            const int32_t yl = n_skip + (int32_t)prefix_popc64(inc_m) + (inc_ev ? 1 : 0) - (int32_t)prefix_popc64(nm_m) - (new_max ? 1 : 0);
-            const int32_t mn = wave_scan_min_incl(yl);
-            const int32_t val = yl - (mn < 0 ? mn : 0);
-            const uint64_t brk = __ballot(inc_ev && val > P.max_skip);
-            const int L = brk ? __ffsll((unsigned long long)brk) - 1 : 63;
-            const int32_t mm = __builtin_amdgcn_readlane(incl, L);
-            if (mm > max_f) {
-                max_f = mm;
-                const uint64_t eq = __ballot((int)lane <= L && scv == mm);
-                max_j = jb - (__ffsll((unsigned long long)eq) - 1);
-            }
-            n_skip = __builtin_amdgcn_readlane(val, L);
-            if (brk) { end_j = jb - L; break; }
+            const WaveScanStep step = chain_wave_scan_step(lane, has ? sc : INT32_MIN, has, is_t, 63, P.max_skip, max_f, n_skip);      // lane 0 = j = jb first
+            max_f = step.max_f; n_skip = step.n_skip;
+            if (step.max_lane >= 0) max_j = jb - step.max_lane;
+            if (step.brk_lane >= 0) { end_j = jb - step.brk_lane; break; }
         }
         // the max_ii shortcut (uniform)
-        bool far = true;
-        if (max_ii >= 0) far = (uint64_t)(li - (uint32_t)x[max_ii]) > (uint64_t)max_dist_x;
-        if (max_ii < 0 || far) {
+        if (!max_ii_in_reach(at, max_ii, 0u, li, max_dist_x)) {
             int32_t bf = INT32_MIN; int bj = -1;
             for (int jb = i - 1; jb >= st; jb -= 64) {
                 const int j = jb - (int)lane;
@@ -1015,16 +1028,11 @@ __device__ inline bool chain_dp_wave(const SliceStore &S, int n, int32_t qlen, c
             }
             max_ii = bj;
         }
-        if (max_ii >= 0 && max_ii < end_j) {
-            int32_t tmp = comput_sc(li, qi, (uint32_t)x[max_ii], q[max_ii] & 0x7fffffffu, max_dist_x, max_dist_y, P);
-            if (tmp != SH_SC_NONE && max_f < tmp + f[max_ii]) { max_f = tmp + f[max_ii]; max_j = max_ii; }
-        }
+        max_ii_apply(at, max_ii, end_j, li, qi, max_dist_x, max_dist_y, P, max_f, max_j);
         if (lane == 0) { f[i] = max_f; pt[2 * i] = max_j; }
         wave_mem_sync();
         if (max_f >= stop_at) return true;           // wave-uniform
-        bool near = false;
-        if (max_ii >= 0) near = (uint64_t)(li - (uint32_t)x[max_ii]) <= (uint64_t)max_dist_x;
-        if (max_ii < 0 || (near && f[max_ii] < max_f)) max_ii = i;
+        if (max_ii_moves(at, max_ii, 0u, li, max_dist_x, max_f)) max_ii = i;
     }
     return false;
 }
@@ -1056,20 +1064,20 @@ __device__ inline bool chain_dp_ring(const uint64_t *gx, const uint32_t *gq, int
     // loops below was a scratch load (five per chunk of predecessors in the ISA)
     const ChainParams P = P_in;
     unsigned long long n_ch_in = 0, n_ch_out = 0, n_far = 0; int n_evt = 0, max_win = 0;
-    int32_t max_dist_y = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap;
-    int32_t max_dist_x;
-    if (P.max_gap_ref > 0) max_dist_x = P.max_gap_ref;
-    else if (P.max_frag_len > 0) { max_dist_x = P.max_frag_len - qlen; if (max_dist_x < P.max_gap) max_dist_x = P.max_gap; }
-    else max_dist_x = P.max_gap;
-    if (max_dist_x < P.bw) max_dist_x = P.bw;
-    if (max_dist_y < P.bw) max_dist_y = P.bw;
+    const int32_t max_dist_x = (int32_t)chain_max_dist_x(P, qlen), max_dist_y = chain_max_dist_y(P, qlen);
     constexpr int M = RING_CAP - 1;
     constexpr int TW = RING_TBITS / 32;
 
     for (int d = (int)lane; d < TW; d += 64) rm.tb[d] = 0;
     int st = 0, sb = 0, max_ii = -1;
     uint32_t sxv = (int)lane < n ? (uint32_t)gx[lane] : 0xffffffffu;      // x of anchor sb + lane (start-of-window search)
-    uint32_t mi_x = 0, mi_q = 0; int32_t mi_f = 0;                           // anchor max_ii
+    struct {      // anchor max_ii, whatever index is asked for: registers, not loads
+        uint32_t x, q; int32_t f;
+        __device__ inline uint32_t grp(int) const { return 0; }
+        __device__ inline uint32_t rlo(int) const { return x; }
+        __device__ inline uint32_t qp(int) const { return q; }
+        __device__ inline int32_t F(int) const { return f; }
+    } mi{0, 0, 0};
     uint32_t nx = 0, nq = 0;                                                  // anchors of the current block of 64
     for (int i = 0; i < n; ++i) {
         if ((i & 63) == 0) {
@@ -1116,28 +1124,10 @@ __device__ inline bool chain_dp_ring(const uint64_t *gx, const uint32_t *gq, int
             if (mk) atomicOr(&rm.tb[(pj & (RING_TBITS - 1)) >> 5], 1u << (pj & 31));
             marked |= __ballot(mk) != 0;
             const bool is_t = has && ((rm.tb[(j & (RING_TBITS - 1)) >> 5] >> (j & 31)) & 1u);
-            // exclusive prefix maximum in scan order (lane 0 = j = jb first), seeded with the running max_f
-            const int32_t incl = wave_scan_max_incl(sc);
-            int32_t excl = wave_shr1(incl, INT32_MIN);
-            if (excl < max_f) excl = max_f;
-            const bool new_max = has && sc > excl;
-            const bool inc_ev = has && !new_max && is_t;
-            // n_skip is a walk reflected at zero (new maximum: max(x - 1, 0); marked non-maximum: x + 1):
-            // x_l = Y_l - min(0, min_{m <= l} Y_m) with the free walk Y_l = n_skip + #inc(<= l) - #new_max(<= l)
-            const uint64_t inc_m = __ballot(inc_ev), nm_m = __ballot(new_max);
-            const int32_t yl = n_skip + (int32_t)prefix_popc64(inc_m) + (inc_ev ? 1 : 0) - (int32_t)prefix_popc64(nm_m) - (new_max ? 1 : 0);
-            const int32_t mn = wave_scan_min_incl(yl);
-            const int32_t val = yl - (mn < 0 ? mn : 0);
-            const uint64_t brk = __ballot(inc_ev && val > P.max_skip);
-            const int L = brk ? __ffsll((unsigned long long)brk) - 1 : 63;
-            const int32_t mm = __builtin_amdgcn_readlane(incl, L);      // max over the lanes up to the break point
-            if (mm > max_f) {
-                max_f = mm;
-                const uint64_t eq = __ballot((int)lane <= L && sc == mm);
-                max_j = jb - (__ffsll((unsigned long long)eq) - 1);
-            }
-            n_skip = __builtin_amdgcn_readlane(val, L);
-            if (brk) { end_j = jb - L; ++n_evt; break; }
+            const WaveScanStep step = chain_wave_scan_step(lane, sc, has, is_t, 63, P.max_skip, max_f, n_skip);      // lane 0 = j = jb first
+            max_f = step.max_f; n_skip = step.n_skip;
+            if (step.max_lane >= 0) max_j = jb - step.max_lane;
+            if (step.brk_lane >= 0) { end_j = jb - step.brk_lane; ++n_evt; break; }
         }
         if (i - st > max_win) max_win = i - st;
         if (marked) {       // clear the marks of this step: they all lie in [st, i)
@@ -1145,9 +1135,7 @@ __device__ inline bool chain_dp_ring(const uint64_t *gx, const uint32_t *gq, int
             for (int d = (st >> 5) + (int)lane; d <= d1; d += 64) rm.tb[d & (TW - 1)] = 0;
         }
         // the max_ii shortcut (uniform)
-        bool far = true;
-        if (max_ii >= 0) far = (uint64_t)(li - mi_x) > (uint64_t)max_dist_x;
-        if (max_ii < 0 || far) {
+        if (!max_ii_in_reach(mi, max_ii, 0u, li, max_dist_x)) {
             int32_t bf = INT32_MIN; int bj = -1;
             int c2 = 0; ++n_far;
             for (int jb = i - 1; jb >= st; jb -= 64, ++c2) {
@@ -1163,20 +1151,15 @@ __device__ inline bool chain_dp_ring(const uint64_t *gx, const uint32_t *gq, int
             }
             max_ii = bj;
             if (bj >= 0) {
-                if (bj >= i - RING_WIN) { mi_x = rm.rec[bj & M].x; mi_q = rm.rec[bj & M].y; }
-                else { mi_x = (uint32_t)gx[bj]; mi_q = gq[bj] & 0x7fffffffu; }
-                mi_f = bf;
+                if (bj >= i - RING_WIN) { mi.x = rm.rec[bj & M].x; mi.q = rm.rec[bj & M].y; }
+                else { mi.x = (uint32_t)gx[bj]; mi.q = gq[bj] & 0x7fffffffu; }
+                mi.f = bf;
             }
         }
-        if (max_ii >= 0 && max_ii < end_j) {
-            int32_t tmp = comput_sc(li, qi, mi_x, mi_q, max_dist_x, max_dist_y, P);
-            if (tmp != SH_SC_NONE && max_f < tmp + mi_f) { max_f = tmp + mi_f; max_j = max_ii; }
-        }
+        max_ii_apply(mi, max_ii, end_j, li, qi, max_dist_x, max_dist_y, P, max_f, max_j);
         if (lane == 0) { rm.rec[i & M].z = (uint32_t)max_f; rm.rec[i & M].w = (uint32_t)max_j; gf[i] = max_f; gpt[2 * i] = max_j; }
         if (max_f >= stop_at) { wave_mem_sync(); return true; }      // wave-uniform
-        bool near = false;
-        if (max_ii >= 0) near = (uint64_t)(li - mi_x) <= (uint64_t)max_dist_x;
-        if (max_ii < 0 || (near && mi_f < max_f)) { max_ii = i; mi_x = li; mi_q = qi; mi_f = max_f; }
+        if (max_ii_moves(mi, max_ii, 0u, li, max_dist_x, max_f)) { max_ii = i; mi.x = li; mi.q = qi; mi.f = max_f; }
     }
     wave_mem_sync();
     if (dbg_cnt && lane == 0) {
@@ -1206,6 +1189,7 @@ __device__ inline int first_chain_quick(const int32_t *gf, const int32_t *gpt, i
     const int32_t zf = (int32_t)(key >> 32);
     int i = (int)(key & 0xffffffff), steps = 0, cnt = 0;
     int32_t max_s = 0;
+    // mg_chain_bk_end restated: the return inside the loop ends the walk early, which chain_bk_end has no way to say
     do {
         i = vpt[2 * i]; ++steps;
         const int32_t s = i < 0 ? zf : zf - vf[i];
@@ -1328,6 +1312,7 @@ __device__ inline void chain_cluster_ring(const uint64_t *gx, uint32_t *gq, int3
                                           int32_t &n_u, int32_t &best, bool first_only, uint32_t lane, RingMem &rm, unsigned long long *dbg_cnt = nullptr,
                                           const ChainSink *sk = nullptr, uint32_t read = 0, uint32_t base = 0, uint64_t *heap = nullptr, bool pre = false)
 {   // pre: f and p are there already (par_fill_block; p as indices into the read's array, this cluster starting at `base`)
+    // (the DP call stands once per mode here: one call site ahead of both modes costs k_cluster_dp 8 B of scratch per lane)
     n_u = 0; best = 0;
     if (sk) {      // hand-over mode: every chain, anchors intact (the heap lives in `heap`, not over the x slice)
         if (!pre) chain_dp_ring(gx, gq, gf, gpt, n, qlen, P, lane, rm, dbg_cnt);
@@ -1353,48 +1338,42 @@ __device__ inline void chain_cluster_ring(const uint64_t *gx, uint32_t *gq, int3
 __device__ inline void chain_cluster_wave(SliceStore &S, int32_t n, int32_t qlen, const ChainParams &P, uint64_t *zbuf, int32_t &n_u, int32_t &best,
                                           bool first_only, uint32_t lane, const ChainSink *sk = nullptr, uint32_t read = 0, uint32_t base = 0, bool pre = false)
 {   // pre: f and p are there already (par_fill_block; S.pbase set by the caller)
-    if (sk) {      // hand-over mode (zbuf must not alias the anchors)
-        const StoreEmit<SliceStore> em{sk, &S, read, base, lane == 0, P.k, region_hash(qlen), qlen, nullptr};
-        if (P.ext_s1 && n >= 2 && n <= 64 && !pre) {
-            // A cluster whose anchors all lie on ONE diagonal, d <= min(max_dist_x, max_dist_y) apart (a copy of the read up to substitutions -
-            // the true locus nearly always): the outcome of mg_lchain_dp + mg_chain_backtrack is known without running them (the argument of
-            // k_pair_pass mode 2; no skip penalty: ext_s1) - every anchor links to its predecessor (it is scanned first and no earlier one can
-            // beat f[i-1] + min(k, d)), f is the running sum, and the backtrack returns the one chain of all n anchors if it clears min_sc /
-            // min_cnt.  f and p are written as the DP would have, then the chain is handed over.
-            int32_t mdy = P.is_sr ? (qlen > P.max_gap ? qlen : P.max_gap) : P.max_gap, mdx;
-            if (P.max_gap_ref > 0) mdx = P.max_gap_ref;
-            else if (P.max_frag_len > 0) { mdx = P.max_frag_len - qlen; if (mdx < P.max_gap) mdx = P.max_gap; }
-            else mdx = P.max_gap;
-            if (mdx < P.bw) mdx = P.bw;
-            if (mdy < P.bw) mdy = P.bw;
-            const int32_t dmax = mdx < mdy ? mdx : mdy;
-            const bool in = (int32_t)lane < n;
-            const uint32_t lo = in ? S.rlo((int32_t)lane) : 0u, qv = in ? S.qp((int32_t)lane) : 0u;
-            const uint32_t dg = lo - qv, dg0 = (uint32_t)__builtin_amdgcn_readlane((int)dg, 0);
-            const int32_t dq = (int32_t)qv - wave_shr1((int32_t)qv, 0);
-            const bool good = !in || (dg == dg0 && (lane == 0 || (dq > 0 && dq <= dmax)));
-            if (__ballot(!good) == 0) {
-                int32_t v = !in ? 0 : (lane == 0 ? P.k : (dq < P.k ? dq : P.k));
-                const int32_t fl = wave_scan_add_incl(v);
-                if (in) { S.setFP((int32_t)lane, fl, (int32_t)lane - 1); S.setT((int32_t)lane, 0); }
-                wave_mem_sync();
-                const int32_t sc = wave_bcast(fl, n - 1);
-                n_u = 0; best = 0;
-                if (sc >= P.min_sc && n >= P.min_cnt) { n_u = 1; best = sc; em((int64_t)(n - 1), (int64_t)-1, sc, (int64_t)n, sc); }
-                wave_mem_sync();
-                return;
-            }
+    if (!sk && first_only && P.flag_stop != INT32_MAX && !pre) { n_u = chain_dp_wave(S, n, qlen, P, lane, P.flag_stop) ? 1 : 0; best = 0; return; }
+    const StoreEmit<SliceStore> em{sk, &S, read, base, lane == 0, P.k, region_hash(qlen), qlen, nullptr};      // hand-over mode only (zbuf must not alias the anchors)
+    if (sk && P.ext_s1 && n >= 2 && n <= 64 && !pre) {
+        // A cluster whose anchors all lie on ONE diagonal, d <= min(max_dist_x, max_dist_y) apart (a copy of the read up to substitutions -
+        // the true locus nearly always): the outcome of mg_lchain_dp + mg_chain_backtrack is known without running them (the argument of
+        // k_pair_pass mode 2; no skip penalty: ext_s1) - every anchor links to its predecessor (it is scanned first and no earlier one can
+        // beat f[i-1] + min(k, d)), f is the running sum, and the backtrack returns the one chain of all n anchors if it clears min_sc /
+        // min_cnt.  f and p are written as the DP would have, then the chain is handed over.
+        const int32_t mdx = (int32_t)chain_max_dist_x(P, qlen), mdy = chain_max_dist_y(P, qlen);
+        const int32_t dmax = mdx < mdy ? mdx : mdy;
+        const bool in = (int32_t)lane < n;
+        const uint32_t lo = in ? S.rlo((int32_t)lane) : 0u, qv = in ? S.qp((int32_t)lane) : 0u;
+        const uint32_t dg = lo - qv, dg0 = (uint32_t)__builtin_amdgcn_readlane((int)dg, 0);
+        const int32_t dq = (int32_t)qv - wave_shr1((int32_t)qv, 0);
+        const bool good = !in || (dg == dg0 && (lane == 0 || (dq > 0 && dq <= dmax)));
+        if (__ballot(!good) == 0) {
+            int32_t v = !in ? 0 : (lane == 0 ? P.k : (dq < P.k ? dq : P.k));
+            const int32_t fl = wave_scan_add_incl(v);
+            if (in) { S.setFP((int32_t)lane, fl, (int32_t)lane - 1); S.setT((int32_t)lane, 0); }
+            wave_mem_sync();
+            const int32_t sc = wave_bcast(fl, n - 1);
+            n_u = 0; best = 0;
+            if (sc >= P.min_sc && n >= P.min_cnt) { n_u = 1; best = sc; em((int64_t)(n - 1), (int64_t)-1, sc, (int64_t)n, sc); }
+            wave_mem_sync();
+            return;
         }
-        if (!pre) chain_dp_wave(S, n, qlen, P, lane);
+    }
+    if (!pre) chain_dp_wave(S, n, qlen, P, lane);
+    if (sk) {
         if (n <= 64) backtrack_mask(S, n, P, n_u, best, false, em);
         else if (sk->best) backtrack_wave_top(S, n, P, n_u, best, em, lane);
         else { backtrack_heap<SliceStore, int32_t, StoreEmit<SliceStore>>(S, n, P, zbuf, n_u, best, false, em); wave_mem_sync(); }
-        return;
+    } else {
+        if (n <= 64) backtrack_mask(S, n, P, n_u, best, first_only);
+        else { backtrack_heap<SliceStore, int32_t>(S, n, P, zbuf, n_u, best, first_only); wave_mem_sync(); }
     }
-    if (first_only && P.flag_stop != INT32_MAX && !pre) { n_u = chain_dp_wave(S, n, qlen, P, lane, P.flag_stop) ? 1 : 0; best = 0; return; }
-    if (!pre) chain_dp_wave(S, n, qlen, P, lane);
-    if (n <= 64) backtrack_mask(S, n, P, n_u, best, first_only);
-    else { backtrack_heap<SliceStore, int32_t>(S, n, P, zbuf, n_u, best, first_only); wave_mem_sync(); }
 }
 
 // DP + backtrack of one cluster.  zbuf: n 8-B words for the heap when n > 32 (may alias the x slice: the
@@ -1402,22 +1381,18 @@ __device__ inline void chain_cluster_wave(SliceStore &S, int32_t n, int32_t qlen
 __device__ inline void chain_cluster(SliceStore &S, int32_t n, int32_t qlen, const ChainParams &P, uint64_t *zbuf, int32_t &n_u, int32_t &best,
                                      bool first_only, const ChainSink *sk = nullptr, uint32_t read = 0, uint32_t base = 0, bool pre = false)
 {   // pre: f and p are there already (par_fill_block; S.pbase set by the caller)
-    if (sk) {      // hand-over mode (zbuf must not alias the anchors)
-        const StoreEmit<SliceStore> em{sk, &S, read, base, true, P.k, region_hash(qlen), qlen, nullptr};
-        if (n <= 64) { if (!pre) chain_dp_mask(S, n, qlen, P); backtrack_mask(S, n, P, n_u, best, false, em); }
-        else { if (!pre) chain_dp<SliceStore, int32_t>(S, n, qlen, P); backtrack_heap<SliceStore, int32_t, StoreEmit<SliceStore>>(S, n, P, zbuf, n_u, best, false, em); }
-        return;
-    }
-    if (first_only && P.flag_stop != INT32_MAX && !pre) {
+    if (!sk && first_only && P.flag_stop != INT32_MAX && !pre) {
         n_u = (n <= 64 ? chain_dp_mask(S, n, qlen, P, P.flag_stop) : chain_dp<SliceStore, int32_t>(S, n, qlen, P, P.flag_stop)) ? 1 : 0;
         best = 0;
         return;
     }
-    if (n <= 64) {
-        if (!pre) chain_dp_mask(S, n, qlen, P);
-        backtrack_mask(S, n, P, n_u, best, first_only);
+    if (!pre) { if (n <= 64) chain_dp_mask(S, n, qlen, P); else chain_dp<SliceStore, int32_t>(S, n, qlen, P); }
+    if (sk) {      // hand-over mode (zbuf must not alias the anchors)
+        const StoreEmit<SliceStore> em{sk, &S, read, base, true, P.k, region_hash(qlen), qlen, nullptr};
+        if (n <= 64) backtrack_mask(S, n, P, n_u, best, false, em);
+        else backtrack_heap<SliceStore, int32_t, StoreEmit<SliceStore>>(S, n, P, zbuf, n_u, best, false, em);
     } else {
-        if (!pre) chain_dp<SliceStore, int32_t>(S, n, qlen, P);
-        backtrack_heap<SliceStore, int32_t>(S, n, P, zbuf, n_u, best, first_only);
+        if (n <= 64) backtrack_mask(S, n, P, n_u, best, first_only);
+        else backtrack_heap<SliceStore, int32_t>(S, n, P, zbuf, n_u, best, first_only);
     }
 }

@@ -897,12 +897,7 @@ __global__ __launch_bounds__(64) void k_pair_pass(K2Args a, int distinct)
             n_seed = info >> 16 & 0x7fffu;
             const uint4 *rec = a.records + (size_t)r * a.seed_cap;
             const int32_t qlen = (int32_t)(a.offsets[r + 1] - a.offsets[r]);
-            int32_t mdy = a.P.is_sr ? (qlen > a.P.max_gap ? qlen : a.P.max_gap) : a.P.max_gap, mdx;
-            if (a.P.max_gap_ref > 0) mdx = a.P.max_gap_ref;
-            else if (a.P.max_frag_len > 0) { mdx = a.P.max_frag_len - qlen; if (mdx < a.P.max_gap) mdx = a.P.max_gap; }
-            else mdx = a.P.max_gap;
-            if (mdx < a.P.bw) mdx = a.P.bw;
-            if (mdy < a.P.bw) mdy = a.P.bw;
+            const int32_t mdx = (int32_t)chain_max_dist_x(a.P, qlen), mdy = chain_max_dist_y(a.P, qlen);
             const int32_t dmax = mdx < mdy ? mdx : mdy;
             bool ok = a.P.ext_s1 != 0 && n_seed >= 2 && (int32_t)n_seed >= a.P.min_cnt && n_seed <= a.seed_cap;
             uint64_t w0 = 0, wl = 0; uint32_t q0 = 0, ql = 0, qp = 0; int32_t unc = 0;

@@ -654,28 +654,11 @@ __device__ inline bool lr_rmq_fill(const LongParams &P, int32_t max_dist_in, int
                     if (has && pj >= st_inner) L.rt[pj & M] = i;      // a mark only matters on an anchor this scan can still visit
                     __builtin_amdgcn_wave_barrier();
                     const bool is_t = has && L.rt[j & M] == i;
-                    const int32_t scv = has ? scj : INT32_MIN;
-                    const int32_t incl = wave_scan_max_incl(scv);
-                    int32_t excl = wave_shr1(incl, INT32_MIN);
-                    if (excl < max_f) excl = max_f;
-                    const bool new_max = has && scj > excl;
-                    const bool inc_ev = has && !new_max && is_t;
-                    const uint64_t inc_m = __ballot(inc_ev), nm_m = __ballot(new_max);
-                    const int32_t yl = n_skip + (int32_t)prefix_popc64(inc_m) + (inc_ev ? 1 : 0) - (int32_t)prefix_popc64(nm_m) - (new_max ? 1 : 0);
-                    const int32_t mn = wave_scan_min_incl(yl);
-                    const int32_t val = yl - (mn < 0 ? mn : 0);
-                    const uint64_t brk = __ballot(inc_ev && val > max_skip);
                     const int nv = (int)__popcll(vm);
-                    int Lb = brk ? __ffsll((unsigned long long)brk) - 1 : 63;
-                    if (Lb > nv - 1) Lb = nv - 1;
-                    const int32_t mm = __builtin_amdgcn_readlane(incl, Lb);
-                    if (mm > max_f) {
-                        max_f = mm;
-                        const uint64_t eq = __ballot(lane <= Lb && scv == mm);
-                        max_j = __builtin_amdgcn_readlane(j, (int)(__ffsll((unsigned long long)eq) - 1));
-                    }
-                    n_skip = __builtin_amdgcn_readlane(val, Lb);
-                    if ((brk && (__ffsll((unsigned long long)brk) - 1) <= nv - 1) || nv < 64) break;
+                    const WaveScanStep step = chain_wave_scan_step((uint32_t)lane, has ? scj : INT32_MIN, has, is_t, nv - 1, max_skip, max_f, n_skip);
+                    max_f = step.max_f; n_skip = step.n_skip;
+                    if (step.max_lane >= 0) max_j = __builtin_amdgcn_readlane(j, step.max_lane);
+                    if (step.brk_lane >= 0 || nv < 64) break;
                 }
             }
         }
