@@ -648,6 +648,32 @@ typedef struct sh_dbg_chain_result { int32_t ret, bt_ret, n_u, best, n_emit, pad
 sh_status sh_dbg_chain(int32_t device, const uint64_t *x, const uint32_t *q, uint64_t n_total, const sh_dbg_chain_case *cases, int32_t n_cases,
                        const int32_t *f_in, const int32_t *p_in, sh_dbg_chain_result *out, int32_t *f, int32_t *p, int32_t *t, int32_t *chains);
 
+/* Test aid: the three minimizer state machines of csrc/sh_sketch.h, called directly (csrc/sh_dbg_sketch.hip; tests/test_sketch_gpu.py compares
+ * them with the oracle's mmo_sketch, integers only).  One lane per sequence, one launch per call.  bases / offsets: host arrays, sequence i is
+ * bases[offsets[i] .. offsets[i + 1]) in ASCII (decoded with sh_nt4).  form 0: SketchState<w> over the whole sequence; 1: SketchPacked<w>, driven
+ * in blocks of w steps with block_end() after each, every push through sh_packed_entry, one push for minimum and tie entries as the read kernel
+ * has it; 2: SketchStateDyn with its ring in HBM.  The pushes of sequence i come back in emission order as (hash, y = pos << 1 | strand) at
+ * hash / y [offsets[i] - offsets[0] + i ..], room for len + 1 of them; count[i] = how many there were (a push beyond the room is counted, not
+ * written).  hash and y hold offsets[n_seq] - offsets[0] + n_seq entries.  w outside {5, 10, 11, 19}, even k, k > 23 (form 1) or 27, a sequence
+ * of more than 1024 bases (form 1): SH_ERR_BAD_ARG before any launch. */
+sh_status sh_dbg_sketch(int32_t device, const uint8_t *bases, const uint64_t *offsets, int32_t n_seq, int32_t w, int32_t k, int32_t form,
+                        uint64_t *hash, uint32_t *y, int32_t *count);
+/* Test aid: the front end of sh_classify_device alone (the read kernel k_sketch_probe, or the segment-parallel long-read kernels, as the
+ * context chooses), on a chunk in HBM of at most the context's max_reads reads of at most its max_read_len bases.  Resets the counters,
+ * launches, synchronises and copies out to host arrays, per read r:
+ *   k1info[r]   as the kernels leave it (read kernel: minimizers | seeds << 16 | tandem << 31; long: minimizers after thinning | seeds << 16);
+ *   route[r]    the work list that names the read: 0 none (decided with no seed), 1 work_small, 2 work_big, 4 work_resketch; more than one bit or
+ *               bit 7 (named twice by one list) is a fault of the front end;
+ *   records     its seed records, four words each (x, y = the slot's payload, z = occurrences | SH_REC_PREV_SAME, w = qpos << 1 | strand), at
+ *               records[4 * rec_off[r] .. 4 * rec_off[r + 1]): the read kernel's first min(seeds, seed_cap), the long front end's all;
+ *   mz_hash / mz_y [mz_off[r] .. mz_off[r + 1])   long front end only: its minimizers as they stand after mm_seed_mz_flt's thinning.
+ * rec_off and mz_off hold n_reads + 1 entries; rec_cap / mz_cap: room in records (records of four words) and mz_hash / mz_y (n_bases + 1 always
+ * suffices; less than needed is SH_ERR_BAD_ARG).  info[5]: front end (1 read kernel, 2 long, 0 neither), seed_cap, and the lengths of work_small,
+ * work_big and work_resketch. */
+sh_status sh_dbg_front_end(sh_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                           uint32_t *k1info, uint8_t *route, uint64_t *rec_off, uint32_t *records, uint64_t rec_cap,
+                           uint64_t *mz_off, uint64_t *mz_hash, uint32_t *mz_y, uint64_t mz_cap, int32_t *info);
+
 /* ---- Kraken arm: database inspection (DESIGN.md §7 "Database inspection"): what kraken2-inspect prints, as recalled from
  * dump_table.cc and CompactHashTable::GetValueCounts: PARITY WITH kraken2-inspect UNPINNED, like the rest of the arm.  One pass over
  * the table in HBM: every non-empty cell (the whole cell is not 0) counts under its value, cell & ((1 << value_bits) - 1).  An

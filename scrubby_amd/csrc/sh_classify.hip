@@ -3885,14 +3885,12 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     return SH_OK;
 }
 
-static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
-                                uint8_t *d_flags, sh_trace *d_trace, hipStream_t s, sh_stats *stats)
+// The front end of a chunk: K1 (reads of at most 1024 bases), the segment-parallel long-read front end, or every read to the re-sketch path.
+// Fills k1info, the seed records and the work lists (sh_dbg_front_end reads them back as they stand here).
+static sh_status launch_front_end(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                  uint8_t *d_flags, sh_trace *d_trace, hipStream_t s)
 {
     const sh_index *idx = c->idx;
-    c->cur_reads = n_reads;
-    SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
-    if (c->ext) { SH_HIP(hipMemsetAsync(c->sink.head, 0xff, n_reads * 4, s)); SH_HIP(hipMemsetAsync(c->sink.best, 0, n_reads * 8, s)); SH_HIP(hipMemsetAsync(c->sink.tie, 0, n_reads * 4, s)); }
-    SH_HIP(hipEventRecord(c->ev[0], s));
     const uint32_t n_tiles = (uint32_t)((n_reads + 63) / 64);
     if (c->use_k1) {
         K1Args a{};
@@ -3933,6 +3931,19 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     } else {
         hipLaunchKernelGGL(k_route_all, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, s, n_reads, c->d_work_resketch, c->d_ctr);
     }
+    return SH_OK;
+}
+
+static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                uint8_t *d_flags, sh_trace *d_trace, hipStream_t s, sh_stats *stats)
+{
+    const sh_index *idx = c->idx;
+    c->cur_reads = n_reads;
+    SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
+    if (c->ext) { SH_HIP(hipMemsetAsync(c->sink.head, 0xff, n_reads * 4, s)); SH_HIP(hipMemsetAsync(c->sink.best, 0, n_reads * 8, s)); SH_HIP(hipMemsetAsync(c->sink.tie, 0, n_reads * 4, s)); }
+    SH_HIP(hipEventRecord(c->ev[0], s));
+    const uint32_t n_tiles = (uint32_t)((n_reads + 63) / 64);
+    { sh_status st = launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, d_trace, s); if (st != SH_OK) return st; }
     SH_HIP(hipEventRecord(c->ev[1], s));
 
     // flag-only shortcuts over the seed records: the pair test (chain-level decision), or with SH_F_CIGAR mode 2 (co-diagonal singletons)
@@ -4624,4 +4635,94 @@ extern "C" sh_status sh_classify_device(sh_ctx *c, const uint8_t *d_bases, const
         if (st != SH_OK) return st;
     }
     return SH_OK;
+}
+
+// Test aid (tests/test_sketch_gpu.py): the front end of one chunk alone - launch_front_end on a context of sh_ctx_create, then what it
+// left behind is copied out per read: k1info, the work list the read was put on, its seed records and (long front end) its minimizers.
+extern "C" sh_status sh_dbg_front_end(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                      uint32_t *k1info, uint8_t *route, uint64_t *rec_off, uint32_t *records, uint64_t rec_cap,
+                                      uint64_t *mz_off, uint64_t *mz_hash, uint32_t *mz_y, uint64_t mz_cap, int32_t *info)
+{
+    SH_CHECK(c && d_offsets && k1info && route && rec_off && records && mz_off && mz_hash && mz_y && info && (d_bases || n_bases == 0), SH_ERR_BAD_ARG, "sh_dbg_front_end: null argument");
+    SH_CHECK(n_reads >= 1 && n_reads <= c->max_reads, SH_ERR_BAD_ARG, "sh_dbg_front_end: %llu reads, the context takes 1 .. %llu", (unsigned long long)n_reads, (unsigned long long)c->max_reads);
+    SH_HIP(hipSetDevice(c->idx->device));
+    std::vector<uint64_t> off(n_reads + 1);
+    SH_HIP(hipMemcpy(off.data(), d_offsets, 8 * (n_reads + 1), hipMemcpyDeviceToHost));
+    for (uint64_t r = 0; r < n_reads; ++r)
+        SH_CHECK(off[r] <= off[r + 1] && off[r + 1] - off[r] <= c->max_read_len, SH_ERR_BAD_ARG, "sh_dbg_front_end: read %llu: offsets decrease or the read is longer than the context's %u", (unsigned long long)r, c->max_read_len);
+    SH_CHECK(off[n_reads] <= n_bases, SH_ERR_BAD_ARG, "sh_dbg_front_end: offsets beyond n_bases");
+    const hipStream_t s = nullptr;
+    uint8_t *d_flags = nullptr;
+    auto run = [&]() -> sh_status {
+        SH_HIP(hipMalloc(&d_flags, n_reads));
+        SH_HIP(hipMemsetAsync(d_flags, 0xff, n_reads, s));
+        SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
+        SH_HIP(hipMemsetAsync(c->d_k1info, 0, n_reads * 4, s));      // a read K1 hands on unsketched (tile beyond the LDS stage) has none
+        c->cur_reads = n_reads;
+        const sh_status st = launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, nullptr, s);
+        if (st != SH_OK) return st;
+        SH_HIP(hipGetLastError());
+        SH_HIP(hipStreamSynchronize(s));
+        Counters ctr;
+        SH_HIP(hipMemcpy(&ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
+        SH_HIP(hipMemcpy(k1info, c->d_k1info, n_reads * 4, hipMemcpyDeviceToHost));
+        info[0] = c->use_k1 ? 1 : c->use_long ? 2 : 0; info[1] = (int32_t)c->seed_cap; info[2] = (int32_t)ctr.n_small; info[3] = (int32_t)ctr.n_big[0]; info[4] = (int32_t)ctr.n_resketch;
+        // the route: which work list names the read (bit 0 work_small, 1 work_big, 2 work_resketch; bit 7: named twice by one list)
+        memset(route, 0, n_reads);
+        const uint32_t *lists[3] = {c->d_work_small, c->d_big[0][0], c->d_work_resketch};
+        const uint32_t cnt[3] = {ctr.n_small, ctr.n_big[0], ctr.n_resketch};
+        std::vector<uint32_t> h;
+        for (int l = 0; l < 3; ++l) {
+            SH_CHECK(cnt[l] <= n_reads, SH_ERR_HIP, "sh_dbg_front_end: work list %d holds %u of %llu reads", l, cnt[l], (unsigned long long)n_reads);
+            h.resize(cnt[l]);
+            if (cnt[l]) SH_HIP(hipMemcpy(h.data(), lists[l], 4 * (size_t)cnt[l], hipMemcpyDeviceToHost));
+            for (uint32_t r : h) {
+                SH_CHECK(r < n_reads, SH_ERR_HIP, "sh_dbg_front_end: work list %d names read %u of %llu", l, r, (unsigned long long)n_reads);
+                route[r] |= (route[r] >> l & 1) ? 0x80 : (uint8_t)(1 << l);
+            }
+        }
+        uint64_t n_rec = 0, n_mz = 0;
+        if (c->use_k1) {
+            std::vector<uint4> hr(n_reads * c->seed_cap);
+            SH_HIP(hipMemcpy(hr.data(), c->d_records, hr.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+            for (uint64_t r = 0; r < n_reads; ++r) {
+                rec_off[r] = n_rec; mz_off[r] = 0;
+                const uint32_t n = std::min<uint32_t>((k1info[r] >> 16) & 0x7fffu, c->seed_cap);
+                SH_CHECK(n_rec + n <= rec_cap, SH_ERR_BAD_ARG, "sh_dbg_front_end: more than rec_cap = %llu seed records", (unsigned long long)rec_cap);
+                memcpy(records + 4 * n_rec, hr.data() + r * c->seed_cap, (size_t)n * sizeof(uint4));
+                n_rec += n;
+            }
+        } else if (c->use_long) {
+            std::vector<uint32_t> seg_base(n_reads + 1);
+            SH_HIP(hipMemcpy(seg_base.data(), c->d_seg_base, 4 * (n_reads + 1), hipMemcpyDeviceToHost));
+            const uint32_t n_segs = seg_base[n_reads];
+            SH_CHECK(n_segs == ctr.n_long_segs && n_segs <= c->max_segs, SH_ERR_HIP, "sh_dbg_front_end: segment table of %u segments (counter %u, room for %llu)", n_segs, ctr.n_long_segs, (unsigned long long)c->max_segs);
+            std::vector<unsigned long long> seg_off((size_t)n_segs + 1), seed_off(n_reads);
+            SH_HIP(hipMemcpy(seg_off.data(), c->d_seg_off, 8 * ((size_t)n_segs + 1), hipMemcpyDeviceToHost));
+            SH_HIP(hipMemcpy(seed_off.data(), c->d_seed_off, 8 * n_reads, hipMemcpyDeviceToHost));
+            const uint64_t tot = std::min<uint64_t>(seg_off[n_segs], c->mz_cap);
+            std::vector<uint64_t> hh(tot); std::vector<uint32_t> hy(tot); std::vector<uint4> hr(tot);
+            if (tot) {
+                SH_HIP(hipMemcpy(hh.data(), c->d_mz_hash, 8 * tot, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(hy.data(), c->d_mz_y, 4 * tot, hipMemcpyDeviceToHost));
+                SH_HIP(hipMemcpy(hr.data(), c->d_lrec, 16 * tot, hipMemcpyDeviceToHost));
+            }
+            for (uint64_t r = 0; r < n_reads; ++r) {
+                rec_off[r] = n_rec; mz_off[r] = n_mz;
+                const uint32_t nm = k1info[r] & 0xffffu, ns = k1info[r] >> 16;
+                const uint64_t mb = seg_off[seg_base[r]], sb = seed_off[r];
+                SH_CHECK(mb + nm <= tot && sb + ns <= tot && ns <= nm, SH_ERR_HIP, "sh_dbg_front_end: read %llu: %u minimizers at %llu, %u records at %llu, of %llu", (unsigned long long)r, nm, (unsigned long long)mb, ns, (unsigned long long)sb, (unsigned long long)tot);
+                SH_CHECK(n_rec + ns <= rec_cap && n_mz + nm <= mz_cap, SH_ERR_BAD_ARG, "sh_dbg_front_end: more than rec_cap = %llu seed records or mz_cap = %llu minimizers", (unsigned long long)rec_cap, (unsigned long long)mz_cap);
+                memcpy(records + 4 * n_rec, hr.data() + sb, (size_t)ns * sizeof(uint4));
+                memcpy(mz_hash + n_mz, hh.data() + mb, (size_t)nm * 8); memcpy(mz_y + n_mz, hy.data() + mb, (size_t)nm * 4);
+                n_rec += ns; n_mz += nm;
+            }
+        } else {
+            for (uint64_t r = 0; r < n_reads; ++r) { rec_off[r] = 0; mz_off[r] = 0; }
+        }
+        rec_off[n_reads] = n_rec; mz_off[n_reads] = n_mz;
+        return SH_OK;
+    };
+    const sh_status st = run();
+    hipFree(d_flags);
+    return st;
 }
