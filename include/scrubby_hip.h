@@ -438,6 +438,46 @@ sh_status sh_k2_format_hits(const sh_k2_hit *entries, uint64_t n_entries, const 
 /* Kraken-style report (pct, clade reads, direct reads, rank code, taxid, indented name) from per-unit calls */
 sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, const char *path);
 
+/* ---- minimizer data (kraken2 --report-minimizer-data; DESIGN.md §7 "Minimizer data"; PARITY UNPINNED) ------------------------
+ * Per taxon: n_minimizers, the lookups that returned it (exactly the ones that count as hit groups, whatever the unit's call),
+ * and a dense HyperLogLog sketch (precision 12: 4096 one-byte registers) of the minimizers looked up.  The clade values are the
+ * sum and the element-wise register maximum over the subtree.  sh_k2_mindata is the accumulator of one database in HBM
+ * (n_nodes * 4096 B of registers and n_nodes counters; the first read-out allocates as much again for the clade values);
+ * classify calls add to it, in any batching: counts add, registers merge by maximum. */
+typedef struct sh_k2_mindata sh_k2_mindata;
+sh_status sh_k2_mindata_create(const sh_k2_db *db, sh_k2_mindata **out);      /* SH_ERR_OOM names the size */
+sh_status sh_k2_mindata_reset(sh_k2_mindata *md);
+sh_status sh_k2_mindata_free(sh_k2_mindata *md);
+/* one general classify entry: the batch (quals nullable, as for the _q entries; device pointers for _device, host pointers
+ * for _batch), optional hit lists (hits nullable; with opts->quick SH_ERR_BAD_ARG, as for the hits entries) and optional
+ * minimizer data (md nullable; the call accumulates into it).  Results and stats are bit-identical to the entries above. */
+typedef struct sh_k2_batch {
+    const uint8_t  *bases;
+    const uint8_t  *quals;
+    const uint64_t *offsets;
+    uint64_t        n_records;
+    int32_t         paired;
+} sh_k2_batch;
+sh_status sh_k2_classify_ex_device(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *batch, sh_k2_result *d_out, void *stream,
+                                   sh_k2_stats *stats, sh_k2_hits **hits, sh_k2_mindata *md);
+sh_status sh_k2_classify_ex_batch(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *batch, sh_k2_result *out, sh_k2_stats *stats,
+                                  sh_k2_hits **hits, sh_k2_mindata *md);
+/* per internal taxon (n_nodes each, any pointer may be NULL): own and clade lookup counts, own and clade distinct estimates */
+sh_status sh_k2_mindata_counts(sh_k2_mindata *md, uint64_t *n_minimizers, uint64_t *clade_minimizers, double *distinct, double *clade_distinct);
+/* the 4096 registers of one taxon (clade != 0: of its clade), for callers that reduce across devices themselves */
+sh_status sh_k2_mindata_registers(sh_k2_mindata *md, uint32_t taxon, uint8_t *out /* 4096 */, int32_t clade);
+/* host only, no GPU: Ertl's improved raw estimator over 4096 registers (values 0..53); element-wise maximum of n registers */
+sh_status sh_k2_hll_estimate(const uint8_t *regs /* 4096 */, double *out);
+sh_status sh_k2_mindata_merge_host(uint8_t *dst_regs, const uint8_t *src_regs, uint64_t n);
+/* host only: the Kraken-style report with two columns after "direct reads": the clade's minimizer count and its distinct
+ * estimate (8 tab-separated columns; rows, order, percent, rank codes and indentation as sh_k2_write_report; the unclassified
+ * row, total_units - clade_reads[1] units, carries 0 for both).  Arrays are per internal taxon. */
+sh_status sh_k2_write_minimizer_report(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *names, uint64_t names_len, const char *ranks,
+                                       uint64_t ranks_len, const uint64_t *clade_reads, const uint64_t *direct_reads, const uint64_t *clade_minimizers,
+                                       const uint64_t *clade_distinct, uint64_t total_units, const char *path);
+/* the same from a database, per-unit calls and an accumulator (estimates rounded to the nearest integer) */
+sh_status sh_k2_mindata_write_report(const sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, sh_k2_mindata *md, const char *path);
+
 /* `scrubby reads -c kraken2 -I DB -T .. -D ..`: Cleaner::run_kraken (cleaner.rs:288-330) in process: classify on the GPU,
  * write kraken.reads / kraken.report into workdir, then the taxid depletion of parse_classifier_output + clean_reads. */
 typedef struct sh_kraken_config {
@@ -456,6 +496,8 @@ typedef struct sh_kraken_config {
     const char *classifier_args;    /* -C verbatim, nullable: echoed as settings.classifier_args in the JSON (report.rs:81) */
     int32_t     min_base_quality;   /* from -C "--minimum-base-quality n"; <= 0: no masking (FASTQ records only) */
     int32_t     quick;              /* from -C "--quick" */
+    int32_t     report_minimizer_data;      /* from -C "--report-minimizer-data": also writes kraken.minimizer.report (8 columns) into
+                                               the workdir; kraken.report keeps its 6 columns (the depletion reads it by position) */
 } sh_kraken_config;
 sh_status sh_kraken_run(const sh_kraken_config *cfg, sh_reads_result *out);
 

@@ -271,7 +271,7 @@ int main(int argc, char **argv)
             p = cargs.find("--minimum-hit-groups");
             if (p != std::string::npos) k.min_hit_groups = atoi(cargs.c_str() + p + 20);
         }
-        {   // --minimum-base-quality n (or =n) and --quick by tokens; any other token is named once on stderr
+        {   // --minimum-base-quality n (or =n), --quick and --report-minimizer-data by tokens; any other token is named once on stderr
             std::vector<std::string> tok, ignored;
             for (size_t p = 0; (p = cargs.find_first_not_of(" \t", p)) != std::string::npos;) {
                 const size_t e = std::min(cargs.find_first_of(" \t", p), cargs.size());
@@ -281,6 +281,7 @@ int main(int argc, char **argv)
                 const std::string &x = tok[t];
                 const bool has_next = t + 1 < tok.size();
                 if (x == "--quick") k.quick = 1;
+                else if (x == "--report-minimizer-data") k.report_minimizer_data = 1;
                 else if (x == "--minimum-base-quality" && has_next) k.min_base_quality = atoi(tok[++t].c_str());
                 else if (x.rfind("--minimum-base-quality=", 0) == 0) k.min_base_quality = atoi(x.c_str() + 23);
                 else if ((x == "--confidence" || x == "--minimum-hit-groups") && has_next) ++t;      // read above

@@ -631,10 +631,14 @@ extern "C" sh_status sh_k2_format_hits(const sh_k2_hit *entries, uint64_t n_entr
 }
 
 sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
-                              bool paired, sh_k2_result *results, ShiKrakenHits &hits)
+                              bool paired, sh_k2_result *results, ShiKrakenHits &hits, sh_k2_mindata *md)
 {
     hits.quick = opts.quick != 0;
-    if (hits.quick) return sh_k2_classify_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr);       // "<taxid>:Q"
+    const sh_k2_batch batch{bases, quals, offsets, n_rec, paired ? 1 : 0};
+    if (hits.quick) {       // "<taxid>:Q"
+        if (md) return sh_k2_classify_ex_batch(db, &opts, &batch, results, nullptr, nullptr, md);
+        return sh_k2_classify_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr);
+    }
     sh_k2_info info;
     sh_status st = sh_k2_info_get(db, &info);
     if (st != SH_OK) return st;
@@ -642,7 +646,8 @@ sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_
     st = sh_k2_export(db, nullptr, nullptr, hits.ext.data());
     if (st != SH_OK) return st;
     sh_k2_hits *h = nullptr;
-    st = sh_k2_classify_hits_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr, &h);
+    if (md) st = sh_k2_classify_ex_batch(db, &opts, &batch, results, nullptr, &h, md);
+    else st = sh_k2_classify_hits_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr, &h);
     if (st != SH_OK) return st;
     uint64_t n_units = 0, n_ent = 0;
     sh_k2_hits_count(h, &n_units, &n_ent, nullptr);
@@ -650,6 +655,12 @@ sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_
     st = sh_k2_hits_copy(h, hits.off.data(), hits.ent.data());
     sh_k2_hits_free(h);
     return st;
+}
+
+sh_status shi_kraken_minimizer_report(const sh_kraken_config *, sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, sh_k2_mindata *md, const std::string &dir)
+{
+    if (!md) return SH_OK;
+    return sh_k2_mindata_write_report(db, results, n_units, md, (dir + "/kraken.minimizer.report").c_str());
 }
 
 // ---- Cleaner::run_kraken (cleaner.rs:288-330) in process: GPU classification instead of the external kraken2 ---------
@@ -720,7 +731,10 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
     bases.resize(bases.size() + 64, 'N');
     if (want_q) quals.resize(bases.size(), 0xff);
     ShiKrakenHits hits;
-    st = shi_kraken_classify(db, opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), offsets.size() - 1, paired, results.data(), hits);
+    sh_k2_mindata *md = nullptr;          // -C "--report-minimizer-data": one accumulator over the run
+    if (c->report_minimizer_data) { st = sh_k2_mindata_create(db, &md); if (st != SH_OK) return fail(st); }
+    struct MdGuard { sh_k2_mindata *m; ~MdGuard() { sh_k2_mindata_free(m); } } md_guard{md};
+    st = shi_kraken_classify(db, opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), offsets.size() - 1, paired, results.data(), hits, md);
     if (st != SH_OK) return fail(st);
     auto t3 = now();
 
@@ -741,6 +755,7 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
         if (fclose(f) != 0) { sh_set_error("short write to %s", reads_path.c_str()); return fail(SH_ERR_IO); }
     }
     st = sh_k2_write_report(db, results.data(), ids.size(), report_path.c_str());
+    if (st == SH_OK) st = shi_kraken_minimizer_report(c, db, results.data(), ids.size(), md, dir);
     sh_k2_free(db);
     if (st != SH_OK) return st;
 

@@ -43,7 +43,10 @@ struct ShiKrakenHits {
         shi_k2_hitlist(o, quick ? nullptr : ent.data() + off[i], quick ? 0 : off[i + 1] - off[i], ext.data(), ext.size(), quick, r.taxid);
     }
 };
+// md (nullable): the run's minimizer-data accumulator (-C "--report-minimizer-data")
 sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
-                              bool paired, sh_k2_result *results, ShiKrakenHits &hits);
+                              bool paired, sh_k2_result *results, ShiKrakenHits &hits, sh_k2_mindata *md = nullptr);
+// kraken.minimizer.report beside kraken.report, when the run keeps an accumulator
+sh_status shi_kraken_minimizer_report(const sh_kraken_config *c, sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, sh_k2_mindata *md, const std::string &dir);
 // database build: the <n> of a `kraken:taxid|<n>` sequence id (sh_host.cpp)
 bool shi_k2_header_taxid(const char *id, size_t len, uint64_t *taxid);

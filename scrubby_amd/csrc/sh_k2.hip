@@ -24,6 +24,9 @@
 //            in an entry without k-mers.  Pass 2 of the drain emits each lane's entries in read order into an RLE state
 //            held in registers.  HITS 1 writes K2_HIT_INLINE entries per unit and counts them all (a longer unit goes on a
 //            list); HITS 2 redoes the listed units and writes their whole lists at their final offsets, nothing else.
+// A fourth switch, MIND (kraken2 --report-minimizer-data), exists for the pass-1 instances only (default, QUICK, HITS 1): every
+// lookup that adds a hit group also counts for its taxon in a sh_k2_mindata accumulator (a counter and 4096 HyperLogLog
+// registers per taxon).  The BIG and HITS 2 passes redo units pass 1 already counted, so they have no MIND form.
 // The bound is the HBM gather rate: one 32-B sector per probe, ~40 probes per 150-bp read.
 #include "sh_common.h"
 #include "sh_k2_db.h"
@@ -141,7 +144,13 @@ struct K2HArgs : K2QArgs {
     uint32_t *hit_over;                                // HITS 1: units with more than K2_HIT_INLINE entries
     const uint64_t *hit_off;                           // HITS 2: first entry of each unit in `hits` (n_units + 1)
 };
-template <bool QMASK, int HITS = 0> using K2ArgsOf = std::conditional_t<HITS != 0, K2HArgs, std::conditional_t<QMASK, K2QArgs, K2Args>>;
+// ... and the MIND instances'
+struct K2MArgs : K2HArgs {
+    uint32_t *md_regs;                                 // K2_MD_WORDS words per taxon: the HLL registers, four to a word
+    unsigned long long *md_cnt;                        // n_minimizers per taxon
+};
+template <bool QMASK, int HITS = 0, bool MIND = false>
+using K2ArgsOf = std::conditional_t<MIND, K2MArgs, std::conditional_t<HITS != 0, K2HArgs, std::conditional_t<QMASK, K2QArgs, K2Args>>>;
 // ctr layout
 #define K2C_OVER 0
 #define K2C_HOVER 1
@@ -293,10 +302,65 @@ struct K2HitState {
 };
 struct K2NoHits {};
 
-template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0>
-__global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
+// ---- minimizer data (kraken2 --report-minimizer-data; hyperloglogplus.cc as recalled: PARITY UNPINNED) ----
+// Dense HyperLogLog, precision 12: the hash is the table's k2_fmix64(minimizer), the register index its top 12 bits, the rank
+// the leading zeros of the other 52 bits + 1 (53 when they are all zero).  One byte per register, four to a 32-bit word.
+#define K2_MD_P 12
+#define K2_MD_M (1u << K2_MD_P)
+#define K2_MD_WORDS (K2_MD_M / 4)
+#define K2_MD_BINS 54       // register values 0 .. 64 - K2_MD_P + 1
+// (register index << 6 | rank) of a hashed minimizer: 18 bits
+__host__ __device__ static inline uint32_t k2_md_code(uint64_t h)
+{
+    const uint64_t w = h << K2_MD_P;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t rank = w ? (uint32_t)__clzll((long long)w) + 1u : 64u - K2_MD_P + 1u;
+#else
+    const uint32_t rank = w ? (uint32_t)__builtin_clzll(w) + 1u : 64u - K2_MD_P + 1u;
+#endif
+    return (uint32_t)(h >> (64 - K2_MD_P)) << 6 | rank;
+}
+// bytewise maximum of two packed words
+__host__ __device__ static inline uint32_t k2_md_max4(uint32_t x, uint32_t y)
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (int b = 0; b < 32; b += 8) { const uint32_t p = (x >> b) & 0xffu, q = (y >> b) & 0xffu; r |= (p > q ? p : q) << b; }
+    return r;
+}
+// One lane's share of the accumulator.  A single-taxon (host depletion) database sends every hit of a batch to one counter
+// and one 4-KiB register file, so neither gets an unconditional atomic per hit: the register word is read first and a CAS
+// loop runs only while the rank is larger than what is there (after warm-up nearly every update is that one cached read);
+// the count stays in the lane, (taxon, pending), across its units and is added when the taxon changes and when the lane is done.
+struct K2MdState {
+    uint32_t tax = 0, n = 0;
+    __device__ inline void flush(unsigned long long *cnt)
+    {
+        if (n) atomicAdd(&cnt[tax], (unsigned long long)n);
+        n = 0;
+    }
+    __device__ inline void hit(const K2MArgs &a, uint32_t taxon, uint32_t code)
+    {
+        if (taxon >= a.n_nodes) return;                 // a value outside the taxonomy (a damaged table) has no registers
+        if (taxon != tax) { flush(a.md_cnt); tax = taxon; }
+        ++n;
+        uint32_t *w = a.md_regs + (uint64_t)taxon * K2_MD_WORDS + (code >> 8);
+        const uint32_t sh = ((code >> 6) & 3u) * 8, rank = code & 63u;
+        uint32_t cur = __atomic_load_n(w, __ATOMIC_RELAXED);      // registers only grow: a stale word costs a CAS, never a rank
+        while (((cur >> sh) & 0xffu) < rank) {
+            const uint32_t prev = atomicCAS(w, cur, (cur & ~(0xffu << sh)) | rank << sh);
+            if (prev == cur) break;
+            cur = prev;
+        }
+    }
+};
+struct K2NoMd {};
+
+template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false>
+__global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> a)
 {
     static_assert(HITS == 0 || !(BIG || QUICK), "the hit list is complete after pass 1 and has no --quick form");
+    static_assert(!MIND || !(BIG || HITS == 2), "the redo passes repeat units pass 1 counted: they must not count them again");
     constexpr bool LIST = BIG || HITS == 2;                // the work is a list of units to redo
     __shared__ uint64_t s_qmin[(K2_QCAP + 1) * 64];       // slot n_pend is written unconditionally, so one spare
     __shared__ uint32_t s_qlen[(K2_QCAP + 1) * 64];
@@ -308,6 +372,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
     const int32_t wlim = a.k - a.l + 1;
     const uint64_t n_work = LIST ? a.n_list : a.n_units;
     unsigned long long probes_thr = 0, kmers_thr = 0; uint32_t class_thr = 0;
+    std::conditional_t<MIND, K2MdState, K2NoMd> M{};       // (an empty object in the other instances)
     for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_work; base += (uint64_t)gridDim.x * 64) {
         const uint64_t wi = base + lane;
         const bool active = wi < n_work;
@@ -331,6 +396,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
             for (uint32_t e0 = 0; e0 < K2_QCAP; e0 += 4) {
                 if (__ballot(e0 < n_pend) == 0) break;
                 uint64_t idx[4]; uint32_t comp[4]; bool go[4]; K2Group G[4];
+                [[maybe_unused]] uint32_t mdc[4];        // MIND: k2_md_code of the hash, kept beside the taxon in the slot's high half
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     go[q] = e0 + q < n_pend;
@@ -340,6 +406,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
                         const uint64_t hc = k2_fmix64(s_qmin[(e0 + q) * 64 + lane]);
                         if (a.min_hash && hc < a.min_hash) { go[q] = false; skipped |= 1u << (e0 + q); }      // down-sampled database: not looked up
                         else { comp[q] = (uint32_t)(hc >> (32 + a.T.value_bits)); idx[q] = k2_mod(hc, a.T.capacity, a.T.inv_capacity); }
+                        if constexpr (MIND) mdc[q] = k2_md_code(hc);
                     }
                 }
 #pragma unroll
@@ -353,8 +420,10 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
                     uint32_t taxon = 0;
                     const bool whole = (idx[q] >> 3) < n_full;
                     const bool done = whole && k2_scan_group(G[q], (uint32_t)idx[q] & 7u, vmask, a.T.value_bits, comp[q], taxon);
-                    if (done) s_qmin[(e0 + q) * 64 + lane] = taxon;      // else the slot keeps the minimizer for pass 2
-                    else undecided |= 1u << (e0 + q);
+                    if (done) {                                               // else the slot keeps the minimizer for pass 2
+                        if constexpr (MIND) s_qmin[(e0 + q) * 64 + lane] = (uint64_t)mdc[q] << 32 | taxon;
+                        else s_qmin[(e0 + q) * 64 + lane] = taxon;
+                    } else undecided |= 1u << (e0 + q);
                 }
             }
             // pass 2: one copy of the long-chain code and of the hit-list update
@@ -372,6 +441,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
                                 R.run_taxon = (undecided >> e) & 1u ? k2_probe_long(a.T, v, n_full) : (uint32_t)v;
                                 if (R.run_taxon) {
                                     ++groups;
+                                    if constexpr (MIND) M.hit(a, R.run_taxon, (undecided >> e) & 1u ? k2_md_code(k2_fmix64(v)) : (uint32_t)(v >> 32));
                                     if constexpr (HITS == 1) H.add(R.run_taxon, len);
                                 }
                             }
@@ -394,6 +464,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
                         }
                         if (taxon) {
                             ++groups;
+                            if constexpr (MIND) M.hit(a, taxon, (undecided >> e) & 1u ? k2_md_code(k2_fmix64(v)) : (uint32_t)(v >> 32));
                             if constexpr (QUICK) {
                                 if ((int32_t)groups >= a.min_hit_groups) { stopped = true; q_call = taxon; q_total = s_qpos[e * 64 + lane]; }
                             } else H.add(taxon, s_qlen[e * 64 + lane]);
@@ -534,6 +605,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS> a)
             }
         }
     }
+    if constexpr (MIND) M.flush(a.md_cnt);
     // statistics: one atomic per wave and counter, 64-way sharded
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -1182,27 +1254,36 @@ extern "C" sh_status sh_k2_open(const char *dir, int device, sh_k2_db **out)
 }
 
 // ---- classification ---------------------------------------------------------------------------------------------------
-template <int W, bool BIG, bool QMASK, bool QUICK, int HITS>
-static void launch_classify(const K2HArgs &a, uint64_t n_work, hipStream_t s)
+template <int W, bool BIG, bool QMASK, bool QUICK, int HITS, bool MIND>
+static void launch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s)
 {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_work + 63) / 64, 1), 256 * 32);
-    const K2ArgsOf<QMASK, HITS> &ka = a;
-    hipLaunchKernelGGL((k_k2_classify<W, BIG, QMASK, QUICK, HITS>), dim3(grid), dim3(64), 0, s, ka);
+    const K2ArgsOf<QMASK, HITS, MIND> &ka = a;
+    hipLaunchKernelGGL((k_k2_classify<W, BIG, QMASK, QUICK, HITS, MIND>), dim3(grid), dim3(64), 0, s, ka);
 }
-template <bool BIG, bool QMASK, bool QUICK, int HITS = 0>
-static void dispatch_w(const K2HArgs &a, uint64_t n_work, hipStream_t s)
+template <bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false>
+static void dispatch_w(const K2MArgs &a, uint64_t n_work, hipStream_t s)
 {
     switch (a.k - a.l + 1) {
-    case 1: launch_classify<1, BIG, QMASK, QUICK, HITS>(a, n_work, s); break;
-    case 5: launch_classify<5, BIG, QMASK, QUICK, HITS>(a, n_work, s); break;
-    default: launch_classify<16, BIG, QMASK, QUICK, HITS>(a, n_work, s); break;
+    case 1: launch_classify<1, BIG, QMASK, QUICK, HITS, MIND>(a, n_work, s); break;
+    case 5: launch_classify<5, BIG, QMASK, QUICK, HITS, MIND>(a, n_work, s); break;
+    default: launch_classify<16, BIG, QMASK, QUICK, HITS, MIND>(a, n_work, s); break;
     }
 }
 // only the instances that are needed: a QUICK unit keeps no hit list, so it never overflows into the BIG pass; the BIG pass
-// needs no HITS instance (pass 1 already emitted the whole list of a unit with many taxa)
+// needs no HITS instance (pass 1 already emitted the whole list of a unit with many taxa); MIND goes with the three pass-1
+// forms only (the two redo passes are never asked for it: their units were counted by pass 1)
 template <bool BIG>
-static sh_status dispatch_classify(const K2HArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool quick, int hits = 0)
+static sh_status dispatch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool quick, int hits = 0, bool mind = false)
 {
+    if constexpr (!BIG) {
+        if (mind && hits != 2) {
+            if (quick) { if (qmask) dispatch_w<false, true, true, 0, true>(a, n_work, s); else dispatch_w<false, false, true, 0, true>(a, n_work, s); }
+            else if (hits == 1) { if (qmask) dispatch_w<false, true, false, 1, true>(a, n_work, s); else dispatch_w<false, false, false, 1, true>(a, n_work, s); }
+            else { if (qmask) dispatch_w<false, true, false, 0, true>(a, n_work, s); else dispatch_w<false, false, false, 0, true>(a, n_work, s); }
+            return SH_OK;
+        }
+    }
     if (BIG) {
         if (qmask) dispatch_w<true, true, false>(a, n_work, s); else dispatch_w<true, false, false>(a, n_work, s);
     } else if (quick) {
@@ -1235,8 +1316,80 @@ __global__ void k_k2_hits_compact(const uint2 *inl, const uint32_t *n_hits, cons
     }
 }
 
+// ---- minimizer data: the accumulator of one database and its three small kernels --------------------------------------
+struct sh_k2_mindata {
+    int device = 0;
+    uint64_t n_nodes = 0;
+    uint32_t *d_parent = nullptr;                // a copy: the accumulator may outlive the database handle
+    uint32_t *d_regs = nullptr;                  // n_nodes * K2_MD_WORDS
+    unsigned long long *d_cnt = nullptr;         // n_nodes
+    // the clade values, made by the first read-out after a classify call or a reset
+    uint32_t *d_clade_regs = nullptr; unsigned long long *d_clade_cnt = nullptr;
+    uint32_t *d_hist = nullptr;                  // 2 * n_nodes * K2_MD_BINS: own, then clade
+    bool clade_valid = false;
+};
+
+__global__ void k_k2_md_clear(uint4 *p, uint64_t n16)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * blockDim.x) p[i] = make_uint4(0, 0, 0, 0);
+}
+
+// Clade values: block t carries taxon t's own registers and count to itself and every ancestor (internal ids are breadth-first,
+// so the walk over parent[] only descends in id and ends at the root, id 1).  Only a taxon with data pushes anything.  The
+// clade buffers start cleared; a word is read first and CASed only where a byte grows, as in the classifier.
+__global__ __launch_bounds__(256) void k_k2_md_clade(const uint32_t *__restrict__ parent, uint32_t n_nodes, const uint32_t *__restrict__ regs,
+                                                     const unsigned long long *__restrict__ cnt, uint32_t *clade_regs, unsigned long long *clade_cnt)
+{
+    for (uint32_t t = blockIdx.x + 1; t < n_nodes; t += gridDim.x) {
+        const unsigned long long c = cnt[t];
+        if (!c) continue;
+        uint32_t mine[K2_MD_WORDS / 256];
+#pragma unroll
+        for (uint32_t j = 0; j < K2_MD_WORDS / 256; ++j) mine[j] = regs[(uint64_t)t * K2_MD_WORDS + j * 256 + threadIdx.x];
+        uint32_t x = t;
+        for (uint32_t depth = 0; depth < n_nodes; ++depth) {      // (the bound only guards against a parent array with a cycle)
+            if (threadIdx.x == 0) atomicAdd(&clade_cnt[x], c);
+#pragma unroll
+            for (uint32_t j = 0; j < K2_MD_WORDS / 256; ++j) {
+                uint32_t *w = clade_regs + (uint64_t)x * K2_MD_WORDS + j * 256 + threadIdx.x;
+                uint32_t cur = __atomic_load_n(w, __ATOMIC_RELAXED);
+                for (;;) {
+                    const uint32_t nw = k2_md_max4(cur, mine[j]);
+                    if (nw == cur) break;
+                    const uint32_t prev = atomicCAS(w, cur, nw);
+                    if (prev == cur) break;
+                    cur = prev;
+                }
+            }
+            const uint32_t up = parent[x];
+            if (x <= 1 || up == 0 || up >= x) break;
+            x = up;
+        }
+    }
+}
+
+// Register histogram (the estimator's input): one block per taxon with data, K2_MD_BINS bins
+__global__ __launch_bounds__(256) void k_k2_md_hist(uint32_t n_nodes, const uint32_t *__restrict__ regs, const unsigned long long *__restrict__ cnt, uint32_t *hist)
+{
+    __shared__ uint32_t s_h[K2_MD_BINS];
+    for (uint32_t t = blockIdx.x + 1; t < n_nodes; t += gridDim.x) {
+        if (!cnt[t]) continue;                    // (block-uniform)
+        if (threadIdx.x < K2_MD_BINS) s_h[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < K2_MD_WORDS; j += 256) {
+            const uint32_t w = regs[(uint64_t)t * K2_MD_WORDS + j];
+#pragma unroll
+            for (int b = 0; b < 32; b += 8) { const uint32_t r = (w >> b) & 0xffu; atomicAdd(&s_h[r < K2_MD_BINS ? r : K2_MD_BINS - 1], 1u); }
+        }
+        __syncthreads();
+        if (threadIdx.x < K2_MD_BINS) hist[(uint64_t)t * K2_MD_BINS + threadIdx.x] = s_h[threadIdx.x];
+        __syncthreads();
+    }
+}
+
 static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
-                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out);
+                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out,
+                             sh_k2_mindata *md = nullptr);
 
 extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
                                            uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats)
@@ -1306,9 +1459,11 @@ extern "C" sh_status sh_k2_hits_free(sh_k2_hits *h)
 }
 
 static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
-                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out)
+                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out,
+                             sh_k2_mindata *md)
 {
     SH_CHECK(db && d_offsets && d_out && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_classify_device: null argument");
+    SH_CHECK(!md || (md->device == db->device && md->n_nodes == db->nodes.size()), SH_ERR_BAD_ARG, "the minimizer data belongs to another database");
     SH_CHECK(!paired || (n_records & 1) == 0, SH_ERR_BAD_ARG, "paired input needs an even number of records (got %llu)", (unsigned long long)n_records);
     SH_HIP(hipSetDevice(db->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1328,7 +1483,8 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     SH_HIP(hipMalloc(&ctr, K2C_WORDS * 8));
     SH_HIP(hipMalloc(&over, n_units * 4));
     SH_HIP(hipMemsetAsync(ctr, 0, K2C_WORDS * 8, s));
-    K2HArgs a{};
+    K2MArgs a{};
+    if (md) { a.md_regs = md->d_regs; a.md_cnt = md->d_cnt; md->clade_valid = false; }
     uint2 *hit_inl = nullptr; uint32_t *n_hits = nullptr, *hit_over = nullptr;
     if (hits_out) {       // pass 1: K2_HIT_INLINE entries per unit in place, every unit's count (one spare: the scan's total)
         SH_HIP(hipMalloc(&hit_inl, n_units * K2_HIT_INLINE * sizeof(uint2)));
@@ -1345,7 +1501,7 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     a.quals = qmask ? d_quals : nullptr; a.min_qual = qmask ? o.min_base_quality : 0;
     SH_HIP(hipEventRecord(e0, s));
     if (qmask) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
-    dispatch_classify<false>(a, n_units, s, qmask, quick, hits_out ? 1 : 0);
+    dispatch_classify<false>(a, n_units, s, qmask, quick, hits_out ? 1 : 0, md != nullptr);      // the only pass that counts minimizers
     SH_HIP(hipEventRecord(e1, s));
     std::vector<unsigned long long> h(K2C_WORDS);
     SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
@@ -1409,7 +1565,8 @@ extern "C" sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *
 }
 
 static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits);
+                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits,
+                                   sh_k2_mindata *md = nullptr);
 
 extern "C" sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
                                             const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats)
@@ -1436,7 +1593,8 @@ extern "C" sh_status sh_k2_classify_hits_batch_q(const sh_k2_db *db, const sh_k2
 }
 
 static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits)
+                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits,
+                                   sh_k2_mindata *md)
 {
     SH_CHECK(db && offsets && out, SH_ERR_BAD_ARG, "sh_k2_classify_batch: null argument");
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -1461,7 +1619,7 @@ static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, c
     SH_HIP(hipMemcpy(d_bases, bases + o0, n_bases, hipMemcpyHostToDevice));
     SH_HIP(hipMemset(d_bases + n_bases, 'N', 64));
     SH_HIP(hipMemcpy(d_off, rel.data(), (n_records + 1) * 8, hipMemcpyHostToDevice));
-    sh_status st = k2_classify(db, opts, d_bases, d_quals, d_off, n_records, paired, d_out, nullptr, stats, hits);
+    sh_status st = k2_classify(db, opts, d_bases, d_quals, d_off, n_records, paired, d_out, nullptr, stats, hits, md);
     if (st == SH_OK && hipMemcpy(out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost) != hipSuccess) { sh_set_error("copy of the results failed"); st = SH_ERR_HIP; }
     hipFree(d_bases); hipFree(d_quals); hipFree(d_off); hipFree(d_out);
     return st;
@@ -1486,4 +1644,234 @@ extern "C" sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *
     const bool ok = fclose(f) == 0;
     SH_CHECK(ok, SH_ERR_IO, "short write to %s", path);
     return SH_OK;
+}
+
+// ---- the general classify entry: one batch struct, optional hit lists, optional minimizer data ---------------------------
+extern "C" sh_status sh_k2_classify_ex_device(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *b, sh_k2_result *d_out, void *stream,
+                                              sh_k2_stats *stats, sh_k2_hits **hits, sh_k2_mindata *md)
+{
+    SH_CHECK(b, SH_ERR_BAD_ARG, "sh_k2_classify_ex_device: null argument");
+    if (hits) *hits = nullptr;
+    SH_CHECK(!hits || !(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: call without one");
+    sh_status st = k2_classify(db, opts, b->bases, b->quals, b->offsets, b->n_records, b->paired, d_out, stream, stats, hits, md);
+    if (st != SH_OK && hits) { sh_k2_hits_free(*hits); *hits = nullptr; }
+    return st;
+}
+
+extern "C" sh_status sh_k2_classify_ex_batch(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *b, sh_k2_result *out, sh_k2_stats *stats,
+                                             sh_k2_hits **hits, sh_k2_mindata *md)
+{
+    SH_CHECK(b, SH_ERR_BAD_ARG, "sh_k2_classify_ex_batch: null argument");
+    if (hits) *hits = nullptr;
+    SH_CHECK(!hits || !(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: call without one");
+    SH_CHECK(!md || (db && md->device == db->device && md->n_nodes == db->nodes.size()), SH_ERR_BAD_ARG, "the minimizer data belongs to another database");
+    sh_status st = k2_classify_batch(db, opts, b->bases, b->quals, b->offsets, b->n_records, b->paired, out, stats, hits, md);
+    if (st != SH_OK && hits) { sh_k2_hits_free(*hits); *hits = nullptr; }
+    return st;
+}
+
+// ---- minimizer data: host side ------------------------------------------------------------------------------------------
+extern "C" sh_status sh_k2_mindata_free(sh_k2_mindata *md)
+{
+    if (!md) return SH_OK;
+    hipSetDevice(md->device);
+    hipFree(md->d_parent); hipFree(md->d_regs); hipFree(md->d_cnt); hipFree(md->d_clade_regs); hipFree(md->d_clade_cnt); hipFree(md->d_hist);
+    delete md;
+    return SH_OK;
+}
+
+static void k2_md_clear(void *p, uint64_t bytes, hipStream_t s)      // bytes: a multiple of 16 (hipMalloc aligns to more)
+{
+    const uint64_t n16 = bytes / 16;
+    if (n16) hipLaunchKernelGGL(k_k2_md_clear, dim3((uint32_t)std::min<uint64_t>((n16 + 255) / 256, 4096)), dim3(256), 0, s, (uint4 *)p, n16);
+}
+// counters are 8 bytes each: round the node count up to an even one
+static uint64_t k2_md_cnt_bytes(uint64_t n_nodes) { return (n_nodes + 1) / 2 * 16; }
+
+extern "C" sh_status sh_k2_mindata_reset(sh_k2_mindata *md)
+{
+    SH_CHECK(md, SH_ERR_BAD_ARG, "sh_k2_mindata_reset: null argument");
+    SH_HIP(hipSetDevice(md->device));
+    k2_md_clear(md->d_regs, md->n_nodes * K2_MD_M, nullptr);
+    k2_md_clear(md->d_cnt, k2_md_cnt_bytes(md->n_nodes), nullptr);
+    md->clade_valid = false;
+    SH_HIP(hipDeviceSynchronize());
+    SH_HIP(hipGetLastError());
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_mindata_create(const sh_k2_db *db, sh_k2_mindata **out)
+{
+    SH_CHECK(db && out, SH_ERR_BAD_ARG, "sh_k2_mindata_create: null argument");
+    *out = nullptr;
+    SH_HIP(hipSetDevice(db->device));
+    sh_k2_mindata *md = new sh_k2_mindata;
+    md->device = db->device; md->n_nodes = db->nodes.size();
+    const uint64_t reg_bytes = md->n_nodes * K2_MD_M, cnt_bytes = k2_md_cnt_bytes(md->n_nodes);
+    if (hipMalloc(&md->d_regs, reg_bytes) != hipSuccess || hipMalloc(&md->d_cnt, cnt_bytes) != hipSuccess || hipMalloc(&md->d_parent, md->n_nodes * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        sh_k2_mindata_free(md);
+        sh_set_error("sh_k2_mindata_create: %llu bytes of registers and counters for %llu taxa do not fit the device", (unsigned long long)(reg_bytes + cnt_bytes),
+                     (unsigned long long)db->nodes.size());
+        return SH_ERR_OOM;
+    }
+    if (hipMemcpy(md->d_parent, db->d_parent, md->n_nodes * 4, hipMemcpyDeviceToDevice) != hipSuccess) { sh_k2_mindata_free(md); sh_set_error("copy of the taxonomy failed"); return SH_ERR_HIP; }
+    sh_status st = sh_k2_mindata_reset(md);
+    if (st != SH_OK) { sh_k2_mindata_free(md); return st; }
+    *out = md;
+    return SH_OK;
+}
+
+// clade registers, clade counts and both histograms, once per state of the accumulator
+static sh_status k2_md_finish(sh_k2_mindata *md)
+{
+    SH_HIP(hipSetDevice(md->device));
+    if (md->clade_valid) return SH_OK;
+    const uint64_t reg_bytes = md->n_nodes * K2_MD_M, cnt_bytes = k2_md_cnt_bytes(md->n_nodes), hist_bytes = (2 * md->n_nodes * K2_MD_BINS * 4 + 15) / 16 * 16;
+    if (!md->d_clade_regs) {
+        if (hipMalloc(&md->d_clade_regs, reg_bytes) != hipSuccess || hipMalloc(&md->d_clade_cnt, cnt_bytes) != hipSuccess || hipMalloc(&md->d_hist, hist_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(md->d_clade_regs); hipFree(md->d_clade_cnt); hipFree(md->d_hist);
+            md->d_clade_regs = nullptr; md->d_clade_cnt = nullptr; md->d_hist = nullptr;
+            sh_set_error("minimizer data: %llu bytes of clade registers for %llu taxa do not fit the device", (unsigned long long)(reg_bytes + cnt_bytes + hist_bytes),
+                         (unsigned long long)md->n_nodes);
+            return SH_ERR_OOM;
+        }
+    }
+    k2_md_clear(md->d_clade_regs, reg_bytes, nullptr);
+    k2_md_clear(md->d_clade_cnt, cnt_bytes, nullptr);
+    k2_md_clear(md->d_hist, hist_bytes, nullptr);
+    const uint32_t n = (uint32_t)md->n_nodes, grid = std::min<uint32_t>(std::max<uint32_t>(n, 1), 65536);
+    hipLaunchKernelGGL(k_k2_md_clade, dim3(grid), dim3(256), 0, nullptr, md->d_parent, n, md->d_regs, md->d_cnt, md->d_clade_regs, md->d_clade_cnt);
+    hipLaunchKernelGGL(k_k2_md_hist, dim3(grid), dim3(256), 0, nullptr, n, md->d_regs, md->d_cnt, md->d_hist);
+    hipLaunchKernelGGL(k_k2_md_hist, dim3(grid), dim3(256), 0, nullptr, n, md->d_clade_regs, md->d_clade_cnt, md->d_hist + md->n_nodes * K2_MD_BINS);
+    SH_HIP(hipDeviceSynchronize());
+    SH_HIP(hipGetLastError());
+    md->clade_valid = true;
+    return SH_OK;
+}
+
+// Ertl's improved raw estimator (kraken2's default, hyperloglogplus.cc as recalled: PARITY UNPINNED) over the register
+// histogram C[0 .. q + 1], q = 64 - p, in doubles
+static double k2_hll_sigma(double x)
+{
+    if (x == 1.0) return INFINITY;
+    double y = 1.0, z = x, zp;
+    do { x *= x; zp = z; z += x * y; y += y; } while (zp != z);
+    return z;
+}
+static double k2_hll_tau(double x)
+{
+    if (x == 0.0 || x == 1.0) return 0.0;
+    double y = 1.0, z = 1.0 - x, zp;
+    do { x = sqrt(x); zp = z; y *= 0.5; z -= (1.0 - x) * (1.0 - x) * y; } while (zp != z);
+    return z / 3.0;
+}
+static double k2_hll_from_hist(const uint32_t *C)
+{
+    const double m = (double)K2_MD_M;
+    const int q = 64 - K2_MD_P;
+    double z = m * k2_hll_tau(1.0 - (double)C[q + 1] / m);
+    for (int k = q; k >= 1; --k) z = 0.5 * (z + (double)C[k]);
+    z += m * k2_hll_sigma((double)C[0] / m);
+    return m * m / (2.0 * log(2.0) * z);       // (all registers empty: z = inf, the estimate 0)
+}
+
+extern "C" sh_status sh_k2_hll_estimate(const uint8_t *regs, double *out)
+{
+    SH_CHECK(regs && out, SH_ERR_BAD_ARG, "sh_k2_hll_estimate: null argument");
+    uint32_t C[K2_MD_BINS] = {0};
+    for (uint32_t i = 0; i < K2_MD_M; ++i) {
+        SH_CHECK(regs[i] < K2_MD_BINS, SH_ERR_BAD_ARG, "sh_k2_hll_estimate: register %u holds %u (at most %d)", i, (unsigned)regs[i], K2_MD_BINS - 1);
+        ++C[regs[i]];
+    }
+    *out = k2_hll_from_hist(C);
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_mindata_merge_host(uint8_t *dst_regs, const uint8_t *src_regs, uint64_t n)
+{
+    SH_CHECK((dst_regs && src_regs) || n == 0, SH_ERR_BAD_ARG, "sh_k2_mindata_merge_host: null argument");
+    for (uint64_t i = 0; i < n; ++i) dst_regs[i] = std::max(dst_regs[i], src_regs[i]);
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_mindata_counts(sh_k2_mindata *md, uint64_t *n_minimizers, uint64_t *clade_minimizers, double *distinct, double *clade_distinct)
+{
+    SH_CHECK(md, SH_ERR_BAD_ARG, "sh_k2_mindata_counts: null argument");
+    sh_status st = k2_md_finish(md);
+    if (st != SH_OK) return st;
+    const uint64_t n = md->n_nodes;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counter width");
+    std::vector<uint64_t> own(n), clade(n);
+    SH_HIP(hipMemcpy(own.data(), md->d_cnt, n * 8, hipMemcpyDeviceToHost));
+    SH_HIP(hipMemcpy(clade.data(), md->d_clade_cnt, n * 8, hipMemcpyDeviceToHost));
+    if (n_minimizers) memcpy(n_minimizers, own.data(), n * 8);
+    if (clade_minimizers) memcpy(clade_minimizers, clade.data(), n * 8);
+    if (distinct || clade_distinct) {
+        std::vector<uint32_t> hist(2 * n * K2_MD_BINS);
+        SH_HIP(hipMemcpy(hist.data(), md->d_hist, hist.size() * 4, hipMemcpyDeviceToHost));
+        for (uint64_t t = 0; t < n; ++t) {       // a taxon without data has no histogram: nothing was seen
+            if (distinct) distinct[t] = own[t] ? k2_hll_from_hist(hist.data() + t * K2_MD_BINS) : 0.0;
+            if (clade_distinct) clade_distinct[t] = clade[t] ? k2_hll_from_hist(hist.data() + (n + t) * K2_MD_BINS) : 0.0;
+        }
+    }
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_mindata_registers(sh_k2_mindata *md, uint32_t taxon, uint8_t *out, int32_t clade)
+{
+    SH_CHECK(md && out, SH_ERR_BAD_ARG, "sh_k2_mindata_registers: null argument");
+    SH_CHECK(taxon < md->n_nodes, SH_ERR_BAD_ARG, "sh_k2_mindata_registers: taxon %u outside the taxonomy of %llu nodes", taxon, (unsigned long long)md->n_nodes);
+    SH_HIP(hipSetDevice(md->device));
+    if (clade) { sh_status st = k2_md_finish(md); if (st != SH_OK) return st; }
+    else SH_HIP(hipDeviceSynchronize());
+    // register i is byte i & 3 of word i >> 2: on a little-endian host the words are the byte array
+    SH_HIP(hipMemcpy(out, (clade ? md->d_clade_regs : md->d_regs) + (uint64_t)taxon * K2_MD_WORDS, K2_MD_M, hipMemcpyDeviceToHost));
+    return SH_OK;
+}
+
+// the estimate as the report prints it
+static uint64_t k2_hll_round(double e) { return !(e < 1.8e19) ? ~0ull : (uint64_t)floor(e + 0.5); }
+
+// kraken2 --report-minimizer-data (reports.cc as recalled: PARITY UNPINNED): the rows of sh_k2_write_report with the clade's
+// minimizer count and distinct-minimizer estimate after "direct reads"; the unclassified row carries 0 for both
+extern "C" sh_status sh_k2_write_minimizer_report(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *names, uint64_t names_len, const char *ranks,
+                                                  uint64_t ranks_len, const uint64_t *clade_reads, const uint64_t *direct_reads, const uint64_t *clade_minimizers,
+                                                  const uint64_t *clade_distinct, uint64_t total_units, const char *path)
+{
+    SH_CHECK(nodes && clade_reads && direct_reads && clade_minimizers && clade_distinct && path && (names || names_len == 0) && (ranks || ranks_len == 0), SH_ERR_BAD_ARG,
+             "sh_k2_write_minimizer_report: null argument");
+    SH_CHECK(n_nodes >= 2, SH_ERR_BAD_ARG, "sh_k2_write_minimizer_report: a taxonomy has at least the empty node and the root");
+    for (uint64_t i = 2; i < n_nodes; ++i)
+        SH_CHECK(nodes[i].parent >= 1 && nodes[i].parent < i, SH_ERR_BAD_ARG, "sh_k2_write_minimizer_report: node %llu: ids must be breadth-first", (unsigned long long)i);
+    SH_CHECK(clade_reads[1] <= total_units, SH_ERR_BAD_ARG, "sh_k2_write_minimizer_report: %llu classified units of %llu", (unsigned long long)clade_reads[1],
+             (unsigned long long)total_units);
+    const std::string name_pool(names ? names : "", names_len), rank_pool(ranks ? ranks : "", ranks_len);
+    FILE *f = fopen(path, "w");
+    SH_CHECK(f, SH_ERR_IO, "cannot write %s", path);
+    const double total = total_units ? (double)total_units : 1.0;
+    const uint64_t unclassified = total_units - clade_reads[1];
+    if (unclassified) fprintf(f, "%6.2f\t%llu\t%llu\t0\t0\tU\t0\tunclassified\n", 100.0 * (double)unclassified / total, (unsigned long long)unclassified, (unsigned long long)unclassified);
+    shi_k2_report_rows(f, nodes, n_nodes, name_pool, rank_pool, clade_reads, direct_reads, total, 0, clade_minimizers, clade_distinct);
+    const bool ok = fclose(f) == 0;
+    SH_CHECK(ok, SH_ERR_IO, "short write to %s", path);
+    return SH_OK;
+}
+
+extern "C" sh_status sh_k2_mindata_write_report(const sh_k2_db *db, const sh_k2_result *res, uint64_t n_units, sh_k2_mindata *md, const char *path)
+{
+    SH_CHECK(db && md && path && (res || n_units == 0), SH_ERR_BAD_ARG, "sh_k2_mindata_write_report: null argument");
+    const size_t n = db->nodes.size();
+    SH_CHECK(md->n_nodes == n, SH_ERR_BAD_ARG, "the minimizer data belongs to another database");
+    std::vector<uint64_t> direct(n, 0), clade, cm(n), cd(n);
+    std::vector<double> est(n);
+    for (uint64_t i = 0; i < n_units; ++i) if (res[i].call && res[i].call < n) ++direct[res[i].call];
+    clade = direct;
+    for (size_t i = n - 1; i >= 2; --i) clade[db->nodes[i].parent] += clade[i];      // parents have smaller ids
+    sh_status st = sh_k2_mindata_counts(md, nullptr, cm.data(), nullptr, est.data());
+    if (st != SH_OK) return st;
+    for (size_t i = 0; i < n; ++i) cd[i] = k2_hll_round(est[i]);
+    return sh_k2_write_minimizer_report(db->nodes.data(), n, db->names.data(), db->names.size(), db->ranks.data(), db->ranks.size(), clade.data(), direct.data(),
+                                        cm.data(), cd.data(), n_units, path);
 }

@@ -219,7 +219,7 @@ static char k2_rank_letter(const std::string &rank)
 }
 
 void shi_k2_report_rows(FILE *f, const sh_k2_taxnode *nodes, size_t n, const std::string &names, const std::string &ranks, const uint64_t *clade,
-                        const uint64_t *direct, double total, int32_t flags)
+                        const uint64_t *direct, double total, int32_t flags, const uint64_t *extra_a, const uint64_t *extra_b)
 {
     const bool zero = (flags & SH_K2_INSPECT_ZERO_COUNTS) != 0, mpa = (flags & SH_K2_INSPECT_MPA) != 0;
     // depth-first from the root, children by clade count (descending; ties by id), rank codes with a depth suffix
@@ -244,8 +244,9 @@ void shi_k2_report_rows(FILE *f, const sh_k2_taxnode *nodes, size_t n, const std
             }
         } else {
             std::string rc = code; if (cd) rc += std::to_string(cd);
-            fprintf(f, "%6.2f\t%llu\t%llu\t%s\t%llu\t", 100.0 * (double)clade[fr.id] / total, (unsigned long long)clade[fr.id], (unsigned long long)direct[fr.id], rc.c_str(),
-                    (unsigned long long)nd.external_id);
+            fprintf(f, "%6.2f\t%llu\t%llu\t", 100.0 * (double)clade[fr.id] / total, (unsigned long long)clade[fr.id], (unsigned long long)direct[fr.id]);
+            if (extra_a && extra_b) fprintf(f, "%llu\t%llu\t", (unsigned long long)extra_a[fr.id], (unsigned long long)extra_b[fr.id]);
+            fprintf(f, "%s\t%llu\t", rc.c_str(), (unsigned long long)nd.external_id);
             for (int i = 0; i < fr.depth; ++i) fputs("  ", f);
             fprintf(f, "%s\n", k2_pool(names, nd.name_offset));
         }

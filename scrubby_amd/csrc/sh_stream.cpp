@@ -1426,7 +1426,10 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
 
     std::vector<sh_k2_result> results(std::max<uint64_t>(n_units, 1));
     ShiKrakenHits hits;             // column 5: the hit lists (with --quick, "<taxid>:Q")
-    st = shi_kraken_classify(db, opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), n_rec, paired, results.data(), hits);
+    sh_k2_mindata *md = nullptr;    // -C "--report-minimizer-data": one accumulator over the run
+    if (c->report_minimizer_data) { st = sh_k2_mindata_create(db, &md); if (st != SH_OK) return st; }
+    struct MdGuard { sh_k2_mindata *m; ~MdGuard() { sh_k2_mindata_free(m); } } md_guard{md};
+    st = shi_kraken_classify(db, opts, bases.data(), want_q ? quals.data() : nullptr, offsets.data(), n_rec, paired, results.data(), hits, md);
     if (st != SH_OK) return st;
     std::vector<uint8_t>().swap(bases);
     std::vector<uint8_t>().swap(quals);
@@ -1479,6 +1482,7 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
         SH_CHECK(ok, SH_ERR_IO, "short write to %s", reads_path.c_str());
     }
     st = sh_k2_write_report(db, results.data(), n_units, report_path.c_str());
+    if (st == SH_OK) st = shi_kraken_minimizer_report(c, db, results.data(), n_units, md, dir);
     if (st != SH_OK) return st;
 
     // ---- parse_classifier_output (cleaner.rs:375-382): taxids from the report, then the reads carrying one of them ----

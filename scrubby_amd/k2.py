@@ -38,7 +38,11 @@ class KrakenConfig(C.Structure):
                 ("confidence", C.c_double), ("min_hit_groups", C.c_int32),
                 ("json", C.c_char_p), ("read_ids", C.c_char_p), ("command", C.c_char_p),
                 ("device", C.c_int32), ("threads", C.c_int32), ("classifier_args", C.c_char_p),
-                ("min_base_quality", C.c_int32), ("quick", C.c_int32)]
+                ("min_base_quality", C.c_int32), ("quick", C.c_int32), ("report_minimizer_data", C.c_int32)]
+
+
+class K2Batch(C.Structure):
+    _fields_ = [("bases", C.c_void_p), ("quals", C.c_void_p), ("offsets", C.c_void_p), ("n_records", C.c_uint64), ("paired", C.c_int32)]
 
 
 class K2TaxonomyInfo(C.Structure):
@@ -130,6 +134,72 @@ def _take_hits(h):
         return offs, ent[: ne.value], nr.value
     finally:
         L.sh_k2_hits_free(h)
+
+
+HLL_REGISTERS = 4096        # per taxon, one byte each (precision 12)
+
+
+def hll_estimate(regs):
+    """Distinct-count estimate of 4096 HyperLogLog registers (sh_k2_hll_estimate: Ertl's improved raw estimator; host only)"""
+    r = np.ascontiguousarray(regs, dtype=np.uint8)
+    assert r.shape == (HLL_REGISTERS,), "4096 registers"
+    e = C.c_double()
+    S.check(S.load().sh_k2_hll_estimate(C.c_void_p(r.ctypes.data), C.byref(e)))
+    return e.value
+
+
+def hll_merge(dst, src):
+    """element-wise maximum of two register arrays into dst (sh_k2_mindata_merge_host; host only)"""
+    assert dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable and len(dst) == len(src)
+    s = np.ascontiguousarray(src, dtype=np.uint8)
+    S.check(S.load().sh_k2_mindata_merge_host(C.c_void_p(dst.ctypes.data), C.c_void_p(s.ctypes.data), C.c_uint64(len(dst))))
+    return dst
+
+
+def write_minimizer_report(nodes, names, ranks, clade_reads, direct_reads, clade_minimizers, clade_distinct, total_units, path):
+    """kraken2 --report-minimizer-data's 8-column report (sh_k2_write_minimizer_report; host only) over a taxonomy in taxo.k2d's
+    layout and four per-taxon arrays"""
+    a = [np.ascontiguousarray(x, dtype=np.uint64) for x in (clade_reads, direct_reads, clade_minimizers, clade_distinct)]
+    assert all(len(x) == len(nodes) for x in a), "one value per taxonomy node"
+    S.check(S.load().sh_k2_write_minimizer_report(nodes, C.c_uint64(len(nodes)), names, C.c_uint64(len(names)), ranks, C.c_uint64(len(ranks)),
+                                                  *[C.c_void_p(x.ctypes.data) for x in a], C.c_uint64(total_units), str(path).encode()))
+
+
+class MinimizerData:
+    """The per-taxon minimizer counts and HyperLogLog registers of one database (sh_k2_mindata), kept in HBM; classify calls
+    given `minimizer_data=` add to it."""
+
+    def __init__(self, db):
+        self.n_nodes = db.info()["n_nodes"]
+        self.h = C.c_void_p()
+        S.check(S.load().sh_k2_mindata_create(db.h, C.byref(self.h)))
+
+    def reset(self):
+        S.check(S.load().sh_k2_mindata_reset(self.h))
+
+    def counts(self):
+        """dict of four arrays by internal taxon: n_minimizers, clade_minimizers (uint64), distinct, clade_distinct (float64)"""
+        n = self.n_nodes
+        r = {"n_minimizers": np.zeros(n, np.uint64), "clade_minimizers": np.zeros(n, np.uint64), "distinct": np.zeros(n, np.float64),
+             "clade_distinct": np.zeros(n, np.float64)}
+        S.check(S.load().sh_k2_mindata_counts(self.h, *[C.c_void_p(r[k].ctypes.data) for k in ("n_minimizers", "clade_minimizers", "distinct", "clade_distinct")]))
+        return r
+
+    def registers(self, taxon, clade=False):
+        out = np.zeros(HLL_REGISTERS, dtype=np.uint8)
+        S.check(S.load().sh_k2_mindata_registers(self.h, C.c_uint32(taxon), C.c_void_p(out.ctypes.data), int(bool(clade))))
+        return out
+
+    def close(self):
+        if self.h:
+            S.load().sh_k2_mindata_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def default_opts():
@@ -456,10 +526,11 @@ class K2Db:
         S.check(S.load().sh_k2_export(self.h, C.c_void_p(cells.ctypes.data), C.c_void_p(parent.ctypes.data), C.c_void_p(ext.ctypes.data)))
         return cells, parent, ext
 
-    def classify(self, bases, offsets, paired=False, opts=None, quals=None, hits=False):
+    def classify(self, bases, offsets, paired=False, opts=None, quals=None, hits=False, minimizer_data=None):
         """quals (optional): Phred+33 bytes at the offsets of `bases` (0xFF = never masked), used when opts.min_base_quality > 0.
         hits=True: also Kraken 2's hit lists (sh_k2_classify_hits_batch_q), returned third as (offsets, entries): unit i's
-        entries (HIT_DTYPE) are entries[offsets[i]:offsets[i + 1]]."""
+        entries (HIT_DTYPE) are entries[offsets[i]:offsets[i + 1]].
+        minimizer_data: a MinimizerData the call adds to (sh_k2_classify_ex_batch); the return values are the same."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         if quals is not None:
@@ -472,11 +543,18 @@ class K2Db:
         args = (self.h, C.byref(opts) if opts is not None else None, C.c_void_p(bases.ctypes.data),
                 C.c_void_p(quals.ctypes.data) if quals is not None else None, C.c_void_p(offsets.ctypes.data), C.c_uint64(n_rec),
                 1 if paired else 0, C.c_void_p(out.ctypes.data), C.byref(st))
-        if not hits:
+        if minimizer_data is not None:
+            b = K2Batch(bases.ctypes.data, quals.ctypes.data if quals is not None else None, offsets.ctypes.data, n_rec, 1 if paired else 0)
+            h = C.c_void_p()
+            S.check(S.load().sh_k2_classify_ex_batch(self.h, args[1], C.byref(b), args[7], args[8], C.byref(h) if hits else None, minimizer_data.h))
+            if not hits:
+                return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
+        elif not hits:
             S.check(S.load().sh_k2_classify_batch_q(*args))
             return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
-        h = C.c_void_p()
-        S.check(S.load().sh_k2_classify_hits_batch_q(*args, C.byref(h)))
+        else:
+            h = C.c_void_p()
+            S.check(S.load().sh_k2_classify_hits_batch_q(*args, C.byref(h)))
         offs, ent, redone = _take_hits(h)
         return out[:n_units], dict({n: getattr(st, n) for n, _ in K2Stats._fields_}, n_hits_redone=redone), (offs, ent)
 
@@ -491,15 +569,21 @@ class K2Db:
         S.check(S.load().sh_k2_export(self.h, None, None, C.c_void_p(ext.ctypes.data)))
         return ext
 
-    def classify_device_hits(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None, to_host=True):
+    def classify_device_hits(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None, to_host=True, minimizer_data=None):
         """sh_k2_classify_hits_device_q: results into d_out; returns (stats, (offsets, entries)) copied to the host, or with
-        to_host=False (stats, (d_offsets_ptr, d_entries_ptr, n_units, n_entries, handle)) - free the handle with free_hits."""
+        to_host=False (stats, (d_offsets_ptr, d_entries_ptr, n_units, n_entries, handle)) - free the handle with free_hits.
+        minimizer_data: a MinimizerData the call adds to (sh_k2_classify_ex_device)."""
         st = K2Stats()
         h = C.c_void_p()
-        S.check(S.load().sh_k2_classify_hits_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
-                                                      C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
-                                                      C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
-                                                      C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st), C.byref(h)))
+        if minimizer_data is not None:
+            b = K2Batch(d_bases.data_ptr(), d_quals.data_ptr() if d_quals is not None else None, d_offsets.data_ptr(), n_records, 1 if paired else 0)
+            S.check(S.load().sh_k2_classify_ex_device(self.h, C.byref(opts) if opts is not None else None, C.byref(b), C.c_void_p(d_out.data_ptr()),
+                                                      S._stream_ptr(), C.byref(st), C.byref(h), minimizer_data.h))
+        else:
+            S.check(S.load().sh_k2_classify_hits_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
+                                                          C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
+                                                          C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
+                                                          C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st), C.byref(h)))
         stats = {n: getattr(st, n) for n, _ in K2Stats._fields_}
         if to_host:
             offs, ent, stats["n_hits_redone"] = _take_hits(h)
@@ -519,8 +603,13 @@ class K2Db:
         S.check(S.load().sh_k2_hits_count(h, None, None, C.byref(r)))
         return r.value
 
-    def classify_device(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None):
+    def classify_device(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None, minimizer_data=None):
         st = K2Stats()
+        if minimizer_data is not None:
+            b = K2Batch(d_bases.data_ptr(), d_quals.data_ptr() if d_quals is not None else None, d_offsets.data_ptr(), n_records, 1 if paired else 0)
+            S.check(S.load().sh_k2_classify_ex_device(self.h, C.byref(opts) if opts is not None else None, C.byref(b), C.c_void_p(d_out.data_ptr()),
+                                                      S._stream_ptr(), C.byref(st), None, minimizer_data.h))
+            return {n: getattr(st, n) for n, _ in K2Stats._fields_}
         S.check(S.load().sh_k2_classify_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
                                                  C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
                                                  C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
@@ -557,6 +646,11 @@ class K2Db:
         r = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
         S.check(S.load().sh_k2_write_report(self.h, C.c_void_p(r.ctypes.data), C.c_uint64(len(r)), str(path).encode()))
 
+    def write_minimizer_report(self, results, minimizer_data, path):
+        """the 8-column report of kraken2 --report-minimizer-data from per-unit results and a MinimizerData"""
+        r = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        S.check(S.load().sh_k2_mindata_write_report(self.h, C.c_void_p(r.ctypes.data), C.c_uint64(len(r)), minimizer_data.h, str(path).encode()))
+
     def close(self):
         if self.h:
             S.load().sh_k2_free(self.h)
@@ -570,7 +664,8 @@ class K2Db:
 
 
 def kraken_run(inputs, outputs, db, taxa=(), taxa_direct=(), workdir=None, confidence=-1.0, min_hit_groups=0, extract=False,
-               json=None, read_ids=None, command="", device=0, threads=4, classifier_args=None, min_base_quality=0, quick=False):
+               json=None, read_ids=None, command="", device=0, threads=4, classifier_args=None, min_base_quality=0, quick=False,
+               report_minimizer_data=False):
     c = KrakenConfig()
     for i, (a, b) in enumerate(zip(inputs, outputs)):
         c.input[i], c.output[i] = str(a).encode(), str(b).encode()
@@ -584,7 +679,7 @@ def kraken_run(inputs, outputs, db, taxa=(), taxa_direct=(), workdir=None, confi
     c.read_ids = str(read_ids).encode() if read_ids else None
     c.command, c.device, c.threads = command.encode(), device, threads
     c.classifier_args = classifier_args.encode() if classifier_args else None
-    c.min_base_quality, c.quick = min_base_quality, int(quick)
+    c.min_base_quality, c.quick, c.report_minimizer_data = min_base_quality, int(quick), int(bool(report_minimizer_data))
     r = S.ReadsResult()
     S.check(S.load().sh_kraken_run(C.byref(c), C.byref(r)))
     return {n: getattr(r, n) for n, _ in S.ReadsResult._fields_}

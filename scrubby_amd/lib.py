@@ -136,6 +136,9 @@ EXPORTS = [
     "sh_k2_classify_device", "sh_k2_classify_batch", "sh_k2_classify_device_q", "sh_k2_classify_batch_q", "sh_k2_write_report", "sh_kraken_run",
     "sh_k2_classify_hits_device", "sh_k2_classify_hits_device_q", "sh_k2_classify_hits_batch", "sh_k2_classify_hits_batch_q",
     "sh_k2_hits_count", "sh_k2_hits_device", "sh_k2_hits_copy", "sh_k2_hits_free", "sh_k2_format_hits",
+    "sh_k2_mindata_create", "sh_k2_mindata_reset", "sh_k2_mindata_free", "sh_k2_classify_ex_device", "sh_k2_classify_ex_batch",
+    "sh_k2_mindata_counts", "sh_k2_mindata_registers", "sh_k2_hll_estimate", "sh_k2_mindata_merge_host",
+    "sh_k2_write_minimizer_report", "sh_k2_mindata_write_report",
     "sh_k2_taxonomy_from_ncbi", "sh_k2_taxonomy_single", "sh_k2_taxonomy_info_get", "sh_k2_taxonomy_copy", "sh_k2_taxonomy_internal",
     "sh_k2_taxonomy_header_taxon", "sh_k2_taxonomy_free", "sh_k2_capacity_plan", "sh_k2_max_db_size", "sh_k2_set_min_acceptable_hash",
     "sh_k2_insert_library_device", "sh_k2_estimator_create", "sh_k2_estimate_capacity_device", "sh_k2_estimator_free", "sh_k2_build_run",
