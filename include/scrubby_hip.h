@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, sh_k2_classify_*_q added; the old layouts are prefixes; + Kraken 2 hit lists: sh_k2_classify_hits_*, sh_k2_hits_*, sh_k2_format_hits added, nothing changed): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
+#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
 
 typedef int32_t sh_status;
 enum {
@@ -388,21 +388,6 @@ sh_status sh_k2_db_opts(const sh_k2_db *db, sh_k2_opts *out);
 /* host copies for the test oracle: cells[capacity], parent[n_nodes], external[n_nodes] (any pointer may be NULL) */
 sh_status sh_k2_export(const sh_k2_db *db, uint32_t *cells, uint32_t *parent, uint32_t *external);
 sh_status sh_k2_free(sh_k2_db *db);
-/* classify device-resident records.  paired != 0: records 2i and 2i+1 are the mates of pair i (n_records even), one
- * result per pair; else one result per record.  d_bases needs 8 readable bytes past the last base. */
-sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
-                                uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats);
-/* the same from host memory */
-sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
-                               uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats);
-/* both with Phred qualities for opts->min_base_quality: quals (nullable: nothing is masked) holds one byte per base at the
- * offsets of bases, 0xFF = never masked (FASTA records).  The device form needs d_quals and d_bases at the same address
- * modulo 8 and 8 readable bytes past the last quality.  With quals = NULL they are the two entries above. */
-sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
-                                  const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
-                                  sh_k2_stats *stats);
-sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                 const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats);
 /* Kraken 2's per-k-mer hit list (column 5 of its output): per unit, in read order, the run-length encoding of the k-mers'
  * taxa.  code = internal taxid (0: not in the table, or not looked up in a down-sampled database), SH_K2_HIT_AMBIGUOUS
  * (ambiguous k-mers, masked bases included) or SH_K2_HIT_BORDER (the mate border of a pair, count 0, never merged).
@@ -410,18 +395,7 @@ sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, con
 #define SH_K2_HIT_AMBIGUOUS 0xFFFFFFFFu
 #define SH_K2_HIT_BORDER    0xFFFFFFFEu
 typedef struct sh_k2_hit { uint32_t code, count; } sh_k2_hit;
-typedef struct sh_k2_hits sh_k2_hits;   /* the lists of one call, in HBM; freed with sh_k2_hits_free */
-/* the classify entries above plus the hit lists (results and stats are bit-identical to theirs); not with opts->quick */
-sh_status sh_k2_classify_hits_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
-                                     uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits);
-sh_status sh_k2_classify_hits_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
-                                       const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
-                                       sh_k2_stats *stats, sh_k2_hits **hits);
-sh_status sh_k2_classify_hits_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
-                                    uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits);
-sh_status sh_k2_classify_hits_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                      const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats,
-                                      sh_k2_hits **hits);
+typedef struct sh_k2_hits sh_k2_hits;   /* the lists of one classify call (below), in HBM; freed with sh_k2_hits_free */
 /* units, entries, and units whose lists were redone by the overflow pass (any pointer may be NULL) */
 sh_status sh_k2_hits_count(const sh_k2_hits *hits, uint64_t *n_units, uint64_t *n_entries, uint64_t *n_redone);
 /* unit i's entries are [offsets[i], offsets[i + 1]); device pointers owned by the handle, or host copies (offsets: n_units + 1,
@@ -448,9 +422,17 @@ typedef struct sh_k2_mindata sh_k2_mindata;
 sh_status sh_k2_mindata_create(const sh_k2_db *db, sh_k2_mindata **out);      /* SH_ERR_OOM names the size */
 sh_status sh_k2_mindata_reset(sh_k2_mindata *md);
 sh_status sh_k2_mindata_free(sh_k2_mindata *md);
-/* one general classify entry: the batch (quals nullable, as for the _q entries; device pointers for _device, host pointers
- * for _batch), optional hit lists (hits nullable; with opts->quick SH_ERR_BAD_ARG, as for the hits entries) and optional
- * minimizer data (md nullable; the call accumulates into it).  Results and stats are bit-identical to the entries above. */
+/* The classify entries: _device takes device-resident records (device pointers in the batch, results to d_out, work on `stream`),
+ * _batch the same from host memory (host pointers, results to out).
+ *   batch   paired != 0: records 2i and 2i+1 are the mates of pair i (n_records even, else SH_ERR_BAD_ARG), one result per pair;
+ *           else one result per record.  Device form: bases needs 8 readable bytes past the last base.
+ *           quals (nullable: nothing is masked) holds Phred qualities for opts->min_base_quality, one byte per base at the
+ *           offsets of bases, 0xFF = never masked (FASTA records).  Device form: quals and bases at the same address modulo 8
+ *           (else SH_ERR_BAD_ARG) and 8 readable bytes past the last quality.
+ *   hits    nullable; else *hits receives Kraken 2's hit lists (above) behind a handle the caller frees; results and stats are
+ *           bit-identical to a call without them.  With opts->quick SH_ERR_BAD_ARG.  *hits is NULL after any failure.
+ *   md      nullable; else the minimizer data of this database (else SH_ERR_BAD_ARG), which the call accumulates into;
+ *           results and stats are bit-identical to a call without it. */
 typedef struct sh_k2_batch {
     const uint8_t  *bases;
     const uint8_t  *quals;

@@ -1,4 +1,4 @@
-"""Cost of Kraken 2's hit lists (k_k2_classify's HITS instance, sh_k2_classify_hits_device) on the configs[4] stand-in of
+"""Cost of Kraken 2's hit lists (k_k2_classify's HITS instance, sh_k2_classify_ex_device) on the configs[4] stand-in of
 bench.py (--workload k2: synthetic 2x150 bp pairs against a 2e9-cell table holding the CHM13-sized synthetic reference under
 Homo sapiens plus filler keys), the same setup as scripts/k2_options_speed.py.
 

@@ -65,6 +65,25 @@ void sh_set_error(const char *fmt, ...);
         }                                 \
     } while (0)
 
+// ---- call-local device scratch: owned by the scope, so every early return above frees it ----------
+struct DevBuf {   // frees on scope exit
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) hipFree(p); }
+    template <class T> T *as() { return (T *)p; }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+struct DevEvent {   // destroyed on scope exit, if it was created
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent &) = delete;
+    DevEvent &operator=(const DevEvent &) = delete;
+    ~DevEvent() { if (e) hipEventDestroy(e); }
+    hipError_t create() { return hipEventCreate(&e); }
+};
+
 // ---- device helpers --------------------------------------------------------------------------
 __host__ __device__ static inline uint64_t sh_hash64(uint64_t key, uint64_t mask)
 {   // minimap2's invertible integer mix on 2k bits

@@ -635,20 +635,18 @@ sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_
 {
     hits.quick = opts.quick != 0;
     const sh_k2_batch batch{bases, quals, offsets, n_rec, paired ? 1 : 0};
-    if (hits.quick) {       // "<taxid>:Q"
-        if (md) return sh_k2_classify_ex_batch(db, &opts, &batch, results, nullptr, nullptr, md);
-        return sh_k2_classify_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr);
+    sh_status st = SH_OK;
+    if (!hits.quick) {      // (with --quick column 5 is "<taxid>:Q": no hit list)
+        sh_k2_info info;
+        st = sh_k2_info_get(db, &info);
+        if (st != SH_OK) return st;
+        hits.ext.assign(info.n_nodes, 0);
+        st = sh_k2_export(db, nullptr, nullptr, hits.ext.data());
+        if (st != SH_OK) return st;
     }
-    sh_k2_info info;
-    sh_status st = sh_k2_info_get(db, &info);
-    if (st != SH_OK) return st;
-    hits.ext.assign(info.n_nodes, 0);
-    st = sh_k2_export(db, nullptr, nullptr, hits.ext.data());
-    if (st != SH_OK) return st;
     sh_k2_hits *h = nullptr;
-    if (md) st = sh_k2_classify_ex_batch(db, &opts, &batch, results, nullptr, &h, md);
-    else st = sh_k2_classify_hits_batch_q(db, &opts, bases, quals, offsets, n_rec, paired ? 1 : 0, results, nullptr, &h);
-    if (st != SH_OK) return st;
+    st = sh_k2_classify_ex_batch(db, &opts, &batch, results, nullptr, hits.quick ? nullptr : &h, md);
+    if (st != SH_OK || hits.quick) return st;
     uint64_t n_units = 0, n_ent = 0;
     sh_k2_hits_count(h, &n_units, &n_ent, nullptr);
     hits.off.assign(n_units + 1, 0); hits.ent.resize(n_ent);

@@ -149,13 +149,6 @@ __global__ void k_ref_pack(const uint8_t *bases, uint64_t n, uint8_t *packed)
     *(uint4 *)(packed + o) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-struct DevBuf {   // frees on scope exit
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    template <class T> T *as() { return (T *)p; }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 sh_status shi_index_build_device(const uint8_t *d_bases, const uint64_t *contig_starts, uint32_t n_contigs,
                                  const sh_opts *opts, int32_t device, hipStream_t s, sh_index **out)
 {

@@ -818,6 +818,23 @@ __global__ __launch_bounds__(64) void k_k2_estimate_lib(K2LibArgs a, uint64_t *b
     });
 }
 
+// the window k - l + 1 as a compile-time constant, handed to a generic lambda: 1, 5 (k = 35, l = 31) and, for every other
+// (k, l), 16 with the live part given at run time (K2Scan)
+template <class F>
+static void k2_with_window(int32_t k, int32_t l, F &&f)
+{
+    switch (k - l + 1) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+template <class F>
+static void k2_with_flag(bool b, F &&f)
+{
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 extern "C" sh_status sh_k2_default_opts(sh_k2_opts *o)
 {
@@ -915,14 +932,6 @@ extern "C" sh_status sh_k2_insert_random(sh_k2_db *db, uint64_t seed, uint64_t n
     return k2_sync_counts(db, s);
 }
 
-template <int W>
-static void launch_insert_seq(sh_k2_db *db, const uint8_t *d_bases, uint64_t n, uint32_t taxon, hipStream_t s, unsigned long long *d_runs)
-{
-    const uint64_t n_seg = (n + K2_SEG - 1) / K2_SEG;
-    hipLaunchKernelGGL(k_k2_insert_seq<W>, dim3((uint32_t)std::min<uint64_t>((n_seg + 63) / 64, 1 << 20)), dim3(64), 0, s, k2_build_args(db), d_bases, n, taxon,
-                       db->opts.k, db->opts.l, db->opts.spaced_seed_mask, db->opts.toggle_mask, db->opts.min_acceptable_hash, d_runs);
-}
-
 extern "C" sh_status sh_k2_insert_sequence_device(sh_k2_db *db, const uint8_t *d_bases, uint64_t n, uint32_t taxon, void *stream, uint64_t *n_inserted)
 {
     SH_CHECK(db && d_bases && taxon >= 1 && taxon < db->nodes.size(), SH_ERR_BAD_ARG, "sh_k2_insert_sequence_device: bad argument");
@@ -931,11 +940,11 @@ extern "C" sh_status sh_k2_insert_sequence_device(sh_k2_db *db, const uint8_t *d
     unsigned long long *d_runs = db->d_ctr + 2;
     SH_HIP(hipMemsetAsync(d_runs, 0, 8, s));
     if (n >= (uint64_t)db->opts.k) {
-        switch (db->opts.k - db->opts.l + 1) {
-        case 1: launch_insert_seq<1>(db, d_bases, n, taxon, s, d_runs); break;
-        case 5: launch_insert_seq<5>(db, d_bases, n, taxon, s, d_runs); break;
-        default: launch_insert_seq<16>(db, d_bases, n, taxon, s, d_runs); break;
-        }
+        const uint64_t n_seg = (n + K2_SEG - 1) / K2_SEG;
+        k2_with_window(db->opts.k, db->opts.l, [&](auto w) {
+            hipLaunchKernelGGL(k_k2_insert_seq<decltype(w)::value>, dim3((uint32_t)std::min<uint64_t>((n_seg + 63) / 64, 1 << 20)), dim3(64), 0, s, k2_build_args(db),
+                               d_bases, n, taxon, db->opts.k, db->opts.l, db->opts.spaced_seed_mask, db->opts.toggle_mask, db->opts.min_acceptable_hash, d_runs);
+        });
     }
     unsigned long long r = 0;
     SH_HIP(hipMemcpyAsync(&r, d_runs, 8, hipMemcpyDeviceToHost, s));
@@ -952,17 +961,18 @@ static uint32_t k2_lib_seg()
     return v >= 64 && v <= (1 << 20) ? (uint32_t)v : K2_LIB_SEG;
 }
 
-// segment counts and their prefix sum in d_seg (n_records + 1 words, caller-owned); everything on stream s, no synchronisation
+// segment counts and their prefix sum in d_seg (n_records + 1 words, caller-owned, as is the scan's scratch, which must outlive
+// the stream's work); everything on stream s, no synchronisation
 static sh_status k2_lib_prepare(K2LibArgs &a, const sh_k2_opts &o, const uint8_t *d_bases, const uint64_t *d_offsets, const uint32_t *d_taxa, uint64_t n_records,
-                                uint64_t *d_seg, void **d_tmp, hipStream_t s)
+                                uint64_t *d_seg, DevBuf &tmp, hipStream_t s)
 {
     a.bases = d_bases; a.offsets = d_offsets; a.taxa = d_taxa; a.n_records = n_records; a.seg_off = d_seg;
     a.seg = k2_lib_seg(); a.k = o.k; a.l = o.l; a.spaced = o.spaced_seed_mask; a.toggle = o.toggle_mask; a.min_hash = o.min_acceptable_hash;
     hipLaunchKernelGGL(k_k2_lib_segcount, dim3((uint32_t)std::min<uint64_t>((n_records + 256) / 256, 4096)), dim3(256), 0, s, a);
     size_t tmp_bytes = 0;
     SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_seg, d_seg, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
-    SH_HIP(hipMalloc(d_tmp, std::max<size_t>(tmp_bytes, 1)));
-    SH_HIP(rocprim::exclusive_scan(*d_tmp, tmp_bytes, d_seg, d_seg, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
+    SH_HIP(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+    SH_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, d_seg, d_seg, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
     return SH_OK;
 }
 #define K2_LIB_GRID (256 * 32)      // one-wave blocks, grid-stride over the work items (their number stays on the device)
@@ -982,34 +992,30 @@ extern "C" sh_status sh_k2_insert_library_device(sh_k2_db *db, const uint8_t *d_
     SH_HIP(hipSetDevice(db->device));
     hipStream_t s = (hipStream_t)stream;
     if (n_records == 0) return k2_sync_counts(db, s);
-    uint64_t *d_seg = nullptr; void *d_tmp = nullptr;
-    SH_HIP(hipMalloc(&d_seg, (n_records + 1) * 8));
-    hipEvent_t e0, e1;
-    SH_HIP(hipEventCreate(&e0)); SH_HIP(hipEventCreate(&e1));
+    DevBuf b_seg, b_tmp;
+    DevEvent e0, e1;
+    SH_HIP(b_seg.alloc((n_records + 1) * 8));
+    SH_HIP(e0.create()); SH_HIP(e1.create());
+    uint64_t *d_seg = b_seg.as<uint64_t>();
     unsigned long long *d_runs = db->d_ctr + 2;
     SH_HIP(hipMemsetAsync(d_runs, 0, 8, s));
-    SH_HIP(hipEventRecord(e0, s));
+    SH_HIP(hipEventRecord(e0.e, s));
     K2LibArgs a{};
     a.n_nodes = (uint32_t)db->nodes.size();
-    sh_status st = k2_lib_prepare(a, db->opts, d_bases, d_offsets, d_taxa, n_records, d_seg, &d_tmp, s);
-    if (st == SH_OK) {
-        switch (db->opts.k - db->opts.l + 1) {
-        case 1: hipLaunchKernelGGL(k_k2_insert_lib<1>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs); break;
-        case 5: hipLaunchKernelGGL(k_k2_insert_lib<5>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs); break;
-        default: hipLaunchKernelGGL(k_k2_insert_lib<16>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs); break;
-        }
-        hipEventRecord(e1, s);
-        unsigned long long r = 0, n_seg = 0;
-        hipMemcpyAsync(&r, d_runs, 8, hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(&n_seg, d_seg + n_records, 8, hipMemcpyDeviceToHost, s);
-        st = k2_sync_counts(db, s);        // the one synchronisation of the batch
-        if (stats) {
-            stats->n_records = n_records; stats->n_segments = n_seg; stats->n_runs = r; stats->size = db->size;
-            hipEventElapsedTime(&stats->ms, e0, e1);
-        }
+    sh_status st = k2_lib_prepare(a, db->opts, d_bases, d_offsets, d_taxa, n_records, d_seg, b_tmp, s);
+    if (st != SH_OK) return st;
+    k2_with_window(db->opts.k, db->opts.l, [&](auto w) {
+        hipLaunchKernelGGL(k_k2_insert_lib<decltype(w)::value>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs);
+    });
+    hipEventRecord(e1.e, s);
+    unsigned long long r = 0, n_seg = 0;
+    hipMemcpyAsync(&r, d_runs, 8, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(&n_seg, d_seg + n_records, 8, hipMemcpyDeviceToHost, s);
+    st = k2_sync_counts(db, s);        // the one synchronisation of the batch
+    if (stats) {
+        stats->n_records = n_records; stats->n_segments = n_seg; stats->n_runs = r; stats->size = db->size;
+        hipEventElapsedTime(&stats->ms, e0.e, e1.e);
     }
-    hipFree(d_seg); hipFree(d_tmp);
-    hipEventDestroy(e0); hipEventDestroy(e1);
     return st;
 }
 
@@ -1047,13 +1053,14 @@ extern "C" sh_status sh_k2_estimator_create(const sh_k2_opts *opts, int device, 
 
 static sh_status k2_estimator_grow(sh_k2_estimator *e, uint64_t cap, hipStream_t s)
 {
-    uint64_t *nb = nullptr, *na = nullptr;
-    SH_HIP(hipMalloc(&nb, cap * 8));
-    SH_HIP(hipMalloc(&na, cap * 8));
-    if (e->n_have) SH_HIP(hipMemcpyAsync(nb, e->d_buf, e->n_have * 8, hipMemcpyDeviceToDevice, s));
+    DevBuf nb, na;
+    SH_HIP(nb.alloc(cap * 8));
+    SH_HIP(na.alloc(cap * 8));
+    if (e->n_have) SH_HIP(hipMemcpyAsync(nb.p, e->d_buf, e->n_have * 8, hipMemcpyDeviceToDevice, s));
     SH_HIP(hipStreamSynchronize(s));
-    hipFree(e->d_buf); hipFree(e->d_alt);
-    e->d_buf = nb; e->d_alt = na; e->cap = cap;
+    void *old_buf = e->d_buf, *old_alt = e->d_alt;
+    e->d_buf = nb.as<uint64_t>(); e->d_alt = na.as<uint64_t>(); e->cap = cap;
+    nb.p = old_buf; na.p = old_alt;      // the handle owns the new pair; the old one is freed on the way out
     return SH_OK;
 }
 
@@ -1065,47 +1072,42 @@ extern "C" sh_status sh_k2_estimate_capacity_device(sh_k2_estimator *e, const ui
     hipStream_t s = (hipStream_t)stream;
     if (n_sampled) *n_sampled = e->n_have;
     if (n_records == 0) return SH_OK;
-    uint64_t *d_seg = nullptr; void *d_tmp = nullptr, *d_tmp2 = nullptr;
-    SH_HIP(hipMalloc(&d_seg, (n_records + 1) * 8));
+    DevBuf b_seg, b_tmp, b_tmp2;
+    SH_HIP(b_seg.alloc((n_records + 1) * 8));
     K2LibArgs a{};
-    sh_status st = k2_lib_prepare(a, e->opts, d_bases, d_offsets, nullptr, n_records, d_seg, &d_tmp, s);
-    auto done = [&](sh_status r) { hipFree(d_seg); hipFree(d_tmp); hipFree(d_tmp2); return r; };
-    if (st != SH_OK) return done(st);
-    if (e->cap < e->n_have + (1u << 16)) { st = k2_estimator_grow(e, e->n_have * 2 + (1u << 20), s); if (st != SH_OK) return done(st); }
+    sh_status st = k2_lib_prepare(a, e->opts, d_bases, d_offsets, nullptr, n_records, b_seg.as<uint64_t>(), b_tmp, s);
+    if (st != SH_OK) return st;
+    if (e->cap < e->n_have + (1u << 16)) { st = k2_estimator_grow(e, e->n_have * 2 + (1u << 20), s); if (st != SH_OK) return st; }
     for (int attempt = 0;; ++attempt) {
         unsigned long long c0 = e->n_have, total = 0;
-        if (hipMemcpyAsync(e->d_ctr, &c0, 8, hipMemcpyHostToDevice, s) != hipSuccess) { sh_set_error("estimator: copy failed"); return done(SH_ERR_HIP); }
-        switch (e->opts.k - e->opts.l + 1) {
-        case 1: hipLaunchKernelGGL(k_k2_estimate_lib<1>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr); break;
-        case 5: hipLaunchKernelGGL(k_k2_estimate_lib<5>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr); break;
-        default: hipLaunchKernelGGL(k_k2_estimate_lib<16>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr); break;
-        }
-        if (hipMemcpyAsync(&total, e->d_ctr, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            sh_set_error("estimator: the scan failed"); return done(SH_ERR_HIP);
-        }
+        SH_CHECK(hipMemcpyAsync(e->d_ctr, &c0, 8, hipMemcpyHostToDevice, s) == hipSuccess, SH_ERR_HIP, "estimator: copy failed");
+        k2_with_window(e->opts.k, e->opts.l, [&](auto w) {
+            hipLaunchKernelGGL(k_k2_estimate_lib<decltype(w)::value>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr);
+        });
+        SH_CHECK(hipMemcpyAsync(&total, e->d_ctr, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && hipGetLastError() == hipSuccess,
+                 SH_ERR_HIP, "estimator: the scan failed");
         if (total > e->cap) {           // more sampled runs than the buffer holds: a larger one, and the batch again
-            if (attempt) { sh_set_error("estimator: sample buffer overflow"); return done(SH_ERR_HIP); }
+            SH_CHECK(!attempt, SH_ERR_HIP, "estimator: sample buffer overflow");
             st = k2_estimator_grow(e, total + (1u << 16), s);
-            if (st != SH_OK) return done(st);
+            if (st != SH_OK) return st;
             continue;
         }
         if (total > e->n_have) {        // sort everything, keep the distinct keys
             size_t b1 = 0, b2 = 0;
-            if (rocprim::radix_sort_keys(nullptr, b1, e->d_buf, e->d_alt, total, 0, 64, s) != hipSuccess ||
-                rocprim::unique(nullptr, b2, e->d_alt, e->d_buf, e->d_ctr + 1, total, rocprim::equal_to<uint64_t>(), s) != hipSuccess ||
-                hipMalloc(&d_tmp2, std::max<size_t>(std::max(b1, b2), 1)) != hipSuccess) { sh_set_error("estimator: scratch allocation failed"); return done(SH_ERR_OOM); }
+            SH_CHECK(rocprim::radix_sort_keys(nullptr, b1, e->d_buf, e->d_alt, total, 0, 64, s) == hipSuccess &&
+                     rocprim::unique(nullptr, b2, e->d_alt, e->d_buf, e->d_ctr + 1, total, rocprim::equal_to<uint64_t>(), s) == hipSuccess &&
+                     b_tmp2.alloc(std::max<size_t>(std::max(b1, b2), 1)) == hipSuccess, SH_ERR_OOM, "estimator: scratch allocation failed");
             unsigned long long uniq = 0;
-            if (rocprim::radix_sort_keys(d_tmp2, b1, e->d_buf, e->d_alt, total, 0, 64, s) != hipSuccess ||
-                rocprim::unique(d_tmp2, b2, e->d_alt, e->d_buf, e->d_ctr + 1, total, rocprim::equal_to<uint64_t>(), s) != hipSuccess ||
-                hipMemcpyAsync(&uniq, e->d_ctr + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                sh_set_error("estimator: sort failed"); return done(SH_ERR_HIP);
-            }
+            SH_CHECK(rocprim::radix_sort_keys(b_tmp2.p, b1, e->d_buf, e->d_alt, total, 0, 64, s) == hipSuccess &&
+                     rocprim::unique(b_tmp2.p, b2, e->d_alt, e->d_buf, e->d_ctr + 1, total, rocprim::equal_to<uint64_t>(), s) == hipSuccess &&
+                     hipMemcpyAsync(&uniq, e->d_ctr + 1, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess,
+                     SH_ERR_HIP, "estimator: sort failed");
             e->n_have = uniq;
         }
         break;
     }
     if (n_sampled) *n_sampled = e->n_have;
-    return done(SH_OK);
+    return SH_OK;
 }
 
 extern "C" sh_status sh_k2_info_get(const sh_k2_db *db, sh_k2_info *o)
@@ -1254,51 +1256,37 @@ extern "C" sh_status sh_k2_open(const char *dir, int device, sh_k2_db **out)
 }
 
 // ---- classification ---------------------------------------------------------------------------------------------------
-template <int W, bool BIG, bool QMASK, bool QUICK, int HITS, bool MIND>
-static void launch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s)
+// one form of the kernel; the window, QMASK and (for a pass-1 form) MIND become compile-time constants here
+template <bool BIG, bool QUICK, int HITS>
+static void launch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool mind)
 {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_work + 63) / 64, 1), 256 * 32);
-    const K2ArgsOf<QMASK, HITS, MIND> &ka = a;
-    hipLaunchKernelGGL((k_k2_classify<W, BIG, QMASK, QUICK, HITS, MIND>), dim3(grid), dim3(64), 0, s, ka);
-}
-template <bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false>
-static void dispatch_w(const K2MArgs &a, uint64_t n_work, hipStream_t s)
-{
-    switch (a.k - a.l + 1) {
-    case 1: launch_classify<1, BIG, QMASK, QUICK, HITS, MIND>(a, n_work, s); break;
-    case 5: launch_classify<5, BIG, QMASK, QUICK, HITS, MIND>(a, n_work, s); break;
-    default: launch_classify<16, BIG, QMASK, QUICK, HITS, MIND>(a, n_work, s); break;
-    }
+    k2_with_window(a.k, a.l, [&](auto w) {
+        k2_with_flag(qmask, [&](auto q) {
+            k2_with_flag(mind, [&](auto m) {
+                constexpr bool QMASK = decltype(q)::value, MIND = decltype(m)::value && !(BIG || HITS == 2);
+                const K2ArgsOf<QMASK, HITS, MIND> &ka = a;
+                hipLaunchKernelGGL((k_k2_classify<decltype(w)::value, BIG, QMASK, QUICK, HITS, MIND>), dim3(grid), dim3(64), 0, s, ka);
+            });
+        });
+    });
 }
 // only the instances that are needed: a QUICK unit keeps no hit list, so it never overflows into the BIG pass; the BIG pass
 // needs no HITS instance (pass 1 already emitted the whole list of a unit with many taxa); MIND goes with the three pass-1
 // forms only (the two redo passes are never asked for it: their units were counted by pass 1)
-template <bool BIG>
-static sh_status dispatch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool quick, int hits = 0, bool mind = false)
+enum K2Form { K2F_PLAIN, K2F_QUICK, K2F_HITS1, K2F_HITS2, K2F_BIG };
+static void dispatch_classify(K2Form form, const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool mind = false)
 {
-    if constexpr (!BIG) {
-        if (mind && hits != 2) {
-            if (quick) { if (qmask) dispatch_w<false, true, true, 0, true>(a, n_work, s); else dispatch_w<false, false, true, 0, true>(a, n_work, s); }
-            else if (hits == 1) { if (qmask) dispatch_w<false, true, false, 1, true>(a, n_work, s); else dispatch_w<false, false, false, 1, true>(a, n_work, s); }
-            else { if (qmask) dispatch_w<false, true, false, 0, true>(a, n_work, s); else dispatch_w<false, false, false, 0, true>(a, n_work, s); }
-            return SH_OK;
-        }
+    switch (form) {
+    case K2F_PLAIN: launch_classify<false, false, 0>(a, n_work, s, qmask, mind); break;
+    case K2F_QUICK: launch_classify<false, true, 0>(a, n_work, s, qmask, mind); break;
+    case K2F_HITS1: launch_classify<false, false, 1>(a, n_work, s, qmask, mind); break;
+    case K2F_HITS2: launch_classify<false, false, 2>(a, n_work, s, qmask, false); break;
+    case K2F_BIG: launch_classify<true, false, 0>(a, n_work, s, qmask, false); break;
     }
-    if (BIG) {
-        if (qmask) dispatch_w<true, true, false>(a, n_work, s); else dispatch_w<true, false, false>(a, n_work, s);
-    } else if (quick) {
-        if (qmask) dispatch_w<false, true, true>(a, n_work, s); else dispatch_w<false, false, true>(a, n_work, s);
-    } else if (hits == 1) {
-        if (qmask) dispatch_w<false, true, false, 1>(a, n_work, s); else dispatch_w<false, false, false, 1>(a, n_work, s);
-    } else if (hits == 2) {
-        if (qmask) dispatch_w<false, true, false, 2>(a, n_work, s); else dispatch_w<false, false, false, 2>(a, n_work, s);
-    } else {
-        if (qmask) dispatch_w<false, true, false>(a, n_work, s); else dispatch_w<false, false, false>(a, n_work, s);
-    }
-    return SH_OK;
 }
 
-// the hit lists of one call (sh_k2_classify_hits_*): per-unit offsets and the entries, compacted, in HBM
+// the hit lists of one call (sh_k2_classify_ex_* with hits): per-unit offsets and the entries, compacted, in HBM
 struct sh_k2_hits {
     int device = 0;
     uint64_t n_units = 0, n_entries = 0, n_redone = 0;
@@ -1387,41 +1375,6 @@ __global__ __launch_bounds__(256) void k_k2_md_hist(uint32_t n_nodes, const uint
     }
 }
 
-static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
-                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out,
-                             sh_k2_mindata *md = nullptr);
-
-extern "C" sh_status sh_k2_classify_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
-                                           uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats)
-{
-    return sh_k2_classify_device_q(db, opts, d_bases, nullptr, d_offsets, n_records, paired, d_out, stream, stats);
-}
-
-extern "C" sh_status sh_k2_classify_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
-                                             const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
-                                             sh_k2_stats *stats)
-{
-    return k2_classify(db, opts, d_bases, d_quals, d_offsets, n_records, paired, d_out, stream, stats, nullptr);
-}
-
-extern "C" sh_status sh_k2_classify_hits_device(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint64_t *d_offsets,
-                                                uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits)
-{
-    return sh_k2_classify_hits_device_q(db, opts, d_bases, nullptr, d_offsets, n_records, paired, d_out, stream, stats, hits);
-}
-
-extern "C" sh_status sh_k2_classify_hits_device_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals,
-                                                  const uint64_t *d_offsets, uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream,
-                                                  sh_k2_stats *stats, sh_k2_hits **hits)
-{
-    SH_CHECK(hits, SH_ERR_BAD_ARG, "sh_k2_classify_hits_device: null argument");
-    *hits = nullptr;
-    SH_CHECK(!(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: use sh_k2_classify_device_q");
-    sh_status st = k2_classify(db, opts, d_bases, d_quals, d_offsets, n_records, paired, d_out, stream, stats, hits);
-    if (st != SH_OK) { sh_k2_hits_free(*hits); *hits = nullptr; }
-    return st;
-}
-
 extern "C" sh_status sh_k2_hits_count(const sh_k2_hits *h, uint64_t *n_units, uint64_t *n_entries, uint64_t *n_redone)
 {
     SH_CHECK(h, SH_ERR_BAD_ARG, "sh_k2_hits_count: null argument");
@@ -1458,94 +1411,105 @@ extern "C" sh_status sh_k2_hits_free(sh_k2_hits *h)
     return SH_OK;
 }
 
+// the handle a classify call is filling: the caller gets it only from a call that succeeds
+struct K2HitsOwner {
+    sh_k2_hits *h = nullptr;
+    ~K2HitsOwner() { sh_k2_hits_free(h); }
+    sh_k2_hits *release() { sh_k2_hits *r = h; h = nullptr; return r; }
+};
+
+// what both entries reach: the checks they share, the passes, the copy of the results to host_out (nullable: the host entry's),
+// and *hits_out (nullable), which is NULL after any failure
 static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
-                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, void *stream, sh_k2_stats *stats, sh_k2_hits **hits_out,
-                             sh_k2_mindata *md)
+                             uint64_t n_records, int32_t paired, sh_k2_result *d_out, sh_k2_result *host_out, void *stream, sh_k2_stats *stats,
+                             sh_k2_hits **hits_out, sh_k2_mindata *md)
 {
-    SH_CHECK(db && d_offsets && d_out && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_classify_device: null argument");
+    if (hits_out) *hits_out = nullptr;
+    SH_CHECK(db && d_offsets && d_out && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_classify_ex: null argument");
     SH_CHECK(!md || (md->device == db->device && md->n_nodes == db->nodes.size()), SH_ERR_BAD_ARG, "the minimizer data belongs to another database");
     SH_CHECK(!paired || (n_records & 1) == 0, SH_ERR_BAD_ARG, "paired input needs an even number of records (got %llu)", (unsigned long long)n_records);
+    const sh_k2_opts &o = opts ? *opts : db->opts;
+    SH_CHECK(!hits_out || !o.quick, SH_ERR_BAD_ARG, "--quick writes no hit list: call with hits = NULL");
     SH_HIP(hipSetDevice(db->device));
     hipStream_t s = (hipStream_t)stream;
-    const sh_k2_opts &o = opts ? *opts : db->opts;
     SH_CHECK(o.k == db->opts.k && o.l == db->opts.l, SH_ERR_BAD_ARG, "options disagree with the database (k, l)");
     const bool qmask = d_quals && o.min_base_quality > 0, quick = o.quick != 0;
     SH_CHECK(!qmask || ((uintptr_t)d_quals & 7) == ((uintptr_t)d_bases & 7), SH_ERR_BAD_ARG,
-             "sh_k2_classify_device_q: qualities and bases must lie at the same address modulo 8");
+             "sh_k2_classify_ex_device: qualities and bases must lie at the same address modulo 8");
     const uint64_t n_units = paired ? n_records / 2 : n_records;
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (hits_out) { *hits_out = new sh_k2_hits; (*hits_out)->device = db->device; }
-    if (n_units == 0) return SH_OK;
+    K2HitsOwner hl;
+    if (hits_out) { hl.h = new sh_k2_hits; hl.h->device = db->device; }
+    if (n_units == 0) { if (hits_out) *hits_out = hl.release(); return SH_OK; }
     SH_CHECK(n_units <= 0xffffffffull, SH_ERR_BAD_ARG, "at most 2^32 - 1 units per call");
-    hipEvent_t e0, e1;
-    SH_HIP(hipEventCreate(&e0)); SH_HIP(hipEventCreate(&e1));
-    unsigned long long *ctr = nullptr; uint32_t *over = nullptr;
-    SH_HIP(hipMalloc(&ctr, K2C_WORDS * 8));
-    SH_HIP(hipMalloc(&over, n_units * 4));
+    DevEvent e0, e1;
+    SH_HIP(e0.create()); SH_HIP(e1.create());
+    DevBuf b_ctr, b_over, b_hit_inl, b_n_hits, b_hit_over, b_big_tax, b_big_cnt;
+    SH_HIP(b_ctr.alloc(K2C_WORDS * 8));
+    SH_HIP(b_over.alloc(n_units * 4));
+    unsigned long long *ctr = b_ctr.as<unsigned long long>();
     SH_HIP(hipMemsetAsync(ctr, 0, K2C_WORDS * 8, s));
     K2MArgs a{};
     if (md) { a.md_regs = md->d_regs; a.md_cnt = md->d_cnt; md->clade_valid = false; }
-    uint2 *hit_inl = nullptr; uint32_t *n_hits = nullptr, *hit_over = nullptr;
     if (hits_out) {       // pass 1: K2_HIT_INLINE entries per unit in place, every unit's count (one spare: the scan's total)
-        SH_HIP(hipMalloc(&hit_inl, n_units * K2_HIT_INLINE * sizeof(uint2)));
-        SH_HIP(hipMalloc(&n_hits, (n_units + 1) * 4));
-        SH_HIP(hipMalloc(&hit_over, n_units * 4));
-        SH_HIP(hipMemsetAsync(n_hits + n_units, 0, 4, s));
-        a.hits = hit_inl; a.n_hits = n_hits; a.hit_over = hit_over;
+        SH_HIP(b_hit_inl.alloc(n_units * K2_HIT_INLINE * sizeof(uint2)));
+        SH_HIP(b_n_hits.alloc((n_units + 1) * 4));
+        SH_HIP(b_hit_over.alloc(n_units * 4));
+        a.hits = b_hit_inl.as<uint2>(); a.n_hits = b_n_hits.as<uint32_t>(); a.hit_over = b_hit_over.as<uint32_t>();
+        SH_HIP(hipMemsetAsync(a.n_hits + n_units, 0, 4, s));
     }
     a.bases = d_bases; a.offsets = d_offsets; a.n_units = n_units; a.paired = paired;
     a.T = K2Table{db->d_cells, db->capacity, db->value_bits, 1.0 / (double)db->capacity}; a.parent = db->d_parent; a.ext = db->d_ext; a.n_nodes = (uint32_t)db->nodes.size();
     a.k = o.k; a.l = o.l; a.spaced = o.spaced_seed_mask; a.toggle = o.toggle_mask; a.min_hash = o.min_acceptable_hash;
     a.min_hit_groups = o.min_hit_groups; a.confidence = o.confidence;
-    a.out = d_out; a.over_list = over; a.ctr = ctr;
+    a.out = d_out; a.over_list = b_over.as<uint32_t>(); a.ctr = ctr;
     a.quals = qmask ? d_quals : nullptr; a.min_qual = qmask ? o.min_base_quality : 0;
-    SH_HIP(hipEventRecord(e0, s));
+    SH_HIP(hipEventRecord(e0.e, s));
     if (qmask) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
-    dispatch_classify<false>(a, n_units, s, qmask, quick, hits_out ? 1 : 0, md != nullptr);      // the only pass that counts minimizers
-    SH_HIP(hipEventRecord(e1, s));
+    dispatch_classify(quick ? K2F_QUICK : hits_out ? K2F_HITS1 : K2F_PLAIN, a, n_units, s, qmask, md != nullptr);      // the only pass that counts minimizers
+    SH_HIP(hipEventRecord(e1.e, s));
     std::vector<unsigned long long> h(K2C_WORDS);
     SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
     SH_HIP(hipStreamSynchronize(s));
     SH_HIP(hipGetLastError());
     const uint64_t n_over = h[K2C_OVER];
-    uint32_t *big_tax = nullptr, *big_cnt = nullptr;
     if (n_over) {       // units with more than K2_HCAP distinct taxa: hit lists in HBM
-        SH_HIP(hipMalloc(&big_tax, n_over * K2_BIG_CAP * 4));
-        SH_HIP(hipMalloc(&big_cnt, n_over * K2_BIG_CAP * 4));
-        a.unit_list = over; a.n_list = (uint32_t)n_over; a.big_tax = big_tax; a.big_cnt = big_cnt;
-        dispatch_classify<true>(a, n_over, s, qmask, quick);
+        SH_HIP(b_big_tax.alloc(n_over * K2_BIG_CAP * 4));
+        SH_HIP(b_big_cnt.alloc(n_over * K2_BIG_CAP * 4));
+        a.unit_list = a.over_list; a.n_list = (uint32_t)n_over; a.big_tax = b_big_tax.as<uint32_t>(); a.big_cnt = b_big_cnt.as<uint32_t>();
+        dispatch_classify(K2F_BIG, a, n_over, s, qmask);
         SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
         SH_HIP(hipStreamSynchronize(s));
         SH_HIP(hipGetLastError());
     }
     if (hits_out) {
         // exact offsets from the counts, the units with longer lists redone straight into place, the rest compacted
-        sh_k2_hits *hl = *hits_out;
-        hl->n_units = n_units;
-        SH_HIP(hipMalloc(&hl->d_off, (n_units + 1) * 8));
-        size_t tmp_bytes = 0; void *tmp = nullptr;
-        SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, n_hits, hl->d_off, (uint64_t)0, n_units + 1, rocprim::plus<uint64_t>(), s));
-        SH_HIP(hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 1)));
-        SH_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, n_hits, hl->d_off, (uint64_t)0, n_units + 1, rocprim::plus<uint64_t>(), s));
-        SH_HIP(hipMemcpyAsync(&hl->n_entries, hl->d_off + n_units, 8, hipMemcpyDeviceToHost, s));
-        SH_HIP(hipStreamSynchronize(s));
-        hipFree(tmp);
-        SH_HIP(hipMalloc(&hl->d_ent, std::max<uint64_t>(hl->n_entries, 1) * sizeof(sh_k2_hit)));
+        hl.h->n_units = n_units;
+        SH_HIP(hipMalloc(&hl.h->d_off, (n_units + 1) * 8));
+        {
+            size_t tmp_bytes = 0; DevBuf tmp;
+            SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, a.n_hits, hl.h->d_off, (uint64_t)0, n_units + 1, rocprim::plus<uint64_t>(), s));
+            SH_HIP(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+            SH_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, a.n_hits, hl.h->d_off, (uint64_t)0, n_units + 1, rocprim::plus<uint64_t>(), s));
+            SH_HIP(hipMemcpyAsync(&hl.h->n_entries, hl.h->d_off + n_units, 8, hipMemcpyDeviceToHost, s));
+            SH_HIP(hipStreamSynchronize(s));
+        }
+        SH_HIP(hipMalloc(&hl.h->d_ent, std::max<uint64_t>(hl.h->n_entries, 1) * sizeof(sh_k2_hit)));
         const uint64_t n_hover = h[K2C_HOVER];
         if (n_hover) {
-            a.unit_list = hit_over; a.n_list = (uint32_t)n_hover; a.hits = (uint2 *)hl->d_ent; a.hit_off = hl->d_off;
-            dispatch_classify<false>(a, n_hover, s, qmask, quick, 2);
+            a.unit_list = a.hit_over; a.n_list = (uint32_t)n_hover; a.hits = (uint2 *)hl.h->d_ent; a.hit_off = hl.h->d_off;
+            dispatch_classify(K2F_HITS2, a, n_hover, s, qmask);
         }
         const uint64_t n_cp = n_units * K2_HIT_INLINE;
-        hipLaunchKernelGGL(k_k2_hits_compact, dim3((uint32_t)std::min<uint64_t>((n_cp + 255) / 256, 65536)), dim3(256), 0, s, hit_inl, n_hits, hl->d_off, n_units,
-                           (uint2 *)hl->d_ent);
+        hipLaunchKernelGGL(k_k2_hits_compact, dim3((uint32_t)std::min<uint64_t>((n_cp + 255) / 256, 65536)), dim3(256), 0, s, b_hit_inl.as<uint2>(), a.n_hits, hl.h->d_off, n_units,
+                           (uint2 *)hl.h->d_ent);
         SH_HIP(hipStreamSynchronize(s));
         SH_HIP(hipGetLastError());
-        hl->n_redone = n_hover;
-        hipFree(hit_inl); hipFree(n_hits); hipFree(hit_over);
+        hl.h->n_redone = n_hover;
     }
+    if (host_out) SH_HIP(hipMemcpy(host_out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost));
     float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
+    hipEventElapsedTime(&ms, e0.e, e1.e);
     if (stats) {
         stats->n_units = n_units; stats->n_overflow = n_over; stats->ms_classify = ms; stats->ms_total = ms;
         for (int i = 0; i < 64; ++i) {
@@ -1553,76 +1517,48 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
             stats->n_masked_bases += h[K2C_MASKED + i];
         }
     }
-    hipFree(ctr); hipFree(over); hipFree(big_tax); hipFree(big_cnt);
-    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (hits_out) *hits_out = hl.release();
     return SH_OK;
 }
 
-extern "C" sh_status sh_k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
-                                          uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats)
+extern "C" sh_status sh_k2_classify_ex_device(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *b, sh_k2_result *d_out, void *stream,
+                                              sh_k2_stats *stats, sh_k2_hits **hits, sh_k2_mindata *md)
 {
-    return sh_k2_classify_batch_q(db, opts, bases, nullptr, offsets, n_records, paired, out, stats);
+    if (hits) *hits = nullptr;
+    SH_CHECK(b, SH_ERR_BAD_ARG, "sh_k2_classify_ex_device: null argument");
+    return k2_classify(db, opts, b->bases, b->quals, b->offsets, b->n_records, b->paired, d_out, nullptr, stream, stats, hits, md);
 }
 
-static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits,
-                                   sh_k2_mindata *md = nullptr);
-
-extern "C" sh_status sh_k2_classify_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                            const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats)
+// the same from host memory: the batch is staged in HBM and the results copied back
+extern "C" sh_status sh_k2_classify_ex_batch(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *b, sh_k2_result *out, sh_k2_stats *stats,
+                                             sh_k2_hits **hits, sh_k2_mindata *md)
 {
-    return k2_classify_batch(db, opts, bases, quals, offsets, n_records, paired, out, stats, nullptr);
-}
-
-extern "C" sh_status sh_k2_classify_hits_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint64_t *offsets,
-                                               uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits)
-{
-    return sh_k2_classify_hits_batch_q(db, opts, bases, nullptr, offsets, n_records, paired, out, stats, hits);
-}
-
-extern "C" sh_status sh_k2_classify_hits_batch_q(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                                 const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats,
-                                                 sh_k2_hits **hits)
-{
-    SH_CHECK(hits, SH_ERR_BAD_ARG, "sh_k2_classify_hits_batch: null argument");
-    *hits = nullptr;
-    SH_CHECK(!(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: use sh_k2_classify_batch_q");
-    sh_status st = k2_classify_batch(db, opts, bases, quals, offsets, n_records, paired, out, stats, hits);
-    if (st != SH_OK) { sh_k2_hits_free(*hits); *hits = nullptr; }
-    return st;
-}
-
-static sh_status k2_classify_batch(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *bases, const uint8_t *quals,
-                                   const uint64_t *offsets, uint64_t n_records, int32_t paired, sh_k2_result *out, sh_k2_stats *stats, sh_k2_hits **hits,
-                                   sh_k2_mindata *md)
-{
-    SH_CHECK(db && offsets && out, SH_ERR_BAD_ARG, "sh_k2_classify_batch: null argument");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (hits && n_records == 0) { *hits = new sh_k2_hits; (*hits)->device = db->device; }
-    if (n_records == 0) return SH_OK;
+    if (hits) *hits = nullptr;
+    SH_CHECK(db && b && b->offsets && out, SH_ERR_BAD_ARG, "sh_k2_classify_ex_batch: null argument");
+    const uint8_t *bases = b->bases, *quals = b->quals; const uint64_t *offsets = b->offsets, n_records = b->n_records;
+    // an empty batch stages nothing: k2_classify touches none of its pointers, but makes its checks and the empty hit list
+    if (n_records == 0) return k2_classify(db, opts, nullptr, nullptr, offsets, 0, b->paired, out, nullptr, nullptr, stats, hits, md);
     SH_HIP(hipSetDevice(db->device));
     const uint64_t o0 = offsets[0], n_bases = offsets[n_records] - o0;
-    const uint64_t n_units = paired ? n_records / 2 : n_records;
+    const uint64_t n_units = b->paired ? n_records / 2 : n_records;
     // qualities are staged only when they can mask something; both arrays come from hipMalloc, so they share the address mod 8
     const bool want_q = quals && (opts ? *opts : db->opts).min_base_quality > 0;
-    uint8_t *d_bases = nullptr, *d_quals = nullptr; uint64_t *d_off = nullptr; sh_k2_result *d_out = nullptr;
+    DevBuf d_bases, d_quals, d_off, d_out;
     if (want_q) {
-        SH_HIP(hipMalloc(&d_quals, n_bases + 64));
-        SH_HIP(hipMemcpy(d_quals, quals + o0, n_bases, hipMemcpyHostToDevice));
-        SH_HIP(hipMemset(d_quals + n_bases, 0xff, 64));
+        SH_HIP(d_quals.alloc(n_bases + 64));
+        SH_HIP(hipMemcpy(d_quals.p, quals + o0, n_bases, hipMemcpyHostToDevice));
+        SH_HIP(hipMemset(d_quals.as<uint8_t>() + n_bases, 0xff, 64));
     }
-    SH_HIP(hipMalloc(&d_bases, n_bases + 64));
-    SH_HIP(hipMalloc(&d_off, (n_records + 1) * 8));
-    SH_HIP(hipMalloc(&d_out, std::max<uint64_t>(n_units, 1) * sizeof(sh_k2_result)));
+    SH_HIP(d_bases.alloc(n_bases + 64));
+    SH_HIP(d_off.alloc((n_records + 1) * 8));
+    SH_HIP(d_out.alloc(std::max<uint64_t>(n_units, 1) * sizeof(sh_k2_result)));
     std::vector<uint64_t> rel(n_records + 1);
     for (uint64_t i = 0; i <= n_records; ++i) rel[i] = offsets[i] - o0;
-    SH_HIP(hipMemcpy(d_bases, bases + o0, n_bases, hipMemcpyHostToDevice));
-    SH_HIP(hipMemset(d_bases + n_bases, 'N', 64));
-    SH_HIP(hipMemcpy(d_off, rel.data(), (n_records + 1) * 8, hipMemcpyHostToDevice));
-    sh_status st = k2_classify(db, opts, d_bases, d_quals, d_off, n_records, paired, d_out, nullptr, stats, hits, md);
-    if (st == SH_OK && hipMemcpy(out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost) != hipSuccess) { sh_set_error("copy of the results failed"); st = SH_ERR_HIP; }
-    hipFree(d_bases); hipFree(d_quals); hipFree(d_off); hipFree(d_out);
-    return st;
+    SH_HIP(hipMemcpy(d_bases.p, bases + o0, n_bases, hipMemcpyHostToDevice));
+    SH_HIP(hipMemset(d_bases.as<uint8_t>() + n_bases, 'N', 64));
+    SH_HIP(hipMemcpy(d_off.p, rel.data(), (n_records + 1) * 8, hipMemcpyHostToDevice));
+    return k2_classify(db, opts, d_bases.as<uint8_t>(), d_quals.as<uint8_t>(), d_off.as<uint64_t>(), n_records, b->paired, d_out.as<sh_k2_result>(), out, nullptr,
+                       stats, hits, md);
 }
 
 // ---- Kraken-style report (SURVEY.md App. B "Outputs consumed by Scrubby"; parsed by classifier.rs:449-466) -------------
@@ -1644,30 +1580,6 @@ extern "C" sh_status sh_k2_write_report(const sh_k2_db *db, const sh_k2_result *
     const bool ok = fclose(f) == 0;
     SH_CHECK(ok, SH_ERR_IO, "short write to %s", path);
     return SH_OK;
-}
-
-// ---- the general classify entry: one batch struct, optional hit lists, optional minimizer data ---------------------------
-extern "C" sh_status sh_k2_classify_ex_device(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *b, sh_k2_result *d_out, void *stream,
-                                              sh_k2_stats *stats, sh_k2_hits **hits, sh_k2_mindata *md)
-{
-    SH_CHECK(b, SH_ERR_BAD_ARG, "sh_k2_classify_ex_device: null argument");
-    if (hits) *hits = nullptr;
-    SH_CHECK(!hits || !(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: call without one");
-    sh_status st = k2_classify(db, opts, b->bases, b->quals, b->offsets, b->n_records, b->paired, d_out, stream, stats, hits, md);
-    if (st != SH_OK && hits) { sh_k2_hits_free(*hits); *hits = nullptr; }
-    return st;
-}
-
-extern "C" sh_status sh_k2_classify_ex_batch(const sh_k2_db *db, const sh_k2_opts *opts, const sh_k2_batch *b, sh_k2_result *out, sh_k2_stats *stats,
-                                             sh_k2_hits **hits, sh_k2_mindata *md)
-{
-    SH_CHECK(b, SH_ERR_BAD_ARG, "sh_k2_classify_ex_batch: null argument");
-    if (hits) *hits = nullptr;
-    SH_CHECK(!hits || !(opts ? opts->quick : db ? db->opts.quick : 0), SH_ERR_BAD_ARG, "--quick writes no hit list: call without one");
-    SH_CHECK(!md || (db && md->device == db->device && md->n_nodes == db->nodes.size()), SH_ERR_BAD_ARG, "the minimizer data belongs to another database");
-    sh_status st = k2_classify_batch(db, opts, b->bases, b->quals, b->offsets, b->n_records, b->paired, out, stats, hits, md);
-    if (st != SH_OK && hits) { sh_k2_hits_free(*hits); *hits = nullptr; }
-    return st;
 }
 
 // ---- minimizer data: host side ------------------------------------------------------------------------------------------

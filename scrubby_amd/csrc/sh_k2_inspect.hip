@@ -162,29 +162,22 @@ extern "C" sh_status sh_k2_value_counts_device(const sh_k2_db *db, uint64_t *d_c
         SH_HIP(hipGetLastError());
         return SH_OK;
     }
-    unsigned long long *d_ctr = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto body = [&]() -> sh_status {
-        SH_HIP(hipMalloc(&d_ctr, 16));
-        SH_HIP(hipEventCreate(&e0)); SH_HIP(hipEventCreate(&e1));
-        SH_HIP(hipMemsetAsync(d_ctr, 0, 16, s));
-        a.ctr = d_ctr;
-        SH_HIP(hipEventRecord(e0, s));
-        hipLaunchKernelGGL(k_k2_value_counts, dim3(grid), dim3(K2I_THREADS), a.lds_bins * 4, s, a);
-        SH_HIP(hipGetLastError());
-        SH_HIP(hipEventRecord(e1, s));
-        unsigned long long ctr[2] = {0, 0};
-        SH_HIP(hipMemcpyAsync(ctr, d_ctr, 16, hipMemcpyDeviceToHost, s));
-        SH_HIP(hipStreamSynchronize(s));
-        stats->n_occupied = ctr[0]; stats->n_bad_values = ctr[1];
-        SH_HIP(hipEventElapsedTime(&stats->ms, e0, e1));
-        return SH_OK;
-    };
-    const sh_status st = body();
-    hipFree(d_ctr);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return st;
+    DevBuf b_ctr;
+    DevEvent e0, e1;
+    SH_HIP(b_ctr.alloc(16));
+    SH_HIP(e0.create()); SH_HIP(e1.create());
+    SH_HIP(hipMemsetAsync(b_ctr.p, 0, 16, s));
+    a.ctr = b_ctr.as<unsigned long long>();
+    SH_HIP(hipEventRecord(e0.e, s));
+    hipLaunchKernelGGL(k_k2_value_counts, dim3(grid), dim3(K2I_THREADS), a.lds_bins * 4, s, a);
+    SH_HIP(hipGetLastError());
+    SH_HIP(hipEventRecord(e1.e, s));
+    unsigned long long ctr[2] = {0, 0};
+    SH_HIP(hipMemcpyAsync(ctr, b_ctr.p, 16, hipMemcpyDeviceToHost, s));
+    SH_HIP(hipStreamSynchronize(s));
+    stats->n_occupied = ctr[0]; stats->n_bad_values = ctr[1];
+    SH_HIP(hipEventElapsedTime(&stats->ms, e0.e, e1.e));
+    return SH_OK;
 }
 
 extern "C" sh_status sh_k2_value_counts(const sh_k2_db *db, uint64_t *counts, sh_k2_inspect_stats *stats)
@@ -192,12 +185,11 @@ extern "C" sh_status sh_k2_value_counts(const sh_k2_db *db, uint64_t *counts, sh
     SH_CHECK(db && counts, SH_ERR_BAD_ARG, "sh_k2_value_counts: null argument");
     SH_HIP(hipSetDevice(db->device));
     const uint64_t n_nodes = db->nodes.size();
-    uint64_t *d_counts = nullptr;
-    SH_HIP(hipMalloc(&d_counts, std::max<uint64_t>(n_nodes, 1) * 8));
+    DevBuf b_counts;
+    SH_HIP(b_counts.alloc(std::max<uint64_t>(n_nodes, 1) * 8));
     sh_k2_inspect_stats local;
-    sh_status st = sh_k2_value_counts_device(db, d_counts, nullptr, stats ? stats : &local);
-    if (st == SH_OK && hipMemcpy(counts, d_counts, n_nodes * 8, hipMemcpyDeviceToHost) != hipSuccess) { sh_set_error("copy of the counts failed"); st = SH_ERR_HIP; }
-    hipFree(d_counts);
+    sh_status st = sh_k2_value_counts_device(db, b_counts.as<uint64_t>(), nullptr, stats ? stats : &local);
+    if (st == SH_OK && hipMemcpy(counts, b_counts.p, n_nodes * 8, hipMemcpyDeviceToHost) != hipSuccess) { sh_set_error("copy of the counts failed"); st = SH_ERR_HIP; }
     return st;
 }
 

@@ -201,39 +201,33 @@ sh_status shi_k2_mask_device(uint8_t *d_bases, const uint64_t *d_offsets, uint64
     const uint64_t n = ends[1] - ends[0];
     SH_CHECK(quiet_head <= n && quiet_tail <= n, SH_ERR_BAD_ARG, "sh_k2_mask_device: margins longer than the batch");
     if (n == 0) return SH_OK;
-    uint64_t *d_tile = nullptr; void *d_tmp = nullptr; uint8_t *d_reach = nullptr; unsigned long long *d_ctr = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto body = [&]() -> sh_status {
-        SH_HIP(hipMalloc(&d_tile, (n_records + 1) * 8));
-        SH_HIP(hipMalloc(&d_reach, n + 64 + 8));
-        SH_HIP(hipMalloc(&d_ctr, 8));
-        SH_HIP(hipEventCreate(&e0)); SH_HIP(hipEventCreate(&e1));
-        SH_HIP(hipMemsetAsync(d_ctr, 0, 8, s));
-        SH_HIP(hipMemsetAsync(d_reach + n, 0, 64 + 8, s));
-        SH_HIP(hipEventRecord(e0, s));
-        K2MaskArgs a{d_bases, d_offsets, n_records, d_tile, d_reach, k2_mask_tile(), window, threshold};
-        hipLaunchKernelGGL(k_k2_mask_tilecount, dim3((uint32_t)std::min<uint64_t>((n_records + 256) / 256, 4096)), dim3(256), 0, s, a);
-        size_t tmp_bytes = 0;
-        SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_tile, d_tile, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
-        SH_HIP(hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 1)));
-        SH_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_tile, d_tile, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
-        hipLaunchKernelGGL(k_k2_mask_scan, dim3(K2M_GRID), dim3(64), 0, s, a);
-        K2MaskApply ap{d_bases + ends[0], d_reach, n, window, replacement, quiet_head, quiet_tail, d_ctr};
-        hipLaunchKernelGGL(k_k2_mask_apply, dim3((uint32_t)std::min<uint64_t>(((n + 7) / 8 + 255) / 256, 1u << 16)), dim3(256), 0, s, ap);
-        SH_HIP(hipEventRecord(e1, s));
-        unsigned long long masked = 0, items = 0;
-        SH_HIP(hipMemcpyAsync(&masked, d_ctr, 8, hipMemcpyDeviceToHost, s));
-        SH_HIP(hipMemcpyAsync(&items, d_tile + n_records, 8, hipMemcpyDeviceToHost, s));
-        SH_HIP(hipStreamSynchronize(s));
-        SH_HIP(hipGetLastError());
-        if (stats) { stats->n_bases = n; stats->n_masked = masked; stats->n_items = items; hipEventElapsedTime(&stats->ms, e0, e1); }
-        return SH_OK;
-    };
-    st = body();
-    hipFree(d_tile); hipFree(d_tmp); hipFree(d_reach); hipFree(d_ctr);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return st;
+    DevBuf b_tile, b_tmp, b_reach, b_ctr;
+    DevEvent e0, e1;
+    SH_HIP(b_tile.alloc((n_records + 1) * 8));
+    SH_HIP(b_reach.alloc(n + 64 + 8));
+    SH_HIP(b_ctr.alloc(8));
+    SH_HIP(e0.create()); SH_HIP(e1.create());
+    uint64_t *d_tile = b_tile.as<uint64_t>(); uint8_t *d_reach = b_reach.as<uint8_t>(); unsigned long long *d_ctr = b_ctr.as<unsigned long long>();
+    SH_HIP(hipMemsetAsync(d_ctr, 0, 8, s));
+    SH_HIP(hipMemsetAsync(d_reach + n, 0, 64 + 8, s));
+    SH_HIP(hipEventRecord(e0.e, s));
+    K2MaskArgs a{d_bases, d_offsets, n_records, d_tile, d_reach, k2_mask_tile(), window, threshold};
+    hipLaunchKernelGGL(k_k2_mask_tilecount, dim3((uint32_t)std::min<uint64_t>((n_records + 256) / 256, 4096)), dim3(256), 0, s, a);
+    size_t tmp_bytes = 0;
+    SH_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_tile, d_tile, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
+    SH_HIP(b_tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+    SH_HIP(rocprim::exclusive_scan(b_tmp.p, tmp_bytes, d_tile, d_tile, (uint64_t)0, n_records + 1, rocprim::plus<uint64_t>(), s));
+    hipLaunchKernelGGL(k_k2_mask_scan, dim3(K2M_GRID), dim3(64), 0, s, a);
+    K2MaskApply ap{d_bases + ends[0], d_reach, n, window, replacement, quiet_head, quiet_tail, d_ctr};
+    hipLaunchKernelGGL(k_k2_mask_apply, dim3((uint32_t)std::min<uint64_t>(((n + 7) / 8 + 255) / 256, 1u << 16)), dim3(256), 0, s, ap);
+    SH_HIP(hipEventRecord(e1.e, s));
+    unsigned long long masked = 0, items = 0;
+    SH_HIP(hipMemcpyAsync(&masked, d_ctr, 8, hipMemcpyDeviceToHost, s));
+    SH_HIP(hipMemcpyAsync(&items, d_tile + n_records, 8, hipMemcpyDeviceToHost, s));
+    SH_HIP(hipStreamSynchronize(s));
+    SH_HIP(hipGetLastError());
+    if (stats) { stats->n_bases = n; stats->n_masked = masked; stats->n_items = items; hipEventElapsedTime(&stats->ms, e0.e, e1.e); }
+    return SH_OK;
 }
 
 extern "C" sh_status sh_k2_mask_device(uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_records, int32_t window, int32_t threshold, int32_t replacement,

@@ -1294,7 +1294,7 @@ extern "C" sh_status sh_reads_run(const sh_reads_config *c, sh_reads_result *res
 // ---- `scrubby reads -c kraken2`: Cleaner::run_kraken (cleaner.rs:288-330) with the chunked reader, the GPU classifier, and the
 // parallel filter of pass 2.  The reference runs the external kraken2, which writes kraken.reads / kraken.report, then reads both
 // files back (parse_classifier_output, :375-382) and filters (clean_reads).  Here: both inputs are parsed in place side by side
-// (chunks retained), mates are interleaved into one batch (records 2i, 2i + 1), sh_k2_classify_batch classifies it, the two text
+// (chunks retained), mates are interleaved into one batch (records 2i, 2i + 1), sh_k2_classify_ex_batch classifies it, the two text
 // files still land in the workdir (formatted by a pool, written at their offsets), the taxid set comes from the report exactly
 // as the reference derives it (shi_taxids_from_report), and a read is selected iff the taxid printed on its line is in that set -
 // decided from the results in memory instead of re-reading the 10^7 lines just written (get_taxid_reads_kraken compares the

@@ -121,6 +121,10 @@ def format_hits(entries, external, quick=False, quick_taxid=0):
     return buf.value.decode()
 
 
+def _stats_dict(st):
+    return {n: getattr(st, n) for n, _ in K2Stats._fields_}
+
+
 def _take_hits(h):
     """offsets (n_units + 1) and entries of a sh_k2_hits handle copied to the host, and the units its overflow pass redid;
     the handle is freed"""
@@ -526,11 +530,22 @@ class K2Db:
         S.check(S.load().sh_k2_export(self.h, C.c_void_p(cells.ctypes.data), C.c_void_p(parent.ctypes.data), C.c_void_p(ext.ctypes.data)))
         return cells, parent, ext
 
+    def _classify(self, device, opts, batch, out_ptr, want_hits, minimizer_data):
+        """the one call behind classify (device=False: sh_k2_classify_ex_batch) and classify_device / classify_device_hits
+        (sh_k2_classify_ex_device on torch's current stream): (stats, the hits handle or None)"""
+        L = S.load()
+        st, h = K2Stats(), C.c_void_p()
+        head = (self.h, C.byref(opts) if opts is not None else None, C.byref(batch), C.c_void_p(out_ptr))
+        tail = (C.byref(st), C.byref(h) if want_hits else None, minimizer_data.h if minimizer_data is not None else None)
+        S.check(L.sh_k2_classify_ex_device(*head, S._stream_ptr(), *tail) if device else L.sh_k2_classify_ex_batch(*head, *tail))
+        return _stats_dict(st), h if want_hits else None
+
     def classify(self, bases, offsets, paired=False, opts=None, quals=None, hits=False, minimizer_data=None):
-        """quals (optional): Phred+33 bytes at the offsets of `bases` (0xFF = never masked), used when opts.min_base_quality > 0.
-        hits=True: also Kraken 2's hit lists (sh_k2_classify_hits_batch_q), returned third as (offsets, entries): unit i's
-        entries (HIT_DTYPE) are entries[offsets[i]:offsets[i + 1]].
-        minimizer_data: a MinimizerData the call adds to (sh_k2_classify_ex_batch); the return values are the same."""
+        """sh_k2_classify_ex_batch.
+        quals (optional): Phred+33 bytes at the offsets of `bases` (0xFF = never masked), used when opts.min_base_quality > 0.
+        hits=True: also Kraken 2's hit lists, returned third as (offsets, entries): unit i's entries (HIT_DTYPE) are
+        entries[offsets[i]:offsets[i + 1]].
+        minimizer_data: a MinimizerData the call adds to; the return values are the same."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         if quals is not None:
@@ -539,24 +554,12 @@ class K2Db:
         n_rec = len(offsets) - 1
         n_units = n_rec // 2 if paired else n_rec
         out = np.zeros(max(n_units, 1), dtype=RESULT_DTYPE)
-        st = K2Stats()
-        args = (self.h, C.byref(opts) if opts is not None else None, C.c_void_p(bases.ctypes.data),
-                C.c_void_p(quals.ctypes.data) if quals is not None else None, C.c_void_p(offsets.ctypes.data), C.c_uint64(n_rec),
-                1 if paired else 0, C.c_void_p(out.ctypes.data), C.byref(st))
-        if minimizer_data is not None:
-            b = K2Batch(bases.ctypes.data, quals.ctypes.data if quals is not None else None, offsets.ctypes.data, n_rec, 1 if paired else 0)
-            h = C.c_void_p()
-            S.check(S.load().sh_k2_classify_ex_batch(self.h, args[1], C.byref(b), args[7], args[8], C.byref(h) if hits else None, minimizer_data.h))
-            if not hits:
-                return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
-        elif not hits:
-            S.check(S.load().sh_k2_classify_batch_q(*args))
-            return out[:n_units], {n: getattr(st, n) for n, _ in K2Stats._fields_}
-        else:
-            h = C.c_void_p()
-            S.check(S.load().sh_k2_classify_hits_batch_q(*args, C.byref(h)))
-        offs, ent, redone = _take_hits(h)
-        return out[:n_units], dict({n: getattr(st, n) for n, _ in K2Stats._fields_}, n_hits_redone=redone), (offs, ent)
+        b = K2Batch(bases.ctypes.data, quals.ctypes.data if quals is not None else None, offsets.ctypes.data, n_rec, 1 if paired else 0)
+        stats, h = self._classify(False, opts, b, out.ctypes.data, hits, minimizer_data)
+        if not hits:
+            return out[:n_units], stats
+        offs, ent, stats["n_hits_redone"] = _take_hits(h)
+        return out[:n_units], stats, (offs, ent)
 
     def classify_hit_strings(self, bases, offsets, paired=False, opts=None, quals=None):
         """results, stats and column 5 of kraken.reads for every unit (strings, external taxids)"""
@@ -570,21 +573,11 @@ class K2Db:
         return ext
 
     def classify_device_hits(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None, to_host=True, minimizer_data=None):
-        """sh_k2_classify_hits_device_q: results into d_out; returns (stats, (offsets, entries)) copied to the host, or with
-        to_host=False (stats, (d_offsets_ptr, d_entries_ptr, n_units, n_entries, handle)) - free the handle with free_hits.
-        minimizer_data: a MinimizerData the call adds to (sh_k2_classify_ex_device)."""
-        st = K2Stats()
-        h = C.c_void_p()
-        if minimizer_data is not None:
-            b = K2Batch(d_bases.data_ptr(), d_quals.data_ptr() if d_quals is not None else None, d_offsets.data_ptr(), n_records, 1 if paired else 0)
-            S.check(S.load().sh_k2_classify_ex_device(self.h, C.byref(opts) if opts is not None else None, C.byref(b), C.c_void_p(d_out.data_ptr()),
-                                                      S._stream_ptr(), C.byref(st), C.byref(h), minimizer_data.h))
-        else:
-            S.check(S.load().sh_k2_classify_hits_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
-                                                          C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
-                                                          C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
-                                                          C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st), C.byref(h)))
-        stats = {n: getattr(st, n) for n, _ in K2Stats._fields_}
+        """sh_k2_classify_ex_device with hit lists: results into d_out; returns (stats, (offsets, entries)) copied to the host, or
+        with to_host=False (stats, (d_offsets_ptr, d_entries_ptr, n_units, n_entries, handle)) - free the handle with free_hits.
+        minimizer_data: a MinimizerData the call adds to."""
+        b = K2Batch(d_bases.data_ptr(), d_quals.data_ptr() if d_quals is not None else None, d_offsets.data_ptr(), n_records, 1 if paired else 0)
+        stats, h = self._classify(True, opts, b, d_out.data_ptr(), True, minimizer_data)
         if to_host:
             offs, ent, stats["n_hits_redone"] = _take_hits(h)
             return stats, (offs, ent)
@@ -604,17 +597,9 @@ class K2Db:
         return r.value
 
     def classify_device(self, d_bases, d_offsets, n_records, paired, d_out, opts=None, d_quals=None, minimizer_data=None):
-        st = K2Stats()
-        if minimizer_data is not None:
-            b = K2Batch(d_bases.data_ptr(), d_quals.data_ptr() if d_quals is not None else None, d_offsets.data_ptr(), n_records, 1 if paired else 0)
-            S.check(S.load().sh_k2_classify_ex_device(self.h, C.byref(opts) if opts is not None else None, C.byref(b), C.c_void_p(d_out.data_ptr()),
-                                                      S._stream_ptr(), C.byref(st), None, minimizer_data.h))
-            return {n: getattr(st, n) for n, _ in K2Stats._fields_}
-        S.check(S.load().sh_k2_classify_device_q(self.h, C.byref(opts) if opts is not None else None, C.c_void_p(d_bases.data_ptr()),
-                                                 C.c_void_p(d_quals.data_ptr()) if d_quals is not None else None,
-                                                 C.c_void_p(d_offsets.data_ptr()), C.c_uint64(n_records), 1 if paired else 0,
-                                                 C.c_void_p(d_out.data_ptr()), S._stream_ptr(), C.byref(st)))
-        return {n: getattr(st, n) for n, _ in K2Stats._fields_}
+        """sh_k2_classify_ex_device without hit lists: results into d_out; returns the stats"""
+        b = K2Batch(d_bases.data_ptr(), d_quals.data_ptr() if d_quals is not None else None, d_offsets.data_ptr(), n_records, 1 if paired else 0)
+        return self._classify(True, opts, b, d_out.data_ptr(), False, minimizer_data)[0]
 
     def value_counts(self, return_stats=False):
         """minimizers of the table per internal taxon (sh_k2_value_counts): uint64[n_nodes]; with return_stats=True also the

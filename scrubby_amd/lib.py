@@ -133,8 +133,7 @@ EXPORTS = [
     "sh_classifier_run", "sh_classifier_taxids", "sh_alignment_run",
     "sh_k2_default_opts", "sh_k2_open", "sh_k2_create", "sh_k2_insert_device", "sh_k2_insert_sequence_device",
     "sh_k2_insert_random", "sh_k2_save", "sh_k2_info_get", "sh_k2_db_opts", "sh_k2_export", "sh_k2_free",
-    "sh_k2_classify_device", "sh_k2_classify_batch", "sh_k2_classify_device_q", "sh_k2_classify_batch_q", "sh_k2_write_report", "sh_kraken_run",
-    "sh_k2_classify_hits_device", "sh_k2_classify_hits_device_q", "sh_k2_classify_hits_batch", "sh_k2_classify_hits_batch_q",
+    "sh_k2_write_report", "sh_kraken_run",
     "sh_k2_hits_count", "sh_k2_hits_device", "sh_k2_hits_copy", "sh_k2_hits_free", "sh_k2_format_hits",
     "sh_k2_mindata_create", "sh_k2_mindata_reset", "sh_k2_mindata_free", "sh_k2_classify_ex_device", "sh_k2_classify_ex_batch",
     "sh_k2_mindata_counts", "sh_k2_mindata_registers", "sh_k2_hll_estimate", "sh_k2_mindata_merge_host",

@@ -1,4 +1,4 @@
-"""Kraken 2's per-k-mer hit list on the GPU (k_k2_classify's HITS instances, sh_k2_classify_hits_*, column 5 of kraken.reads)
+"""Kraken 2's per-k-mer hit list on the GPU (k_k2_classify's HITS instances, sh_k2_classify_ex_* with hits, column 5 of kraken.reads)
 against the per-k-mer taxa of oracle/k2_oracle.c, run-length encoded as tests/test_k2_hitlist_cpu.py restates it.  The
 table is built on the GPU and exported, so both sides probe the same cells."""
 import os

@@ -250,6 +250,50 @@ def test_minimum_base_quality(K, oracle, db, table, md, cfg1):
     check_md(md, R.Expected(t.parent).add(ev))
 
 
+def test_rejected_calls_count_nothing_and_leave_the_handles_usable(K, oracle, db, table, md, cfg1):
+    """The checks the host and the device entry share, through each: --quick with hit lists, the minimizer data of another
+    database (another node count), paired with an odd record count.  Each is SH_ERR_BAD_ARG and counts nothing; the same
+    database and accumulator then classify the batch as the oracle does."""
+    import torch
+    from scrubby_amd.lib import ScrubbyHipError
+    from tests.test_k2_options_gpu import same
+    P, Rp, ref, seqs, reads, off = cfg1
+    t, ext = table
+    n = 10
+    bases, offs = reads[: n * 150], off[: n + 1]
+    d_b = torch.from_numpy(np.concatenate([bases, np.full(64, ord("N"), np.uint8)])).cuda()
+    d_off = torch.from_numpy(offs.astype(np.int64)).cuda()
+    d_out = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
+    quick = db.opts(); quick.quick = 1
+    small = K.K2Db.create(K.default_opts(), 1009, [0, 0, 1], [0, 1, 2], ["", "root", "other"], ["", "no rank", "species"])
+    other = K.MinimizerData(small)
+    want = t.classify(oracle.k2_default_opts(), bases, offs, paired=False)
+    exp = R.Expected(t.parent).add(R.Model(oracle, t, oracle.k2_default_opts()).events(bases, offs, False))
+    rejected = {
+        "quick with hits": (lambda: db.classify(bases, offs, opts=quick, hits=True, minimizer_data=md),
+                            lambda: db.classify_device_hits(d_b, d_off, n, False, d_out, opts=quick, minimizer_data=md)),
+        "minimizer data of another database": (lambda: db.classify(bases, offs, minimizer_data=other),
+                                               lambda: db.classify_device(d_b, d_off, n, False, d_out, minimizer_data=other)),
+        "paired, odd record count": (lambda: db.classify(bases[: 9 * 150], offs[:10], paired=True, minimizer_data=md),
+                                     lambda: db.classify_device(d_b, d_off, 9, True, d_out, minimizer_data=md)),
+    }
+    try:
+        md.reset()
+        for name, calls in rejected.items():
+            for call in calls:
+                with pytest.raises(ScrubbyHipError) as ei:
+                    call()
+                assert ei.value.status == 1, name                      # SH_ERR_BAD_ARG
+                assert not md.counts()["n_minimizers"].any() and not other.counts()["n_minimizers"].any(), name
+            got, st, lists = db.classify(bases, offs, hits=True, minimizer_data=md)
+            same(got, want, ext)
+            assert len(lists[0]) == n + 1 and int(lists[0][-1]) == len(lists[1]) > 0
+            check_md(md, exp)
+            md.reset()
+    finally:
+        other.close(); small.close()
+
+
 def test_down_sampled_database(K, oracle, cfg1, tax):
     P, Rp, ref, seqs, reads, off = cfg1
     parents, externals, names, ranks, ids = tax

@@ -1,4 +1,4 @@
-"""kraken2's --minimum-base-quality and --quick on the GPU (k_k2_classify's QMASK / QUICK instances, sh_k2_classify_*_q,
+"""kraken2's --minimum-base-quality and --quick on the GPU (k_k2_classify's QMASK / QUICK instances, sh_k2_classify_ex_*,
 sh_kraken_run, the CLI's -C), against oracle/k2_oracle.c on host-masked bases and against the restated classify loop of
 tests/test_k2_options_cpu.py.  The table is built on the GPU and exported, so both sides probe the same cells.
 """
