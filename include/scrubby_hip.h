@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
+#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair; + the Kraken arm's wave route: sh_k2_opts grew long_unit_bases, sh_k2_stats n_long_units / ms_long, the old layouts are prefixes, the version kept): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
 
 typedef int32_t sh_status;
 enum {
@@ -343,6 +343,10 @@ typedef struct sh_k2_opts {
                                        needs the qualities of the _q entries */
     int32_t  quick;                 /* --quick, default 0: the call is the first hit once min_hit_groups are seen, no ResolveTree
                                        (unclassified when no k-mer gets there); total_kmers counts the k-mers before that hit */
+    int32_t  long_unit_bases;       /* a unit whose longer fragment has at least this many bases is classified by one wave
+                                       (k_k2_classify_wave) instead of one lane; 0 = the default (DESIGN.md §7 "Long reads"),
+                                       negative = never.  The answers do not depend on it; --quick units never take that route */
+    int32_t  pad_;
 } sh_k2_opts;
 
 typedef struct sh_k2_taxnode {      /* taxo.k2d node: 7 x u64 */
@@ -365,9 +369,14 @@ typedef struct sh_k2_stats {
     uint64_t n_units, n_classified, n_probes, n_kmers, n_overflow;
     float    ms_classify, ms_total;
     uint64_t n_masked_bases;        /* bases of the batch masked by min_base_quality */
+    uint64_t n_long_units;          /* units classified one wave per unit (opts.long_unit_bases) */
+    float    ms_long;               /* that kernel's share of ms_classify */
+    int32_t  pad_;
 } sh_k2_stats;
 
 sh_status sh_k2_default_opts(sh_k2_opts *out);
+/* k-mers per tile of the wave route (a fragment with more of them is scanned in several tiles) */
+uint32_t sh_k2_wave_tile(void);
 /* open a Kraken2 database directory (hash.k2d, opts.k2d, taxo.k2d) into HBM */
 sh_status sh_k2_open(const char *dbdir, int device, sh_k2_db **out);
 /* an empty table of `capacity` cells over a caller-supplied taxonomy (synthetic databases, tests).  Node 0 is the

@@ -28,9 +28,13 @@
 // lookup that adds a hit group also counts for its taxon in a sh_k2_mindata accumulator (a counter and 4096 HyperLogLog
 // registers per taxon).  The BIG and HITS 2 passes redo units pass 1 already counted, so they have no MIND form.
 // The bound is the HBM gather rate: one 32-B sector per probe, ~40 probes per 150-bp read.
+//
+// k_k2_classify_wave: one wave per unit, for the units of at least opts.long_unit_bases bases (long reads): the 64 lanes scan 64
+// consecutive segments of the read side by side.  Same answers, hit lists, minimizer data and counters; its own comment says why.
 #include "sh_common.h"
 #include "sh_k2_db.h"
 #include "sh_k2_inspect.h"
+#include "sh_wave.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <cmath>
@@ -356,12 +360,14 @@ struct K2MdState {
 };
 struct K2NoMd {};
 
-template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false>
+// SUB: pass 1 over the units of a.unit_list only (the others went the wave route: k_k2_classify_wave)
+template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false, bool SUB = false>
 __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> a)
 {
+    static_assert(!SUB || !(BIG || QUICK || HITS == 2), "a subset is a pass-1 matter, and --quick units all stay here");
     static_assert(HITS == 0 || !(BIG || QUICK), "the hit list is complete after pass 1 and has no --quick form");
     static_assert(!MIND || !(BIG || HITS == 2), "the redo passes repeat units pass 1 counted: they must not count them again");
-    constexpr bool LIST = BIG || HITS == 2;                // the work is a list of units to redo
+    constexpr bool LIST = BIG || HITS == 2 || SUB;         // the work is a list of units
     __shared__ uint64_t s_qmin[(K2_QCAP + 1) * 64];       // slot n_pend is written unconditionally, so one spare
     __shared__ uint32_t s_qlen[(K2_QCAP + 1) * 64];
     __shared__ uint32_t s_qpos[QUICK ? (K2_QCAP + 1) * 64 : 1];      // QUICK: k-mers of the unit before the run's first one
@@ -633,6 +639,327 @@ __global__ void k_k2_count_masked(const uint8_t *quals, const uint64_t *offsets,
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&ctr[K2C_MASKED + (blockIdx.x & 63)], n);
 }
 
+// ---- the wave route: one wave classifies one unit (DESIGN.md §7 "Long reads") -------------------------------------------
+// A fragment's k-mers are cut into tiles of 64 segments of `seg` k-mers, one segment per lane.  A lane restarts the scanner
+// k - 1 bases before its first k-mer (the state at a k-mer depends on that k-mer's bases only) and sees the events the
+// sequential scan sees; a run is probed where it starts in the lane, and the first run of a lane becomes a hit group, a
+// counted probe and a minimizer-data lookup only once the wave has seen that the last valid minimizer before the segment
+// (lanes back, or in the tile before) differs.  K-mer counts go to one taxon table per wave in LDS (open addressing, LDS
+// atomics); once it holds K2_WT_CAP taxa new ones go to the block's table in HBM, and a unit that spilled resolves from
+// that table after the LDS entries have joined it.  ResolveTree runs across the lanes (the scores in parallel, the tie rule
+// an LCA fold over the lanes, each level of the confidence climb one wave sum).  HITS: the tile's per-k-mer codes go to LDS
+// and the wave run-length encodes them 64 at a time; form 1 counts the entries and writes the first K2_HIT_INLINE in place,
+// form 2 writes the listed units' whole lists at hit_off, as the lane kernel's forms do.
+#define K2_WAVE_SEG 63u                     // k-mers per lane and tile at most; odd, so the lanes' code stores hit 64 banks
+#define K2_WAVE_TILE (64u * K2_WAVE_SEG)    // k-mers per tile (exported: sh_k2_wave_tile)
+#define K2_WAVE_WORDS ((K2_WAVE_TILE + 80u) / 8u)      // the tile's bases: its k-mers + k - 1 <= 45 more + 7 of misalignment, in 8-byte words
+#define K2_WT_SLOTS 512u                    // the LDS taxon table
+#define K2_WT_CAP 384u                      // ... takes new taxa up to here (64 lanes may pass it together: 448 < 512)
+#define K2_WS_SLOTS (2u * K2_BIG_CAP)       // the HBM table of a block; it takes new taxa up to K2_BIG_CAP, the BIG pass's limit
+// ctr words of the wave kernels
+#define K2C_WTICKET 2
+#define K2C_WHOVER 3
+#define K2C_WOVER 4
+#define K2C_WTICKET2 5
+static_assert((K2_WAVE_TILE + 80u) % 8u == 0 && (K2_WT_SLOTS & (K2_WT_SLOTS - 1)) == 0 && K2_WS_SLOTS == 8192u, "wave route sizes");
+
+struct K2Wave {
+    uint32_t *spill_tax, *spill_cnt;        // K2_WS_SLOTS each per block, zero between units
+    uint32_t *hit_over;                     // HITS 1: the wave route's units with more than K2_HIT_INLINE entries
+};
+
+// one probe from the hash to the taxon (the lane kernel splits this over its two drain passes)
+__device__ static inline uint32_t k2_probe(const K2Table &T, uint64_t hc)
+{
+    const uint32_t vmask = (1u << T.value_bits) - 1, comp = (uint32_t)(hc >> (32 + T.value_bits));
+    const uint64_t idx = k2_mod(hc, T.capacity, T.inv_capacity), n_full = T.capacity / 8;
+    if ((idx >> 3) >= n_full) return k2_finish_probe(T, idx, T.cells[idx], comp);
+    uint32_t taxon;
+    if (k2_scan_group(k2_load_group(T.cells, idx >> 3), (uint32_t)idx & 7u, vmask, T.value_bits, comp, taxon)) return taxon;
+    return k2_probe_rest(T, idx >> 3, comp);
+}
+
+// the spill table is touched by atomics and agent-scope loads and stores only: nothing of it may sit in the CU's L1
+__device__ static inline uint32_t k2_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ static inline void k2_st(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct K2WaveTable {
+    uint32_t *tax, *cnt, *n;                // LDS: the table, n[0] taxa in it, n[1] taxa in the spill table
+    uint32_t *stax, *scnt;
+    __device__ inline void add_spill(uint32_t t, uint32_t c)
+    {
+        uint32_t h = (t * 0x9E3779B1u) >> 19;
+        for (uint32_t step = 0; step < K2_WS_SLOTS; ++step, h = (h + 1) & (K2_WS_SLOTS - 1)) {
+            uint32_t cur = k2_ld(&stax[h]);
+            if (cur == 0) {
+                if (__hip_atomic_load(&n[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= K2_BIG_CAP) return;      // the BIG pass's silent limit
+                cur = atomicCAS(&stax[h], 0u, t);
+                if (cur == 0) { atomicAdd(&n[1], 1u); cur = t; }
+            }
+            if (cur == t) { atomicAdd(&scnt[h], c); return; }
+        }
+    }
+    __device__ inline void add(uint32_t t, uint32_t c)
+    {
+        uint32_t h = (t * 0x9E3779B1u) >> 23;
+        for (uint32_t step = 0; step < K2_WT_SLOTS; ++step, h = (h + 1) & (K2_WT_SLOTS - 1)) {
+            uint32_t cur = __hip_atomic_load(&tax[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (cur == 0) {
+                if (__hip_atomic_load(&n[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= K2_WT_CAP) break;
+                cur = atomicCAS(&tax[h], 0u, t);
+                if (cur == 0) { atomicAdd(&n[0], 1u); cur = t; }
+            }
+            if (cur == t) { atomicAdd(&cnt[h], c); return; }
+        }
+        add_spill(t, c);       // (a taxon may then sit in both tables: the LDS entries join the spill table before it is read)
+    }
+};
+struct K2LdsEntries {
+    const uint32_t *t, *c;
+    __device__ inline uint32_t tax(uint32_t i) const { return t[i]; }
+    __device__ inline uint32_t cnt(uint32_t i) const { return c[i]; }
+};
+struct K2SpillEntries {
+    const uint32_t *t, *c;
+    __device__ inline uint32_t tax(uint32_t i) const { return k2_ld(t + i); }
+    __device__ inline uint32_t cnt(uint32_t i) const { return k2_ld(c + i); }
+};
+
+// k2_resolve over n dense entries, by the whole wave (every lane returns the call).  Order-free: a score is a sum over the
+// entries, the tie rule leaves the LCA of exactly the taxa with the maximal score, each level of the climb is a sum.
+template <class E>
+__device__ static inline uint32_t k2_resolve_wave(const E &H, uint32_t n, const uint32_t *__restrict__ parent, uint32_t total_kmers, double confidence, uint32_t lane)
+{
+    const uint32_t required = (uint32_t)ceil(confidence * (double)total_kmers);
+    uint32_t best_s = 0, best_t = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+        const uint32_t ti = i0 + lane < n ? H.tax(i0 + lane) : 0u;
+        uint32_t score = 0;
+        for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+            const uint32_t tj = j0 + lane < n ? H.tax(j0 + lane) : 0u, cj = j0 + lane < n ? H.cnt(j0 + lane) : 0u;
+            const uint32_t m = n - j0 < 64u ? n - j0 : 64u;
+            for (uint32_t jj = 0; jj < m; ++jj) {
+                const uint32_t t = (uint32_t)wave_bcast((int32_t)tj, (int)jj), c = (uint32_t)wave_bcast((int32_t)cj, (int)jj);
+                if (k2_is_ancestor(parent, t, ti)) score += c;
+            }
+        }
+        if (ti) {
+            if (score > best_s) { best_s = score; best_t = ti; }
+            else if (score == best_s) best_t = k2_lca(parent, best_t, ti);
+        }
+    }
+    const uint32_t top = wave_all_max_u32(best_s);
+    uint32_t max_taxon = best_s == top ? best_t : 0u;       // 0 is the fold's identity
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) max_taxon = k2_lca(parent, max_taxon, (uint32_t)__shfl_xor((int)max_taxon, o));
+    uint32_t s = 0;
+    for (uint32_t i = lane; i < n; i += 64) if (H.tax(i) == max_taxon) s = H.cnt(i);
+    uint32_t max_score = (uint32_t)wave_all_add((int32_t)s);
+    while (max_taxon && max_score < required) {
+        s = 0;
+        for (uint32_t i = lane; i < n; i += 64) if (k2_is_ancestor(parent, max_taxon, H.tax(i))) s += H.cnt(i);
+        max_score = (uint32_t)wave_all_add((int32_t)s);
+        if (max_score >= required) return max_taxon;
+        max_taxon = parent[max_taxon];
+    }
+    return max_taxon;
+}
+
+template <int W, bool QMASK, int HITS = 0, bool MIND = false>
+__global__ __launch_bounds__(64) void k_k2_classify_wave(K2ArgsOf<QMASK, HITS, MIND> a, K2Wave wv)
+{
+    static_assert(!MIND || HITS != 2, "the redo pass repeats units pass 1 counted");
+    constexpr bool COUNT = HITS != 2;                      // HITS 2 only writes the lists
+    __shared__ uint64_t s_bases[K2_WAVE_WORDS];
+    __shared__ uint64_t s_quals[QMASK ? K2_WAVE_WORDS : 1];
+    __shared__ uint32_t s_code[HITS ? K2_WAVE_TILE : 1];
+    __shared__ uint32_t s_ttax[COUNT ? K2_WT_SLOTS : 1], s_tcnt[COUNT ? K2_WT_SLOTS : 1];
+    __shared__ uint32_t s_n[2];
+    const uint32_t lane = threadIdx.x;
+    const unsigned long long lt = (1ull << lane) - 1;      // the lanes below this one
+    const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
+    const int32_t wlim = a.k - a.l + 1;
+    K2WaveTable H{s_ttax, s_tcnt, s_n, wv.spill_tax + (uint64_t)blockIdx.x * K2_WS_SLOTS, wv.spill_cnt + (uint64_t)blockIdx.x * K2_WS_SLOTS};
+    unsigned long long probes_thr = 0, kmers_thr = 0; uint32_t class_thr = 0, over_thr = 0;
+    std::conditional_t<MIND, K2MdState, K2NoMd> M{};
+    for (;;) {
+        uint32_t ticket = 0;
+        if (lane == 0) ticket = (uint32_t)atomicAdd(&a.ctr[HITS == 2 ? K2C_WTICKET2 : K2C_WTICKET], 1ull);
+        ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);
+        if (ticket >= a.n_list) break;
+        const uint64_t u = a.unit_list[ticket];
+        __syncthreads();                                   // the unit before is done with the table
+        if constexpr (COUNT) {
+            for (uint32_t i = lane; i < K2_WT_SLOTS; i += 64) { s_ttax[i] = 0; s_tcnt[i] = 0; }
+            if (lane < 2) s_n[lane] = 0;
+        }
+        uint32_t total = 0, groups = 0;
+        // HITS: the list's state, the same on every lane: the open entry, the entries closed so far, where they go
+        uint32_t r_code = K2_HIT_NONE, r_cnt = 0, r_n = 0, r_cap = 0, last_code = K2_HIT_NONE;
+        uint2 *r_out = nullptr;
+        if constexpr (HITS == 1) { r_out = a.hits + u * K2_HIT_INLINE; r_cap = K2_HIT_INLINE; }
+        if constexpr (HITS == 2) { r_out = a.hits + a.hit_off[u]; r_cap = (uint32_t)(a.hit_off[u + 1] - a.hit_off[u]); }
+        auto put = [&](uint32_t at, uint32_t c, uint32_t k) { if (at < r_cap) r_out[at] = make_uint2(c, k); };
+        const int n_frag = a.paired ? 2 : 1;
+        for (int f = 0; f < n_frag; ++f) {
+            const uint64_t rec = a.paired ? 2 * u + (uint64_t)f : u;
+            const uint64_t o_beg = a.offsets[rec];
+            const int32_t len = (int32_t)(a.offsets[rec + 1] - o_beg);
+            const uint32_t nk = len >= a.k ? (uint32_t)(len - a.k + 1) : 0u;
+            uint32_t seg = ((nk + 63u) / 64u) | 1u;
+            seg = seg < K2_WAVE_SEG ? seg : K2_WAVE_SEG;
+            bool carry_valid = false; uint64_t carry_min = 0;      // the last valid minimizer of the tiles before (none at a fragment's start)
+            for (uint32_t t0 = 0; t0 < nk; t0 += 64u * seg) {
+                const uint32_t tile_nk = nk - t0 < 64u * seg ? nk - t0 : 64u * seg;
+                // the tile's bases, k-mers t0 .. t0 + tile_nk - 1 = bases t0 .. t0 + tile_nk + k - 2, as the aligned words that hold them
+                const uintptr_t pa = (uintptr_t)(a.bases + o_beg + t0);
+                const uint32_t d = (uint32_t)(pa & 7), n_words = (d + tile_nk + (uint32_t)a.k - 1u + 7u) / 8u;
+                __syncthreads();                           // the tile before has been read
+                for (uint32_t w = lane; w < n_words; w += 64) s_bases[w] = ((const uint64_t *)(pa & ~(uintptr_t)7))[w];
+                if constexpr (QMASK) {                     // same offsets, same address mod 8
+                    const uintptr_t qa = (uintptr_t)(a.quals + o_beg + t0) & ~(uintptr_t)7;
+                    for (uint32_t w = lane; w < n_words; w += 64) s_quals[w] = ((const uint64_t *)qa)[w];
+                }
+                __syncthreads();
+                const uint8_t *sb = (const uint8_t *)s_bases + d;
+                [[maybe_unused]] const uint8_t *sq = (const uint8_t *)s_quals + d;
+                const uint32_t a0 = lane * seg, b0 = a0 + seg < tile_nk ? a0 + seg : tile_nk;      // this lane's k-mers [a0, b0) of the tile
+                const bool mine = a0 < tile_nk;
+                const uint32_t n_steps = seg + (uint32_t)a.k - 1u;
+                K2Scan<W> S; S.reset();
+                bool have = false, f_skip = false; uint64_t cur_min = 0, f_min = 0; uint32_t cur_tax = 0, f_tax = 0;
+                uint32_t acc_tax = 0, acc_cnt = 0;         // k-mers of the taxon being counted, not yet in the table
+#pragma nounroll
+                for (uint32_t s = 0; s < n_steps; ++s) {
+                    const uint32_t i = a0 + s;             // base of the tile
+                    const bool in = mine && i < b0 + (uint32_t)a.k - 1u;
+                    uint32_t code = in ? sh_nt4(sb[i]) : 4u;
+                    if constexpr (QMASK) code = in && k2_masked(sq[i], a.min_qual) ? 4u : code;
+                    uint64_t m;
+                    int ev = S.step_w(code, (int32_t)(t0 + i + 1u), a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
+                    ev = in && s >= (uint32_t)a.k - 1u ? ev : 0;      // the warm-up reports nothing
+                    total += ev != 0;
+                    uint32_t kc = SH_K2_HIT_AMBIGUOUS;
+                    if (ev == 2) {
+                        if (!have || m != cur_min) {       // a run starts here (the lane's first one: perhaps only continues)
+                            const uint64_t hc = k2_fmix64(m);
+                            const bool skip = a.min_hash && hc < a.min_hash;      // down-sampled database: not looked up
+                            const uint32_t tx = skip ? 0u : k2_probe(a.T, hc);
+                            if (!have) { f_min = m; f_tax = tx; f_skip = skip; }
+                            else if (COUNT && !skip) {
+                                ++probes_thr;
+                                if (tx) { ++groups; if constexpr (MIND) M.hit(a, tx, k2_md_code(hc)); }
+                            }
+                            have = true; cur_min = m; cur_tax = tx;
+                        }
+                        kc = cur_tax;
+                        if (COUNT && cur_tax) {
+                            if (cur_tax != acc_tax) { if (acc_cnt) H.add(acc_tax, acc_cnt); acc_tax = cur_tax; acc_cnt = 0; }
+                            ++acc_cnt;
+                        }
+                    }
+                    if constexpr (HITS != 0) { if (ev) s_code[i - ((uint32_t)a.k - 1u)] = kc; }
+                }
+                if (COUNT && acc_cnt) H.add(acc_tax, acc_cnt);
+                // whose first run is a run's head: the last lane before this one with a valid k-mer, else the carry
+                const unsigned long long vm = __ballot(have);
+                const int pl = (vm & lt) ? 63 - __clzll((long long)(vm & lt)) : 0;
+                const uint64_t p_min = (uint64_t)__shfl((unsigned long long)cur_min, pl);
+                const bool pred = (vm & lt) ? true : carry_valid;
+                const uint64_t pm = (vm & lt) ? p_min : carry_min;
+                if (COUNT && have && !(pred && pm == f_min) && !f_skip) {
+                    ++probes_thr;
+                    if (f_tax) { ++groups; if constexpr (MIND) M.hit(a, f_tax, k2_md_code(k2_fmix64(f_min))); }
+                }
+                if (vm) { carry_min = (uint64_t)__shfl((unsigned long long)cur_min, 63 - __clzll((long long)vm)); carry_valid = true; }
+                if constexpr (HITS != 0) {
+                    __syncthreads();                       // the codes are in LDS
+                    for (uint32_t c0 = 0; c0 < tile_nk; c0 += 64) {
+                        const uint32_t nv = tile_nk - c0 < 64u ? tile_nk - c0 : 64u;
+                        const uint32_t code = lane < nv ? s_code[c0 + lane] : 0u;
+                        uint32_t prev = (uint32_t)__shfl_up((int)code, 1);
+                        prev = lane == 0 ? last_code : prev;
+                        const bool head = lane < nv && code != prev;      // (a border is never a k-mer's code)
+                        const unsigned long long hm = __ballot(head);
+                        if (!hm) r_cnt += nv;
+                        else {
+                            const uint32_t fl = (uint32_t)__ffsll((unsigned long long)hm) - 1u;
+                            if (r_code != K2_HIT_NONE) { if (lane == 0) put(r_n, r_code, r_cnt + fl); ++r_n; }
+                            const unsigned long long rest = lane < 63 ? hm >> (lane + 1) : 0ull;
+                            if (head && rest) put(r_n + (uint32_t)__popcll(hm & lt), code, (uint32_t)__ffsll(rest));
+                            r_n += (uint32_t)__popcll(hm) - 1u;
+                            const int hl = 63 - __clzll((long long)hm);
+                            r_code = (uint32_t)__shfl((int)code, hl); r_cnt = nv - (uint32_t)hl;
+                        }
+                        last_code = (uint32_t)__shfl((int)code, (int)nv - 1);
+                    }
+                }
+            }
+            if constexpr (HITS != 0) {
+                if (a.paired && f == 0) {                  // the mate border: closes the open entry, never merges
+                    if (r_code != K2_HIT_NONE) { if (lane == 0) put(r_n, r_code, r_cnt); ++r_n; }
+                    r_code = SH_K2_HIT_BORDER; r_cnt = 0; last_code = SH_K2_HIT_BORDER;
+                }
+            }
+        }
+        if constexpr (HITS != 0) {
+            if (r_code != K2_HIT_NONE) { if (lane == 0) put(r_n, r_code, r_cnt); ++r_n; }
+            if (HITS == 1 && lane == 0) {
+                a.n_hits[u] = r_n;
+                if (r_n > K2_HIT_INLINE) wv.hit_over[(uint32_t)atomicAdd(&a.ctr[K2C_WHOVER], 1ull)] = (uint32_t)u;
+            }
+        }
+        if constexpr (COUNT) {
+            total = (uint32_t)wave_all_add((int32_t)total);
+            groups = (uint32_t)wave_all_add((int32_t)groups);
+            __syncthreads();                               // every lane's counts are in the tables
+            uint32_t call, n = 0;
+            const bool spilled = s_n[1] != 0;
+            if (!spilled) {                                // the table's entries to its front (a slot moves to a lower or the same index)
+                for (uint32_t c0 = 0; c0 < K2_WT_SLOTS; c0 += 64) {
+                    const uint32_t t = s_ttax[c0 + lane], c = s_tcnt[c0 + lane];
+                    const unsigned long long tm = __ballot(t != 0);
+                    if (t) { const uint32_t at = n + (uint32_t)__popcll(tm & lt); s_ttax[at] = t; s_tcnt[at] = c; }
+                    n += (uint32_t)__popcll(tm);
+                }
+                __syncthreads();
+                call = k2_resolve_wave(K2LdsEntries{s_ttax, s_tcnt}, n, a.parent, total, a.confidence, lane);
+            } else {
+                for (uint32_t i = lane; i < K2_WT_SLOTS; i += 64) if (s_ttax[i]) H.add_spill(s_ttax[i], s_tcnt[i]);
+                __threadfence(); __syncthreads();
+                for (uint32_t c0 = 0; c0 < K2_WS_SLOTS; c0 += 64) {
+                    const uint32_t t = k2_ld(&H.stax[c0 + lane]), c = k2_ld(&H.scnt[c0 + lane]);
+                    const unsigned long long tm = __ballot(t != 0);
+                    if (t) { const uint32_t at = n + (uint32_t)__popcll(tm & lt); k2_st(&H.stax[at], t); k2_st(&H.scnt[at], c); }
+                    n += (uint32_t)__popcll(tm);
+                }
+                __threadfence(); __syncthreads();
+                call = k2_resolve_wave(K2SpillEntries{H.stax, H.scnt}, n, a.parent, total, a.confidence, lane);
+                for (uint32_t i = lane; i < K2_WS_SLOTS; i += 64) { k2_st(&H.stax[i], 0u); k2_st(&H.scnt[i], 0u); }
+                __threadfence();
+            }
+            if (call && groups < (uint32_t)a.min_hit_groups) call = 0;
+            if (lane == 0) {
+                sh_k2_result r{call ? a.ext[call] : 0u, call, total, groups};
+                a.out[u] = r;
+                kmers_thr += total; class_thr += call != 0; over_thr += n > K2_HCAP;      // n_overflow keeps its meaning
+            }
+        }
+    }
+    if constexpr (MIND) M.flush(a.md_cnt);
+    if constexpr (COUNT) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) probes_thr += (unsigned long long)__shfl_xor((long long)probes_thr, o);
+        if (lane == 0) {
+            const uint32_t sh = blockIdx.x & 63;
+            if (probes_thr) atomicAdd(&a.ctr[K2C_PROBES + sh], probes_thr);
+            if (kmers_thr) atomicAdd(&a.ctr[K2C_KMERS + sh], kmers_thr);
+            if (class_thr) atomicAdd(&a.ctr[K2C_CLASSIFIED + sh], (unsigned long long)class_thr);
+            if (over_thr) atomicAdd(&a.ctr[K2C_WOVER], (unsigned long long)over_thr);
+        }
+    }
+}
+
 // ---- table construction ----------------------------------------------------------------------------------------------
 struct K2Build { uint32_t *cells; uint64_t capacity; int32_t value_bits; const uint32_t *parent; unsigned long long *ctr; };
 
@@ -847,6 +1174,7 @@ extern "C" sh_status sh_k2_default_opts(sh_k2_opts *o)
     o->min_hit_groups = 2;
     o->confidence = 0.0;
     o->min_base_quality = 0; o->quick = 0;
+    o->long_unit_bases = 0;
     return SH_OK;
 }
 
@@ -1123,6 +1451,7 @@ extern "C" sh_status sh_k2_db_opts(const sh_k2_db *db, sh_k2_opts *o)
 {
     SH_CHECK(db && o, SH_ERR_BAD_ARG, "sh_k2_db_opts: null argument");
     *o = db->opts;
+    o->long_unit_bases = 0; o->pad_ = 0;
     return SH_OK;
 }
 
@@ -1258,15 +1587,18 @@ extern "C" sh_status sh_k2_open(const char *dir, int device, sh_k2_db **out)
 // ---- classification ---------------------------------------------------------------------------------------------------
 // one form of the kernel; the window, QMASK and (for a pass-1 form) MIND become compile-time constants here
 template <bool BIG, bool QUICK, int HITS>
-static void launch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool mind)
+static void launch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool mind, bool sub)
 {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_work + 63) / 64, 1), 256 * 32);
     k2_with_window(a.k, a.l, [&](auto w) {
         k2_with_flag(qmask, [&](auto q) {
             k2_with_flag(mind, [&](auto m) {
-                constexpr bool QMASK = decltype(q)::value, MIND = decltype(m)::value && !(BIG || HITS == 2);
-                const K2ArgsOf<QMASK, HITS, MIND> &ka = a;
-                hipLaunchKernelGGL((k_k2_classify<decltype(w)::value, BIG, QMASK, QUICK, HITS, MIND>), dim3(grid), dim3(64), 0, s, ka);
+                k2_with_flag(sub, [&](auto sb) {
+                    constexpr bool QMASK = decltype(q)::value, MIND = decltype(m)::value && !(BIG || HITS == 2);
+                    constexpr bool SUB = decltype(sb)::value && !(BIG || QUICK || HITS == 2);
+                    const K2ArgsOf<QMASK, HITS, MIND> &ka = a;
+                    hipLaunchKernelGGL((k_k2_classify<decltype(w)::value, BIG, QMASK, QUICK, HITS, MIND, SUB>), dim3(grid), dim3(64), 0, s, ka);
+                });
             });
         });
     });
@@ -1275,15 +1607,71 @@ static void launch_classify(const K2MArgs &a, uint64_t n_work, hipStream_t s, bo
 // needs no HITS instance (pass 1 already emitted the whole list of a unit with many taxa); MIND goes with the three pass-1
 // forms only (the two redo passes are never asked for it: their units were counted by pass 1)
 enum K2Form { K2F_PLAIN, K2F_QUICK, K2F_HITS1, K2F_HITS2, K2F_BIG };
-static void dispatch_classify(K2Form form, const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool mind = false)
+// sub: a pass-1 form over a.unit_list (the units the wave route left)
+static void dispatch_classify(K2Form form, const K2MArgs &a, uint64_t n_work, hipStream_t s, bool qmask, bool mind = false, bool sub = false)
 {
     switch (form) {
-    case K2F_PLAIN: launch_classify<false, false, 0>(a, n_work, s, qmask, mind); break;
-    case K2F_QUICK: launch_classify<false, true, 0>(a, n_work, s, qmask, mind); break;
-    case K2F_HITS1: launch_classify<false, false, 1>(a, n_work, s, qmask, mind); break;
-    case K2F_HITS2: launch_classify<false, false, 2>(a, n_work, s, qmask, false); break;
-    case K2F_BIG: launch_classify<true, false, 0>(a, n_work, s, qmask, false); break;
+    case K2F_PLAIN: launch_classify<false, false, 0>(a, n_work, s, qmask, mind, sub); break;
+    case K2F_QUICK: launch_classify<false, true, 0>(a, n_work, s, qmask, mind, false); break;
+    case K2F_HITS1: launch_classify<false, false, 1>(a, n_work, s, qmask, mind, sub); break;
+    case K2F_HITS2: launch_classify<false, false, 2>(a, n_work, s, qmask, false, false); break;
+    case K2F_BIG: launch_classify<true, false, 0>(a, n_work, s, qmask, false, false); break;
     }
+}
+
+// the wave route's forms (PLAIN, HITS1, HITS2) over a.unit_list: one block of 64 threads per unit in flight, units drawn by ticket
+#define K2_WAVE_GRID 2048u      // 8 waves per CU; each block owns a 64-KiB spill table
+template <int HITS>
+static void launch_classify_wave(const K2MArgs &a, const K2Wave &wv, hipStream_t s, bool qmask, bool mind)
+{
+    const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(a.n_list, 1), K2_WAVE_GRID);
+    k2_with_window(a.k, a.l, [&](auto w) {
+        k2_with_flag(qmask, [&](auto q) {
+            k2_with_flag(mind, [&](auto m) {
+                constexpr bool QMASK = decltype(q)::value, MIND = decltype(m)::value && HITS != 2;
+                const K2ArgsOf<QMASK, HITS, MIND> &ka = a;
+                hipLaunchKernelGGL((k_k2_classify_wave<decltype(w)::value, QMASK, HITS, MIND>), dim3(grid), dim3(64), 0, s, ka, wv);
+            });
+        });
+    });
+}
+static void dispatch_classify_wave(K2Form form, const K2MArgs &a, const K2Wave &wv, hipStream_t s, bool qmask, bool mind = false)
+{
+    switch (form) {
+    case K2F_HITS1: launch_classify_wave<1>(a, wv, s, qmask, mind); break;
+    case K2F_HITS2: launch_classify_wave<2>(a, wv, s, qmask, false); break;
+    default: launch_classify_wave<0>(a, wv, s, qmask, mind); break;
+    }
+}
+
+extern "C" uint32_t sh_k2_wave_tile(void) { return K2_WAVE_TILE; }
+
+// opts.long_unit_bases resolved: the wave route's threshold in bases, 0 = no unit takes it
+#define K2_LONG_DEFAULT 8192      // measured choice: DESIGN.md §7 "Long reads"
+static uint64_t k2_long_threshold(const sh_k2_opts &o)
+{
+    if (o.quick || o.long_unit_bases < 0 || (o.long_unit_bases == 0 && K2_LONG_DEFAULT < 0)) return 0;
+    return o.long_unit_bases ? (uint64_t)o.long_unit_bases : (uint64_t)K2_LONG_DEFAULT;
+}
+// the units of a batch that take the wave route
+struct K2IsLong {
+    const uint64_t *off; int32_t paired; uint64_t thr;
+    __host__ __device__ bool operator()(uint32_t u) const
+    {
+        if (!paired) return off[u + 1] - off[u] >= thr;
+        const uint64_t l0 = off[2 * (uint64_t)u + 1] - off[2 * (uint64_t)u], l1 = off[2 * (uint64_t)u + 2] - off[2 * (uint64_t)u + 1];
+        return (l0 > l1 ? l0 : l1) >= thr;
+    }
+};
+// how many there are: the cheap question first, so that a batch without one pays for no list
+#define K2C_NLONG 7
+__global__ void k_k2_count_long(K2IsLong is_long, uint64_t n_units, unsigned long long *out)
+{
+    unsigned long long n = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_units; i += (uint64_t)gridDim.x * blockDim.x) n += is_long((uint32_t)i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += (unsigned long long)__shfl_xor((long long)n, o);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
 }
 
 // the hit lists of one call (sh_k2_classify_ex_* with hits): per-unit offsets and the entries, compacted, in HBM
@@ -1422,7 +1810,7 @@ struct K2HitsOwner {
 // and *hits_out (nullable), which is NULL after any failure
 static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets,
                              uint64_t n_records, int32_t paired, sh_k2_result *d_out, sh_k2_result *host_out, void *stream, sh_k2_stats *stats,
-                             sh_k2_hits **hits_out, sh_k2_mindata *md)
+                             sh_k2_hits **hits_out, sh_k2_mindata *md, bool may_be_long = true)
 {
     if (hits_out) *hits_out = nullptr;
     SH_CHECK(db && d_offsets && d_out && (d_bases || n_records == 0), SH_ERR_BAD_ARG, "sh_k2_classify_ex: null argument");
@@ -1444,7 +1832,8 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     SH_CHECK(n_units <= 0xffffffffull, SH_ERR_BAD_ARG, "at most 2^32 - 1 units per call");
     DevEvent e0, e1;
     SH_HIP(e0.create()); SH_HIP(e1.create());
-    DevBuf b_ctr, b_over, b_hit_inl, b_n_hits, b_hit_over, b_big_tax, b_big_cnt;
+    DevBuf b_ctr, b_over, b_hit_inl, b_n_hits, b_hit_over, b_big_tax, b_big_cnt, b_split, b_n_long, b_spill, b_whit_over;
+    DevEvent e2, e3;
     SH_HIP(b_ctr.alloc(K2C_WORDS * 8));
     SH_HIP(b_over.alloc(n_units * 4));
     unsigned long long *ctr = b_ctr.as<unsigned long long>();
@@ -1464,9 +1853,51 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     a.min_hit_groups = o.min_hit_groups; a.confidence = o.confidence;
     a.out = d_out; a.over_list = b_over.as<uint32_t>(); a.ctr = ctr;
     a.quals = qmask ? d_quals : nullptr; a.min_qual = qmask ? o.min_base_quality : 0;
+    // the split: are there long units at all (one pass over the offsets, an 8-byte read-back); if so, the long units first in b_split
+    // (by unit), the others behind them (last unit first: rocprim::partition's layout).  Nothing of it when no unit can be long
+    const uint64_t long_thr = may_be_long ? k2_long_threshold(o) : 0;
+    uint64_t n_long = 0;
+    K2Wave wv{};
+    if (long_thr) {
+        const K2IsLong is_long{d_offsets, paired, long_thr};
+        unsigned long long n_counted = 0;
+        hipLaunchKernelGGL(k_k2_count_long, dim3((uint32_t)std::min<uint64_t>((n_units + 255) / 256, 1024)), dim3(256), 0, s, is_long, n_units, ctr + K2C_NLONG);
+        SH_HIP(hipMemcpyAsync(&n_counted, ctr + K2C_NLONG, 8, hipMemcpyDeviceToHost, s));
+        SH_HIP(hipStreamSynchronize(s));
+        n_long = n_counted;
+    }
+    if (n_long) {
+        SH_HIP(b_split.alloc(n_units * 4));
+        SH_HIP(b_n_long.alloc(8));
+        size_t tmp_bytes = 0; DevBuf tmp;      // (the partition's own count lands in b_n_long: the same number)
+        const K2IsLong is_long{d_offsets, paired, long_thr};
+        SH_HIP(rocprim::partition(nullptr, tmp_bytes, rocprim::counting_iterator<uint32_t>(0), b_split.as<uint32_t>(), b_n_long.as<size_t>(), (size_t)n_units, is_long, s));
+        SH_HIP(tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+        SH_HIP(rocprim::partition(tmp.p, tmp_bytes, rocprim::counting_iterator<uint32_t>(0), b_split.as<uint32_t>(), b_n_long.as<size_t>(), (size_t)n_units, is_long, s));
+    }
+    if (n_long) {
+        const uint64_t grid = std::min<uint64_t>(n_long, K2_WAVE_GRID);
+        SH_HIP(b_spill.alloc(grid * K2_WS_SLOTS * 8));
+        SH_HIP(hipMemsetAsync(b_spill.p, 0, grid * K2_WS_SLOTS * 8, s));
+        wv.spill_tax = b_spill.as<uint32_t>(); wv.spill_cnt = wv.spill_tax + grid * K2_WS_SLOTS;
+        if (hits_out) { SH_HIP(b_whit_over.alloc(n_long * 4)); wv.hit_over = b_whit_over.as<uint32_t>(); }
+        SH_HIP(e2.create()); SH_HIP(e3.create());
+    }
+    const K2Form form1 = quick ? K2F_QUICK : hits_out ? K2F_HITS1 : K2F_PLAIN;
     SH_HIP(hipEventRecord(e0.e, s));
     if (qmask) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
-    dispatch_classify(quick ? K2F_QUICK : hits_out ? K2F_HITS1 : K2F_PLAIN, a, n_units, s, qmask, md != nullptr);      // the only pass that counts minimizers
+    if (!n_long) dispatch_classify(form1, a, n_units, s, qmask, md != nullptr);      // the only pass that counts minimizers
+    else {       // the long units one wave each, then the others one lane each
+        K2MArgs al = a;
+        al.unit_list = b_split.as<uint32_t>(); al.n_list = (uint32_t)n_long;
+        SH_HIP(hipEventRecord(e2.e, s));
+        dispatch_classify_wave(form1, al, wv, s, qmask, md != nullptr);
+        SH_HIP(hipEventRecord(e3.e, s));
+        if (n_long < n_units) {
+            al.unit_list += n_long; al.n_list = (uint32_t)(n_units - n_long);
+            dispatch_classify(form1, al, n_units - n_long, s, qmask, md != nullptr, true);
+        }
+    }
     SH_HIP(hipEventRecord(e1.e, s));
     std::vector<unsigned long long> h(K2C_WORDS);
     SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
@@ -1495,23 +1926,30 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
             SH_HIP(hipStreamSynchronize(s));
         }
         SH_HIP(hipMalloc(&hl.h->d_ent, std::max<uint64_t>(hl.h->n_entries, 1) * sizeof(sh_k2_hit)));
-        const uint64_t n_hover = h[K2C_HOVER];
+        const uint64_t n_hover = h[K2C_HOVER], n_whover = h[K2C_WHOVER];
         if (n_hover) {
             a.unit_list = a.hit_over; a.n_list = (uint32_t)n_hover; a.hits = (uint2 *)hl.h->d_ent; a.hit_off = hl.h->d_off;
             dispatch_classify(K2F_HITS2, a, n_hover, s, qmask);
+        }
+        if (n_whover) {       // the wave route's long lists
+            K2MArgs al = a;
+            al.unit_list = wv.hit_over; al.n_list = (uint32_t)n_whover; al.hits = (uint2 *)hl.h->d_ent; al.hit_off = hl.h->d_off;
+            dispatch_classify_wave(K2F_HITS2, al, wv, s, qmask);
         }
         const uint64_t n_cp = n_units * K2_HIT_INLINE;
         hipLaunchKernelGGL(k_k2_hits_compact, dim3((uint32_t)std::min<uint64_t>((n_cp + 255) / 256, 65536)), dim3(256), 0, s, b_hit_inl.as<uint2>(), a.n_hits, hl.h->d_off, n_units,
                            (uint2 *)hl.h->d_ent);
         SH_HIP(hipStreamSynchronize(s));
         SH_HIP(hipGetLastError());
-        hl.h->n_redone = n_hover;
+        hl.h->n_redone = n_hover + n_whover;
     }
     if (host_out) SH_HIP(hipMemcpy(host_out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost));
-    float ms = 0;
+    float ms = 0, ms_long = 0;
     hipEventElapsedTime(&ms, e0.e, e1.e);
+    if (n_long) hipEventElapsedTime(&ms_long, e2.e, e3.e);
     if (stats) {
-        stats->n_units = n_units; stats->n_overflow = n_over; stats->ms_classify = ms; stats->ms_total = ms;
+        stats->n_units = n_units; stats->n_overflow = n_over + h[K2C_WOVER]; stats->ms_classify = ms; stats->ms_total = ms;
+        stats->n_long_units = n_long; stats->ms_long = ms_long;
         for (int i = 0; i < 64; ++i) {
             stats->n_probes += h[K2C_PROBES + i]; stats->n_kmers += h[K2C_KMERS + i]; stats->n_classified += h[K2C_CLASSIFIED + i];
             stats->n_masked_bases += h[K2C_MASKED + i];
@@ -1557,8 +1995,14 @@ extern "C" sh_status sh_k2_classify_ex_batch(const sh_k2_db *db, const sh_k2_opt
     SH_HIP(hipMemcpy(d_bases.p, bases + o0, n_bases, hipMemcpyHostToDevice));
     SH_HIP(hipMemset(d_bases.as<uint8_t>() + n_bases, 'N', 64));
     SH_HIP(hipMemcpy(d_off.p, rel.data(), (n_records + 1) * 8, hipMemcpyHostToDevice));
+    // the host offsets tell whether any unit can take the wave route
+    bool any_long = false;
+    if (const uint64_t thr = k2_long_threshold(opts ? *opts : db->opts)) {
+        const K2IsLong is_long{rel.data(), b->paired, thr};
+        for (uint64_t u = 0; u < n_units && !any_long; ++u) any_long = is_long((uint32_t)u);
+    }
     return k2_classify(db, opts, d_bases.as<uint8_t>(), d_quals.as<uint8_t>(), d_off.as<uint64_t>(), n_records, b->paired, d_out.as<sh_k2_result>(), out, nullptr,
-                       stats, hits, md);
+                       stats, hits, md, any_long);
 }
 
 // ---- Kraken-style report (SURVEY.md App. B "Outputs consumed by Scrubby"; parsed by classifier.rs:449-466) -------------

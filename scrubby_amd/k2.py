@@ -13,7 +13,8 @@ from . import lib as S
 class K2Opts(C.Structure):
     _fields_ = [("k", C.c_int32), ("l", C.c_int32), ("spaced_seed_mask", C.c_uint64), ("toggle_mask", C.c_uint64),
                 ("min_acceptable_hash", C.c_uint64), ("value_bits", C.c_int32), ("min_hit_groups", C.c_int32),
-                ("confidence", C.c_double), ("min_base_quality", C.c_int32), ("quick", C.c_int32)]
+                ("confidence", C.c_double), ("min_base_quality", C.c_int32), ("quick", C.c_int32),
+                ("long_unit_bases", C.c_int32), ("pad_", C.c_int32)]
 
 
 class K2TaxNode(C.Structure):
@@ -27,7 +28,8 @@ class K2Info(C.Structure):
 
 class K2Stats(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("n_classified", C.c_uint64), ("n_probes", C.c_uint64), ("n_kmers", C.c_uint64),
-                ("n_overflow", C.c_uint64), ("ms_classify", C.c_float), ("ms_total", C.c_float), ("n_masked_bases", C.c_uint64)]
+                ("n_overflow", C.c_uint64), ("ms_classify", C.c_float), ("ms_total", C.c_float), ("n_masked_bases", C.c_uint64),
+                ("n_long_units", C.c_uint64), ("ms_long", C.c_float), ("pad_", C.c_int32)]
 
 
 class KrakenConfig(C.Structure):
@@ -121,8 +123,12 @@ def format_hits(entries, external, quick=False, quick_taxid=0):
     return buf.value.decode()
 
 
+# k-mers per tile of the wave route (sh_k2_wave_tile; units of at least opts.long_unit_bases bases are classified one wave each)
+K2_WAVE_TILE = 64 * 63
+
+
 def _stats_dict(st):
-    return {n: getattr(st, n) for n, _ in K2Stats._fields_}
+    return {n: getattr(st, n) for n, _ in K2Stats._fields_ if n != "pad_"}
 
 
 def _take_hits(h):
