@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair; + the Kraken arm's wave route: sh_k2_opts grew long_unit_bases, sh_k2_stats n_long_units / ms_long, the old layouts are prefixes, the version kept): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
+#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair; + the Kraken arm's wave route: sh_k2_opts grew long_unit_bases, sh_k2_stats n_long_units / ms_long, the old layouts are prefixes, the version kept; + the Kraken arm's abundance re-estimation: sh_k2_distrib_*, sh_k2_bracken_* added, nothing changed, the version kept): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
 
 typedef int32_t sh_status;
 enum {
@@ -728,6 +728,118 @@ sh_status sh_k2_inspect_header(const sh_k2_db *db, char *buf, uint64_t cap, uint
 typedef struct sh_k2_inspect_config { const char *db, *output; int32_t skip_counts, report_zero_counts, use_mpa_style, device; } sh_k2_inspect_config;
 typedef struct sh_k2_inspect_result { uint64_t capacity, size_header, n_occupied, n_bad_values, n_nodes, n_taxa_with_minimizers; double s_open, s_count, s_report, s_total; } sh_k2_inspect_result;
 sh_status sh_k2_inspect_run(const sh_k2_inspect_config *cfg, sh_k2_inspect_result *out);
+
+/* ---- Kraken arm: abundance re-estimation (DESIGN.md §7 "Abundance re-estimation"): bracken-build's k-mer distribution on the GPU
+ * and Bracken's estimate on the host.  The method of Lu et al. 2017 as this project states it; Bracken's sources were not at hand:
+ * PARITY WITH Bracken's OWN PROGRAMS UNPINNED, like the rest of the arm.
+ * Codes: every k-mer of a library record has the code the hit lists give it (internal taxon of its minimizer, 0, or
+ * SH_K2_HIT_AMBIGUOUS).  Windows: for a read length L (k <= L <= 1024) and W = L - k + 1, a record of len bases under internal taxon
+ * g != 0 has len - L + 1 windows (none when len < L); window p holds k-mers p .. p + W - 1 and its call is Kraken 2's ResolveTree
+ * over the counts of its codes other than 0 and ambiguous (total W, confidence 0, no minimum-hit-groups test; no counted code: call
+ * 0).  Distribution: the map (g, call) -> windows, and per g the windows in all, unclassified ones included.  It does not depend on
+ * batching, record order, or where a long record is cut (pieces repeat L - 1 bases, so every window lies in exactly one piece).
+ * Several accumulators (one per GPU) add: entries add per (genome, mapped), totals add per genome. */
+typedef struct sh_k2_distrib sh_k2_distrib;            /* accumulator of one database and one read length, in HBM */
+typedef struct sh_k2_distrib_entry { uint32_t genome, mapped; uint64_t windows; } sh_k2_distrib_entry;      /* internal ids */
+typedef struct sh_k2_distrib_stats {
+    uint64_t n_records;
+    uint64_t n_windows;             /* windows of the call */
+    uint64_t n_items;               /* (record, stretch of window starts) work items */
+    uint64_t n_big;                 /* stretches finished by the second instance (a window with more distinct taxa than the LDS table holds) */
+    float    ms;
+    int32_t  pad;
+} sh_k2_distrib_stats;
+/* window starts per work item of the window kernel */
+uint32_t sh_k2_distrib_stretch(void);
+/* the database must outlive the accumulator.  SH_ERR_OOM names the size */
+sh_status sh_k2_distrib_create(const sh_k2_db *db, int32_t read_len, sh_k2_distrib **out);
+sh_status sh_k2_distrib_reset(sh_k2_distrib *d);
+sh_status sh_k2_distrib_free(sh_k2_distrib *d);
+/* Adds the windows of a batch in HBM: layout, taxon rules (0 or >= n_nodes = skip) and the readable tail as for
+ * sh_k2_insert_library_device.  Calls add up in any batching.  One synchronisation per call (a second one, and the batch again,
+ * when the code scratch has to grow).  SH_ERR_OOM names the size when the (genome, mapped) table is full: the accumulator then
+ * refuses further batches until it is reset. */
+sh_status sh_k2_distrib_add_device(sh_k2_distrib *d, const uint8_t *d_bases, const uint64_t *d_offsets, const uint32_t *d_taxa, uint64_t n_records,
+                                   void *stream, sh_k2_distrib_stats *stats);
+/* the two kernels' shares of the last call's ms (measurement aid; any pointer may be NULL) */
+sh_status sh_k2_distrib_last_ms(const sh_k2_distrib *d, float *ms_codes, float *ms_windows);
+sh_status sh_k2_distrib_count(sh_k2_distrib *d, uint64_t *n_entries);
+/* entries sorted by (genome, mapped), call 0 included; totals: n_nodes uint64 by internal id (any pointer may be NULL) */
+sh_status sh_k2_distrib_copy(sh_k2_distrib *d, sh_k2_distrib_entry *entries, uint64_t *totals);
+/* Host only (no GPU), over host arrays.
+ * _write: Bracken's database<L>mers.kmer_distrib: the header line "mapped_taxid\tgenome_taxids:kmers_mapped:total_genome_kmers", then
+ * one line per mapped taxon, external ids, ascending: "<mapped>\t<g>:<windows>:<total(g)>" with the entries separated by single
+ * spaces and genomes ascending.  Rows for call 0 are not written (the totals still include those windows).  An id outside the
+ * taxonomy is SH_ERR_BAD_ARG.
+ * _read: that file back into entries sorted by (genome, mapped) and totals (n_nodes, zeroed first).  entries NULL or cap too small:
+ * only *n_entries is set.  A taxid outside the taxonomy is named once on stderr and skipped; a malformed line is SH_ERR_IO naming
+ * the line. */
+sh_status sh_k2_distrib_write(const sh_k2_distrib_entry *entries, uint64_t n, const uint64_t *totals, const uint32_t *external, uint64_t n_nodes,
+                              int32_t read_len, const char *path);
+sh_status sh_k2_distrib_read(const char *path, const uint32_t *external, uint64_t n_nodes, sh_k2_distrib_entry *entries, uint64_t cap,
+                             uint64_t *n_entries, uint64_t *totals);
+/* Bracken's estimate.  level: one of D K P C O F G S (the rank names of sh_k2_write_report).  lvl(x) = the nearest ancestor-or-self
+ * of x whose rank is the level's (0: none); clade(x) = direct_reads summed over x's subtree.  Taxa of the level with clade >=
+ * max(threshold, 1) are kept; the others' clade reads are reads_below_threshold.  For every node n != 0 in ascending id with
+ * direct_reads[n] > 0 and lvl(n) == 0, and every kept s in ascending id: m = sum over the genomes g with lvl(g) == s of
+ * windows(g -> n), T = sum over those genomes of total(g), w(s) = m / T * clade(s) in doubles in this order (0 when T is 0).  When
+ * the sum of w is positive, added(s) += direct_reads[n] * w(s) / sum; else direct_reads[n] goes to reads_undistributed.
+ * new_est(s) = floor(clade(s) + added(s) + 0.5); fraction = new_est(s) / sum of new_est.  rows: one per kept taxon in ascending
+ * internal id, room for n_nodes. */
+typedef struct sh_k2_bracken_row { uint32_t taxon, pad; uint64_t assigned, new_est; double added, fraction; } sh_k2_bracken_row;
+typedef struct sh_k2_bracken_summary {
+    uint64_t n_rows;
+    uint64_t reads_total;           /* sum of direct_reads */
+    uint64_t reads_at_level;        /* clade reads of the kept taxa */
+    uint64_t reads_below_threshold; /* clade reads of the level's other taxa */
+    uint64_t reads_distributed, reads_undistributed;       /* direct reads of the nodes above the level */
+    uint64_t new_est_total;
+} sh_k2_bracken_summary;
+sh_status sh_k2_bracken_estimate(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *ranks, uint64_t ranks_len, const uint64_t *direct_reads,
+                                 const sh_k2_distrib_entry *entries, uint64_t n, const uint64_t *totals, int32_t level, uint64_t threshold,
+                                 sh_k2_bracken_row *rows, sh_k2_bracken_summary *summary);
+/* the table: name, taxonomy_id, taxonomy_lvl, kraken_assigned_reads, added_reads (new_est - assigned), new_est_reads,
+ * fraction_total_reads (%.5f); tab-separated with a header row, rows in ascending external taxid.  path NULL or "-" = stdout */
+sh_status sh_k2_bracken_write(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *names, uint64_t names_len, const sh_k2_bracken_row *rows,
+                              uint64_t n_rows, int32_t level, const char *path);
+
+/* `scrubby-hip k2-bracken-build`: the distribution of one database and one read length over library FASTA files (plain, gzip, bzip2,
+ * xz), streamed in batches as sh_k2_build_run does (a record beyond chunk_bytes is cut with read_len - 1 bases repeated).  A record's
+ * taxon: the header rule of sh_k2_taxonomy_header_taxon over the database's own taxonomy (seqid2taxid and / or kraken:taxid|n), or
+ * `taxid` for every record; records without a taxon in the database are skipped and counted. */
+typedef struct sh_k2_distrib_config {
+    const char *db;                 /* database directory */
+    const char *const *input;  uint32_t n_input;
+    int32_t     read_len;
+    const char *seqid2taxid;        /* nullable */
+    uint64_t    taxid;              /* != 0: every record's (external) taxon */
+    const char *output;             /* NULL: <db>/database<L>mers.kmer_distrib */
+    uint64_t    chunk_bytes;        /* bases per batch, 0: 256 MiB */
+    int32_t     device, pad;
+} sh_k2_distrib_config;
+typedef struct sh_k2_distrib_result {
+    uint64_t n_records, n_skipped, n_bases, n_batches, n_cuts;
+    uint64_t n_windows, n_items, n_big, n_entries;
+    double   s_open, s_gpu, s_read, s_write, s_total;
+} sh_k2_distrib_result;
+sh_status sh_k2_distrib_run(const sh_k2_distrib_config *cfg, sh_k2_distrib_result *out);
+/* `scrubby-hip k2-bracken`: re-estimates one sample from its kraken.report (as sh_k2_write_report writes it; rows are matched by
+ * the taxid column, a taxid the database lacks is named once and its direct reads count as undistributed).  The taxonomy is the
+ * database's (taxo.k2d is read on the host: no GPU). */
+typedef struct sh_k2_bracken_config {
+    const char *db;                 /* database directory */
+    const char *report;             /* kraken.report */
+    int32_t     read_len;           /* names the default distribution file */
+    int32_t     level;              /* 0: 'S' */
+    int64_t     threshold;          /* < 0: 10 */
+    const char *kmer_distrib;       /* NULL: <db>/database<L>mers.kmer_distrib */
+    const char *output;
+} sh_k2_bracken_config;
+typedef struct sh_k2_bracken_result {
+    sh_k2_bracken_summary summary;
+    uint64_t n_report_rows, n_unknown_taxa;
+} sh_k2_bracken_result;
+sh_status sh_k2_bracken_run(const sh_k2_bracken_config *cfg, sh_k2_bracken_result *out);
 
 #ifdef __cplusplus
 }

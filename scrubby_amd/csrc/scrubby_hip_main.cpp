@@ -23,7 +23,10 @@ static void usage()
             "                  [--mask-low-complexity [--mask-window 64] [--mask-threshold 20]]\n"
             "scrubby-hip k2-mask -i <in.fa[.gz|.bz2|.xz]> -o <out.fa[.gz|.bz2|.xz]> [-W 64] [-T 20] [-r x | --soft] [--line-width 60]\n"
             "                  [--chunk-bytes N]\n"
-            "scrubby-hip k2-inspect -d <db dir> [-o report.txt] [--skip-counts] [--report-zero-counts] [--use-mpa-style] [--device N]\n");
+            "scrubby-hip k2-inspect -d <db dir> [-o report.txt] [--skip-counts] [--report-zero-counts] [--use-mpa-style] [--device N]\n"
+            "scrubby-hip k2-bracken-build -d <db dir> -i <library.fna[.gz]>.. [-m <seqid2taxid.map> | --taxid N] -l <read length> [-o FILE]\n"
+            "                  [--chunk-bytes N] [--device N]\n"
+            "scrubby-hip k2-bracken -d <db dir> -r <kraken.report> -l <read length> [-L S] [-t 10] [-k <kmer_distrib>] -o <sample.bracken>\n");
 }
 
 // `scrubby classifier` (/root/reference/src/terminal.rs:204-279): clean reads from precomputed Kraken2 / Metabuli outputs
@@ -179,6 +182,74 @@ static int main_k2_inspect(int argc, char **argv)
     return 0;
 }
 
+// `scrubby-hip k2-bracken-build`: bracken-build's k-mer distribution of a database at one read length, on the GPU
+static int main_k2_bracken_build(int argc, char **argv)
+{
+    std::vector<std::string> in;
+    std::string db, map, out;
+    sh_k2_distrib_config c{};
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
+        auto multi = [&](std::vector<std::string> &v) { while (i + 1 < argc && argv[i + 1][0] != '-') v.push_back(argv[++i]); };
+        if (a == "-d" || a == "--db") db = val();
+        else if (a == "-i" || a == "--input") multi(in);
+        else if (a == "-m" || a == "--seqid2taxid") map = val();
+        else if (a == "--taxid") c.taxid = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "-l" || a == "--read-len") c.read_len = atoi(val().c_str());
+        else if (a == "-o" || a == "--output") out = val();
+        else if (a == "--chunk-bytes") c.chunk_bytes = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "--device") c.device = atoi(val().c_str());
+        else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+    }
+    if (db.empty() || in.empty() || c.read_len <= 0) { fprintf(stderr, "error: a database directory (-d), library files (-i) and a read length (-l) are required\n"); usage(); return 2; }
+    std::vector<const char *> ip;
+    for (auto &f : in) ip.push_back(f.c_str());
+    c.db = db.c_str(); c.input = ip.data(); c.n_input = (uint32_t)ip.size();
+    c.seqid2taxid = map.empty() ? nullptr : map.c_str(); c.output = out.empty() ? nullptr : out.c_str();
+    sh_k2_distrib_result r{};
+    sh_status st = sh_k2_distrib_run(&c, &r);
+    if (st != SH_OK) { fprintf(stderr, "error (%d): %s\n", st, sh_last_error()); return 1; }
+    fprintf(stderr, "[scrubby-hip] %llu records (%llu skipped), %llu bases, %llu batches (%llu cuts): %llu windows, %llu stretches (%llu redone), %llu entries; "
+            "open %.3f s, gpu %.3f s, read %.3f s, total %.3f s\n",
+            (unsigned long long)r.n_records, (unsigned long long)r.n_skipped, (unsigned long long)r.n_bases, (unsigned long long)r.n_batches, (unsigned long long)r.n_cuts,
+            (unsigned long long)r.n_windows, (unsigned long long)r.n_items, (unsigned long long)r.n_big, (unsigned long long)r.n_entries, r.s_open, r.s_gpu, r.s_read, r.s_total);
+    return 0;
+}
+
+// `scrubby-hip k2-bracken`: Bracken's abundance estimate of one sample from its kraken.report (host only)
+static int main_k2_bracken(int argc, char **argv)
+{
+    std::string db, report, dist, out;
+    sh_k2_bracken_config c{};
+    c.threshold = -1;
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
+        if (a == "-d" || a == "--db") db = val();
+        else if (a == "-r" || a == "--report") report = val();
+        else if (a == "-l" || a == "--read-len") c.read_len = atoi(val().c_str());
+        else if (a == "-L" || a == "--level") { const std::string v = val(); c.level = v.size() == 1 ? v[0] : '?'; }
+        else if (a == "-t" || a == "--threshold") c.threshold = atoll(val().c_str());
+        else if (a == "-k" || a == "--kmer-distrib") dist = val();
+        else if (a == "-o" || a == "--output") out = val();
+        else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+    }
+    if (db.empty() || report.empty() || out.empty() || (dist.empty() && c.read_len <= 0)) {
+        fprintf(stderr, "error: a database directory (-d), a report (-r), a read length (-l) or a distribution file (-k), and an output (-o) are required\n");
+        usage();
+        return 2;
+    }
+    c.db = db.c_str(); c.report = report.c_str(); c.output = out.c_str(); c.kmer_distrib = dist.empty() ? nullptr : dist.c_str();
+    sh_k2_bracken_result r{};
+    sh_status st = sh_k2_bracken_run(&c, &r);
+    if (st != SH_OK) { fprintf(stderr, "error (%d): %s\n", st, sh_last_error()); return 1; }
+    fprintf(stderr, "[scrubby-hip] %llu taxa at the level: %llu reads there, %llu below the threshold, %llu distributed, %llu undistributed; new estimate %llu reads\n",
+            (unsigned long long)r.summary.n_rows, (unsigned long long)r.summary.reads_at_level, (unsigned long long)r.summary.reads_below_threshold,
+            (unsigned long long)r.summary.reads_distributed, (unsigned long long)r.summary.reads_undistributed, (unsigned long long)r.summary.new_est_total);
+    return 0;
+}
+
 // `scrubby alignment` (/root/reference/src/terminal.rs:281-360)
 static int main_alignment(int argc, char **argv, const std::string &command)
 {
@@ -221,6 +292,8 @@ int main(int argc, char **argv)
     if (argc >= 2 && std::string(argv[1]) == "k2-build") return main_k2_build(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "k2-mask") return main_k2_mask(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "k2-inspect") return main_k2_inspect(argc, argv);
+    if (argc >= 2 && std::string(argv[1]) == "k2-bracken-build") return main_k2_bracken_build(argc, argv);
+    if (argc >= 2 && std::string(argv[1]) == "k2-bracken") return main_k2_bracken(argc, argv);
     if (argc >= 2 && (std::string(argv[1]) == "classifier" || std::string(argv[1]) == "alignment")) {
         std::string command;
         for (int i = 0; i < argc; ++i) { if (i) command += ' '; command += argv[i]; }

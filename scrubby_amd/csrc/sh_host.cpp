@@ -18,6 +18,7 @@
 #include <chrono>
 #include <thread>
 #include <ctime>
+#include <memory>
 #include <unordered_set>
 #include <unordered_map>
 #include <algorithm>
@@ -1042,6 +1043,54 @@ extern "C" sh_status sh_k2_taxonomy_single(uint64_t taxid, const char *name, con
     sh_status st = k2_taxonomy_bits(t, value_bits);
     if (st != SH_OK) { delete t; return st; }
     *out = t;
+    return SH_OK;
+}
+
+sh_status shi_k2_taxonomy_of_nodes(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *seqid2taxid_map, uint64_t single_taxid, sh_k2_taxonomy **out)
+{
+    SH_CHECK(nodes && n_nodes >= 2 && out, SH_ERR_BAD_ARG, "shi_k2_taxonomy_of_nodes: null argument");
+    std::unique_ptr<sh_k2_taxonomy> t(new sh_k2_taxonomy);
+    t->nodes.assign(nodes, nodes + n_nodes);
+    t->parent.resize(n_nodes);
+    for (uint64_t i = 0; i < n_nodes; ++i) {
+        SH_CHECK(i <= 1 || nodes[i].parent < i, SH_ERR_BAD_ARG, "taxonomy: node %llu has parent %llu (ids must be breadth-first)", (unsigned long long)i,
+                 (unsigned long long)nodes[i].parent);
+        t->parent[i] = (uint32_t)nodes[i].parent;
+        if (i) t->ext2int[nodes[i].external_id] = (uint32_t)i;
+    }
+    std::unordered_set<uint64_t> missing;
+    auto internal = [&](uint64_t ext) -> uint32_t {
+        auto it = t->ext2int.find(ext);
+        if (it != t->ext2int.end()) return it->second;
+        if (missing.insert(ext).second) fprintf(stderr, "[scrubby-hip] taxid %llu is not in the database's taxonomy: its sequences are skipped\n", (unsigned long long)ext);
+        return 0;
+    };
+    if (single_taxid) {
+        t->single = internal(single_taxid);
+        SH_CHECK(t->single, SH_ERR_BAD_ARG, "taxid %llu is not in the database's taxonomy", (unsigned long long)single_taxid);
+    }
+    if (seqid2taxid_map) {       // two tab- or space-separated columns, as sh_k2_taxonomy_from_ncbi reads them
+        FILE *fp = fopen(seqid2taxid_map, "r");
+        SH_CHECK(fp, SH_ERR_IO, "cannot open %s", seqid2taxid_map);
+        char *line = nullptr; size_t cap = 0;
+        while (getline(&line, &cap, fp) > 0) {
+            const char *b = line;
+            while (*b == ' ' || *b == '\t') ++b;
+            const char *e = b;
+            while (*e && *e != ' ' && *e != '\t' && *e != '\n' && *e != '\r') ++e;
+            if (e == b) continue;
+            const char *v = e;
+            while (*v == ' ' || *v == '\t') ++v;
+            if (*v < '0' || *v > '9') continue;
+            const uint32_t one = internal(strtoull(v, nullptr, 10));
+            if (one) t->seq2int[std::string(b, e)] = one;
+        }
+        free(line);
+        fclose(fp);
+    }
+    t->n_missing = missing.size();
+    t->value_bits = k2_min_value_bits(n_nodes);
+    *out = t.release();
     return SH_OK;
 }
 

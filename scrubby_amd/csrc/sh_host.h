@@ -50,3 +50,7 @@ sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_
 sh_status shi_kraken_minimizer_report(const sh_kraken_config *c, sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, sh_k2_mindata *md, const std::string &dir);
 // database build: the <n> of a `kraken:taxid|<n>` sequence id (sh_host.cpp)
 bool shi_k2_header_taxid(const char *id, size_t len, uint64_t *taxid);
+// abundance re-estimation: the header -> taxon rule of sh_k2_taxonomy_header_taxon over the taxonomy a database already has (its
+// nodes), with an id map (nullable) or one external taxid for every record (0: none).  A taxid the database lacks is named once on
+// stderr; its sequences get no taxon.  Freed with sh_k2_taxonomy_free (sh_host.cpp)
+sh_status shi_k2_taxonomy_of_nodes(const sh_k2_taxnode *nodes, uint64_t n_nodes, const char *seqid2taxid_map, uint64_t single_taxid, sh_k2_taxonomy **out);

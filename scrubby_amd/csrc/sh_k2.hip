@@ -34,6 +34,7 @@
 #include "sh_common.h"
 #include "sh_k2_db.h"
 #include "sh_k2_inspect.h"
+#include "sh_k2_distrib.h"
 #include "sh_wave.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
@@ -60,19 +61,6 @@ __host__ __device__ static inline uint64_t k2_fmix64(uint64_t k)
     k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL;
     k ^= k >> 33;
     return k;
-}
-
-__device__ static inline uint32_t k2_lca(const uint32_t *__restrict__ parent, uint32_t a, uint32_t b)
-{
-    if (!a || !b) return a ? a : b;
-    while (a != b) { if (a > b) a = parent[a]; else b = parent[b]; }
-    return a;
-}
-__device__ static inline bool k2_is_ancestor(const uint32_t *__restrict__ parent, uint32_t a, uint32_t b)
-{
-    if (!a || !b) return false;
-    while (b > a) b = parent[b];
-    return a == b;
 }
 
 struct K2Table { const uint32_t *cells; uint64_t capacity; int32_t value_bits; double inv_capacity; };
@@ -1435,6 +1423,84 @@ extern "C" sh_status sh_k2_estimate_capacity_device(sh_k2_estimator *e, const ui
         break;
     }
     if (n_sampled) *n_sampled = e->n_have;
+    return SH_OK;
+}
+
+// ---- per-k-mer codes of a library batch (DESIGN.md §7 "Abundance re-estimation"; the windows over them: sh_k2_distrib.hip) ----
+// The work items and the character loop of k2_lib_scan, in a copy of its own: this caller needs every k-mer, not only the first
+// of a run, and the ambiguous ones too, and the two build kernels keep the code they had.  Consecutive k-mers with one minimizer
+// share one probe; a segment's first valid k-mer probes whatever the segment before it ended with (the code is a function of the
+// minimizer alone, so the repeated probe changes no answer: it costs one lookup per 1024 bases).
+template <int W>
+__global__ __launch_bounds__(64) void k_k2_codes_lib(K2LibArgs a, K2Table T, uint32_t *codes, uint64_t cap, unsigned long long *need)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint64_t n_bases = a.offsets[a.n_records];
+    if (n_bases > cap) {        // the scratch is too small for this batch: say how much it takes, write nothing
+        if (blockIdx.x == 0 && lane == 0) *need = n_bases;
+        return;
+    }
+    const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
+    const int32_t wlim = a.k - a.l + 1;
+    const uint64_t n_items = a.seg_off[a.n_records];
+    for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_items; base += (uint64_t)gridDim.x * 64) {
+        const uint64_t item = base + lane;
+        int32_t n = 0, lead = 0;
+        const uint8_t *p = a.bases;
+        uint64_t d0 = 0;                 // the k-mer that ends at the segment's character i (i >= k - 1) has its code at codes[d0 + i - (k - 1)]
+        if (item < n_items) {
+            uint64_t lo = 0, hi = a.n_records;
+            while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (a.seg_off[mid] <= item) lo = mid; else hi = mid; }
+            const uint64_t r0 = a.offsets[lo], len = a.offsets[lo + 1] - r0;
+            const uint64_t s0 = (item - a.seg_off[lo]) * a.seg, s1 = s0 + a.seg < len ? s0 + a.seg : len;
+            const uint64_t from = s0 >= (uint64_t)(a.k - 1) ? s0 - (uint64_t)(a.k - 1) : 0;
+            p = a.bases + r0 + from; n = (int32_t)(s1 - from); lead = (int32_t)(s0 - from);
+            d0 = r0 + from;
+        }
+        int32_t n_max = n;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const int32_t t = __shfl_xor(n_max, o); n_max = t > n_max ? t : n_max; }
+        const uint64_t *wp = (const uint64_t *)((uintptr_t)p & ~(uintptr_t)7);
+        const int32_t off8 = (int32_t)((uintptr_t)p & 7); const uint32_t sh = (uint32_t)off8 * 8;
+        uint64_t w_cur = n > 0 ? wp[0] : 0, w_next = n + off8 > 8 ? wp[1] : 0;
+        K2Scan<W> S; S.reset();
+        uint64_t last = 0; bool have = false; uint32_t taxon = 0;
+        const int32_t n_chunks = (n_max + 7) / 8;
+#pragma nounroll
+        for (int32_t c = 0; c < n_chunks; ++c) {
+            uint64_t w = sh ? (w_cur >> sh) | (w_next << (64 - sh)) : w_cur;
+            w_cur = w_next;
+            w_next = (c + 2) * 8 < n + off8 ? wp[c + 2] : 0;
+#pragma nounroll
+            for (int32_t j = 0; j < 8; ++j) {
+                const int32_t i = c * 8 + j;
+                uint64_t m;
+                const int ev = S.step_w(sh_nt4((uint32_t)w & 0xffu), i + 1 < a.k ? i + 1 : a.k, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
+                w >>= 8;
+                if (ev == 0 || i >= n || i < lead) continue;
+                if (ev == 2 && !(have && m == last)) {
+                    const uint64_t hc = k2_fmix64(m);
+                    taxon = a.min_hash && hc < a.min_hash ? 0u : k2_probe(T, hc);
+                    taxon = taxon < a.n_nodes ? taxon : 0u;       // a cell value outside the taxonomy counts for nobody
+                    last = m; have = true;
+                }
+                codes[d0 + (uint64_t)(i - (a.k - 1))] = ev == 2 ? taxon : SH_K2_HIT_AMBIGUOUS;
+            }
+        }
+    }
+}
+
+sh_status shi_k2_codes_device(const sh_k2_db *db, const uint8_t *d_bases, const uint64_t *d_offsets, const uint32_t *d_taxa, uint64_t n_records,
+                              uint64_t *d_seg, DevBuf &tmp, uint32_t *d_codes, uint64_t codes_cap, unsigned long long *d_need, hipStream_t s)
+{
+    K2LibArgs a{};
+    a.n_nodes = (uint32_t)db->nodes.size();
+    sh_status st = k2_lib_prepare(a, db->opts, d_bases, d_offsets, d_taxa, n_records, d_seg, tmp, s);
+    if (st != SH_OK) return st;
+    const K2Table T{db->d_cells, db->capacity, db->value_bits, 1.0 / (double)db->capacity};
+    k2_with_window(db->opts.k, db->opts.l, [&](auto w) {
+        hipLaunchKernelGGL(k_k2_codes_lib<decltype(w)::value>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, T, d_codes, codes_cap, d_need);
+    });
     return SH_OK;
 }
 

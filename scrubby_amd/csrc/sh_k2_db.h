@@ -1,4 +1,5 @@
-// sh_k2_db.h - the Kraken arm's database handle, shared by sh_k2.hip (build, classify, files) and sh_k2_inspect.hip (inspection)
+// sh_k2_db.h - the Kraken arm's database handle and the two walks over its taxonomy, shared by sh_k2.hip (build, classify, files),
+// sh_k2_inspect.hip (inspection) and sh_k2_distrib.hip (window calls)
 #pragma once
 #include "sh_common.h"
 
@@ -14,3 +15,17 @@ struct sh_k2_db {
     // opts.k2d fields carried through save/open
     int32_t dna_db = 1, revcom_version = 1, db_version = 0, db_type = 0;
 };
+
+// breadth-first ids: a parent's id is smaller than its child's; 0 is no taxon
+__device__ static inline uint32_t k2_lca(const uint32_t *__restrict__ parent, uint32_t a, uint32_t b)
+{
+    if (!a || !b) return a ? a : b;
+    while (a != b) { if (a > b) a = parent[a]; else b = parent[b]; }
+    return a;
+}
+__device__ static inline bool k2_is_ancestor(const uint32_t *__restrict__ parent, uint32_t a, uint32_t b)
+{
+    if (!a || !b) return false;
+    while (b > a) b = parent[b];
+    return a == b;
+}

@@ -21,6 +21,7 @@
 // case handed to the collect-then-map form in sh_host.cpp.
 #include "sh_host.h"
 #include "sh_k2_mask.h"
+#include "sh_k2_db.h"
 #include <zlib.h>
 #include "sh_codec.h"
 #include <fcntl.h>
@@ -1841,6 +1842,70 @@ extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_re
     res->size = info.size; res->capacity = capacity; res->n_nodes = ti.n_nodes; res->min_acceptable_hash = min_hash; res->value_bits = ti.value_bits;
     res->s_save = sec(t3, t4); res->s_read = s_read; res->s_total = sec(t_begin, t4);
     res->n_masked_bases = n_masked; res->s_mask = s_mask;
+    return SH_OK;
+}
+
+// ---- `scrubby-hip k2-bracken-build` (DESIGN.md §7 "Abundance re-estimation"): the library streams through the accumulator in
+// batches; a record beyond the chunk is cut with read_len - 1 bases repeated, so every window lies in exactly one piece
+extern "C" sh_status sh_k2_distrib_run(const sh_k2_distrib_config *c, sh_k2_distrib_result *res)
+{
+    SH_CHECK(c && res, SH_ERR_BAD_ARG, "sh_k2_distrib_run: null argument");
+    SH_CHECK(c->db && c->input && c->n_input >= 1, SH_ERR_BAD_ARG, "k2-bracken-build: a database (-d) and library files (-i) are required");
+    for (uint32_t i = 0; i < c->n_input; ++i) SH_CHECK(c->input[i], SH_ERR_BAD_ARG, "k2-bracken-build: input %u missing", i);
+    SH_CHECK(c->read_len >= 1, SH_ERR_BAD_ARG, "k2-bracken-build: a read length (-l) is required");
+    memset(res, 0, sizeof(*res));
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto sec = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t0 = now();
+    sh_k2_db *db = nullptr;
+    sh_status st = sh_k2_open(c->db, c->device, &db);
+    if (st != SH_OK) return st;
+    struct DbGuard { sh_k2_db *d; ~DbGuard() { sh_k2_free(d); } } guard{db};
+    sh_k2_distrib *d = nullptr;
+    st = sh_k2_distrib_create(db, c->read_len, &d);
+    if (st != SH_OK) return st;
+    struct DG { sh_k2_distrib *d; ~DG() { sh_k2_distrib_free(d); } } dg{d};
+    sh_k2_taxonomy *tax = nullptr;
+    st = shi_k2_taxonomy_of_nodes(db->nodes.data(), db->nodes.size(), c->seqid2taxid, c->taxid, &tax);
+    if (st != SH_OK) return st;
+    struct TG { sh_k2_taxonomy *t; ~TG() { sh_k2_taxonomy_free(t); } } tg{tax};
+    const uint64_t chunk = std::max<uint64_t>(c->chunk_bytes ? c->chunk_bytes : env_mb("SCRUBBY_HIP_K2_BUILD_CHUNK_MB", 256ull << 20), (uint64_t)(4 * c->read_len));
+    SH_CHECK(chunk < (1ull << 31), SH_ERR_BAD_ARG, "k2-bracken-build: batches of at most 2 GiB");
+    const auto t1 = now();
+    res->s_open = sec(t0, t1);
+    K2DevBatch dev;
+    K2LibCounts cn;
+    st = k2_stream_library(c->input, c->n_input, chunk, c->read_len, true,
+        [&](const std::string &h) -> uint32_t { uint32_t t = 0; sh_k2_taxonomy_header_taxon(tax, h.data(), h.size(), &t); return t; },
+        [&](const K2Batch &b) -> sh_status {
+            sh_status u = dev.upload(b);
+            if (u != SH_OK) return u;
+            const auto g0 = now();
+            sh_k2_distrib_stats ds{};
+            u = sh_k2_distrib_add_device(d, dev.bases, dev.off, dev.taxa, b.taxa.size(), nullptr, &ds);
+            res->s_gpu += sec(g0, now());
+            res->n_windows += ds.n_windows; res->n_items += ds.n_items; res->n_big += ds.n_big;
+            return u;
+        }, cn);
+    if (st != SH_OK) return st;
+    const auto t2 = now();
+    res->s_read = sec(t1, t2) - res->s_gpu;
+    uint64_t ne = 0;
+    st = sh_k2_distrib_count(d, &ne);
+    if (st != SH_OK) return st;
+    std::vector<sh_k2_distrib_entry> entries(std::max<uint64_t>(ne, 1));
+    std::vector<uint64_t> totals(db->nodes.size(), 0);
+    st = sh_k2_distrib_copy(d, entries.data(), totals.data());
+    if (st != SH_OK) return st;
+    std::vector<uint32_t> ext(db->nodes.size());
+    for (size_t i = 0; i < ext.size(); ++i) ext[i] = (uint32_t)db->nodes[i].external_id;
+    const std::string out = c->output ? std::string(c->output) : std::string(c->db) + "/database" + std::to_string(c->read_len) + "mers.kmer_distrib";
+    st = sh_k2_distrib_write(entries.data(), ne, totals.data(), ext.data(), ext.size(), c->read_len, out.c_str());
+    if (st != SH_OK) return st;
+    const auto t3 = now();
+    res->n_records = cn.n_records; res->n_skipped = cn.n_skipped; res->n_bases = cn.n_bases; res->n_batches = cn.n_batches; res->n_cuts = cn.n_cuts;
+    res->n_entries = ne;
+    res->s_write = sec(t2, t3); res->s_total = sec(t0, t3);
     return SH_OK;
 }
 

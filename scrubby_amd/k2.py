@@ -4,6 +4,7 @@ Mirrors what the reference reaches through the external `kraken2` process (Clean
 /root/reference/src/cleaner.rs:288-330).  No CPU path: everything here needs the HIP library and a GPU.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -101,6 +102,38 @@ class K2InspectResult(C.Structure):
                [(n, C.c_double) for n in ("s_open", "s_count", "s_report", "s_total")]
 
 
+class K2DistribStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_windows", C.c_uint64), ("n_items", C.c_uint64), ("n_big", C.c_uint64), ("ms", C.c_float), ("pad", C.c_int32)]
+
+
+class K2BrackenRow(C.Structure):
+    _fields_ = [("taxon", C.c_uint32), ("pad", C.c_uint32), ("assigned", C.c_uint64), ("new_est", C.c_uint64), ("added", C.c_double), ("fraction", C.c_double)]
+
+
+class K2BrackenSummary(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "reads_total", "reads_at_level", "reads_below_threshold", "reads_distributed", "reads_undistributed",
+                                           "new_est_total")]
+
+
+class K2DistribConfig(C.Structure):
+    _fields_ = [("db", C.c_char_p), ("input", C.POINTER(C.c_char_p)), ("n_input", C.c_uint32), ("read_len", C.c_int32), ("seqid2taxid", C.c_char_p),
+                ("taxid", C.c_uint64), ("output", C.c_char_p), ("chunk_bytes", C.c_uint64), ("device", C.c_int32), ("pad", C.c_int32)]
+
+
+class K2DistribResult(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_skipped", "n_bases", "n_batches", "n_cuts", "n_windows", "n_items", "n_big", "n_entries")] + \
+               [(n, C.c_double) for n in ("s_open", "s_gpu", "s_read", "s_write", "s_total")]
+
+
+class K2BrackenConfig(C.Structure):
+    _fields_ = [("db", C.c_char_p), ("report", C.c_char_p), ("read_len", C.c_int32), ("level", C.c_int32), ("threshold", C.c_int64),
+                ("kmer_distrib", C.c_char_p), ("output", C.c_char_p)]
+
+
+class K2BrackenResult(C.Structure):
+    _fields_ = [("summary", K2BrackenSummary), ("n_report_rows", C.c_uint64), ("n_unknown_taxa", C.c_uint64)]
+
+
 INSPECT_ZERO_COUNTS, INSPECT_MPA = 1, 2
 
 RESULT_DTYPE = np.dtype([("taxid", "<u4"), ("call", "<u4"), ("total_kmers", "<u4"), ("hit_groups", "<u4")])
@@ -121,6 +154,11 @@ def format_hits(entries, external, quick=False, quick_taxid=0):
     buf = C.create_string_buffer(n.value + 1)
     S.check(L.sh_k2_format_hits(*args, buf, C.c_uint64(n.value + 1), C.byref(n)))
     return buf.value.decode()
+
+
+# one entry of a k-mer distribution: of the windows of library genome `genome`, `windows` are called `mapped` (internal ids; 0 = unclassified)
+DISTRIB_DTYPE = np.dtype([("genome", "<u4"), ("mapped", "<u4"), ("windows", "<u8")])
+BRACKEN_ROW_DTYPE = np.dtype([("taxon", "<u4"), ("pad", "<u4"), ("assigned", "<u8"), ("new_est", "<u8"), ("added", "<f8"), ("fraction", "<f8")])
 
 
 # k-mers per tile of the wave route (sh_k2_wave_tile; units of at least opts.long_unit_bases bases are classified one wave each)
@@ -444,6 +482,152 @@ def inspect_database(db_dir, output=None, skip_counts=False, report_zero_counts=
     r = K2InspectResult()
     S.check(S.load().sh_k2_inspect_run(C.byref(c), C.byref(r)))
     return {n: getattr(r, n) for n, _ in K2InspectResult._fields_}
+
+
+def distrib_stretch():
+    """window starts per work item of the window kernel (sh_k2_distrib_stretch)"""
+    return int(S.load().sh_k2_distrib_stretch())
+
+
+class KmerDistrib:
+    """bracken-build's k-mer distribution of one database at one read length (sh_k2_distrib), accumulated in HBM: for every
+    window of read_len bases of every library record, what Kraken 2 would call it.  Calls add up in any batching."""
+
+    def __init__(self, db, read_len):
+        S.require_gpu()
+        self.db, self.read_len = db, read_len          # the database must outlive the accumulator
+        self.n_nodes = db.info()["n_nodes"]
+        self.h = C.c_void_p()
+        S.check(S.load().sh_k2_distrib_create(db.h, C.c_int32(read_len), C.byref(self.h)))
+
+    def add_device(self, d_bases, d_offsets, d_taxa, n_records):
+        """sh_k2_distrib_add_device on torch tensors (uint8 bases readable 8 bytes past the end, int64 offsets, int32 taxa);
+        returns the call's statistics"""
+        st = K2DistribStats()
+        S.check(S.load().sh_k2_distrib_add_device(self.h, C.c_void_p(d_bases.data_ptr()), C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_taxa.data_ptr()),
+                                                  C.c_uint64(n_records), S._stream_ptr(), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in K2DistribStats._fields_ if n != "pad"}
+
+    def add_library(self, records, taxa, misalign=0):
+        """One call over a list of sequences, record i under internal taxon taxa[i] (0 = skip).  misalign: the batch's first base
+        sits that many bytes behind an 8-byte boundary."""
+        import torch
+        assert len(records) == len(taxa)
+        d_bases, d_off, n = _library_to_device([b"N" * misalign] + list(records) if misalign else records)
+        t = ([0] if misalign else []) + [int(x) for x in taxa]
+        d_taxa = torch.from_numpy(np.asarray(t + [0], dtype=np.uint32).view(np.int32).copy()).cuda()
+        return self.add_device(d_bases, d_off, d_taxa, n)
+
+    def last_ms(self):
+        """(codes kernel, window kernels) milliseconds of the last call"""
+        a, b = C.c_float(), C.c_float()
+        S.check(S.load().sh_k2_distrib_last_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _copy(self):
+        n = C.c_uint64()
+        S.check(S.load().sh_k2_distrib_count(self.h, C.byref(n)))
+        ent = np.zeros(max(n.value, 1), dtype=DISTRIB_DTYPE)
+        tot = np.zeros(self.n_nodes, dtype=np.uint64)
+        S.check(S.load().sh_k2_distrib_copy(self.h, C.c_void_p(ent.ctypes.data), C.c_void_p(tot.ctypes.data)))
+        return ent[: n.value], tot
+
+    def entries(self):
+        """DISTRIB_DTYPE array sorted by (genome, mapped), unclassified windows (mapped 0) included"""
+        return self._copy()[0]
+
+    def totals(self):
+        """windows per genome (uint64 by internal id), unclassified ones included"""
+        return self._copy()[1]
+
+    def reset(self):
+        S.check(S.load().sh_k2_distrib_reset(self.h))
+
+    def close(self):
+        if self.h:
+            S.load().sh_k2_distrib_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_kmer_distrib(entries, totals, external, read_len, path):
+    """Bracken's database<L>mers.kmer_distrib (sh_k2_distrib_write; host only, no GPU needed): entries = DISTRIB_DTYPE array,
+    totals = windows per genome, external = the taxonomy's external ids, both by internal id"""
+    e = np.ascontiguousarray(entries, dtype=DISTRIB_DTYPE)
+    t = np.ascontiguousarray(totals, dtype=np.uint64)
+    x = np.ascontiguousarray(external, dtype=np.uint32)
+    assert len(t) == len(x), "one total per taxonomy node"
+    S.check(S.load().sh_k2_distrib_write(C.c_void_p(e.ctypes.data), C.c_uint64(len(e)), C.c_void_p(t.ctypes.data), C.c_void_p(x.ctypes.data), C.c_uint64(len(x)),
+                                         C.c_int32(read_len), str(path).encode()))
+
+
+def read_kmer_distrib(path, external):
+    """(entries, totals) of a kmer_distrib file (sh_k2_distrib_read; host only): entries sorted by (genome, mapped), internal ids"""
+    x = np.ascontiguousarray(external, dtype=np.uint32)
+    n = C.c_uint64()
+    head = (str(path).encode(), C.c_void_p(x.ctypes.data), C.c_uint64(len(x)))
+    tot = np.zeros(len(x), dtype=np.uint64)
+    # room for every (genome, mapped) pair the file can hold is not known before it is read: size from its bytes (an entry has 5 at least)
+    cap = os.path.getsize(path) // 5 + 1
+    ent = np.zeros(cap, dtype=DISTRIB_DTYPE)
+    S.check(S.load().sh_k2_distrib_read(*head, C.c_void_p(ent.ctypes.data), C.c_uint64(cap), C.byref(n), C.c_void_p(tot.ctypes.data)))
+    return ent[: n.value].copy(), tot
+
+
+def bracken_estimate(nodes, ranks, direct_reads, entries, totals, level="S", threshold=10):
+    """Bracken's estimate (sh_k2_bracken_estimate; host only) over a taxonomy in taxo.k2d's layout: (rows, summary) with rows a
+    BRACKEN_ROW_DTYPE array by ascending internal id of the kept taxa and summary a dict"""
+    d = np.ascontiguousarray(direct_reads, dtype=np.uint64)
+    e = np.ascontiguousarray(entries, dtype=DISTRIB_DTYPE)
+    t = np.ascontiguousarray(totals, dtype=np.uint64)
+    assert len(d) == len(nodes) and len(t) == len(nodes), "one value per taxonomy node"
+    rows = np.zeros(len(nodes), dtype=BRACKEN_ROW_DTYPE)
+    sm = K2BrackenSummary()
+    S.check(S.load().sh_k2_bracken_estimate(nodes, C.c_uint64(len(nodes)), ranks, C.c_uint64(len(ranks)), C.c_void_p(d.ctypes.data), C.c_void_p(e.ctypes.data),
+                                            C.c_uint64(len(e)), C.c_void_p(t.ctypes.data), C.c_int32(ord(level)), C.c_uint64(threshold),
+                                            C.c_void_p(rows.ctypes.data), C.byref(sm)))
+    return rows[: sm.n_rows].copy(), {n: getattr(sm, n) for n, _ in K2BrackenSummary._fields_}
+
+
+def write_bracken(nodes, names, rows, level, path):
+    """Bracken's output table (sh_k2_bracken_write; host only)"""
+    r = np.ascontiguousarray(rows, dtype=BRACKEN_ROW_DTYPE)
+    S.check(S.load().sh_k2_bracken_write(nodes, C.c_uint64(len(nodes)), names, C.c_uint64(len(names)), C.c_void_p(r.ctypes.data), C.c_uint64(len(r)),
+                                         C.c_int32(ord(level)), None if path is None else str(path).encode()))
+
+
+def build_kmer_distrib(db_dir, inputs, read_len, seqid2taxid=None, taxid=0, output=None, chunk_bytes=0, device=0):
+    """`scrubby-hip k2-bracken-build` (sh_k2_distrib_run): the k-mer distribution of a database directory at one read length over
+    library FASTA files, written to `output` or <db>/database<L>mers.kmer_distrib; returns the result fields as a dict."""
+    S.require_gpu()
+    c = K2DistribConfig()
+    files = [inputs] if isinstance(inputs, (str, bytes)) or hasattr(inputs, "__fspath__") else list(inputs)
+    arr = (C.c_char_p * len(files))(*[str(f).encode() for f in files])
+    c.db, c.input, c.n_input, c.read_len = str(db_dir).encode(), arr, len(files), read_len
+    c.seqid2taxid = str(seqid2taxid).encode() if seqid2taxid else None
+    c.taxid, c.output, c.chunk_bytes, c.device = taxid, str(output).encode() if output else None, chunk_bytes, device
+    r = K2DistribResult()
+    S.check(S.load().sh_k2_distrib_run(C.byref(c), C.byref(r)))
+    return {n: getattr(r, n) for n, _ in K2DistribResult._fields_}
+
+
+def bracken(db_dir, report, output, read_len=0, level="S", threshold=10, kmer_distrib=None):
+    """`scrubby-hip k2-bracken` (sh_k2_bracken_run; host only): re-estimates one sample from its kraken.report; returns the
+    summary fields, n_report_rows and n_unknown_taxa as a dict."""
+    c = K2BrackenConfig()
+    c.db, c.report, c.output = str(db_dir).encode(), str(report).encode(), str(output).encode()
+    c.read_len, c.level, c.threshold = read_len, ord(level), threshold
+    c.kmer_distrib = str(kmer_distrib).encode() if kmer_distrib else None
+    r = K2BrackenResult()
+    S.check(S.load().sh_k2_bracken_run(C.byref(c), C.byref(r)))
+    out = {n: getattr(r.summary, n) for n, _ in K2BrackenSummary._fields_}
+    out.update(n_report_rows=r.n_report_rows, n_unknown_taxa=r.n_unknown_taxa)
+    return out
 
 
 class K2Db:
