@@ -17,6 +17,7 @@
 #pragma once
 #include "sh_common.h"
 #include "sh_wave.h"
+#include "sh_ksw_band.h"
 
 #define KSW_NEG_INF (-0x40000000)
 #define EZ_RIGHT 0x02
@@ -202,9 +203,17 @@ struct AlignLdsT {
 typedef AlignLdsT<AL_R, AL_PRI> AlignLds;
 typedef AlignLdsT<16, 16> AlignLdsTop;
 
+// DBG_STATS: where a wave of the regs[0] pass spends its time (100-MHz ticks per phase, summed over the launch's waves) and what its
+// ksw_extd2 calls look like.  hist: [0..7] calls by T16 (<= 16, 32, 64, 128, 256, AL_T16, more), [8..15] by Q16 (.. 256, AL_Q16, more),
+// [16..19] by direction bytes (<= AL_P, <= 2 AL_P + 1648: what kmem, kH and kp hold together, <= 32 KiB, more), 20 calls, 21 calls with
+// T16 <= 256, Q16 <= AL_Q16 and the exact maximum (four cells per lane would cover the target), 22 reads; diag: anti-diagonals by the T16 bins.
+enum { ACLK_FILL = 0, ACLK_BACKTRACK = 1, ACLK_STAGING = 2, ACLK_LANE0 = 3, ACLK_OTHER = 4, ACLK_N = 5 };
+struct AlignClk { unsigned long long t[ACLK_N], last; uint32_t *hist; unsigned long long *diag; };
+
 struct AlignScratch {       // one per wave, in HBM; sized by the host from max_read_len (align_scratch_bytes)
+    AlignClk *clk = nullptr;      // the launch's clocks when it counts (read by the CLK instances alone: al_tick<true>)
     uint8_t *qseq, *tseq, *kmem, *kp;
-    int32_t *kH, *koff;
+    int32_t *kH, *koff;      // koff: unused since the band is computed (ksw_band); it keeps its place in the layout
     uint32_t *ez_cigar, *r_cigar;
     RegLite *regs;
     uint64_t *kz, *kx, *kk;
@@ -251,6 +260,23 @@ __device__ inline void align_scratch_carve(AlignScratch &A, uint8_t *p, uint32_t
     A.kp = take(pcap);
 }
 
+template <bool CLK>
+__device__ inline void al_tick(AlignScratch &A, int ph)
+{
+    if constexpr (CLK) { const unsigned long long now = wall_clock64(); A.clk->t[ph] += now - A.clk->last; A.clk->last = now; }
+}
+__device__ inline void al_count_call(AlignScratch &A, int32_t qlen, int32_t tlen, unsigned long long p_need, int32_t flag)
+{
+    if (al_lane() != 0) return;
+    const int32_t T16 = (tlen + 15) / 16 * 16, Q16 = (qlen + 15) / 16 * 16;
+    auto bin = [](int32_t v, int32_t cap) { return v <= 16 ? 0 : v <= 32 ? 1 : v <= 64 ? 2 : v <= 128 ? 3 : v <= 256 ? 4 : v <= cap ? 5 : 6; };
+    atomicAdd(&A.clk->hist[bin(T16, AL_T16)], 1u); atomicAdd(&A.clk->hist[8 + bin(Q16, AL_Q16)], 1u);
+    atomicAdd(&A.clk->hist[16 + (p_need <= AL_P ? 0 : p_need <= 2 * AL_P + 1648 ? 1 : p_need <= 32768 ? 2 : 3)], 1u);
+    atomicAdd(&A.clk->hist[20], 1u);
+    if (T16 <= 256 && Q16 <= AL_Q16 && !(flag & EZ_APPROX_MAX)) atomicAdd(&A.clk->hist[21], 1u);
+    atomicAdd(&A.clk->diag[bin(T16, AL_T16)], (unsigned long long)(qlen + tlen - 1));
+}
+
 struct Ez { int32_t max, zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, reach_end, n_cigar; };
 
 __device__ inline void ez_reset(Ez &ez)
@@ -261,9 +287,10 @@ __device__ inline void ez_reset(Ez &ez)
 }
 
 // ksw_backtrack (rotated).  Every lane runs the walk on the same data (uniform loads); the cigar array is written by lane 0
-// alone, which is also its only later reader; the merge test works on a register copy of the last word.
+// alone, which is also its only later reader; the merge test works on a register copy of the last word.  The rounded range of each
+// anti-diagonal comes from ksw_band (w: resolved): a few scalar instructions instead of two loads from the wave's scratch per step.
 template <class RD>
-__device__ inline void ksw_backtrack_dev(bool is_rev, RD rd, const int32_t *off, const int32_t *off_end, int32_t n_col, int32_t i0, int32_t j0,
+__device__ inline void ksw_backtrack_dev(bool is_rev, RD rd, int32_t qlen, int32_t tlen, int32_t w, int32_t n_col, int32_t i0, int32_t j0,
                                          uint32_t *cigar, int32_t &n_cigar_out)
 {
     int32_t n = 0, i = i0, j = j0, state = 0;
@@ -276,7 +303,8 @@ __device__ inline void ksw_backtrack_dev(bool is_rev, RD rd, const int32_t *off,
     while (i >= 0 && j >= 0) {
         int32_t force_state = -1;
         const int32_t r = i + j;
-        const int32_t o = (int32_t)cc_u32(off + r), oe = (int32_t)cc_u32(off_end + r);
+        const KswBand bd = ksw_band(r, qlen, tlen, w);
+        const int32_t o = bd.st, oe = bd.en;
         if (i < o) force_state = 2;
         if (i > oe) force_state = 1;
         const uint32_t tmp = force_state < 0 ? rd((unsigned long long)r * (unsigned long long)n_col + (unsigned long long)(i - o)) : 0u;
@@ -300,7 +328,7 @@ __device__ inline void ksw_backtrack_dev(bool is_rev, RD rd, const int32_t *off,
 // G = the buffers are the wave's HBM scratch; false = LDS (every pointer then derives from Ls alone, so the accesses compile to ds_*)
 // G: the DP state (u v x y x2 y2 s | sf | qr, H) in the wave's HBM scratch instead of LDS; GP: the direction bytes there.  Three forms: all in
 // LDS (short extensions), state in LDS + directions in HBM (written once, read by the backtrack only), all in HBM (beyond AL_T16 / AL_Q16).
-template <bool G, bool GP, class LDS>
+template <bool G, bool GP, class LDS, bool CLK = false>
 __device__ inline void ksw_extd2_core(int32_t qlen, const uint8_t *query, bool qg, int32_t tlen, const uint8_t *target, bool tg,
                                       int8_t sc_mch, int8_t sc_mis, int8_t sc_N, int32_t q, int32_t e, int32_t q2, int32_t e2, int32_t w,
                                       int32_t zdrop, int32_t end_bonus, int32_t flag, Ez &ez, uint32_t *cigar, AlignScratch &A, LDS &Ls)
@@ -311,7 +339,7 @@ __device__ inline void ksw_extd2_core(int32_t qlen, const uint8_t *query, bool q
     if (qlen <= 0 || tlen <= 0) return;
     if (q2 + e2 < q + e) { int32_t t = q; q = q2; q2 = t; t = e; e = e2; e2 = t; }
     const int32_t qe = q + e, qe2 = q2 + e2;
-    if (w < 0) w = tlen > qlen ? tlen : qlen;
+    w = ksw_band_width(qlen, tlen, w);
     const int32_t tlen_ = (tlen + 15) / 16, qlen_ = (qlen + 15) / 16, T16 = tlen_ * 16;
     int32_t n_col_ = qlen < tlen ? qlen : tlen;
     n_col_ = ((n_col_ < w + 1 ? n_col_ : w + 1) + 15) / 16 + 1;
@@ -330,7 +358,6 @@ __device__ inline void ksw_extd2_core(int32_t qlen, const uint8_t *query, bool q
     uint8_t *mem = G ? A.kmem : Ls.kmem;
     int32_t *H = G ? A.kH : Ls.kH;
     uint8_t *p = GP ? A.kp : Ls.kp;
-    int32_t *off = A.koff, *off_end = A.koff + (qlen + tlen);
     int8_t *u = (int8_t *)mem, *v = u + T16, *x = v + T16, *y = x + T16, *x2 = y + T16, *y2 = x2 + T16, *s = y2 + T16;
     uint8_t *sf = (uint8_t *)(s + T16), *qr = sf + T16;
     const int32_t qr_cap = qlen_ * 16 + 16;
@@ -346,14 +373,9 @@ __device__ inline void ksw_extd2_core(int32_t qlen, const uint8_t *query, bool q
 
     int32_t last_st = -1, last_en = -1, r, H0 = 0, last_H0_t = 0;
     for (r = 0; r < qlen + tlen - 1; ++r) {
-        int32_t st = 0, en = tlen - 1;
-        if (st < r - qlen + 1) st = r - qlen + 1;
-        if (en > r) en = r;
-        if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-        if (en > (r + w) >> 1) en = (r + w) >> 1;
-        if (st > en) { ez.zdropped = 1; break; }
-        const int32_t st0 = st, en0 = en;
-        st = st / 16 * 16; en = (en + 16) / 16 * 16 - 1;
+        const KswBand bd = ksw_band(r, qlen, tlen, w);
+        if (bd.st0 > bd.en0) { ez.zdropped = 1; break; }
+        const int32_t st0 = bd.st0, en0 = bd.en0, st = bd.st, en = bd.en;
         int8_t x1, x21, v1;
         if (st > 0) {
             if (st - 1 >= last_st && st - 1 <= last_en) { x1 = ld8s(x + st - 1, g); x21 = ld8s(x2 + st - 1, g); v1 = ld8s(v + st - 1, g); }
@@ -380,7 +402,6 @@ __device__ inline void ksw_extd2_core(int32_t qlen, const uint8_t *query, bool q
                 }
             }
         }
-        if (lane == 0) { off[r] = st; off_end[r] = en; }
         dsync();
         if (en - st + 1 > AL_WIDE_MIN) {
             // core loop over the rounded range, FOUR cells per lane (256 a step: the state arrays move as dwords - the byte-wide form issued
@@ -559,17 +580,19 @@ __device__ inline void ksw_extd2_core(int32_t qlen, const uint8_t *query, bool q
         last_st = st; last_en = en;
     }
     al_sync();
+    al_tick<CLK>(A, ACLK_FILL);
     auto rd = [&](unsigned long long i) -> uint32_t { return in_lds ? (uint32_t)p[i] : (uint32_t)cc_u8(p + i); };
     const bool rev_cigar = (flag & EZ_REV_CIGAR) != 0;
-    if (!ez.zdropped && !(flag & EZ_EXTZ_ONLY)) ksw_backtrack_dev(rev_cigar, rd, off, off_end, n_col, tlen - 1, qlen - 1, cigar, ez.n_cigar);
+    if (!ez.zdropped && !(flag & EZ_EXTZ_ONLY)) ksw_backtrack_dev(rev_cigar, rd, qlen, tlen, w, n_col, tlen - 1, qlen - 1, cigar, ez.n_cigar);
     else if (!ez.zdropped && (flag & EZ_EXTZ_ONLY) && ez.mqe + end_bonus > ez.max) {
         ez.reach_end = 1;
-        ksw_backtrack_dev(rev_cigar, rd, off, off_end, n_col, ez.mqe_t, qlen - 1, cigar, ez.n_cigar);
-    } else if (ez.max_t >= 0 && ez.max_q >= 0) ksw_backtrack_dev(rev_cigar, rd, off, off_end, n_col, ez.max_t, ez.max_q, cigar, ez.n_cigar);
+        ksw_backtrack_dev(rev_cigar, rd, qlen, tlen, w, n_col, ez.mqe_t, qlen - 1, cigar, ez.n_cigar);
+    } else if (ez.max_t >= 0 && ez.max_q >= 0) ksw_backtrack_dev(rev_cigar, rd, qlen, tlen, w, n_col, ez.max_t, ez.max_q, cigar, ez.n_cigar);
     al_sync();
+    al_tick<CLK>(A, ACLK_BACKTRACK);
 }
 
-template <class LDS>
+template <class LDS, bool CLK = false>
 __device__ inline void ksw_extd2_wave(int32_t qlen, const uint8_t *query, bool qg, int32_t tlen, const uint8_t *target, bool tg,
                                       int8_t sc_mch, int8_t sc_mis, int8_t sc_N, int32_t q, int32_t e, int32_t q2, int32_t e2, int32_t w,
                                       int32_t zdrop, int32_t end_bonus, int32_t flag, Ez &ez, uint32_t *cigar, AlignScratch &A, LDS &Ls)
@@ -579,9 +602,10 @@ __device__ inline void ksw_extd2_wave(int32_t qlen, const uint8_t *query, bool q
     nc = (((nc < ww + 1 ? nc : ww + 1) + 15) / 16 + 1) * 16;
     const bool mem_lds = qlen > 0 && tlen > 0 && T16 <= AL_T16 && Q16 <= AL_Q16;
     const bool p_lds = mem_lds && (unsigned long long)(qlen + tlen - 1) * (unsigned long long)nc <= AL_P;
-    if (p_lds) ksw_extd2_core<false, false>(qlen, query, qg, tlen, target, tg, sc_mch, sc_mis, sc_N, q, e, q2, e2, w, zdrop, end_bonus, flag, ez, cigar, A, Ls);
-    else if (mem_lds) ksw_extd2_core<false, true>(qlen, query, qg, tlen, target, tg, sc_mch, sc_mis, sc_N, q, e, q2, e2, w, zdrop, end_bonus, flag, ez, cigar, A, Ls);
-    else ksw_extd2_core<true, true>(qlen, query, qg, tlen, target, tg, sc_mch, sc_mis, sc_N, q, e, q2, e2, w, zdrop, end_bonus, flag, ez, cigar, A, Ls);
+    if constexpr (CLK) if (qlen > 0 && tlen > 0) al_count_call(A, qlen, tlen, (unsigned long long)(qlen + tlen - 1) * (unsigned long long)nc, flag);
+    if (p_lds) ksw_extd2_core<false, false, LDS, CLK>(qlen, query, qg, tlen, target, tg, sc_mch, sc_mis, sc_N, q, e, q2, e2, w, zdrop, end_bonus, flag, ez, cigar, A, Ls);
+    else if (mem_lds) ksw_extd2_core<false, true, LDS, CLK>(qlen, query, qg, tlen, target, tg, sc_mch, sc_mis, sc_N, q, e, q2, e2, w, zdrop, end_bonus, flag, ez, cigar, A, Ls);
+    else ksw_extd2_core<true, true, LDS, CLK>(qlen, query, qg, tlen, target, tg, sc_mch, sc_mis, sc_N, q, e, q2, e2, w, zdrop, end_bonus, flag, ez, cigar, A, Ls);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -800,7 +824,7 @@ __device__ inline int32_t top_chain_settles(const AlignIn &in, const AlignParams
 // `mappings.len() > 0`); else every region is aligned and the counts / fingerprint are those of the oracle's trace.
 // top_z != 0: only the chain with that z - regs[0] of mm_gen_regs, which is aligned whatever the other chains are - goes through
 // mm_align1; a surviving region settles the read (n_regs > 0), none means the caller must run the full procedure on all chains.
-template <class LDS>
+template <class LDS, bool CLK = false>
 __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, uint32_t read, bool flag_only, AlignScratch &A, LDS &Ls,
                                        AlignOut &out, uint32_t *overflow, unsigned long long top_z = 0)
 {
@@ -949,6 +973,8 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
     if (ld32((const int32_t *)overflow, true) != 0) return false;
 
     // ---- mm_align_skeleton ---------------------------------------------------------------------------------------
+    al_tick<CLK>(A, ACLK_OTHER);
+    if constexpr (CLK) if (lane == 0) atomicAdd(&A.clk->hist[22], 1u);
     const bool sg = qlen > AL_Q;                 // query codes / reference window in HBM scratch
     uint8_t *qseq0 = sg ? A.qseq : Ls.qseq, *tseq = sg ? A.tseq : Ls.tseq;
     if (sg && ((uint32_t)qlen > A.qcap)) { if (lane == 0) atomicExch(overflow, 4u); return false; }
@@ -961,6 +987,7 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
         }
         al_sync();
     }
+    al_tick<CLK>(A, ACLK_STAGING);
     const int8_t sc_mch = (int8_t)(P.a < 0 ? -P.a : P.a), sc_mis = (int8_t)(P.b > 0 ? -P.b : P.b), sc_amb = (int8_t)(P.sc_ambi > 0 ? -P.sc_ambi : P.sc_ambi);
     const int8_t sc_N = sc_amb == 0 ? (int8_t)(-P.e2) : sc_amb;      // ksw_extd2: sc_N = mat[24] == 0 ? -e2 : mat[24]; every other user reads mat[24]
     const int32_t bw = (int32_t)(P.bw * 1.5 + 1.);
@@ -999,6 +1026,7 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
             as1 = max_i; cnt1 = max_len;
         }
         as1 = al_b0(as1); cnt1 = al_b0(cnt1);
+        al_tick<CLK>(A, ACLK_LANE0);
         const unsigned long long sa = r.as + (unsigned long long)as1;        // first anchor of the stretch
         int32_t rs = (int32_t)in.cx[sa] + 1 - P.k, qs = (int32_t)in.cq[sa] + 1 - P.k;
         int32_t re = (int32_t)in.cx[sa + cnt1 - 1] + 1, qe = (int32_t)in.cq[sa + cnt1 - 1] + 1;
@@ -1018,18 +1046,21 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
             getseq_wave(in, rid, rs0, rs, tseq);
             seq_rev_wave(qs - qs0, qrow + qs0, sg);
             seq_rev_wave(rs - rs0, tseq, sg);
-            ksw_extd2_wave(qs - qs0, qrow + qs0, sg, rs - rs0, tseq, sg, sc_mch, sc_mis, sc_N, P.q, P.e, P.q2, P.e2, bw, P.zdrop, P.end_bonus,
+            al_tick<CLK>(A, ACLK_STAGING);
+            ksw_extd2_wave<LDS, CLK>(qs - qs0, qrow + qs0, sg, rs - rs0, tseq, sg, sc_mch, sc_mis, sc_N, P.q, P.e, P.q2, P.e2, bw, P.zdrop, P.end_bonus,
                            EZ_EXTZ_ONLY | EZ_RIGHT | EZ_REV_CIGAR, ez, ezc, A, Ls);
             if (lane == 0 && ez.n_cigar > 0) append_cigar0(rc, rn, ez.n_cigar, ezc);
             rs1 = rs - (ez.reach_end ? ez.mqe_t + 1 : ez.max_t + 1);
             qs1 = qs - (ez.reach_end ? qs - qs0 : ez.max_q + 1);
             seq_rev_wave(qs - qs0, qrow + qs0, sg);
+            al_tick<CLK>(A, ACLK_STAGING);
         } else { rs1 = rs; qs1 = qs; }
         re1 = rs; qe1 = qs;
         {   // gap filling: the whole stretch, ungapped
             re = (int32_t)in.cx[sa + cnt1 - 1] + 1; qe = (int32_t)in.cq[sa + cnt1 - 1] + 1;
             re1 = re; qe1 = qe;
             getseq_wave(in, rid, rs, re, tseq);
+            al_tick<CLK>(A, ACLK_STAGING);
             // mm_test_zdrop on one M of qe - qs (lane 0)
             int32_t zcode = 0;
             if (lane == 0) {
@@ -1044,9 +1075,10 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
                 ezc[0] = (uint32_t)(qe - qs) << 4;
             }
             zcode = al_b0(zcode);
+            al_tick<CLK>(A, ACLK_LANE0);
             ez_reset(ez); ez.n_cigar = 1;
             if (zcode != 0)
-                ksw_extd2_wave(qe - qs, qrow + qs, sg, re - rs, tseq, sg, sc_mch, sc_mis, sc_N, P.q, P.e, P.q2, P.e2, bw_long, P.zdrop, -1, 0, ez, ezc, A, Ls);
+                ksw_extd2_wave<LDS, CLK>(qe - qs, qrow + qs, sg, re - rs, tseq, sg, sc_mch, sc_mis, sc_N, P.q, P.e, P.q2, P.e2, bw_long, P.zdrop, -1, 0, ez, ezc, A, Ls);
             if (lane == 0 && ez.n_cigar > 0) append_cigar0(rc, rn, ez.n_cigar, ezc);
             if (ez.zdropped) {
                 int32_t j = cnt1 - 2;
@@ -1061,10 +1093,12 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
                     if (n > 0 && n < r.cnt) { split_n = n; r2_cnt = r.cnt - n; }
                 }
             } else { rs = re; qs = qe; }
+            al_tick<CLK>(A, ACLK_LANE0);
         }
         if (!dropped && qe < qe0 && re < re0) {   // right extension
             getseq_wave(in, rid, re, re0, tseq);
-            ksw_extd2_wave(qe0 - qe, qrow + qe, sg, re0 - re, tseq, sg, sc_mch, sc_mis, sc_N, P.q, P.e, P.q2, P.e2, bw, P.zdrop, P.end_bonus, EZ_EXTZ_ONLY, ez, ezc, A, Ls);
+            al_tick<CLK>(A, ACLK_STAGING);
+            ksw_extd2_wave<LDS, CLK>(qe0 - qe, qrow + qe, sg, re0 - re, tseq, sg, sc_mch, sc_mis, sc_N, P.q, P.e, P.q2, P.e2, bw, P.zdrop, P.end_bonus, EZ_EXTZ_ONLY, ez, ezc, A, Ls);
             if (lane == 0 && ez.n_cigar > 0) append_cigar0(rc, rn, ez.n_cigar, ezc);
             re1 = re + (ez.reach_end ? ez.mqe_t + 1 : ez.max_t + 1);
             qe1 = qe + (ez.reach_end ? qe0 - qe : ez.max_q + 1);
@@ -1086,7 +1120,9 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
         r.rs = rs1; r.re = re1;
         if (rev) { r.qs = qlen - qe1; r.qe = qlen - qs1; } else { r.qs = qs1; r.qe = qe1; }
         // mm_update_extra + this region's share of mm_filter_regs (lane 0)
+        al_tick<CLK>(A, ACLK_LANE0);      // the CIGAR appends, a split
         getseq_wave(in, rid, rs1, re1, tseq);
+        al_tick<CLK>(A, ACLK_STAGING);
         int32_t keep = 0, mlen = 0, blen = 0, dpm = 0;
         if (lane == 0) {
             update_extra0(r, rc, rn, qrow + qs1, sg, tseq, sg, P, mlen, blen, dpm);
@@ -1104,6 +1140,7 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
             }
         }
         keep = al_b0(keep);
+        al_tick<CLK>(A, ACLK_LANE0);
         if (keep && flag_only) { out.n_regs = 1; return true; }
     }
     out.n_regs = al_b0(n_keep); out.dp_max = al_b0(dp_best); out.sig = out.n_regs > 0 ? (uint32_t)al_b0((int32_t)sig) : 0u;

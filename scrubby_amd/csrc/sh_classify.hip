@@ -101,6 +101,7 @@ struct Counters {
     uint32_t n_locus[3], locus_ticket[3], lr_n_fb, lr_locus_reads; unsigned long long lr_locus_in, lr_locus_kept;
     uint32_t lr_fb_why[8], lr_fb_had, lr_pad, lr_probe_why[8];
     uint32_t lext_n_unres, lext_ticket_unres, lext_n_unres_in, lext_pad4, lext_n_exact, lext_ticket_exact, lext_rmq_open, lext_pad5;      // reads beyond the stage's second working-memory size: redone with memory allocated for them
+    unsigned long long ext_clk[8], ext_diag[8]; uint32_t ext_hist[24];      // DBG_STATS, k_regs_align_top_stats (AlignClk): contiguous, cleared together
     unsigned long long lext_slow2, lext_slow3, lext_slow_part[4], lext_sum_part[4], lext_clk_big[LR_NCLK], lext_d_big[8], lext_phase_max[LR_NCLK];
     uint32_t lext_started, lext_t0_done;      // SCRUBBY_HIP_DBG: the slowest read of the chains kernel (time << 32 | read length / read)
     unsigned long long stage_cursor;      // k_expand's raw anchors of the reads k_lr_locus will thin out (their own buffer: 12 B per anchor)
@@ -2820,14 +2821,48 @@ struct ExtArgs {
     const unsigned long long *best; const uint32_t *tie;      // first pass of a flag-only call: decide from the top chain, or queue for the full pass
     uint32_t *redo, *redo2; int32_t top_only;                 // k_regs_align, top_only: align regs[0] alone; reads it does not settle go to redo2
     uint32_t *unres_list, *n_unres;                           // k_regs_align: reads with more chains / regions than this launch's working memory holds (redone with more)
+    int32_t stats;                                            // DBG_STATS: k_regs_align_top clocks its phases and counts its ksw_extd2 calls (Counters::ext_clk ..)
 };
 
-__global__ void k_ext_list(ExtArgs a)
+// Persistent: a wave takes slabs of EXT_SLAB consecutive reads.  It keeps a slab's 64 ballots (lane k holds the one of reads
+// [64 k, 64 k + 64)), reserves the slab's stretch of the list with ONE atomic and writes its reads there in ascending order: a few thousand
+// atomics on the counter for a 20 M-read chunk where an append per wave of 64 reads made one for every wave that held a hit.  The order of
+// the list differs from launch to launch (slabs land in the order of their atomics), as it did; nothing downstream reads it as an order.
+#define EXT_SLAB 4096
+#define EXT_LIST_BLOCKS 2048
+__global__ __launch_bounds__(256) void k_ext_list(ExtArgs a)
 {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool has = r < a.n_reads && a.in.head[r] != ~0u;
-    const uint32_t li = wave_append(a.n_list, has);
-    if (has) a.list[li] = (uint32_t)r;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t base = wave * EXT_SLAB; base < a.n_reads; base += n_waves * EXT_SLAB) {
+        uint64_t mine = 0;
+        for (uint32_t k0 = 0; k0 < 64; k0 += 16) {      // sixteen independent loads in flight per lane
+            uint32_t h[16];
+#pragma unroll
+            for (uint32_t u = 0; u < 16; ++u) {
+                const uint64_t r = base + (uint64_t)(k0 + u) * 64 + lane;
+                h[u] = r < a.n_reads ? a.in.head[r] : ~0u;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 16; ++u) {
+                const uint64_t m = __ballot(h[u] != ~0u);
+                if (lane == k0 + u) mine = m;
+            }
+        }
+        const uint32_t cnt = (uint32_t)__popcll(mine);
+        const uint32_t incl = (uint32_t)wave_scan_add_incl((int32_t)cnt);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int32_t)incl, 63);
+        if (total == 0) continue;
+        uint32_t li = 0;
+        if (lane == 0) li = atomicAdd(a.n_list, total);
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)li) + incl - cnt;      // of this lane's 64 reads
+        for (int k = 0; k < 64; ++k) {
+            const uint64_t m = wave_readlane_u64(mine, k);
+            if (m == 0) continue;
+            const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int32_t)first, k);
+            if (m >> lane & 1) a.list[o + prefix_popc(m)] = (uint32_t)(base + (uint64_t)k * 64 + lane);
+        }
+    }
 }
 
 // flag-only first pass, one LANE per read of the list: regs[0] settles nearly every read (top_chain_settles); the others are queued
@@ -2933,13 +2968,16 @@ __global__ __launch_bounds__(64) void k_regs_align(ExtArgs a)
 // regs[0] alone (flag-only second pass): one chain, a handful of regions - a third less LDS per wave than k_regs_align, half as many waves
 // again per CU.  A read that outgrows the small arrays is not an error here: it joins the reads regs[0] did not settle (redo2) and
 // meets the full-size kernel there.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_regs_align_top(ExtArgs a)
+template <bool CLK>
+__device__ inline void regs_align_top_body(const ExtArgs &a)
 {
     __shared__ AlignLdsTop Ls;
     __shared__ uint32_t s_ovf;
     const uint32_t lane = threadIdx.x;
     AlignScratch A;
     align_scratch_carve(A, a.scratch + (unsigned long long)blockIdx.x * a.scratch_per_wave, a.max_read_len, a.reg_cap);
+    AlignClk clk{};
+    if constexpr (CLK) { A.clk = &clk; clk.hist = a.ctr->ext_hist; clk.diag = a.ctr->ext_diag; clk.last = wall_clock64(); }
     const uint32_t n_list = *a.n_list;
     uint32_t n_regions = 0;
     for (;;) {
@@ -2950,7 +2988,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         __syncthreads();
         const uint32_t r = a.list[t];
         AlignOut o;
-        const bool done = align_read_wave(a.in, a.P, r, true, A, Ls, o, &s_ovf, a.best[r]);
+        const bool done = align_read_wave<AlignLdsTop, CLK>(a.in, a.P, r, true, A, Ls, o, &s_ovf, a.best[r]);
         if (lane == 0) {
             if (done && o.n_regs > 0) a.flags[r] = 1;
             else a.redo2[atomicAdd(&a.ctr->ext_n_redo2, 1u)] = r;
@@ -2959,7 +2997,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         __syncthreads();
     }
     if (lane == 0 && n_regions) atomicAdd(&a.ctr->ext_regions, n_regions);
+    if constexpr (CLK) { al_tick<true>(A, ACLK_OTHER); if (lane == 0) for (int i = 0; i < ACLK_N; ++i) atomicAdd(&a.ctr->ext_clk[i], clk.t[i]); }
 }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_regs_align_top(ExtArgs a) { regs_align_top_body<false>(a); }
+// the same with the phase clocks and the call statistics running (DBG_STATS)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_regs_align_top_stats(ExtArgs a) { regs_align_top_body<true>(a); }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -4485,7 +4527,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             return SH_OK;
         };
         SH_HIP(hipEventRecord(c->ev_ext[0], s));
-        hipLaunchKernelGGL(k_ext_list, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, s, x);
+        hipLaunchKernelGGL(k_ext_list, dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_reads + 4 * EXT_SLAB - 1) / (4 * EXT_SLAB), 1), EXT_LIST_BLOCKS)), dim3(256), 0, s, x);
         if (d_trace != nullptr) {
             // trace mode: every read that handed over a chain goes through mm_gen_regs .. mm_filter_regs (one wave per read)
             hipLaunchKernelGGL(k_regs_align, dim3(c->ext_waves), dim3(64), 0, s, x);
@@ -4509,13 +4551,28 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             ExtArgs x1 = x;
             x1.list = c->d_ext_redo; x1.n_list = &c->d_ctr->ext_n_redo; x1.ticket = &c->d_ctr->ext_ticket2; x1.top_only = 1; x1.redo2 = c->d_ext_list;     // the first list is spent
             x1.scratch_per_wave = c->ext_scratch_per_wave_top; x1.reg_cap = 64;
-            hipLaunchKernelGGL(k_regs_align_top, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
+            x1.stats = (cs.dbg & DBG_STATS) != 0;
+            if (x1.stats) {
+                SH_HIP(hipMemsetAsync(c->d_ctr->ext_clk, 0, sizeof(c->d_ctr->ext_clk) + sizeof(c->d_ctr->ext_diag) + sizeof(c->d_ctr->ext_hist), s));
+                hipLaunchKernelGGL(k_regs_align_top_stats, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
+            } else hipLaunchKernelGGL(k_regs_align_top, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
             SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
             SH_HIP(hipStreamSynchronize(s));
             SH_HIP(hipGetLastError());
             SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
             n_redo2 = c->h_ctr->ext_n_redo2;
             c->dbg_ptr[2] = c->d_ext_list; c->dbg_n[2] = n_redo2;
+            if (x1.stats) {
+                const Counters &h = *c->h_ctr;
+                unsigned long long tot = 0;
+                for (int i = 0; i < ACLK_N; ++i) tot += h.ext_clk[i];
+                fprintf(stderr, "[dbg] k_regs_align_top, %u waves: ksw fill %.1f  ksw backtrack %.1f  staging %.1f  lane-0 walks %.1f  other %.1f %% of %.3f wave-s; %u reads, %u ksw_extd2 calls (%u with T16 <= 256, Q16 <= 336 and the exact maximum)\n",
+                        c->ext_waves_top, 100. * h.ext_clk[0] / (tot + 1), 100. * h.ext_clk[1] / (tot + 1), 100. * h.ext_clk[2] / (tot + 1), 100. * h.ext_clk[3] / (tot + 1), 100. * h.ext_clk[4] / (tot + 1), tot / 1e8, h.ext_hist[22], h.ext_hist[20], h.ext_hist[21]);
+                fprintf(stderr, "[dbg] ksw_extd2 calls by T16 (<= 16, 32, 64, 128, 256, 448, more): %u %u %u %u %u %u %u; anti-diagonals: %llu %llu %llu %llu %llu %llu %llu\n", h.ext_hist[0], h.ext_hist[1], h.ext_hist[2], h.ext_hist[3], h.ext_hist[4], h.ext_hist[5], h.ext_hist[6],
+                        h.ext_diag[0], h.ext_diag[1], h.ext_diag[2], h.ext_diag[3], h.ext_diag[4], h.ext_diag[5], h.ext_diag[6]);
+                fprintf(stderr, "[dbg] ksw_extd2 calls by Q16 (<= 16, 32, 64, 128, 256, 336, more): %u %u %u %u %u %u %u; by direction bytes (<= 4096, <= 9840, <= 32768, more): %u %u %u %u\n", h.ext_hist[8], h.ext_hist[9], h.ext_hist[10], h.ext_hist[11], h.ext_hist[12], h.ext_hist[13], h.ext_hist[14],
+                        h.ext_hist[16], h.ext_hist[17], h.ext_hist[18], h.ext_hist[19]);
+            }
         }
         uint32_t n_fallback = 0; double ms_fallback = 0;
         if (n_redo2 > 0) {
