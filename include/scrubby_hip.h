@@ -346,7 +346,9 @@ typedef struct sh_k2_opts {
     int32_t  long_unit_bases;       /* a unit whose longer fragment has at least this many bases is classified by one wave
                                        (k_k2_classify_wave) instead of one lane; 0 = the default (DESIGN.md §7 "Long reads"),
                                        negative = never.  The answers do not depend on it; --quick units never take that route */
-    int32_t  pad_;
+    int32_t  protein;               /* 1: the database holds amino-acid minimizers and reads are searched in six translated frames
+                                       (DESIGN.md §7 "Translated search"); 0: nucleotides.  Set from opts.k2d on open; a call whose
+                                       value disagrees with the database is SH_ERR_BAD_ARG */
 } sh_k2_opts;
 
 typedef struct sh_k2_taxnode {      /* taxo.k2d node: 7 x u64 */
@@ -371,10 +373,25 @@ typedef struct sh_k2_stats {
     uint64_t n_masked_bases;        /* bases of the batch masked by min_base_quality */
     uint64_t n_long_units;          /* units classified one wave per unit (opts.long_unit_bases) */
     float    ms_long;               /* that kernel's share of ms_classify */
-    int32_t  pad_;
+    float    ms_translate;          /* protein databases: the six-frame translation of the batch (k_k2_translate), not in ms_classify */
 } sh_k2_stats;
 
 sh_status sh_k2_default_opts(sh_k2_opts *out);
+/* the same for a protein database: k 15, l 12 (amino acids), no spaced seed, the same toggle mask, protein 1 */
+sh_status sh_k2_default_protein_opts(sh_k2_opts *out);
+/* Six-frame translation (DESIGN.md §7 "Translated search"; aa_translate.cc as recalled: PARITY UNPINNED).  Record r of n bases
+ * gives frames 0..5 of (n-1)/3, (n-2)/3, n/3 residues forward and as many reverse (none for n < 3): the codon that ends at base i
+ * is residue (i-2)/3 of forward frame i % 3, and its reverse complement residue n_f-1-(i-2)/3 of frame 3 + i % 3; a codon with a
+ * base outside ACGTacgt, or one whose quality is below min_qual (quals nullable, byte 0xFF never masked), is X.  The frames are
+ * written back to back in frame order from out[2 * (offsets[r] - offsets[0])]; out holds 2 * n_bases + 8 bytes, the bytes
+ * between records are not written.  An output byte is the amino-acid scanner's code 0..15 (0x80: ambiguous, X), or with
+ * as_letters != 0 the residue itself (A..Y, *, X).  _device: device pointers, work on `stream`, one synchronisation (the batch's
+ * extent is read back before the launch; the kernel itself is only enqueued).
+ * _host: the same on the CPU (no GPU needed). */
+sh_status sh_k2_translate_device(const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets, uint64_t n_records, int32_t min_qual,
+                                 int32_t as_letters, uint8_t *d_out, void *stream);
+sh_status sh_k2_translate_host(const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_records, int32_t min_qual,
+                               int32_t as_letters, uint8_t *out);
 /* k-mers per tile of the wave route (a fragment with more of them is scanned in several tiles) */
 uint32_t sh_k2_wave_tile(void);
 /* open a Kraken2 database directory (hash.k2d, opts.k2d, taxo.k2d) into HBM */
@@ -568,7 +585,8 @@ typedef struct sh_k2_build_config {
     int32_t     mask_low_complexity;        /* 1: both passes mask every batch on the GPU first (sh_k2_mask_device, masked bases
                                              * become 'x'); 0: the library is taken as given */
     int32_t     mask_window, mask_threshold;        /* 0: 64, 20 */
-    int32_t     pad2;
+    int32_t     protein;            /* 1: kraken2-build --protein: the library is amino-acid FASTA, the defaults k 15, l 12, no minimizer
+                                     * spaces (minimizer_spaces 0 or negative); mask_low_complexity is then SH_ERR_BAD_ARG */
 } sh_k2_build_config;
 typedef struct sh_k2_build_result {
     uint64_t n_records, n_skipped, n_bases, n_batches, n_cuts;

@@ -21,6 +21,8 @@ static void usage()
             "                  [--kmer-len 35] [--minimizer-len 31] [--minimizer-spaces 7] [--capacity N] [--load-factor 0.7]\n"
             "                  [--max-db-size BYTES] [--value-bits N] [--chunk-bytes N]\n"
             "                  [--mask-low-complexity [--mask-window 64] [--mask-threshold 20]]\n"
+            "                  [--protein]   (an amino-acid FASTA library: k 15, l 12, no minimizer spaces; reads are then searched in\n"
+            "                                 six translated frames; no --mask-low-complexity, --quick, hit lists or minimizer data)\n"
             "scrubby-hip k2-mask -i <in.fa[.gz|.bz2|.xz]> -o <out.fa[.gz|.bz2|.xz]> [-W 64] [-T 20] [-r x | --soft] [--line-width 60]\n"
             "                  [--chunk-bytes N]\n"
             "scrubby-hip k2-inspect -d <db dir> [-o report.txt] [--skip-counts] [--report-zero-counts] [--use-mpa-style] [--device N]\n"
@@ -97,6 +99,7 @@ static int main_k2_build(int argc, char **argv)
         else if (a == "--value-bits") c.value_bits = atoi(val().c_str());
         else if (a == "--chunk-bytes") c.chunk_bytes = strtoull(val().c_str(), nullptr, 10);
         else if (a == "--mask-low-complexity") c.mask_low_complexity = 1;
+        else if (a == "--protein") c.protein = 1;
         else if (a == "--mask-window") c.mask_window = atoi(val().c_str());
         else if (a == "--mask-threshold") c.mask_threshold = atoi(val().c_str());
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }

@@ -631,12 +631,25 @@ extern "C" sh_status sh_k2_format_hits(const sh_k2_hit *entries, uint64_t n_entr
     return SH_OK;
 }
 
+sh_status shi_kraken_protein_checks(const sh_kraken_config *c, const sh_k2_opts &db_opts)
+{
+    if (!db_opts.protein) return SH_OK;
+    SH_CHECK(!c->quick, SH_ERR_BAD_ARG, "%s is a protein database: --quick is not supported", c->db);
+    SH_CHECK(!c->report_minimizer_data, SH_ERR_BAD_ARG, "%s is a protein database: --report-minimizer-data is not supported", c->db);
+    return SH_OK;
+}
+
 sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
                               bool paired, sh_k2_result *results, ShiKrakenHits &hits, sh_k2_mindata *md)
 {
     hits.quick = opts.quick != 0;
     const sh_k2_batch batch{bases, quals, offsets, n_rec, paired ? 1 : 0};
     sh_status st = SH_OK;
+    if (opts.protein) {     // translated search keeps no hit lists: column 5 of kraken.reads is "0:0"
+        hits.none = true;
+        fprintf(stderr, "[scrubby-hip] note: protein database: kraken.reads carries no hit lists (column 5 is 0:0)\n");
+        return sh_k2_classify_ex_batch(db, &opts, &batch, results, nullptr, nullptr, nullptr);
+    }
     if (!hits.quick) {      // (with --quick column 5 is "<taxid>:Q": no hit list)
         sh_k2_info info;
         st = sh_k2_info_get(db, &info);
@@ -689,6 +702,8 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
     if (c->min_hit_groups > 0) opts.min_hit_groups = c->min_hit_groups;   // -C "--minimum-hit-groups n"
     opts.min_base_quality = c->min_base_quality > 0 ? c->min_base_quality : 0;    // -C "--minimum-base-quality n"
     opts.quick = c->quick != 0;                                            // -C "--quick"
+    st = shi_kraken_protein_checks(c, opts);
+    if (st != SH_OK) { sh_k2_free(db); return st; }
     const bool want_q = opts.min_base_quality > 0;        // qualities at the offsets of the bases; 0xFF: FASTA, never masked
     auto t1 = now();
 

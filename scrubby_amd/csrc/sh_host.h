@@ -34,18 +34,23 @@ bool shi_k2_hitlist(std::string &o, const sh_k2_hit *e, uint64_t n, const uint32
 // the Kraken arm's classification of one host batch for both writers: the results and, unless opts.quick, every unit's hit list
 struct ShiKrakenHits {
     bool quick = false;
+    bool none = false;                  // a protein database: no hit lists, column 5 is "0:0"
+
     std::vector<uint64_t> off;          // n_units + 1
     std::vector<sh_k2_hit> ent;
     std::vector<uint32_t> ext;          // external ids of the taxonomy
     // column 5 of unit i (r: its result) appended to o
     void append(std::string &o, uint64_t i, const sh_k2_result &r) const
     {
+        if (none) { o += "0:0"; return; }
         shi_k2_hitlist(o, quick ? nullptr : ent.data() + off[i], quick ? 0 : off[i + 1] - off[i], ext.data(), ext.size(), quick, r.taxid);
     }
 };
 // md (nullable): the run's minimizer-data accumulator (-C "--report-minimizer-data")
 sh_status shi_kraken_classify(sh_k2_db *db, const sh_k2_opts &opts, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_rec,
                               bool paired, sh_k2_result *results, ShiKrakenHits &hits, sh_k2_mindata *md = nullptr);
+// a protein database (DESIGN.md §7 "Translated search"): --quick and --report-minimizer-data are refused by name
+sh_status shi_kraken_protein_checks(const sh_kraken_config *c, const sh_k2_opts &db_opts);
 // kraken.minimizer.report beside kraken.report, when the run keeps an accumulator
 sh_status shi_kraken_minimizer_report(const sh_kraken_config *c, sh_k2_db *db, const sh_k2_result *results, uint64_t n_units, sh_k2_mindata *md, const std::string &dir);
 // database build: the <n> of a `kraken:taxid|<n>` sequence id (sh_host.cpp)

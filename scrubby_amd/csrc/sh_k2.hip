@@ -35,6 +35,7 @@
 #include "sh_k2_db.h"
 #include "sh_k2_inspect.h"
 #include "sh_k2_distrib.h"
+#include "sh_k2_tx.h"
 #include "sh_wave.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
@@ -78,8 +79,10 @@ __device__ static inline uint64_t k2_mod(uint64_t hc, uint64_t capacity, double 
 }
 
 // rolling scanner state of one lane; the window holds k - l + 1 candidates (<= W; the instantiations are W = 1, 5 and,
-// for every other (k, l), 16 with the live part given at run time)
-template <int W>
+// for every other (k, l), 16 with the live part given at run time; the amino-acid form has W = 4 for k = 15, l = 12, and 16).
+// AA: the amino-acid form (mmscanner.cc as recalled: PARITY UNPINNED): the code byte is taken as given, 0..15 (anything above is
+// ambiguous), the l-mer is the last l codes at 4 bits each, and there is no reverse complement and no canonical form.
+template <int W, bool AA = false>
 struct K2Scan {
     uint64_t fw, rc, c[W];
     int32_t loaded;
@@ -97,12 +100,12 @@ struct K2Scan {
     }
     __device__ inline int step_w(uint32_t code, int32_t pos, int32_t k, int32_t l, uint64_t lmask, uint64_t spaced, uint64_t toggle, uint64_t &m, int32_t wlim)
     {   // branch-free: 64 lanes scan 64 different reads
-        const bool amb = code > 3;
-        fw = amb ? 0ull : ((fw << 2) | code) & lmask;
-        rc = amb ? 0ull : (rc >> 2) | ((uint64_t)(3u - code) << (2 * (l - 1)));
+        const bool amb = code > (AA ? 15u : 3u);
+        fw = amb ? 0ull : ((fw << (AA ? 4 : 2)) | code) & lmask;
+        if constexpr (!AA) rc = amb ? 0ull : (rc >> 2) | ((uint64_t)(3u - code) << (2 * (l - 1)));
         loaded = amb ? 0 : (loaded < l ? loaded + 1 : l);
         const bool full = loaded == l;
-        uint64_t canon = fw < rc ? fw : rc;
+        uint64_t canon = AA ? fw : (fw < rc ? fw : rc);
         if (spaced) canon &= spaced;
         const uint64_t cand = canon ^ toggle;
 #pragma unroll
@@ -267,12 +270,6 @@ __device__ static inline uint32_t k2_probe_long(const K2Table &T, uint64_t v, ui
     return (idx >> 3) < n_full ? k2_probe_rest(T, idx >> 3, comp) : k2_finish_probe(T, idx, T.cells[idx], comp);
 }
 
-// kraken2 --minimum-base-quality (MaskLowQualityBases): Phred score below the threshold; 0xFF = a FASTA record, never masked
-__host__ __device__ static inline bool k2_masked(uint32_t q, int32_t min_qual)
-{
-    return q != 0xffu && (int32_t)q - '!' < min_qual;
-}
-
 // HITS: one lane's hit-list state, kept in registers across drains: the open piece (ambiguous k-mers before it, K2Q_PROBE
 // if it starts a run), the ambiguous k-mers after its last k-mer, the taxon of the run the drain last looked up, and the RLE
 // state (the code and count not yet written, the entries so far, where they go and how many fit)
@@ -349,9 +346,16 @@ struct K2MdState {
 struct K2NoMd {};
 
 // SUB: pass 1 over the units of a.unit_list only (the others went the wave route: k_k2_classify_wave)
-template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false, bool SUB = false>
+// PROT: translated search over a protein database (DESIGN.md §7 "Translated search"; classify.cc as recalled: PARITY UNPINNED).
+// a.bases is k_k2_translate's output (scanner codes), a.offsets the nucleotide offsets.  A unit has 6 or 12 fragments, frames
+// 0..5 of mate 1 and then of mate 2, whose extents in the code array are arithmetic from the mates' nucleotide extents
+// (k2_tx_frame_lens); they run through the same character loop, so last_minimizer is forgotten at the start of every frame, and
+// hit groups and taxon counts pool over all of them.  total_kmers is the number of k-mers over all frames; ResolveTree's
+// threshold takes K2_TX_S_READ / K2_TX_S_PAIR more (sh_k2_tx.h).  Forms: pass 1 and BIG only.
+template <int W, bool BIG, bool QMASK, bool QUICK, int HITS = 0, bool MIND = false, bool SUB = false, bool PROT = false>
 __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> a)
 {
+    static_assert(!PROT || !(QMASK || QUICK || HITS != 0 || MIND || SUB), "translated search: qualities mask at translation; no --quick, hit list, minimizer data or subset form");
     static_assert(!SUB || !(BIG || QUICK || HITS == 2), "a subset is a pass-1 matter, and --quick units all stay here");
     static_assert(HITS == 0 || !(BIG || QUICK), "the hit list is complete after pass 1 and has no --quick form");
     static_assert(!MIND || !(BIG || HITS == 2), "the redo passes repeat units pass 1 counted: they must not count them again");
@@ -362,11 +366,12 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
     __shared__ uint32_t s_qamb[HITS ? (K2_QCAP + 1) * 64 : 1];       // HITS: K2Q_* word of the entry
     __shared__ uint32_t s_htax[BIG || QUICK || HITS == 2 ? 1 : K2_HCAP * 64], s_hcnt[BIG || QUICK || HITS == 2 ? 1 : K2_HCAP * 64];
     const uint32_t lane = threadIdx.x;
-    const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
+    const uint64_t lmask = PROT ? (a.l < 16 ? ((1ULL << (4 * a.l)) - 1) : ~0ULL) : (a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL);
     const int32_t wlim = a.k - a.l + 1;
     const uint64_t n_work = LIST ? a.n_list : a.n_units;
     unsigned long long probes_thr = 0, kmers_thr = 0; uint32_t class_thr = 0;
     std::conditional_t<MIND, K2MdState, K2NoMd> M{};       // (an empty object in the other instances)
+    [[maybe_unused]] const uint64_t tx_beg = PROT ? a.offsets[0] : 0;      // PROT: the batch's first base (the code array starts there)
     for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_work; base += (uint64_t)gridDim.x * 64) {
         const uint64_t wi = base + lane;
         const bool active = wi < n_work;
@@ -377,7 +382,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
         H.n = 0; H.over = false;
         uint32_t total = 0, groups = 0, n_pend = 0, probes_unit = 0;
         bool stopped = false; uint32_t q_call = 0, q_total = 0;      // QUICK: the unit's scan has stopped on q_call
-        const int n_frag = a.paired ? 2 : 1;
+        const int n_mates = a.paired ? 2 : 1, n_frag = PROT ? 6 * n_mates : n_mates;
         std::conditional_t<HITS != 0, K2HitState, K2NoHits> R{};       // (an empty object in the other instances)
         if constexpr (HITS == 1) { R.out = a.hits + u * K2_HIT_INLINE; R.cap = active ? K2_HIT_INLINE : 0; }
         if constexpr (HITS == 2) { if (active) { R.out = a.hits + a.hit_off[u]; R.cap = (uint32_t)(a.hit_off[u + 1] - a.hit_off[u]); } }
@@ -472,18 +477,20 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
         // [f * n_chunks_max, (f + 1) * n_chunks_max) of the wave, each lane idling past its own read's end.
         uint64_t o_beg[2] = {0, 0}; int32_t len[2] = {0, 0};
         int32_t max_len = 0;
-        for (int f = 0; f < n_frag; ++f) {
+        for (int f = 0; f < n_mates; ++f) {
             const uint64_t rec = a.paired ? 2 * u + (uint64_t)f : u;
             o_beg[f] = active ? a.offsets[rec] : 0;
             len[f] = active ? (int32_t)(a.offsets[rec + 1] - o_beg[f]) : 0;
-            max_len = len[f] > max_len ? len[f] : max_len;
+            const int32_t frag_len = PROT ? (len[f] >= 3 ? len[f] / 3 : 0) : len[f];      // PROT: a mate's longest frame (frame 2)
+            max_len = frag_len > max_len ? frag_len : max_len;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { int32_t t = __shfl_xor(max_len, o); max_len = t > max_len ? t : max_len; }
         const int32_t n_chunks = (max_len + 7) / 8;
-        K2Scan<W> S; S.reset();
+        K2Scan<W, PROT> S; S.reset();
         uint64_t last_min = ~0ull; uint32_t run = 0, run_pos = 0;
         int32_t my_len = 0, off8 = 0; uint32_t sh = 0;
+        [[maybe_unused]] int32_t frag = 0, frag_c0 = 0;      // PROT: the fragment the loop is in and its first chunk
         const uint64_t *wp = nullptr, *qp = nullptr;
         uint64_t w_cur = 0, w_next = 0, q_cur = 0, q_next = 0, qw = 0;
         // ONE loop over the characters of both fragments with ONE call site of drain (the probe code is large): step s is
@@ -493,7 +500,11 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
 #pragma nounroll
         for (int32_t s = 0;; ++s) {
             const bool end = s == n_steps;
-            const int32_t cc = s >> 3, c = cc < n_chunks ? cc : cc - n_chunks;
+            const int32_t cc = s >> 3;
+            if constexpr (PROT) {
+                if ((s & 7) == 0 && !end && cc - frag_c0 == n_chunks) { ++frag; frag_c0 = cc; }      // (wave-uniform) on to the next frame
+            }
+            const int32_t c = PROT ? cc - frag_c0 : (cc < n_chunks ? cc : cc - n_chunks);
             if ((s & 7) == 0) {
                 if (c == 0 || end) {       // (wave-uniform) fragment boundary: flush the last run, restart the scanner
                     s_qmin[n_pend * 64 + lane] = last_min; s_qlen[n_pend * 64 + lane] = run;
@@ -509,9 +520,22 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
                     }
                     S.reset(); last_min = ~0ull; run = 0;
                     if (!end) {
-                        const int f = cc < n_chunks ? 0 : 1;
-                        my_len = len[f];
-                        const uintptr_t pa = (uintptr_t)(a.bases + o_beg[f]);
+                        uintptr_t pa;
+                        [[maybe_unused]] const int f = cc < n_chunks ? 0 : 1;
+                        if constexpr (PROT) {
+                            // frame fr of mate m: forward frames 0, 1, 2 and then the reverse ones, back to back from
+                            // 2 * (the mate's first base - the batch's); no per-fragment array, only selects
+                            const bool m = frag >= 6;
+                            const int fr = m ? frag - 6 : frag, g = fr >= 3 ? fr - 3 : fr;
+                            uint64_t n0, n1, n2;
+                            k2_tx_frame_lens((uint64_t)(m ? len[1] : len[0]), n0, n1, n2);
+                            my_len = (int32_t)(g == 0 ? n0 : g == 1 ? n1 : n2);
+                            const uint64_t at = (fr >= 3 ? n0 + n1 + n2 : 0) + (g >= 1 ? n0 : 0) + (g >= 2 ? n1 : 0);
+                            pa = (uintptr_t)(a.bases + 2 * ((m ? o_beg[1] : o_beg[0]) - tx_beg) + at);
+                        } else {
+                            my_len = len[f];
+                            pa = (uintptr_t)(a.bases + o_beg[f]);
+                        }
                         wp = (const uint64_t *)(pa & ~(uintptr_t)7); off8 = (int32_t)(pa & 7); sh = (uint32_t)off8 * 8;
                         // only the aligned words that overlap the read are ever loaded
                         w_cur = my_len > 0 ? wp[0] : 0;
@@ -544,7 +568,7 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
             if (end) break;
             const int32_t i = c * 8 + (s & 7);
             uint64_t m;
-            uint32_t code = sh_nt4((uint32_t)w & 0xffu);
+            uint32_t code = PROT ? (uint32_t)w & 0xffu : sh_nt4((uint32_t)w & 0xffu);
             if constexpr (QMASK) { code = k2_masked((uint32_t)qw & 0xffu, a.min_qual) ? 4u : code; qw >>= 8; }
             int ev = S.step_w(code, i + 1, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
             w >>= 8;
@@ -590,7 +614,8 @@ __global__ __launch_bounds__(64) void k_k2_classify(K2ArgsOf<QMASK, HITS, MIND> 
                 uint32_t call;
                 if constexpr (QUICK) call = stopped ? q_call : 0u;       // no stop: unclassified, whatever ResolveTree would say
                 else {
-                    call = k2_resolve(H, a.parent, total, a.confidence);
+                    if constexpr (PROT) call = k2_resolve(H, a.parent, total + (a.paired ? K2_TX_S_PAIR : K2_TX_S_READ), a.confidence);
+                    else call = k2_resolve(H, a.parent, total, a.confidence);
                     if (call && groups < (uint32_t)a.min_hit_groups) call = 0;
                 }
                 sh_k2_result r{call ? a.ext[call] : 0u, call, total, groups};
@@ -1050,11 +1075,12 @@ __global__ void k_k2_lib_segcount(K2LibArgs a)
     }
 }
 
-template <int W, typename Emit>
+// AA: a protein library, a.bases holding scanner codes (k_k2_aa_encode), scanned by the amino-acid form of K2Scan
+template <int W, bool AA, typename Emit>
 __device__ static inline void k2_lib_scan(const K2LibArgs &a, Emit emit)
 {
     const uint32_t lane = threadIdx.x;
-    const uint64_t lmask = a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL;
+    const uint64_t lmask = AA ? (a.l < 16 ? ((1ULL << (4 * a.l)) - 1) : ~0ULL) : (a.l < 32 ? ((1ULL << (2 * a.l)) - 1) : ~0ULL);
     const int32_t wlim = a.k - a.l + 1;
     const uint64_t n_items = a.seg_off[a.n_records];
     for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_items; base += (uint64_t)gridDim.x * 64) {
@@ -1078,7 +1104,7 @@ __device__ static inline void k2_lib_scan(const K2LibArgs &a, Emit emit)
         const int32_t off8 = (int32_t)((uintptr_t)p & 7); const uint32_t sh = (uint32_t)off8 * 8;
         // only the aligned words that overlap the segment are ever loaded
         uint64_t w_cur = n > 0 ? wp[0] : 0, w_next = n + off8 > 8 ? wp[1] : 0;
-        K2Scan<W> S; S.reset();
+        K2Scan<W, AA> S; S.reset();
         uint64_t last = ~0ull;
         const int32_t n_chunks = (n_max + 7) / 8;
 #pragma nounroll
@@ -1091,7 +1117,7 @@ __device__ static inline void k2_lib_scan(const K2LibArgs &a, Emit emit)
                 const int32_t i = c * 8 + j;
                 uint64_t m;
                 // `pos` only gates "a full k-mer has been read": counted from the warm-up start, never above k
-                const int ev = S.step_w(sh_nt4((uint32_t)w & 0xffu), i + 1 < a.k ? i + 1 : a.k, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
+                const int ev = S.step_w(AA ? (uint32_t)w & 0xffu : sh_nt4((uint32_t)w & 0xffu), i + 1 < a.k ? i + 1 : a.k, a.k, a.l, lmask, a.spaced, a.toggle, m, wlim);
                 w >>= 8;
                 const bool fresh = ev == 2 && i < n && i >= lead && m != last;
                 last = fresh ? m : last;
@@ -1101,11 +1127,11 @@ __device__ static inline void k2_lib_scan(const K2LibArgs &a, Emit emit)
     }
 }
 
-template <int W>
+template <int W, bool AA = false>
 __global__ __launch_bounds__(64) void k_k2_insert_lib(K2Build B, K2LibArgs a, unsigned long long *n_runs)
 {
     unsigned long long runs = 0;
-    k2_lib_scan<W>(a, [&](bool go, uint64_t m, uint32_t taxon) {
+    k2_lib_scan<W, AA>(a, [&](bool go, uint64_t m, uint32_t taxon) {
         if (go) { k2_insert(B, m, taxon); ++runs; }
     });
 #pragma unroll
@@ -1116,11 +1142,11 @@ __global__ __launch_bounds__(64) void k_k2_insert_lib(K2Build B, K2LibArgs a, un
 // estimate_capacity.cc as recalled: minimizers whose hash falls in 4 of 1024 residues are collected; the distinct ones are
 // counted on the host side of the call (sort + unique).  One atomic per wave and step that samples anything; ctr[0] counts
 // every sampled run, also those that no longer fit `cap` (the caller grows the buffer and repeats the batch).
-template <int W>
+template <int W, bool AA = false>
 __global__ __launch_bounds__(64) void k_k2_estimate_lib(K2LibArgs a, uint64_t *buf, uint64_t cap, unsigned long long *ctr)
 {
     const uint32_t lane = threadIdx.x;
-    k2_lib_scan<W>(a, [&](bool go, uint64_t m, uint32_t) {
+    k2_lib_scan<W, AA>(a, [&](bool go, uint64_t m, uint32_t) {
         const bool take = go && (k2_fmix64(m) & 1023u) < 4u;
         const unsigned long long mask = __ballot(take);
         if (!mask) return;
@@ -1144,6 +1170,12 @@ static void k2_with_window(int32_t k, int32_t l, F &&f)
     default: f(std::integral_constant<int, 16>{}); break;
     }
 }
+// ... of the amino-acid scanner: 4 (k = 15, l = 12) and the generic 16
+template <class F>
+static void k2_with_window_aa(int32_t k, int32_t l, F &&f)
+{
+    if (k - l + 1 == 4) f(std::integral_constant<int, 4>{}); else f(std::integral_constant<int, 16>{});
+}
 template <class F>
 static void k2_with_flag(bool b, F &&f)
 {
@@ -1165,6 +1197,25 @@ extern "C" sh_status sh_k2_default_opts(sh_k2_opts *o)
     o->long_unit_bases = 0;
     return SH_OK;
 }
+
+// kraken2-build --protein as recalled (PARITY UNPINNED): k = 15 and l = 12 amino acids, no spaced seed
+extern "C" sh_status sh_k2_default_protein_opts(sh_k2_opts *o)
+{
+    sh_status st = sh_k2_default_opts(o);
+    if (st != SH_OK) return st;
+    o->k = 15; o->l = 12; o->spaced_seed_mask = 0; o->protein = 1;
+    return SH_OK;
+}
+
+// (k, l) a scanner exists for: the l-mer fits 64 bits (2 bits a base, 4 bits an amino acid), the window 16 candidates
+static bool k2_kl_ok(const sh_k2_opts &o)
+{
+    return o.l >= 1 && o.l <= (o.protein ? 15 : 31) && o.k >= o.l && o.k - o.l + 1 <= 16;
+}
+static const char *k2_kind(int32_t protein) { return protein ? "protein" : "nucleotide"; }
+// the check every call with options of its own makes: they are for the kind of database they are used on
+#define K2_CHECK_KIND(db, o, who) \
+    SH_CHECK(((o).protein != 0) == ((db)->opts.protein != 0), SH_ERR_BAD_ARG, "%s: %s options on a %s database", who, k2_kind((o).protein), k2_kind((db)->opts.protein))
 
 static sh_status k2_upload_taxonomy(sh_k2_db *db)
 {
@@ -1196,7 +1247,7 @@ extern "C" sh_status sh_k2_create(const sh_k2_opts *opts, uint64_t capacity, con
                                   const char *names, uint64_t names_len, const char *ranks, uint64_t ranks_len, int device, sh_k2_db **out)
 {
     SH_CHECK(opts && nodes && out && capacity > 0 && n_nodes >= 2, SH_ERR_BAD_ARG, "sh_k2_create: bad argument");
-    SH_CHECK(opts->l >= 1 && opts->l <= 31 && opts->k >= opts->l && opts->k - opts->l + 1 <= 16, SH_ERR_BAD_ARG, "sh_k2_create: unsupported k=%d l=%d", opts->k, opts->l);
+    SH_CHECK(k2_kl_ok(*opts), SH_ERR_BAD_ARG, "sh_k2_create: unsupported k=%d l=%d for a %s database", opts->k, opts->l, k2_kind(opts->protein));
     SH_CHECK(opts->value_bits >= 1 && opts->value_bits <= 31 && n_nodes <= (1ull << opts->value_bits), SH_ERR_BAD_ARG,
              "sh_k2_create: %llu taxonomy nodes do not fit %d value bits", (unsigned long long)n_nodes, opts->value_bits);
     int n_dev = 0;
@@ -1204,6 +1255,7 @@ extern "C" sh_status sh_k2_create(const sh_k2_opts *opts, uint64_t capacity, con
     SH_HIP(hipSetDevice(device));
     sh_k2_db *db = new sh_k2_db;
     db->device = device; db->opts = *opts; db->capacity = capacity; db->value_bits = opts->value_bits; db->key_bits = 32 - opts->value_bits;
+    db->opts.protein = opts->protein != 0; db->dna_db = !db->opts.protein;
     db->nodes.assign(nodes, nodes + n_nodes);
     if (names) db->names.assign(names, names + names_len);
     if (ranks) db->ranks.assign(ranks, ranks + ranks_len);
@@ -1251,6 +1303,7 @@ extern "C" sh_status sh_k2_insert_random(sh_k2_db *db, uint64_t seed, uint64_t n
 extern "C" sh_status sh_k2_insert_sequence_device(sh_k2_db *db, const uint8_t *d_bases, uint64_t n, uint32_t taxon, void *stream, uint64_t *n_inserted)
 {
     SH_CHECK(db && d_bases && taxon >= 1 && taxon < db->nodes.size(), SH_ERR_BAD_ARG, "sh_k2_insert_sequence_device: bad argument");
+    SH_CHECK(!db->opts.protein, SH_ERR_BAD_ARG, "sh_k2_insert_sequence_device: a protein database is filled by sh_k2_insert_library_device");
     SH_HIP(hipSetDevice(db->device));
     hipStream_t s = (hipStream_t)stream;
     unsigned long long *d_runs = db->d_ctr + 2;
@@ -1293,6 +1346,27 @@ static sh_status k2_lib_prepare(K2LibArgs &a, const sh_k2_opts &o, const uint8_t
 }
 #define K2_LIB_GRID (256 * 32)      // one-wave blocks, grid-stride over the work items (their number stays on the device)
 
+// A protein library batch (amino-acid FASTA residues, either case): its scanner codes in call-scoped scratch, one streaming pass
+// (k_k2_aa_encode).  *d_codes is the array to scan in place of d_bases (indexed by the same offsets, same address modulo 8).
+// One synchronisation: the batch's extent is read back.
+static sh_status k2_lib_encode(const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_records, DevBuf &scratch, const uint8_t **d_codes, hipStream_t s)
+{
+    uint64_t ends[2];
+    SH_HIP(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, s));
+    SH_HIP(hipMemcpyAsync(&ends[1], d_offsets + n_records, 8, hipMemcpyDeviceToHost, s));
+    SH_HIP(hipStreamSynchronize(s));
+    SH_CHECK(ends[1] >= ends[0], SH_ERR_BAD_ARG, "protein library: offsets decrease");
+    const uint64_t n = ends[1] - ends[0];
+    const uintptr_t mis = (uintptr_t)(d_bases + ends[0]) & 7;
+    SH_HIP(scratch.alloc(n + 24));
+    SH_HIP(hipMemsetAsync(scratch.p, (int)K2_AA_AMBIG, n + 24, s));          // the bytes around the batch: ambiguous, as 'N' is around a nucleotide batch
+    uint8_t *codes = scratch.as<uint8_t>() + mis;
+    sh_status st = shi_k2_aa_encode_device(d_bases + ends[0], codes, n, s);
+    if (st != SH_OK) return st;
+    *d_codes = (const uint8_t *)((uintptr_t)codes - (uintptr_t)ends[0]);
+    return SH_OK;
+}
+
 extern "C" sh_status sh_k2_set_min_acceptable_hash(sh_k2_db *db, uint64_t min_acceptable_hash)
 {
     SH_CHECK(db, SH_ERR_BAD_ARG, "sh_k2_set_min_acceptable_hash: null argument");
@@ -1318,9 +1392,15 @@ extern "C" sh_status sh_k2_insert_library_device(sh_k2_db *db, const uint8_t *d_
     SH_HIP(hipEventRecord(e0.e, s));
     K2LibArgs a{};
     a.n_nodes = (uint32_t)db->nodes.size();
-    sh_status st = k2_lib_prepare(a, db->opts, d_bases, d_offsets, d_taxa, n_records, d_seg, b_tmp, s);
+    DevBuf b_codes;
+    sh_status st = SH_OK;
+    if (db->opts.protein) { st = k2_lib_encode(d_bases, d_offsets, n_records, b_codes, &d_bases, s); if (st != SH_OK) return st; }
+    st = k2_lib_prepare(a, db->opts, d_bases, d_offsets, d_taxa, n_records, d_seg, b_tmp, s);
     if (st != SH_OK) return st;
-    k2_with_window(db->opts.k, db->opts.l, [&](auto w) {
+    if (db->opts.protein) k2_with_window_aa(db->opts.k, db->opts.l, [&](auto w) {
+        hipLaunchKernelGGL((k_k2_insert_lib<decltype(w)::value, true>), dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs);
+    });
+    else k2_with_window(db->opts.k, db->opts.l, [&](auto w) {
         hipLaunchKernelGGL(k_k2_insert_lib<decltype(w)::value>, dim3(K2_LIB_GRID), dim3(64), 0, s, k2_build_args(db), a, d_runs);
     });
     hipEventRecord(e1.e, s);
@@ -1355,7 +1435,7 @@ extern "C" sh_status sh_k2_estimator_free(sh_k2_estimator *e)
 extern "C" sh_status sh_k2_estimator_create(const sh_k2_opts *opts, int device, sh_k2_estimator **out)
 {
     SH_CHECK(opts && out, SH_ERR_BAD_ARG, "sh_k2_estimator_create: null argument");
-    SH_CHECK(opts->l >= 1 && opts->l <= 31 && opts->k >= opts->l && opts->k - opts->l + 1 <= 16, SH_ERR_BAD_ARG, "sh_k2_estimator_create: unsupported k=%d l=%d", opts->k, opts->l);
+    SH_CHECK(k2_kl_ok(*opts), SH_ERR_BAD_ARG, "sh_k2_estimator_create: unsupported k=%d l=%d for a %s database", opts->k, opts->l, k2_kind(opts->protein));
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= device) { sh_set_error("no HIP device %d", device); return SH_ERR_NO_DEVICE; }
     SH_HIP(hipSetDevice(device));
@@ -1388,16 +1468,21 @@ extern "C" sh_status sh_k2_estimate_capacity_device(sh_k2_estimator *e, const ui
     hipStream_t s = (hipStream_t)stream;
     if (n_sampled) *n_sampled = e->n_have;
     if (n_records == 0) return SH_OK;
-    DevBuf b_seg, b_tmp, b_tmp2;
+    DevBuf b_seg, b_tmp, b_tmp2, b_codes;
     SH_HIP(b_seg.alloc((n_records + 1) * 8));
     K2LibArgs a{};
-    sh_status st = k2_lib_prepare(a, e->opts, d_bases, d_offsets, nullptr, n_records, b_seg.as<uint64_t>(), b_tmp, s);
+    sh_status st = SH_OK;
+    if (e->opts.protein) { st = k2_lib_encode(d_bases, d_offsets, n_records, b_codes, &d_bases, s); if (st != SH_OK) return st; }
+    st = k2_lib_prepare(a, e->opts, d_bases, d_offsets, nullptr, n_records, b_seg.as<uint64_t>(), b_tmp, s);
     if (st != SH_OK) return st;
     if (e->cap < e->n_have + (1u << 16)) { st = k2_estimator_grow(e, e->n_have * 2 + (1u << 20), s); if (st != SH_OK) return st; }
     for (int attempt = 0;; ++attempt) {
         unsigned long long c0 = e->n_have, total = 0;
         SH_CHECK(hipMemcpyAsync(e->d_ctr, &c0, 8, hipMemcpyHostToDevice, s) == hipSuccess, SH_ERR_HIP, "estimator: copy failed");
-        k2_with_window(e->opts.k, e->opts.l, [&](auto w) {
+        if (e->opts.protein) k2_with_window_aa(e->opts.k, e->opts.l, [&](auto w) {
+            hipLaunchKernelGGL((k_k2_estimate_lib<decltype(w)::value, true>), dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr);
+        });
+        else k2_with_window(e->opts.k, e->opts.l, [&](auto w) {
             hipLaunchKernelGGL(k_k2_estimate_lib<decltype(w)::value>, dim3(K2_LIB_GRID), dim3(64), 0, s, a, e->d_buf, e->cap, e->d_ctr);
         });
         SH_CHECK(hipMemcpyAsync(&total, e->d_ctr, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && hipGetLastError() == hipSuccess,
@@ -1517,7 +1602,7 @@ extern "C" sh_status sh_k2_db_opts(const sh_k2_db *db, sh_k2_opts *o)
 {
     SH_CHECK(db && o, SH_ERR_BAD_ARG, "sh_k2_db_opts: null argument");
     *o = db->opts;
-    o->long_unit_bases = 0; o->pad_ = 0;
+    o->long_unit_bases = 0;
     return SH_OK;
 }
 
@@ -1607,9 +1692,9 @@ extern "C" sh_status sh_k2_open(const char *dir, int device, sh_k2_db **out)
         db->opts.min_acceptable_hash = got >= 48 ? of.minimum_acceptable_hash_value : 0;
         db->dna_db = got >= 33 ? of.dna_db : 1; db->revcom_version = got >= 52 ? of.revcom_version : 0;
         db->db_version = got >= 56 ? of.db_version : 0; db->db_type = got >= 60 ? of.db_type : 0;
-        if (!db->dna_db) { sh_set_error("%s: protein databases are not supported", dir); return fail(SH_ERR_BAD_ARG); }
-        if (!(db->opts.l >= 1 && db->opts.l <= 31 && db->opts.k >= db->opts.l && db->opts.k - db->opts.l + 1 <= 16)) {
-            sh_set_error("%s: unsupported k=%d l=%d", dir, db->opts.k, db->opts.l); return fail(SH_ERR_BAD_ARG);
+        db->opts.protein = !db->dna_db;
+        if (!k2_kl_ok(db->opts)) {
+            sh_set_error("%s: unsupported k=%d l=%d for a %s database", dir, db->opts.k, db->opts.l, k2_kind(db->opts.protein)); return fail(SH_ERR_BAD_ARG);
         }
     }
     {
@@ -1683,6 +1768,17 @@ static void dispatch_classify(K2Form form, const K2MArgs &a, uint64_t n_work, hi
     case K2F_HITS2: launch_classify<false, false, 2>(a, n_work, s, qmask, false, false); break;
     case K2F_BIG: launch_classify<true, false, 0>(a, n_work, s, qmask, false, false); break;
     }
+}
+
+// translated search: the two forms a protein database has (pass 1 over every unit, BIG over a.unit_list)
+template <bool BIG>
+static void launch_classify_prot(const K2MArgs &a, uint64_t n_work, hipStream_t s)
+{
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_work + 63) / 64, 1), 256 * 32);
+    k2_with_window_aa(a.k, a.l, [&](auto w) {
+        const K2Args &ka = a;
+        hipLaunchKernelGGL((k_k2_classify<decltype(w)::value, BIG, false, false, 0, false, false, true>), dim3(grid), dim3(64), 0, s, ka);
+    });
 }
 
 // the wave route's forms (PLAIN, HITS1, HITS2) over a.unit_list: one block of 64 threads per unit in flight, units drawn by ticket
@@ -1883,11 +1979,18 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     SH_CHECK(!md || (md->device == db->device && md->n_nodes == db->nodes.size()), SH_ERR_BAD_ARG, "the minimizer data belongs to another database");
     SH_CHECK(!paired || (n_records & 1) == 0, SH_ERR_BAD_ARG, "paired input needs an even number of records (got %llu)", (unsigned long long)n_records);
     const sh_k2_opts &o = opts ? *opts : db->opts;
+    K2_CHECK_KIND(db, o, "sh_k2_classify_ex");
+    const bool prot = db->opts.protein != 0;
+    // what translated search leaves out (DESIGN.md §7 "Translated search")
+    SH_CHECK(!prot || !o.quick, SH_ERR_BAD_ARG, "--quick is not supported on a protein database");
+    SH_CHECK(!prot || !hits_out, SH_ERR_BAD_ARG, "hit lists are not supported on a protein database: call with hits = NULL");
+    SH_CHECK(!prot || !md, SH_ERR_BAD_ARG, "minimizer data is not supported on a protein database: call with md = NULL");
     SH_CHECK(!hits_out || !o.quick, SH_ERR_BAD_ARG, "--quick writes no hit list: call with hits = NULL");
     SH_HIP(hipSetDevice(db->device));
     hipStream_t s = (hipStream_t)stream;
     SH_CHECK(o.k == db->opts.k && o.l == db->opts.l, SH_ERR_BAD_ARG, "options disagree with the database (k, l)");
-    const bool qmask = d_quals && o.min_base_quality > 0, quick = o.quick != 0;
+    // a protein database: the qualities mask at translation, the classify kernel sees codes only
+    const bool qmask_any = d_quals && o.min_base_quality > 0, qmask = qmask_any && !prot, quick = o.quick != 0;
     SH_CHECK(!qmask || ((uintptr_t)d_quals & 7) == ((uintptr_t)d_bases & 7), SH_ERR_BAD_ARG,
              "sh_k2_classify_ex_device: qualities and bases must lie at the same address modulo 8");
     const uint64_t n_units = paired ? n_records / 2 : n_records;
@@ -1898,8 +2001,8 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     SH_CHECK(n_units <= 0xffffffffull, SH_ERR_BAD_ARG, "at most 2^32 - 1 units per call");
     DevEvent e0, e1;
     SH_HIP(e0.create()); SH_HIP(e1.create());
-    DevBuf b_ctr, b_over, b_hit_inl, b_n_hits, b_hit_over, b_big_tax, b_big_cnt, b_split, b_n_long, b_spill, b_whit_over;
-    DevEvent e2, e3;
+    DevBuf b_ctr, b_over, b_hit_inl, b_n_hits, b_hit_over, b_big_tax, b_big_cnt, b_split, b_n_long, b_spill, b_whit_over, b_codes;
+    DevEvent e2, e3, et0, et1;
     SH_HIP(b_ctr.alloc(K2C_WORDS * 8));
     SH_HIP(b_over.alloc(n_units * 4));
     unsigned long long *ctr = b_ctr.as<unsigned long long>();
@@ -1921,7 +2024,7 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
     a.quals = qmask ? d_quals : nullptr; a.min_qual = qmask ? o.min_base_quality : 0;
     // the split: are there long units at all (one pass over the offsets, an 8-byte read-back); if so, the long units first in b_split
     // (by unit), the others behind them (last unit first: rocprim::partition's layout).  Nothing of it when no unit can be long
-    const uint64_t long_thr = may_be_long ? k2_long_threshold(o) : 0;
+    const uint64_t long_thr = may_be_long && !prot ? k2_long_threshold(o) : 0;      // a protein database: every unit takes the lane route
     uint64_t n_long = 0;
     K2Wave wv{};
     if (long_thr) {
@@ -1949,10 +2052,25 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
         if (hits_out) { SH_HIP(b_whit_over.alloc(n_long * 4)); wv.hit_over = b_whit_over.as<uint32_t>(); }
         SH_HIP(e2.create()); SH_HIP(e3.create());
     }
+    if (prot) {       // the batch's six frames as scanner codes in call-scoped scratch (k_k2_translate); the kernels below read them
+        uint64_t ends[2];
+        SH_HIP(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, s));
+        SH_HIP(hipMemcpyAsync(&ends[1], d_offsets + n_records, 8, hipMemcpyDeviceToHost, s));
+        SH_HIP(hipStreamSynchronize(s));
+        SH_CHECK(ends[1] >= ends[0], SH_ERR_BAD_ARG, "sh_k2_classify_ex: offsets decrease");
+        SH_HIP(b_codes.alloc(2 * (ends[1] - ends[0]) + 8));
+        SH_HIP(et0.create()); SH_HIP(et1.create());
+        SH_HIP(hipEventRecord(et0.e, s));
+        sh_status st = shi_k2_translate_device(d_bases, d_quals, d_offsets, n_records, ends[0], ends[1] - ends[0], qmask_any ? o.min_base_quality : 0, 0, b_codes.as<uint8_t>(), s);
+        if (st != SH_OK) return st;
+        SH_HIP(hipEventRecord(et1.e, s));
+        a.bases = b_codes.as<uint8_t>();
+    }
     const K2Form form1 = quick ? K2F_QUICK : hits_out ? K2F_HITS1 : K2F_PLAIN;
     SH_HIP(hipEventRecord(e0.e, s));
-    if (qmask) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
-    if (!n_long) dispatch_classify(form1, a, n_units, s, qmask, md != nullptr);      // the only pass that counts minimizers
+    if (qmask_any) hipLaunchKernelGGL(k_k2_count_masked, dim3(1024), dim3(256), 0, s, d_quals, d_offsets, n_records, o.min_base_quality, ctr);
+    if (prot) launch_classify_prot<false>(a, n_units, s);
+    else if (!n_long) dispatch_classify(form1, a, n_units, s, qmask, md != nullptr);      // the only pass that counts minimizers
     else {       // the long units one wave each, then the others one lane each
         K2MArgs al = a;
         al.unit_list = b_split.as<uint32_t>(); al.n_list = (uint32_t)n_long;
@@ -1974,7 +2092,8 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
         SH_HIP(b_big_tax.alloc(n_over * K2_BIG_CAP * 4));
         SH_HIP(b_big_cnt.alloc(n_over * K2_BIG_CAP * 4));
         a.unit_list = a.over_list; a.n_list = (uint32_t)n_over; a.big_tax = b_big_tax.as<uint32_t>(); a.big_cnt = b_big_cnt.as<uint32_t>();
-        dispatch_classify(K2F_BIG, a, n_over, s, qmask);
+        if (prot) launch_classify_prot<true>(a, n_over, s);
+        else dispatch_classify(K2F_BIG, a, n_over, s, qmask);
         SH_HIP(hipMemcpyAsync(h.data(), ctr, K2C_WORDS * 8, hipMemcpyDeviceToHost, s));
         SH_HIP(hipStreamSynchronize(s));
         SH_HIP(hipGetLastError());
@@ -2010,12 +2129,13 @@ static sh_status k2_classify(const sh_k2_db *db, const sh_k2_opts *opts, const u
         hl.h->n_redone = n_hover + n_whover;
     }
     if (host_out) SH_HIP(hipMemcpy(host_out, d_out, n_units * sizeof(sh_k2_result), hipMemcpyDeviceToHost));
-    float ms = 0, ms_long = 0;
+    float ms = 0, ms_long = 0, ms_tx = 0;
     hipEventElapsedTime(&ms, e0.e, e1.e);
     if (n_long) hipEventElapsedTime(&ms_long, e2.e, e3.e);
+    if (prot) hipEventElapsedTime(&ms_tx, et0.e, et1.e);
     if (stats) {
-        stats->n_units = n_units; stats->n_overflow = n_over + h[K2C_WOVER]; stats->ms_classify = ms; stats->ms_total = ms;
-        stats->n_long_units = n_long; stats->ms_long = ms_long;
+        stats->n_units = n_units; stats->n_overflow = n_over + h[K2C_WOVER]; stats->ms_classify = ms; stats->ms_total = ms + ms_tx;
+        stats->n_long_units = n_long; stats->ms_long = ms_long; stats->ms_translate = ms_tx;
         for (int i = 0; i < 64; ++i) {
             stats->n_probes += h[K2C_PROBES + i]; stats->n_kmers += h[K2C_KMERS + i]; stats->n_classified += h[K2C_CLASSIFIED + i];
             stats->n_masked_bases += h[K2C_MASKED + i];

@@ -29,3 +29,9 @@ __device__ static inline bool k2_is_ancestor(const uint32_t *__restrict__ parent
     while (b > a) b = parent[b];
     return a == b;
 }
+
+// kraken2 --minimum-base-quality (MaskLowQualityBases): Phred score below the threshold; 0xFF = a FASTA record, never masked
+__host__ __device__ static inline bool k2_masked(uint32_t q, int32_t min_qual)
+{
+    return q != 0xffu && (int32_t)q - '!' < min_qual;
+}

@@ -244,6 +244,7 @@ extern "C" sh_status sh_k2_distrib_reset(sh_k2_distrib *d)
 extern "C" sh_status sh_k2_distrib_create(const sh_k2_db *db, int32_t read_len, sh_k2_distrib **out)
 {
     SH_CHECK(db && out, SH_ERR_BAD_ARG, "sh_k2_distrib_create: null argument");
+    SH_CHECK(!db->opts.protein, SH_ERR_BAD_ARG, "sh_k2_distrib_create: Bracken's k-mer distribution is not supported on a protein database");
     SH_CHECK(read_len >= db->opts.k && read_len <= K2D_MAX_READ_LEN, SH_ERR_BAD_ARG, "sh_k2_distrib_create: read length %d outside [k = %d, %d]", read_len,
              db->opts.k, K2D_MAX_READ_LEN);
     SH_HIP(hipSetDevice(db->device));

@@ -280,8 +280,10 @@ static void k2_binary(std::string &o, uint64_t v, int digits)
 extern "C" sh_status sh_k2_inspect_header(const sh_k2_db *db, char *buf, uint64_t cap, uint64_t *len)
 {
     SH_CHECK(db && (buf || cap == 0), SH_ERR_BAD_ARG, "sh_k2_inspect_header: null argument");
-    std::string o = "# Database options: nucleotide db, k = " + std::to_string(db->opts.k) + ", l = " + std::to_string(db->opts.l) + "\n# Spaced mask = ";
-    k2_binary(o, db->opts.spaced_seed_mask, 2 * db->opts.l);
+    // (kraken2-inspect as recalled: "protein db" for a protein database, whose l-mer has 4 bits a character)
+    std::string o = std::string("# Database options: ") + (db->opts.protein ? "protein" : "nucleotide") + " db, k = " + std::to_string(db->opts.k) + ", l = " +
+                    std::to_string(db->opts.l) + "\n# Spaced mask = ";
+    k2_binary(o, db->opts.spaced_seed_mask, (db->opts.protein ? 4 : 2) * db->opts.l);
     o += "\n# Toggle mask = ";
     k2_binary(o, db->opts.toggle_mask, 64);
     o += "\n# Total taxonomy nodes: " + std::to_string(db->nodes.size()) + "\n# Table size: " + std::to_string(db->size) + "\n# Table capacity: " +

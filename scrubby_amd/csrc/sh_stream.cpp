@@ -1381,6 +1381,8 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     if (c->min_hit_groups > 0) opts.min_hit_groups = c->min_hit_groups;   // -C "--minimum-hit-groups n"
     opts.min_base_quality = c->min_base_quality > 0 ? c->min_base_quality : 0;    // -C "--minimum-base-quality n"
     opts.quick = c->quick != 0;                                            // -C "--quick"
+    st = shi_kraken_protein_checks(c, opts);                               // before any input is read
+    if (st != SH_OK) return st;
     const auto t1 = now();
 
     // ---- ingest: both files side by side, parsed in place ----
@@ -1660,13 +1662,14 @@ sh_status k2_stream_library(const char *const *input, uint32_t n_input, uint64_t
 }
 
 // kraken2-build's construct_seed_template + build_db's two bits per position: l - 2s ones, then s times "01", each doubled
-uint64_t k2_spaced_mask(int32_t l, int32_t spaces)
+// (bits = 2), or for a protein database each taken four times (bits = 4)
+uint64_t k2_spaced_mask(int32_t l, int32_t spaces, int32_t bits = 2)
 {
     uint64_t m = 0;
     for (int32_t i = 0; i < l; ++i) {
         const int32_t from_end = l - 1 - i;
         const bool one = from_end >= 2 * spaces || (from_end & 1) == 0;
-        m = m << 2 | (one ? 3u : 0u);
+        m = m << bits | (one ? (1u << bits) - 1u : 0u);
     }
     return m;
 }
@@ -1703,14 +1706,18 @@ extern "C" sh_status sh_k2_build_run(const sh_k2_build_config *c, sh_k2_build_re
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto sec = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
     const auto t_begin = now();
+    // --protein (kraken2-build --protein as recalled: PARITY UNPINNED): an amino-acid FASTA library, k 15, l 12, no minimizer spaces
+    const bool protein = c->protein != 0;
     sh_k2_opts opts;
-    sh_k2_default_opts(&opts);
+    if (protein) sh_k2_default_protein_opts(&opts); else sh_k2_default_opts(&opts);
     if (c->k > 0) opts.k = c->k;
     if (c->l > 0) opts.l = c->l;
-    SH_CHECK(opts.l >= 1 && opts.l <= 31 && opts.k >= opts.l && opts.k - opts.l + 1 <= 16, SH_ERR_BAD_ARG, "k2-build: unsupported k=%d l=%d", opts.k, opts.l);
-    const int32_t spaces = c->minimizer_spaces == 0 ? 7 : std::max(c->minimizer_spaces, 0);
+    SH_CHECK(opts.l >= 1 && opts.l <= (protein ? 15 : 31) && opts.k >= opts.l && opts.k - opts.l + 1 <= 16, SH_ERR_BAD_ARG, "k2-build: unsupported k=%d l=%d%s", opts.k, opts.l,
+             protein ? " for a protein database" : "");
+    SH_CHECK(!protein || !c->mask_low_complexity, SH_ERR_BAD_ARG, "k2-build: --mask-low-complexity is not supported with --protein (the mask is for nucleotides)");
+    const int32_t spaces = c->minimizer_spaces == 0 && !protein ? 7 : std::max(c->minimizer_spaces, 0);
     SH_CHECK(spaces <= opts.l / 4, SH_ERR_BAD_ARG, "k2-build: at most l / 4 = %d minimizer spaces", opts.l / 4);
-    opts.spaced_seed_mask = k2_spaced_mask(opts.l, spaces);
+    opts.spaced_seed_mask = protein ? (spaces ? k2_spaced_mask(opts.l, spaces, 4) : 0) : k2_spaced_mask(opts.l, spaces);
     const uint64_t chunk = std::max<uint64_t>(c->chunk_bytes ? c->chunk_bytes : env_mb("SCRUBBY_HIP_K2_BUILD_CHUNK_MB", 256ull << 20), (uint64_t)(4 * opts.k));
     SH_CHECK(chunk < (1ull << 31), SH_ERR_BAD_ARG, "k2-build: batches of at most 2 GiB");
     // low-complexity masking (off: the library is taken as given, byte for byte what it was)

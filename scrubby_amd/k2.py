@@ -15,7 +15,7 @@ class K2Opts(C.Structure):
     _fields_ = [("k", C.c_int32), ("l", C.c_int32), ("spaced_seed_mask", C.c_uint64), ("toggle_mask", C.c_uint64),
                 ("min_acceptable_hash", C.c_uint64), ("value_bits", C.c_int32), ("min_hit_groups", C.c_int32),
                 ("confidence", C.c_double), ("min_base_quality", C.c_int32), ("quick", C.c_int32),
-                ("long_unit_bases", C.c_int32), ("pad_", C.c_int32)]
+                ("long_unit_bases", C.c_int32), ("protein", C.c_int32)]
 
 
 class K2TaxNode(C.Structure):
@@ -30,7 +30,7 @@ class K2Info(C.Structure):
 class K2Stats(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("n_classified", C.c_uint64), ("n_probes", C.c_uint64), ("n_kmers", C.c_uint64),
                 ("n_overflow", C.c_uint64), ("ms_classify", C.c_float), ("ms_total", C.c_float), ("n_masked_bases", C.c_uint64),
-                ("n_long_units", C.c_uint64), ("ms_long", C.c_float), ("pad_", C.c_int32)]
+                ("n_long_units", C.c_uint64), ("ms_long", C.c_float), ("ms_translate", C.c_float)]
 
 
 class KrakenConfig(C.Structure):
@@ -63,7 +63,7 @@ class K2BuildConfig(C.Structure):
                 ("k", C.c_int32), ("l", C.c_int32), ("minimizer_spaces", C.c_int32), ("value_bits", C.c_int32),
                 ("capacity", C.c_uint64), ("load_factor", C.c_double), ("max_db_size", C.c_uint64), ("chunk_bytes", C.c_uint64),
                 ("device", C.c_int32), ("pad", C.c_int32),
-                ("mask_low_complexity", C.c_int32), ("mask_window", C.c_int32), ("mask_threshold", C.c_int32), ("pad2", C.c_int32)]
+                ("mask_low_complexity", C.c_int32), ("mask_window", C.c_int32), ("mask_threshold", C.c_int32), ("protein", C.c_int32)]
 
 
 class K2BuildResult(C.Structure):
@@ -166,7 +166,7 @@ K2_WAVE_TILE = 64 * 63
 
 
 def _stats_dict(st):
-    return {n: getattr(st, n) for n, _ in K2Stats._fields_ if n != "pad_"}
+    return {n: getattr(st, n) for n, _ in K2Stats._fields_}
 
 
 def _take_hits(h):
@@ -254,6 +254,58 @@ def default_opts():
     o = K2Opts()
     S.check(S.load().sh_k2_default_opts(C.byref(o)))
     return o
+
+
+def default_protein_opts():
+    """the defaults of a protein database (sh_k2_default_protein_opts): k 15, l 12 amino acids, no spaced seed, protein = 1"""
+    o = K2Opts()
+    S.check(S.load().sh_k2_default_protein_opts(C.byref(o)))
+    return o
+
+
+AA_AMBIGUOUS = 0x80         # a translated code byte that is no amino acid of the reduced alphabet (X)
+
+
+def _records_flat(records, pad, fill):
+    arrs = [np.frombuffer(bytes(r), dtype=np.uint8) if not isinstance(r, np.ndarray) else np.ascontiguousarray(r, dtype=np.uint8) for r in records]
+    off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    if arrs:
+        off[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+    return np.concatenate(arrs + [np.full(pad, fill, np.uint8)]), off
+
+
+def translate_host(records, quals=None, min_qual=0, as_letters=False):
+    """Six-frame translation on the CPU (sh_k2_translate_host; no GPU needed) of a list of nucleotide sequences (quals: a list of
+    Phred+33 byte strings, or None).  Returns (out, offsets): record r's frames 0..5 lie back to back from
+    out[2 * offsets[r]], (n-1)//3, (n-2)//3 and n//3 residues forward and as many reverse; scanner codes 0..15 and AA_AMBIGUOUS,
+    or with as_letters the residues themselves.  Bytes between records are zero."""
+    flat, off = _records_flat(records, 8, ord("N"))
+    q = _records_flat(quals, 8, 0xff)[0] if quals is not None else None
+    out = np.zeros(2 * int(off[-1]) + 8, dtype=np.uint8)
+    S.check(S.load().sh_k2_translate_host(C.c_void_p(flat.ctypes.data), C.c_void_p(q.ctypes.data) if q is not None else None, C.c_void_p(off.ctypes.data),
+                                          C.c_uint64(len(off) - 1), C.c_int32(min_qual), C.c_int32(int(bool(as_letters))), C.c_void_p(out.ctypes.data)))
+    return out, off
+
+
+def translate_device(records, quals=None, min_qual=0, as_letters=False, misalign=0):
+    """The same on the GPU (sh_k2_translate_device, k_k2_translate).  misalign: the batch's first base sits that many bytes behind
+    an 8-byte boundary (and offsets[0] = misalign), the output starts as many bytes behind one."""
+    import torch
+    S.require_gpu()
+    flat, off = _records_flat([b"N" * misalign] + list(records) if misalign else records, 8, ord("N"))
+    n_rec = len(off) - 1 - (1 if misalign else 0)
+    d_bases = torch.from_numpy(flat).cuda()
+    d_off = torch.from_numpy(off[1 if misalign else 0:].view(np.int64).copy()).cuda()
+    d_q = None
+    if quals is not None:
+        d_q = torch.from_numpy(_records_flat([b"!" * misalign] + list(quals) if misalign else quals, 8, 0xff)[0]).cuda()
+    n_bases = int(off[-1]) - misalign
+    d_out = torch.zeros(2 * n_bases + 8 + misalign, dtype=torch.uint8, device="cuda")
+    S.check(S.load().sh_k2_translate_device(C.c_void_p(d_bases.data_ptr()), C.c_void_p(d_q.data_ptr()) if d_q is not None else None, C.c_void_p(d_off.data_ptr()),
+                                            C.c_uint64(n_rec), C.c_int32(min_qual), C.c_int32(int(bool(as_letters))), C.c_void_p(d_out.data_ptr() + misalign),
+                                            S._stream_ptr()))
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy()[misalign:], (off[1 if misalign else 0:] - np.uint64(misalign))
 
 
 def make_taxonomy(parents, externals, names, ranks):
@@ -439,10 +491,11 @@ def mask_file(input, output, window=0, threshold=0, replacement=b"x", soft=False
 
 def build_database(inputs, output_dir, taxonomy_dir=None, seqid2taxid=None, taxid=0, name=None, rank=None, k=0, l=0, minimizer_spaces=0,
                    capacity=0, load_factor=0.0, max_db_size=0, value_bits=0, chunk_bytes=0, device=0, mask=False, mask_window=0,
-                   mask_threshold=0):
+                   mask_threshold=0, protein=False):
     """`scrubby-hip k2-build` (sh_k2_build_run): FASTA library files + (taxonomy directory [+ id map] | one taxid) -> a database
     directory.  minimizer_spaces: 0 = Kraken 2's 7, negative = none.  mask=True: low-complexity sequence is masked on the GPU
-    before both passes (kraken2-build's default; off here).  Returns the result fields as a dict."""
+    before both passes (kraken2-build's default; off here).  protein=True: kraken2-build --protein, an amino-acid FASTA library
+    (defaults k 15, l 12, no minimizer spaces; mask=True is then refused).  Returns the result fields as a dict."""
     S.require_gpu()
     c = K2BuildConfig()
     files = [inputs] if isinstance(inputs, (str, bytes)) or hasattr(inputs, "__fspath__") else list(inputs)
@@ -455,6 +508,7 @@ def build_database(inputs, output_dir, taxonomy_dir=None, seqid2taxid=None, taxi
     c.k, c.l, c.minimizer_spaces, c.value_bits = k, l, minimizer_spaces, value_bits
     c.capacity, c.load_factor, c.max_db_size, c.chunk_bytes, c.device = capacity, load_factor, max_db_size, chunk_bytes, device
     c.mask_low_complexity, c.mask_window, c.mask_threshold = int(bool(mask)), mask_window, mask_threshold
+    c.protein = int(bool(protein))
     r = K2BuildResult()
     S.check(S.load().sh_k2_build_run(C.byref(c), C.byref(r)))
     return {n: getattr(r, n) for n, _ in K2BuildResult._fields_ if n != "pad"}

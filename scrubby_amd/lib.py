@@ -142,6 +142,7 @@ EXPORTS = [
     "sh_k2_taxonomy_header_taxon", "sh_k2_taxonomy_free", "sh_k2_capacity_plan", "sh_k2_max_db_size", "sh_k2_set_min_acceptable_hash",
     "sh_k2_insert_library_device", "sh_k2_estimator_create", "sh_k2_estimate_capacity_device", "sh_k2_estimator_free", "sh_k2_build_run",
     "sh_k2_mask_device", "sh_k2_mask_host", "sh_k2_mask_run",
+    "sh_k2_default_protein_opts", "sh_k2_translate_device", "sh_k2_translate_host",
     "sh_k2_value_counts_device", "sh_k2_value_counts", "sh_k2_counts_report", "sh_k2_inspect_header", "sh_k2_inspect_run",
     "sh_k2_distrib_stretch", "sh_k2_distrib_create", "sh_k2_distrib_reset", "sh_k2_distrib_free", "sh_k2_distrib_add_device", "sh_k2_distrib_last_ms",
     "sh_k2_distrib_count", "sh_k2_distrib_copy", "sh_k2_distrib_write", "sh_k2_distrib_read", "sh_k2_bracken_estimate", "sh_k2_bracken_write",
