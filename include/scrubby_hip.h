@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair; + the Kraken arm's wave route: sh_k2_opts grew long_unit_bases, sh_k2_stats n_long_units / ms_long, the old layouts are prefixes, the version kept; + the Kraken arm's abundance re-estimation: sh_k2_distrib_*, sh_k2_bracken_* added, nothing changed, the version kept): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
+#define SH_VERSION 104   /* 0.1.3 (+ kraken2 --minimum-base-quality / --quick: fields appended to sh_k2_opts, sh_k2_stats, sh_kraken_config, classify entries that take qualities added; the old layouts are prefixes; + Kraken 2 hit lists: classify entries that return them, sh_k2_hits_*, sh_k2_format_hits added, nothing changed; + the eight older Kraken classify entries removed, the version kept: sh_k2_classify_ex_device / _batch is the one pair; + the Kraken arm's wave route: sh_k2_opts grew long_unit_bases, sh_k2_stats n_long_units / ms_long, the old layouts are prefixes, the version kept; + the Kraken arm's abundance re-estimation: sh_k2_distrib_*, sh_k2_bracken_* added, nothing changed, the version kept; + DEFLATE on the device: sh_deflate_*, sh_deflater_*, sh_gzip_member added, nothing changed, the version kept): sh_index_replicate / sh_classify_sharded, sh_ctx_debug_list 3..10, the long join's tree in LDS (round 5); 0.1.2: sh_stats grew n_locus_* / n_rmq_exact (round 4); 0.1.1: sh_opts grew the rmq_* fields (round 3); sh_trace has 12 words since 0.1.0's second round */
 
 typedef int32_t sh_status;
 enum {
@@ -858,6 +858,26 @@ typedef struct sh_k2_bracken_result {
     uint64_t n_report_rows, n_unknown_taxa;
 } sh_k2_bracken_result;
 sh_status sh_k2_bracken_run(const sh_k2_bracken_config *cfg, sh_k2_bracken_result *out);
+
+/* ---- DEFLATE on the device (sh_deflate.hip): the encoder behind .gz outputs when SCRUBBY_HIP_GZ_DEVICE=1 ----
+ * The input is cut into blocks of block_bytes (1024..65535; 0: 32768), each compressed on its own - no match reaches before its
+ * block's first byte - and written as one RFC 1951 block that starts on a byte boundary: dynamic Huffman, or stored when that is no
+ * larger, so the stream is never larger than n + 5 * max(1, ceil(n / block_bytes)): the bound.  n == 0 gives the two bytes 03 00.
+ * The output is the same bytes from run to run. */
+typedef struct sh_deflater sh_deflater;        /* scratch for inputs of up to max_bytes at one block size; one call at a time */
+typedef struct sh_deflate_stats { uint64_t n_blocks, n_stored, n_matches, n_literals, out_bytes; float ms; } sh_deflate_stats;
+#define SH_DEFLATE_LITERALS_ONLY 1             /* flags bit 0: no matches, Huffman coding only */
+uint64_t  sh_deflate_bound(uint64_t n, uint32_t block_bytes);
+sh_status sh_deflater_create(int32_t device, uint64_t max_bytes, uint32_t block_bytes, sh_deflater **out);
+/* raw DEFLATE stream; device pointers; d_in at any alignment; *out_len valid after the call (one synchronisation).
+ * out_cap below the bound, or n above max_bytes: SH_ERR_BAD_ARG naming the sizes. */
+sh_status sh_deflate_device(sh_deflater *df, const uint8_t *d_in, uint64_t n, int32_t flags, uint8_t *d_out, uint64_t out_cap,
+                            uint64_t *out_len, void *stream, sh_deflate_stats *stats);
+/* one complete gzip member from host memory: staged up through pinned memory, deflated, staged down, 10-byte header (1f 8b 08 00,
+ * mtime 0, xfl 0, os 3), CRC-32 (zlib's crc32 on the host) and ISIZE.  out_cap: the bound + 18. */
+sh_status sh_gzip_member(sh_deflater *df, const uint8_t *in, uint64_t n, int32_t flags, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                         sh_deflate_stats *stats);
+sh_status sh_deflater_free(sh_deflater *df);
 
 #ifdef __cplusplus
 }

@@ -121,3 +121,10 @@ sh_status shi_ctx_rebind(sh_ctx *c, const sh_index *idx);
 uint64_t shi_ctx_max_reads(const sh_ctx *c);
 uint64_t shi_ctx_max_bases(const sh_ctx *c);
 uint32_t shi_ctx_max_len(const sh_ctx *c);
+
+// sh_deflate.hip: sh_gzip_member with the CRC-32 of the input already known (pass 2 computes it before it takes a deflater), and the
+// stages of a deflater's last member in ms - staging up, kernels, staging down
+uint32_t shi_crc32(const uint8_t *in, uint64_t n);
+sh_status shi_gzip_member_crc(sh_deflater *df, const uint8_t *in, uint64_t n, int32_t flags, uint32_t crc, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                              sh_deflate_stats *stats);
+void shi_deflater_stage_ms(const sh_deflater *df, double ms3[3]);

@@ -486,6 +486,80 @@ bool gz_member(const char *src, size_t n, int level, std::string &dst)
     return ok;
 }
 
+// SCRUBBY_HIP_GZ_DEVICE=1: pass 2 hands the filtered chunks of .gz outputs to a few device deflaters (sh_deflate.hip) instead of zlib.
+// A deflater serves one chunk at a time; a worker that finds none free waits for one.  Whatever goes wrong - no deflater could be made,
+// a chunk larger than they were sized for, a failing call - sends that chunk through zlib, and the run says so once.
+struct GzDevicePool {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<sh_deflater *> idle;
+    int n_made = 0;
+    size_t max_bytes = 0;
+    std::atomic<bool> said{false};
+    std::atomic<uint64_t> n_device{0}, n_host{0}, us_wait{0}, us_h2d{0}, us_kernel{0}, us_d2h{0}, us_crc{0};      // SCRUBBY_HIP_DBG_HOST=1
+
+    static bool wanted() { const char *e = getenv("SCRUBBY_HIP_GZ_DEVICE"); return e && *e == '1'; }
+
+    GzDevicePool(int device, size_t chunk_bytes, int n)
+    {
+        max_bytes = chunk_bytes + chunk_bytes / 8 + (64u << 10);      // a chunk is cut at the record that passes chunk_bytes, and rewritten records may grow
+        for (int i = 0; i < n; ++i) {
+            sh_deflater *df = nullptr;
+            if (sh_deflater_create(device, max_bytes, 0, &df) != SH_OK) { say(sh_last_error()); break; }
+            idle.push_back(df); ++n_made;
+        }
+    }
+    ~GzDevicePool() { for (sh_deflater *df : idle) sh_deflater_free(df); }
+    GzDevicePool(const GzDevicePool &) = delete;
+    GzDevicePool &operator=(const GzDevicePool &) = delete;
+
+    void say(const char *why)
+    {
+        if (!said.exchange(true)) fprintf(stderr, "[scrubby-hip] SCRUBBY_HIP_GZ_DEVICE: %s; zlib deflates what the device does not\n", why);
+    }
+
+    // one gzip member of src[0, n) in dst; false: the caller deflates this chunk with zlib
+    bool member(const char *src, size_t n, std::string &dst)
+    {
+        if (n_made == 0) { ++n_host; return false; }
+        if (n > max_bytes) { say("a chunk is larger than the deflaters were sized for"); ++n_host; return false; }
+        auto tick = [] { return std::chrono::steady_clock::now(); };
+        auto usd = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
+        const auto tc = tick();
+        const uint32_t crc = shi_crc32((const uint8_t *)src, n);      // before a deflater is held: the others' chunks go through meanwhile
+        const auto t0 = tick();
+        us_crc += usd(tc, t0);
+        sh_deflater *df;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return !idle.empty(); });
+            df = idle.back(); idle.pop_back();
+        }
+        us_wait += usd(t0, tick());
+        dst.resize(sh_deflate_bound(n, 0) + 18);
+        uint64_t len = 0;
+        const sh_status rc = shi_gzip_member_crc(df, (const uint8_t *)src, n, 0, crc, (uint8_t *)dst.data(), dst.size(), &len, nullptr);
+        double ms3[3] = {0, 0, 0};
+        if (rc == SH_OK) shi_deflater_stage_ms(df, ms3);
+        const std::string why = rc == SH_OK ? std::string() : std::string(sh_last_error());
+        { std::lock_guard<std::mutex> lk(mu); idle.push_back(df); }
+        cv.notify_one();
+        if (rc != SH_OK) { say(why.c_str()); ++n_host; return false; }
+        dst.resize(len);
+        ++n_device;
+        us_h2d += (uint64_t)(ms3[0] * 1e3); us_kernel += (uint64_t)(ms3[1] * 1e3); us_d2h += (uint64_t)(ms3[2] * 1e3);
+        return true;
+    }
+
+    void finish() const { if (const char *e = getenv("SCRUBBY_HIP_DBG_HOST")) if (*e == '1') report(); }
+    void report() const
+    {
+        fprintf(stderr, "[scrubby-hip] pass 2 device deflate: %d deflaters, %llu chunks on the device, %llu through zlib; CRC-32 %.0f ms, waiting for a deflater %.0f ms, "
+                        "staging up %.0f ms, kernels %.0f ms, staging down %.0f ms (summed over workers, inside filter + deflate)\n",
+                n_made, (unsigned long long)n_device.load(), (unsigned long long)n_host.load(), us_crc / 1e3, us_wait / 1e3, us_h2d / 1e3, us_kernel / 1e3, us_d2h / 1e3);
+    }
+};
+
 // FastqCleaner::clean_reads over one chunk (cleaner.rs:731-760): keep a record iff (id in set) == extract
 struct FilterOut {
     std::string bytes;
@@ -494,7 +568,7 @@ struct FilterOut {
     std::string error;
 };
 
-void filter_chunk(const Chunk &c, const ShardedIdSet &ids, bool extract, bool gz, bool want_dropped, FilterOut &o)
+void filter_chunk(const Chunk &c, const ShardedIdSet &ids, bool extract, bool gz, bool want_dropped, FilterOut &o, GzDevicePool *gz_device = nullptr)
 {
     std::string plain;
     plain.reserve(c.len + 64);
@@ -520,7 +594,8 @@ void filter_chunk(const Chunk &c, const ShardedIdSet &ids, bool extract, bool gz
     }
     flush();
     if (!gz) { o.bytes.swap(plain); return; }
-    if (!plain.empty() && !gz_member(plain.data(), plain.size(), 6, o.bytes)) o.error = "deflate failed";
+    if (plain.empty() || (gz_device && gz_device->member(plain.data(), plain.size(), o.bytes))) return;
+    if (!gz_member(plain.data(), plain.size(), 6, o.bytes)) o.error = "deflate failed";
 }
 
 // pass 2 for one file: sources chunks (retained, or streamed again), filters on `n_workers` threads, writes in order
@@ -531,6 +606,7 @@ struct FileFilter {
     const ShardedIdSet *ids;
     bool extract, want_dropped;
     int n_workers;
+    GzDevicePool *gz_device = nullptr;                      // SCRUBBY_HIP_GZ_DEVICE=1 and a .gz output: the run's deflaters
     uint64_t n_in = 0, n_out = 0;
     std::vector<std::string> dropped;
     std::string error;
@@ -588,7 +664,7 @@ struct FileFilter {
                 }
                 FilterOut o;
                 const auto t0 = tick();
-                filter_chunk(*ch, *ids, extract, gz, want_dropped, o);
+                filter_chunk(*ch, *ids, extract, gz, want_dropped, o, gz ? gz_device : nullptr);
                 if (retained) (*retained)[i].reset();      // each index is visited once; the unmap of ~64 MB happens here, on this worker
                 ch.reset();
                 const auto t1 = tick();
@@ -643,6 +719,17 @@ size_t env_mb(const char *name, size_t dflt_bytes)
 {
     const char *e = getenv(name);
     return e && *e ? (size_t)strtoull(e, nullptr, 10) << 20 : dflt_bytes;
+}
+
+// the run's device deflaters: made when SCRUBBY_HIP_GZ_DEVICE=1 (read per run) and some output is .gz; else null and nothing changes
+std::unique_ptr<GzDevicePool> make_gz_device_pool(const char *const *output, uint32_t n_files, int device, size_t chunk_bytes)
+{
+    bool any_gz = false;
+    for (uint32_t i = 0; i < n_files; ++i) any_gz = any_gz || ends_with(output[i], ".gz");
+    if (!any_gz || !GzDevicePool::wanted()) return nullptr;
+    const char *e = getenv("SCRUBBY_HIP_GZ_DEVICE_POOL");
+    const int n = e && *e ? std::min(16, std::max(1, atoi(e))) : 4;
+    return std::unique_ptr<GzDevicePool>(new GzDevicePool(device, chunk_bytes, n));
 }
 
 size_t retain_budget()
@@ -1252,12 +1339,16 @@ extern "C" sh_status sh_reads_run(const sh_reads_config *c, sh_reads_result *res
     sh_status fst[2] = {SH_OK, SH_OK};
     std::string ferr[2];
     std::vector<std::thread> filters;
+    std::unique_ptr<GzDevicePool> gz_device = make_gz_device_pool(c->output, c->n_files, c->device, chunk_bytes);
     for (uint32_t i = 0; i < c->n_files; ++i) {
         ff[i] = FileFilter{c->input[i], c->output[i], retained ? &kept[i] : nullptr, chunk_bytes, &depleted, c->extract != 0, (bool)want_dropped,
                            std::max(1, threads / (int)c->n_files)};
+        ff[i].gz_device = gz_device.get();
         filters.emplace_back([&, i]() { fst[i] = ff[i].run(); if (fst[i] != SH_OK) ferr[i] = sh_last_error(); });
     }
     for (auto &t : filters) t.join();
+    if (gz_device) gz_device->finish();
+    gz_device.reset();
     for (uint32_t i = 0; i < c->n_files; ++i)
         if (fst[i] != SH_OK) { sh_set_error("%s", ferr[i].c_str()); return fst[i]; }
     kept[0].clear(); kept[1].clear();
@@ -1525,11 +1616,14 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     std::string ferr[2];
     {
         std::vector<std::thread> filters;
+        std::unique_ptr<GzDevicePool> gz_device = make_gz_device_pool(c->output, c->n_files, c->device, chunk_bytes);
         for (uint32_t i = 0; i < c->n_files; ++i) {
             ff[i] = FileFilter{c->input[i], c->output[i], &pf[i].chunks, chunk_bytes, &dep, c->extract != 0, (bool)want_dropped, std::max(1, threads / (int)c->n_files)};
+            ff[i].gz_device = gz_device.get();
             filters.emplace_back([&, i]() { fst[i] = ff[i].run(); if (fst[i] != SH_OK) ferr[i] = sh_last_error(); });
         }
         for (auto &t : filters) t.join();
+        if (gz_device) gz_device->finish();
     }
     for (uint32_t i = 0; i < c->n_files; ++i) if (fst[i] != SH_OK) { sh_set_error("%s", ferr[i].c_str()); return fst[i]; }
     const auto t4 = now();

@@ -122,6 +122,16 @@ class ReadParams(C.Structure):
                 ("sub_per_10k", C.c_uint32), ("n_read_pct", C.c_uint32)]
 
 
+class DeflateStats(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("n_stored", C.c_uint64), ("n_matches", C.c_uint64), ("n_literals", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SH_DEFLATE_LITERALS_ONLY = 1
+
 EXPORTS = [
     "sh_version", "sh_device_count", "sh_last_error", "sh_preset",
     "sh_index_build", "sh_index_build_device", "sh_index_build_fasta", "sh_index_save", "sh_index_load",
@@ -147,6 +157,7 @@ EXPORTS = [
     "sh_k2_distrib_stretch", "sh_k2_distrib_create", "sh_k2_distrib_reset", "sh_k2_distrib_free", "sh_k2_distrib_add_device", "sh_k2_distrib_last_ms",
     "sh_k2_distrib_count", "sh_k2_distrib_copy", "sh_k2_distrib_write", "sh_k2_distrib_read", "sh_k2_bracken_estimate", "sh_k2_bracken_write",
     "sh_k2_distrib_run", "sh_k2_bracken_run",
+    "sh_deflate_bound", "sh_deflater_create", "sh_deflate_device", "sh_gzip_member", "sh_deflater_free",
 ]
 
 _LIB = None
@@ -205,10 +216,16 @@ def load():
     L.sh_host_filter_fastx.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u64, i32, C.POINTER(u64), C.POINTER(u64)]
     L.sh_host_filter_fastx_stream.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u64, i32, u64, i32, i32, C.POINTER(u64), C.POINTER(u64)]
     L.sh_host_read_difference.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.sh_deflate_bound.argtypes = [u64, u32]
+    L.sh_deflater_create.argtypes = [i32, u64, u32, C.POINTER(vp)]
+    L.sh_deflate_device.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), vp, C.POINTER(DeflateStats)]
+    L.sh_gzip_member.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(DeflateStats)]
+    L.sh_deflater_free.argtypes = [vp]
     for name in EXPORTS:
-        if name not in ("sh_version", "sh_device_count", "sh_last_error", "sh_index_set_size"):
+        if name not in ("sh_version", "sh_device_count", "sh_last_error", "sh_index_set_size", "sh_deflate_bound"):
             getattr(L, name).restype = i32
     L.sh_index_set_size.restype = u32
+    L.sh_deflate_bound.restype = u64
     _LIB = L
     return L
 
@@ -585,3 +602,56 @@ def synth_long_reads_device(P, R, r0, n_records, d_offsets, n_bases, out):
     """Long reads of the config-4 stand-in; d_offsets: int64 CUDA tensor [n_records+1] (lengths from the CPU twin)."""
     check(require_gpu().sh_synth_long_reads_device(C.byref(P), C.byref(R), r0, n_records, C.c_void_p(d_offsets.data_ptr()), n_bases,
                                                   C.c_void_p(out.data_ptr()), _stream_ptr()))
+
+
+def deflate_bound(n, block_bytes=0):
+    """The most bytes a stream of n input bytes in blocks of block_bytes takes (sh_deflate_bound)."""
+    return int(load().sh_deflate_bound(n, block_bytes))
+
+
+class Deflater:
+    """Owns an sh_deflater: DEFLATE on the device for inputs of up to max_bytes in blocks of block_bytes (0: 32768)."""
+
+    def __init__(self, max_bytes, block_bytes=0, device=0):
+        L = require_gpu()
+        self.h = C.c_void_p()
+        self.max_bytes, self.block_bytes = max_bytes, block_bytes
+        check(L.sh_deflater_create(device, max_bytes, block_bytes, C.byref(self.h)))
+
+    def deflate_device(self, d_in, n, d_out, flags=0, out_cap=None):
+        """d_in / d_out: torch uint8 CUDA tensors (d_in at any offset of its storage); raw DEFLATE stream -> (out_len, stats)."""
+        st, out_len = DeflateStats(), C.c_uint64(0)
+        cap = d_out.numel() if out_cap is None else out_cap
+        check(load().sh_deflate_device(self.h, C.c_void_p(d_in.data_ptr() if n else 0), n, flags, C.c_void_p(d_out.data_ptr()), cap, C.byref(out_len),
+                                       _stream_ptr(), C.byref(st)))
+        return out_len.value, st.as_dict()
+
+    def deflate(self, data, flags=0):
+        """bytes in, (raw DEFLATE stream as bytes, stats) out, through device tensors."""
+        import torch
+        n = len(data)
+        d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if n else torch.zeros(1, dtype=torch.uint8, device="cuda")
+        d_out = torch.zeros(deflate_bound(n, self.block_bytes), dtype=torch.uint8, device="cuda")
+        out_len, st = self.deflate_device(d_in, n, d_out, flags)
+        return d_out[:out_len].cpu().numpy().tobytes(), st
+
+    def gzip_member(self, data, flags=0, out_cap=None):
+        """bytes in, (one gzip member as bytes, stats) out (sh_gzip_member: host memory both ways)."""
+        n = len(data)
+        cap = deflate_bound(n, self.block_bytes) + 18 if out_cap is None else out_cap
+        src = np.frombuffer(data, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        st, out_len = DeflateStats(), C.c_uint64(0)
+        check(load().sh_gzip_member(self.h, src.ctypes.data, n, flags, out.ctypes.data, cap, C.byref(out_len), C.byref(st)))
+        return out[:out_len.value].tobytes(), st.as_dict()
+
+    def close(self):
+        if self.h:
+            load().sh_deflater_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
