@@ -135,6 +135,7 @@ typedef struct sh_stats {
     uint64_t n_rmq_exact;      /* long-read presets: reads whose RMQ join was redone on the literal krmq tree (tied priorities, windows beyond the LDS ring, rmq_size_cap) */
     uint64_t n_rmq_open;       /* ... reads that met such a tie and kept the scan's choice (smallest index): 0 by default since round 5 (every tied read takes the tree); only with SCRUBBY_HIP_RMQ_EXACT_MAX = N >= 0, for reads of more than N chain anchors */
     uint64_t n_ext_ondemand;   /* reads beyond the extension stage's prepared working-memory sizes, redone with memory allocated for them (visits, both kernels) */
+    uint64_t n_lc_filtered;    /* SH_F_CIGAR flag-only, counted with SCRUBBY_HIP_DBG & 16 only: reads k_local_cluster decided although a seed of theirs lies above mid_occ (part of n_ext_shortcut) */
 } sh_stats;
 
 typedef struct sh_index sh_index;

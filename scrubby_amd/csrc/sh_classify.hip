@@ -80,7 +80,9 @@ struct Counters {
     uint32_t n_long_segs, pad2;
     uint32_t ext_reason[8];       // why the top chain did not settle a read (k_ext_top)
     uint32_t lext_exact_direct, lext_pad_d;      // giants whose first pass ran on the EXACT instance and asked the tree
-    uint32_t ext_s3[8];           // SCRUBBY_HIP_DBG & 16: outcome of the local-cluster shortcut (k_expand): 0 tried, 1 no singleton / filtered seed, 2 singletons apart, 3 window grew / too many, 4 K > 64, 5 no margin over U_out, 6 lemma, 7 decided
+    // SCRUBBY_HIP_DBG & 16 (k_local_cluster<true>; the plain kernel has no such store): how each read of k_local_cluster's list ended (LC_*), and
+    // per outcome the anchors the occurrence filter admits for those reads (sum of occ over the seeds at or below mid_occ: what k_expand generates)
+    uint32_t lc_why[16]; unsigned long long lc_anchors[16];
     uint32_t ext_overflow, ext_n_list, ext_ticket, ext_regions, ext_dropped, ext_n_redo, ext_n_list2, ext_ticket2, ext_n_redo2, ext_ticket3, ext_n_unres, ext_ticket_unres, ext_n_unres_in, ext_pad8;      // extension stage (sh_align.h)
     uint32_t ext_n_recs[SINK_SHARDS]; unsigned long long ext_n_anch[SINK_SHARDS];                 // hand-over cursors, one per shard
     uint32_t lext_n_exact2, lext_ticket_exact2;      // the exact pass's second list (reads of the 4096-anchor ring)
@@ -1023,9 +1025,19 @@ __device__ inline void wave_rank_sort(uint64_t &x, uint32_t &q, uint32_t n, uint
 //   2. a chain made of anchors outside K only uses seeds that have occurrences outside K; its score is at most the query bases
 //      those seeds' k-mers cover (U_out: a link adds min(k, dq) at most);
 //   3. so if K's top chain scores more than U_out it is regs[0] of mm_gen_regs whatever the rest holds, it is aligned, and chain_lemma
-//      decides whether it survives.  Anything else (no singleton, a seed above mid_occ, singletons at several loci, K beyond 64 anchors,
-//      no such margin, a stretch the lemma cannot vouch for) stays on the list for the full path.
+//      decides whether it survives.  Anything else (no singleton, singletons at several loci, K beyond 64 anchors, no such margin, a
+//      stretch the lemma cannot vouch for) stays on the list for the full path.
+// Seeds above mid_occ.  Where the read's length makes every streak of mm_seed_select keep none of them
+// (max_high_occ = (int)(len / occ_dist + .499) = 0: k_expand's `no_keep`, below 250 bases at occ_dist = 500), the mid_occ pass filters such
+// a seed: it is no anchor there.  The max_occ pass, which would bring it back, only happens when the mid_occ pass found no chain at all
+// (k_finalize: n_u == 0 && rep_len > 0).  So if K's top chain exists and wins, the read is decided in the mid_occ pass whatever the
+// filtered seeds hold: the lane of such a seed takes no part here - it is no singleton, is never searched, adds nothing to K and nothing
+// to U_out - and steps 1 to 3 hold for the anchor set of the mid_occ pass.  A read long enough for a streak to keep a seed is declined.
 // Its own kernel (not a step of k_expand): ~60 registers instead of ~150, so three times the waves hide the dependent list probes.
+// STATS (SCRUBBY_HIP_DBG & 16, k_local_cluster<true>): every read's outcome is counted in Counters::lc_why / lc_anchors.  The kernel itself is
+// the template: as a __device__ body that two kernels handed their K2Args by reference, the same text decided no read at all (measured).
+enum { LC_TRIED = 0, LC_NO_SINGLETON, LC_HIGH_SEED, LC_APART, LC_WINDOW, LC_K_SIZE, LC_MARGIN, LC_LEMMA, LC_DECIDED, LC_DECIDED_FILTERED, LC_N_SEED };
+template <bool STATS>      // true: k_local_cluster<true> counts, false: the plain kernel
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_local_cluster(K2Args a)
 {
     __shared__ uint64_t e_x[64];
@@ -1052,13 +1064,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         const uint32_t n_seed = info >> 16 & 0x7fffu;
         const int32_t qlen = (int32_t)(a.offsets[r + 1] - a.offsets[r]);
         bool decided = false;
+        uint32_t why = LC_N_SEED, adm = 0;      // STATS only
         if (n_seed <= 64u && n_seed >= 2u) {
             const bool have0 = lane < n_seed;
             const uint4 rec0 = have0 ? a.records[(size_t)r * a.seed_cap + lane] : make_uint4(0, 0, 0, 0);
             const uint32_t occ0 = rec0.z & SH_REC_OCC_MASK;
-            const bool single = have0 && occ0 == 1u;
+            const bool high0 = have0 && occ0 > (uint32_t)P.mid_occ;      // filtered in the mid_occ pass (see above): the lane sits out
+            const bool single = have0 && occ0 == 1u && !high0;
             const uint64_t sm = __ballot(single);
-            bool ok = sm != 0 && __ballot(have0 && occ0 > (uint32_t)P.mid_occ) == 0;       // no seed is filtered: every occurrence is an anchor
+            const bool any_high = __ballot(high0) != 0;
+            bool ok = sm != 0;
+            // the same expression as k_expand's no_keep, with max_occ = mid_occ
+            if (ok && any_high) ok = (!(P.occ_dist > 0 && P.max_max_occ > P.mid_occ) || (int32_t)((double)qlen / (double)P.occ_dist + .499) <= 0);
+            if (STATS) { adm = wave_sum_u32(have0 && !high0 ? occ0 : 0u); why = sm == 0 ? LC_NO_SINGLETON : (!ok ? LC_HIGH_SEED : LC_LEMMA); }
             uint64_t xs = 0; uint32_t qs_ = 0;
             if (single) make_anchor((uint64_t)rec0.y << 32 | rec0.x, rec0.w, qlen, P.k, xs, qs_);
             const int fl = sm ? __ffsll((unsigned long long)sm) - 1 : 0;
@@ -1068,11 +1086,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             uint32_t lo = s_in ? (uint32_t)xs : 0xffffffffu, hi = s_in ? (uint32_t)xs : 0u;
             lo = wave_all_min_u32(lo); hi = wave_all_max_u32(hi);
             const uint32_t mdx = chain_max_dist_x(P, qlen);
+            if (STATS && ok && hi - lo > 4u * mdx) why = LC_APART;
             ok = ok && hi - lo <= 4u * mdx;                       // singletons of one locus; far-apart ones on one contig: full path
             const uint32_t rel = hiw >> 31;                      // strand relation of K's anchors
             const uint64_t w1m = (uint64_t)rec0.y << 32 | rec0.x;
             const uint64_t *__restrict__ lst = a.positions + (w1m >> SH_SLOT_NBITS);
-            const bool multi = have0 && occ0 > 1u;
+            const bool multi = have0 && occ0 > 1u && !high0;
             uint32_t c_l = s_in ? 1u : 0u, first_l = 0;
             if (ok) {
                 for (int round = 0; round < 4; ++round) {
@@ -1118,13 +1137,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                         }
                     }
                     nlo = wave_all_min_u32(nlo); nhi = wave_all_max_u32(nhi);
-                    if (__ballot(c_l > 16u) != 0) { ok = false; break; }
+                    if (__ballot(c_l > 16u) != 0) { ok = false; if (STATS) why = LC_WINDOW; break; }
                     if (nlo == lo && nhi == hi) break;
-                    if (round == 3) { ok = false; break; }
+                    if (round == 3) { ok = false; if (STATS) why = LC_WINDOW; break; }
                     lo = nlo; hi = nhi;
                 }
             }
             const uint32_t n_k = ok ? wave_sum_u32(c_l) : 0u;
+            if (STATS && ok && !(n_k >= 2 && n_k <= 64)) why = LC_K_SIZE;
             if (ok && n_k >= 2 && n_k <= 64) {
                 // K's anchors in generation order (seed order, then occurrence order): the order the full expansion gives them
                 const uint32_t ex = wave_excl_scan_u32(c_l, lane);
@@ -1156,7 +1176,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                 const uint32_t clen = start ? (above ? (uint32_t)__ffsll((unsigned long long)above) - 1u : n_k) - lane : 0u;
                 __syncthreads();
                 // U_out: query bases covered by the k-mers of the seeds that have occurrences outside K (lanes are in query order)
-                const bool outside = have0 && occ0 > c_l;
+                const bool outside = have0 && !high0 && occ0 > c_l;
                 const uint64_t om = __ballot(outside);
                 const uint64_t below = om & ((1ULL << lane) - 1);
                 const int32_t prev_en = (int32_t)((uint32_t)__shfl((int)rec0.w, below ? 63 - __clzll((unsigned long long)below) : 0) >> 1) + 1;
@@ -1192,7 +1212,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                                 mid.rid = (int32_t)(hi_w & 0x7fffffffu); mid.rev = (int32_t)(hi_w >> 31);
                                 mid.qs = (int32_t)q_first + 1 - P.k; mid.qe = (int32_t)q_last + 1; mid.rs = (int32_t)lo_first + 1 - P.k;
                             }
-                        } else fast = false;      // not regs[0] for sure, or too short: the general way (which will also decline)
+                        } else { fast = false; if (STATS && covered <= u_out) why = LC_MARGIN; }      // not regs[0] for sure, or too short: the general way (which will also decline)
                     }
                 }
                 // else K's clusters one after the other, each chained by the WHOLE wave (64 predecessors at a time, then the backtrack executed
@@ -1214,10 +1234,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                     SliceStore S{(const uint64_t *)&e_x[bc.base], (const uint32_t *)&e_q[bc.base], e_f + bc.base, e_pt + 2 * (size_t)bc.base};
                     code = chain_lemma(S, bc.zi, bc.end_i, P, (uint32_t)(S.X(bc.zi) >> 32), mid);
                 }
+                if (STATS && !fast && bc.n > 0 && !bc.tie && bc.score <= u_out) why = LC_MARGIN;
                 const bool mid_ok = resolve_mid_wave(code == 2, mid, a.bases + a.offsets[r], qlen, a.BC, P);
                 decided = __ballot(code == 1 || (code == 2 && mid_ok)) != 0;
+                if (STATS && decided) why = any_high ? LC_DECIDED_FILTERED : LC_DECIDED;
                 __syncthreads();
             }
+        }
+        if (STATS && lane == 0) {
+            if (why != LC_N_SEED) { atomicAdd(&a.ctr->lc_why[LC_TRIED], 1u); atomicAdd(&a.ctr->lc_anchors[LC_TRIED], (unsigned long long)adm); }
+            atomicAdd(&a.ctr->lc_why[why], 1u); atomicAdd(&a.ctr->lc_anchors[why], (unsigned long long)adm);
         }
         if (decided) { if (lane == 0) a.flags[r] = 1; ++n_hit; }
         else if (lane == 0) a.leftover[atomicAdd(a.leftover_count, 1u)] = r;
@@ -4073,7 +4099,8 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         K2Args pb = b;
         pb.work = c->d_big[0][cur0]; pb.work_count = &c->d_ctr->n_big[0];
         pb.leftover = c->d_big[0][cur0 ^ 1]; pb.leftover_count = &c->d_ctr->n_big_defer[0];
-        hipLaunchKernelGGL(k_local_cluster, dim3(256 * 32), dim3(64), 0, s, pb);      // latency-bound list probes: every wave slot
+        if (k.dbg & DBG_STATS) hipLaunchKernelGGL(k_local_cluster<true>, dim3(256 * 32), dim3(64), 0, s, pb);
+        else hipLaunchKernelGGL(k_local_cluster<false>, dim3(256 * 32), dim3(64), 0, s, pb);      // latency-bound list probes: every wave slot
         hipLaunchKernelGGL(k_pair_swap, dim3(1), dim3(1), 0, s, c->d_ctr);
         cur0 ^= 1;
     }
@@ -4108,7 +4135,13 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", c->h_ctr->cl_tot[0], c->h_ctr->cl_tot[1], c->h_ctr->cl_tot[2], c->h_ctr->cl_tot[3], c->h_ctr->cl_anchor_tot[0], c->h_ctr->cl_anchor_tot[1], c->h_ctr->cl_anchor_tot[2], c->h_ctr->cl_anchor_tot[3]);
             if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", c->h_ctr->sort_tot[6], c->h_ctr->sort_anchor_tot[6], c->h_ctr->sort_tot[0], c->h_ctr->sort_anchor_tot[0], c->h_ctr->sort_tot[1], c->h_ctr->sort_anchor_tot[1], c->h_ctr->sort_tot[2], c->h_ctr->sort_anchor_tot[2], c->h_ctr->sort_tot[3], c->h_ctr->sort_anchor_tot[3], c->h_ctr->sort_tot[4], c->h_ctr->sort_anchor_tot[4], c->h_ctr->sort_tot[5], c->h_ctr->sort_anchor_tot[5]);
             if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", c->h_ctr->pair_mid[0], c->h_ctr->pair_mid[1], c->h_ctr->pair_mid[2], c->h_ctr->pair_mid[3]);
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] local-cluster shortcut: tried %u, no singleton / filtered %u, singletons apart %u, window %u, K size %u, no margin %u, decided %u\n", c->h_ctr->ext_s3[0], c->h_ctr->ext_s3[1], c->h_ctr->ext_s3[2], c->h_ctr->ext_s3[3], c->h_ctr->ext_s3[4], c->h_ctr->ext_s3[5], c->h_ctr->ext_s3[7]);
+            if (k.dbg & DBG_STATS) {
+                const Counters &h = *c->h_ctr;
+                static const char *const lc_name[] = {"tried", "no singleton", "a seed above mid_occ", "singletons apart", "window grew / too many", "K size", "no margin over U_out", "lemma / no chain / tie", "decided", "decided, seeds filtered", "seeds not 2..64"};
+                fprintf(stderr, "[dbg] local-cluster shortcut, reads (anchors the occurrence filter admits):");
+                for (int i = 0; i <= LC_N_SEED; ++i) fprintf(stderr, "%s %s %u (%llu)", i ? "," : "", lc_name[i], h.lc_why[i], h.lc_anchors[i]);
+                fprintf(stderr, "\n");
+            }
             if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] ring DP: chunks in window %llu, beyond %llu, far rescans %llu; clusters %llu (anchors %llu), with a max_skip break %llu (anchors %llu), widest window %llu, anchors of clusters with a window > 64: %llu, > 128: %llu\n", c->h_ctr->cl_dbg[0], c->h_ctr->cl_dbg[1], c->h_ctr->cl_dbg[2], c->h_ctr->cl_dbg[3], c->h_ctr->cl_dbg[6], c->h_ctr->cl_dbg[4], c->h_ctr->cl_dbg[5], c->h_ctr->cl_dbg[7], c->h_ctr->cl_dbg[8], c->h_ctr->cl_dbg[9]);
             if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] parallel fill: reads done %llu (anchors %llu), not applicable %llu (anchors %llu), dirty anchors %llu; k_cluster_dp clusters prefilled %llu, sequential %llu (anchors %llu); read-level backtracks tried %llu, candidates listed %llu, given up (too many) %llu, chains visited %llu\n", c->h_ctr->pf_dbg[0], c->h_ctr->pf_dbg[3], c->h_ctr->pf_dbg[1], c->h_ctr->pf_dbg[4], c->h_ctr->pf_dbg[2], c->h_ctr->pf_dbg[5], c->h_ctr->pf_dbg[6], c->h_ctr->pf_dbg[7], c->h_ctr->pf_dbg[8], c->h_ctr->pf_dbg[11], c->h_ctr->pf_dbg[12], c->h_ctr->pf_dbg[10]);
             resk_done = c->h_ctr->n_resketch;
@@ -4644,6 +4677,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         uint64_t sum_host = 0, sum_mini = 0, sum_anchors = 0, sum_clusters = 0, sum_pair = 0, sum_lemma = 0, sum_pf = 0, sum_pfd = 0, sum_top = 0;
         for (int i = 0; i < 64; ++i) sum_lemma += c->h_ctr->sh_lemma[i];
         stats->n_ext_shortcut += sum_lemma;
+        stats->n_lc_filtered += c->h_ctr->lc_why[LC_DECIDED_FILTERED];
         for (int i = 0; i < 64; ++i) { sum_host += c->h_ctr->sh_host[i]; sum_mini += c->h_ctr->sh_mini[i]; sum_anchors += c->h_ctr->sh_anchors[i]; sum_clusters += c->h_ctr->sh_clusters[i]; sum_pair += c->h_ctr->sh_pair[i]; sum_pf += c->h_ctr->sh_pf_reads[i]; sum_pfd += c->h_ctr->sh_pf_dirty[i]; sum_top += c->h_ctr->sh_top[i]; }
         stats->n_reads += n_reads; stats->n_bases += n_bases;
         stats->n_host += sum_host - ext_dropped - c->h_ctr->lr_fb_had;
