@@ -880,6 +880,32 @@ sh_status sh_gzip_member(sh_deflater *df, const uint8_t *in, uint64_t n, int32_t
                          sh_deflate_stats *stats);
 sh_status sh_deflater_free(sh_deflater *df);
 
+/* ---- BGZF inflate on the device (sh_inflate.hip): the decoder behind .gz inputs when SCRUBBY_HIP_GUNZIP_DEVICE=1 ----
+ * A BGZF file (what bgzip writes) is a chain of gzip members of at most 64 KiB, each with its own compressed size in a BC extra
+ * subfield and no reference to anything before itself.  One wave inflates one member: stored, fixed and dynamic blocks, any number per
+ * member; every read stays inside the member's input extent, every write inside its ISIZE bytes, every distance inside what the member
+ * has produced.  CRC-32 of the output is taken on the device and compared with the trailer's.
+ * A member's status: 0 ok, 1 bad block type, 2 bad code lengths, 3 invalid symbol, 4 distance too far back, 5 input overrun,
+ * 6 output overrun, 7 output short of ISIZE, 8 stored LEN/NLEN mismatch, 9 CRC mismatch. */
+typedef struct sh_gz_member { uint64_t file_off, in_off; uint32_t in_len, out_len, crc32, status; } sh_gz_member;
+typedef struct sh_inflater sh_inflater;        /* scratch for calls of up to max_members members; one call at a time */
+typedef struct sh_inflate_stats { uint64_t n_members, n_stored_blocks, n_fixed_blocks, n_dynamic_blocks, in_bytes, out_bytes; float ms; } sh_inflate_stats;
+/* host only: the members of buf[0, n), a window of a file.  file_off: the member's offset in buf; in_off / in_len: its raw DEFLATE
+ * data; out_len / crc32: ISIZE and CRC-32 of its trailer.  *n_members found (at most cap), *consumed = bytes of buf they cover,
+ * *stopped = 0 end of buffer (or cap reached), 1 incomplete member, 2 not BGZF (not gzip, no BC subfield, ISIZE above 65536). */
+sh_status sh_bgzf_scan(const uint8_t *buf, uint64_t n, sh_gz_member *members, uint64_t cap, uint64_t *n_members, uint64_t *consumed, int32_t *stopped);
+sh_status sh_inflater_create(int32_t device, uint64_t max_in_bytes, uint64_t max_out_bytes, uint64_t max_members, sh_inflater **out);
+/* device pointers; members on the host, in any order: member i's bytes go to d_out + the sum of out_len before it, its data is
+ * d_in[in_off, in_off + in_len), and its status is filled on return (one synchronisation).  SH_ERR_IO names the first bad member's
+ * file_off and status.  More members, an input extent or an output larger than the inflater was made for, or out_cap below the sum of
+ * out_len: SH_ERR_BAD_ARG naming the sizes, before any launch. */
+sh_status sh_inflate_members_device(sh_inflater *inf, const uint8_t *d_in, sh_gz_member *members, uint64_t n_members, uint8_t *d_out, uint64_t out_cap,
+                                    void *stream, sh_inflate_stats *stats);
+/* host memory in and out through pinned staging: scan + inflate of a buffer that holds whole members only (else SH_ERR_IO naming
+ * the offset where the scan stopped) */
+sh_status sh_gunzip_bgzf(sh_inflater *inf, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_len, sh_inflate_stats *stats);
+sh_status sh_inflater_free(sh_inflater *inf);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,9 +14,56 @@
 #include <string>
 #include <vector>
 #include <dlfcn.h>
+#include <fcntl.h>
+#include <unistd.h>
 #include <zlib.h>
+#include "sh_common.h"
+#include "sh_inflate.h"
 
 namespace shc {
+
+// ---- SCRUBBY_HIP_GUNZIP_DEVICE=1: BGZF inputs inflated on the device (sh_inflate.hip) ----------------------------------------------------
+// A reader takes a window of compressed bytes, scans its member headers, and has a pooled inflater inflate the whole members of the
+// window; what the scan does not take goes through zlib from that member's file offset on.
+constexpr uint64_t GUNZIP_WINDOW_BYTES = 32ull << 20;      // compressed bytes per window: ~2000 members of FASTQ, one per wave the device holds
+constexpr uint64_t GUNZIP_OUT_BYTES = 192ull << 20;        // inflated bytes per call; a window that holds more is inflated in several calls
+constexpr uint64_t GUNZIP_MAX_MEMBERS = 1ull << 18;
+constexpr uint64_t GUNZIP_READER_MEMBERS = 1ull << 15;     // members a reader takes per fill (1 MiB of descriptors); a window with more is served in several fills
+constexpr uint64_t GUNZIP_FIRST_WINDOW_BYTES = 256ull << 10;      // the first window of a file is small: file_is_empty opens every input for one byte
+bool gunzip_device_wanted();                      // the switch, read at every call: only "1" turns it on
+int gunzip_reader_device();                       // the open run's device, else the calling thread's current one
+sh_inflater *gunzip_pool_acquire(int device);     // an idle inflater of that device, else a new one on it; nullptr: no device or no memory
+void gunzip_pool_release(sh_inflater *inf);
+void gunzip_note_zlib(const char *path, uint64_t file_off, const char *why);      // a file handed to zlib: counted, announced once per process
+void gunzip_count(uint64_t members, uint64_t bytes);
+struct GunzipRun {      // around a run: zeroes the counts, and at the end prints the SCRUBBY_HIP_DBG_HOST=1 line when the switch is on
+    explicit GunzipRun(int device);
+    ~GunzipRun();
+    GunzipRun(const GunzipRun &) = delete;
+};
+
+// the members of win[0, n) in calls that fit the inflater, appended to `out` (host) or written to d_out (device, contiguous); file_off of
+// the members is what an error names
+inline sh_status gunzip_window(sh_inflater *inf, const uint8_t *win, sh_gz_member *m, uint64_t n_members, std::vector<uint8_t> *out, uint8_t *d_out)
+{
+    for (uint64_t i = 0; i < n_members;) {
+        uint64_t j = i, bytes = 0;
+        while (j < n_members && j - i < GUNZIP_MAX_MEMBERS && bytes + m[j].out_len <= GUNZIP_OUT_BYTES) bytes += m[j++].out_len;
+        // the call's input is the stretch of the window its members lie in
+        const uint64_t base = m[i].in_off, end = m[j - 1].in_off + m[j - 1].in_len;
+        for (uint64_t k = i; k < j; ++k) m[k].in_off -= base;
+        size_t at = 0;
+        if (out) { at = out->size(); out->resize(at + bytes); }
+        uint64_t got = 0;
+        const sh_status rc = shi_gunzip_members(inf, win + base, end - base, m + i, j - i, out ? out->data() + at : nullptr, d_out, bytes, &got, nullptr);
+        for (uint64_t k = i; k < j; ++k) m[k].in_off += base;
+        if (rc != SH_OK) return rc;
+        if (d_out) d_out += bytes;
+        gunzip_count(j - i, bytes);
+        i = j;
+    }
+    return SH_OK;
+}
 
 // ---- libbz2 ---------------------------------------------------------------------------------------------------------------------
 struct bz_stream_t {
@@ -99,6 +146,88 @@ class In {
     bz_stream_t bz_{}; lzma_stream_t xz_{};
     bool codec_open_ = false, src_eof_ = false, end_ = false;
     std::vector<uint8_t> in_;
+    // SCRUBBY_HIP_GUNZIP_DEVICE=1 and a file whose first member is BGZF: fp_ is the file, in_[0, win_n_) the window of compressed bytes
+    // that begins at file offset foff_, inflated_[served_, ...) what the last window gave and has not been served yet
+    bool bgzf_ = false, first_window_ = true;
+    std::string path_;
+    uint64_t foff_ = 0;
+    size_t win_n_ = 0, served_ = 0;
+    std::vector<uint8_t> inflated_;
+    std::vector<sh_gz_member> members_;
+
+    // what gzread does for the plain and gzip files: -1 = error
+    long read_gz(void *buf, size_t n)
+    {
+        size_t done = 0;
+        while (done < n) {
+            const unsigned want = (unsigned)std::min<size_t>(n - done, 1u << 30);
+            const int got = gzread(gz_, (char *)buf + done, want);
+            if (got < 0) { int e; error = std::string("read error: ") + gzerror(gz_, &e); return -1; }
+            done += (size_t)got;
+            if ((unsigned)got < want) {
+                int e = Z_OK;
+                const char *msg = gzerror(gz_, &e);      // a truncated .gz ends with Z_BUF_ERROR, not with a clean end of stream
+                if (e != Z_OK && e != Z_STREAM_END) { error = std::string("read error: ") + (msg && *msg ? msg : "truncated gzip stream"); return -1; }
+                break;
+            }
+        }
+        return (long)done;
+    }
+    // the rest of the file, from the member at foff_ on, goes through zlib.  1 = gz_ reads on, 0 = what follows is no gzip member (zlib
+    // ignores such a tail behind a member), -1 = error
+    int bgzf_to_zlib(const char *why)
+    {
+        const bool gzip_here = win_n_ >= 2 && in_[0] == 0x1f && in_[1] == 0x8b;
+        bgzf_ = false;
+        fclose(fp_); fp_ = nullptr;
+        if (!gzip_here) { end_ = true; return 0; }
+        gunzip_note_zlib(path_.c_str(), foff_, why);
+        const int fd = ::open(path_.c_str(), O_RDONLY);
+        if (fd < 0 || lseek(fd, (off_t)foff_, SEEK_SET) < 0 || !(gz_ = gzdopen(fd, "rb"))) { if (fd >= 0) ::close(fd); error = "cannot open " + path_; return -1; }
+        gzbuffer(gz_, 1 << 20);
+        return 1;
+    }
+    // the next window: 1 = inflated_ holds bytes, 2 = handed to zlib, 0 = end of the file, -1 = error
+    int bgzf_fill()
+    {
+        for (;;) {
+            const size_t want = first_window_ ? (size_t)GUNZIP_FIRST_WINDOW_BYTES : (size_t)GUNZIP_WINDOW_BYTES;
+            if (in_.size() < want) in_.resize(want);
+            while (win_n_ < want && !src_eof_) {
+                const size_t got = fread(in_.data() + win_n_, 1, want - win_n_, fp_);
+                if (got == 0) { if (ferror(fp_)) { error = "read error"; return -1; } src_eof_ = true; }
+                win_n_ += got;
+            }
+            if (win_n_ == 0) { end_ = true; return 0; }
+            if (members_.empty()) members_.resize(GUNZIP_READER_MEMBERS);
+            uint64_t n_members = 0, consumed = 0;
+            const int stopped = shin_bgzf_scan(in_.data(), win_n_, (ShinMember *)members_.data(), members_.size(), &n_members, &consumed);
+            // one inflate call's worth of output at a time: the members past GUNZIP_OUT_BYTES of ISIZE stay in the window for the next fill,
+            // so inflated_ never holds more than that, however well the file compresses
+            for (uint64_t i = 0, bytes = 0; i < n_members; ++i) {
+                bytes += members_[i].out_len;
+                if (bytes > GUNZIP_OUT_BYTES) { n_members = i; consumed = members_[i].file_off; break; }
+            }
+            if (n_members == 0) {
+                if (stopped == 1 && src_eof_) { error = "read error: truncated BGZF member at file offset " + std::to_string(foff_); return -1; }
+                if (stopped == 1) { first_window_ = false; continue; }      // a member larger than the first window
+                const int r = bgzf_to_zlib("a gzip member that is not BGZF");
+                return r > 0 ? 2 : r;
+            }
+            sh_inflater *inf = gunzip_pool_acquire(gunzip_reader_device());
+            if (!inf) { const int r = bgzf_to_zlib("no device inflater"); return r > 0 ? 2 : r; }
+            for (uint64_t i = 0; i < n_members; ++i) members_[i].file_off += foff_;
+            inflated_.clear();
+            served_ = 0;
+            const sh_status rc = gunzip_window(inf, in_.data(), members_.data(), n_members, &inflated_, nullptr);
+            gunzip_pool_release(inf);
+            if (rc != SH_OK) { error = std::string("read error: ") + sh_last_error(); return -1; }
+            memmove(in_.data(), in_.data() + consumed, win_n_ - consumed);
+            win_n_ -= consumed; foff_ += consumed;
+            first_window_ = false;
+            if (!inflated_.empty()) return 1;
+        }
+    }
 public:
     std::string error;
     In() = default;
@@ -115,6 +244,20 @@ public:
         if (n >= 3 && m[0] == 'B' && m[1] == 'Z' && m[2] == 'h') kind_ = Kind::Bzip2;
         else if (n >= 6 && m[0] == 0xFD && m[1] == '7' && m[2] == 'z' && m[3] == 'X' && m[4] == 'Z' && m[5] == 0x00) kind_ = Kind::Xz;
         else kind_ = Kind::Plain;      // (gzip and plain alike: gzread passes plain bytes through)
+        if (kind_ == Kind::Plain && n >= 2 && m[0] == 0x1f && m[1] == 0x8b && gunzip_device_wanted()) {
+            rewind(f);
+            in_.resize((size_t)GUNZIP_FIRST_WINDOW_BYTES);
+            win_n_ = fread(in_.data(), 1, in_.size(), f);
+            sh_gz_member first;
+            uint64_t n_members = 0, consumed = 0;
+            const int stopped = shin_bgzf_scan(in_.data(), win_n_, (ShinMember *)&first, 1, &n_members, &consumed);
+            if (n_members == 1 || stopped == 1) {      // the first member is BGZF (or the beginning of one): the inflater is taken at the first read
+                fp_ = f; path_ = path; bgzf_ = true; first_window_ = true; foff_ = 0; served_ = 0;
+                inflated_.clear();
+                return true;
+            }
+            win_n_ = 0;
+        }
         if (kind_ == Kind::Plain) {
             fclose(f);
             gz_ = gzopen(path, "rb");
@@ -144,22 +287,22 @@ public:
     long read(void *buf, size_t n)
     {
         if (n == 0) return 0;
-        if (gz_) {
+        if (bgzf_) {
             size_t done = 0;
             while (done < n) {
-                const unsigned want = (unsigned)std::min<size_t>(n - done, 1u << 30);
-                const int got = gzread(gz_, (char *)buf + done, want);
-                if (got < 0) { int e; error = std::string("read error: ") + gzerror(gz_, &e); return -1; }
-                done += (size_t)got;
-                if ((unsigned)got < want) {
-                    int e = Z_OK;
-                    const char *msg = gzerror(gz_, &e);      // a truncated .gz ends with Z_BUF_ERROR, not with a clean end of stream
-                    if (e != Z_OK && e != Z_STREAM_END) { error = std::string("read error: ") + (msg && *msg ? msg : "truncated gzip stream"); return -1; }
-                    break;
+                if (served_ == inflated_.size()) {
+                    const int r = bgzf_fill();
+                    if (r < 0) return -1;
+                    if (r == 0) break;
+                    if (r == 2) { const long g = read_gz((char *)buf + done, n - done); return g < 0 ? -1 : (long)done + g; }
                 }
+                const size_t k = std::min(n - done, inflated_.size() - served_);
+                memcpy((char *)buf + done, inflated_.data() + served_, k);
+                done += k; served_ += k;
             }
             return (long)done;
         }
+        if (gz_) return read_gz(buf, n);
         if (!fp_ || end_) return 0;
         size_t done = 0;
         while (done < n && !end_) {
@@ -206,6 +349,8 @@ public:
         if (codec_open_) { if (kind_ == Kind::Bzip2) Bz2Api::get().DecompressEnd(&bz_); else if (kind_ == Kind::Xz) LzmaApi::get().end(&xz_); codec_open_ = false; }
         if (fp_) { fclose(fp_); fp_ = nullptr; }
         src_eof_ = end_ = false;
+        bgzf_ = false; win_n_ = 0; served_ = 0; foff_ = 0;
+        inflated_.clear();
     }
 };
 

@@ -128,3 +128,8 @@ uint32_t shi_crc32(const uint8_t *in, uint64_t n);
 sh_status shi_gzip_member_crc(sh_deflater *df, const uint8_t *in, uint64_t n, int32_t flags, uint32_t crc, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                               sh_deflate_stats *stats);
 void shi_deflater_stage_ms(const sh_deflater *df, double ms3[3]);
+
+// sh_inflate.hip: the members of a host buffer (in_off relative to `in`, n bytes; file_off as the caller wants it named) inflated into
+// host memory through the inflater's pinned staging; d_out != nullptr: the bytes stay on the device there and `out` is not written
+sh_status shi_gunzip_members(sh_inflater *inf, const uint8_t *in, uint64_t n, sh_gz_member *members, uint64_t n_members, uint8_t *out, uint8_t *d_out, uint64_t out_cap,
+                             uint64_t *out_len, sh_inflate_stats *stats);

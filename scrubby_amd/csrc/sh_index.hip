@@ -17,6 +17,7 @@
 // timed hot path); sketching and the table are hand-written.
 #include "sh_common.h"
 #include "sh_sketch.h"
+#include "sh_codec.h"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <atomic>
@@ -421,6 +422,88 @@ __global__ __launch_bounds__(FA_TPB) void k_fa_scatter(const uint8_t *raw, const
     }
 }
 
+// SCRUBBY_HIP_GUNZIP_DEVICE=1 and a .gz whose members are all BGZF: the headers are hopped on the host (the BC subfield gives each member's
+// size, its trailer the ISIZE), d_raw is allocated to the sum of ISIZE, and the compressed bytes go up window by window and are inflated
+// straight into d_raw (sh_inflate.hip) - the text never exists on the host.  *taken = false: some member is not one the scan takes (not
+// BGZF, ISIZE above 65 536, cut short) or there is no inflater; the whole file then goes through zlib, which also words the errors.
+static sh_status fasta_bgzf_to_device(const char *path, int32_t device, DevBuf &d_raw, uint64_t &n, bool *taken)
+{
+    *taken = false;
+    const int fd = open(path, O_RDONLY);
+    SH_CHECK(fd >= 0, SH_ERR_IO, "cannot open %s", path);
+    struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SH_OK;
+    const uint64_t size = (uint64_t)sb.st_size;
+    uint64_t total = 0, n_members = 0;
+    std::vector<uint8_t> hdr(12 + 65535);
+    for (uint64_t off = 0; off < size;) {      // header to header: two or three short reads a member, none of the data
+        const ssize_t got = pread(fd, hdr.data(), 64, (off_t)off);
+        const char *why = nullptr;
+        uint64_t bsize = 0;
+        if (got < 12 || hdr[0] != 0x1f || hdr[1] != 0x8b || hdr[2] != 8 || (hdr[3] & 0xe0) || !(hdr[3] & 4)) why = "a gzip member that is not BGZF";
+        else {
+            const uint64_t xlen = (uint64_t)hdr[10] | (uint64_t)hdr[11] << 8;
+            if (12 + xlen > (uint64_t)got && pread(fd, hdr.data() + 12, xlen, (off_t)(off + 12)) != (ssize_t)xlen) why = "a member that is cut short";
+            for (uint64_t q = 12; !why && !bsize && q + 4 <= 12 + xlen;) {
+                const uint64_t slen = (uint64_t)hdr[q + 2] | (uint64_t)hdr[q + 3] << 8;
+                if (q + 4 + slen > 12 + xlen) break;
+                if (hdr[q] == 66 && hdr[q + 1] == 67 && slen == 2) bsize = ((uint64_t)hdr[q + 4] | (uint64_t)hdr[q + 5] << 8) + 1;
+                q += 4 + slen;
+            }
+            uint8_t t[8];
+            if (!why && !bsize) why = "a gzip member that is not BGZF";
+            else if (!why && (bsize < 12 + xlen + 8 || off + bsize > size || pread(fd, t, 8, (off_t)(off + bsize - 8)) != 8)) why = "a member that is cut short";
+            else if (!why) {
+                const uint32_t isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+                if (isize > SHIN_MAX_ISIZE) why = "a member with ISIZE above 65536";
+                total += isize;
+            }
+        }
+        if (why) { if (n_members) shc::gunzip_note_zlib(path, off, why); return SH_OK; }
+        off += bsize; ++n_members;
+    }
+    if (total == 0) return SH_OK;
+    sh_inflater *inf = shc::gunzip_pool_acquire(device);
+    if (!inf) { shc::gunzip_note_zlib(path, 0, "no device inflater"); return SH_OK; }
+    struct Releaser { sh_inflater *inf; ~Releaser() { shc::gunzip_pool_release(inf); } } releaser{inf};
+    SH_CHECK(d_raw.alloc(total + 64) == hipSuccess, SH_ERR_OOM, "out of device memory for %s", path);
+    std::vector<uint8_t> win(shc::GUNZIP_WINDOW_BYTES);
+    std::vector<sh_gz_member> members(shc::GUNZIP_MAX_MEMBERS);
+    uint64_t foff = 0, have = 0, out_off = 0;
+    while (foff < size) {
+        while (have < win.size() && foff + have < size) {
+            const ssize_t r = pread(fd, win.data() + have, std::min<uint64_t>(win.size() - have, size - foff - have), (off_t)(foff + have));
+            SH_CHECK(r > 0, SH_ERR_IO, "error while reading %s", path);
+            have += (uint64_t)r;
+        }
+        uint64_t n_win = 0, consumed = 0;
+        shin_bgzf_scan(win.data(), have, (ShinMember *)members.data(), members.size(), &n_win, &consumed);
+        uint64_t bytes = 0;
+        for (uint64_t i = 0; i < n_win; ++i) { members[i].file_off += foff; bytes += members[i].out_len; }
+        // the scan reads more of a header than the hop did (FNAME, FCOMMENT, FHCRC): a member it does not take, or sizes that no longer
+        // add up, send the whole file through zlib like any other member the device does not take
+        if (n_win == 0 || out_off + bytes > total) {
+            hipFree(d_raw.p); d_raw.p = nullptr;
+            shc::gunzip_note_zlib(path, foff + consumed, "a gzip member that is not BGZF");
+            return SH_OK;
+        }
+        const sh_status rc = shc::gunzip_window(inf, win.data(), members.data(), n_win, nullptr, d_raw.as<uint8_t>() + out_off);
+        if (rc != SH_OK) { sh_set_error("%s: %s", path, std::string(sh_last_error()).c_str()); return rc; }
+        out_off += bytes;
+        memmove(win.data(), win.data() + consumed, have - consumed);
+        have -= consumed; foff += consumed;
+    }
+    if (out_off != total) {
+        hipFree(d_raw.p); d_raw.p = nullptr;
+        shc::gunzip_note_zlib(path, foff, "a gzip member that is not BGZF");
+        return SH_OK;
+    }
+    n = total;
+    *taken = true;
+    return SH_OK;
+}
+
 // Reads `path` (plain: parallel preads; gzip: one inflating reader) into HBM and strips it there.  *handled = false: not a
 // FASTA this reader takes (the caller falls back to the line reader).
 static sh_status fasta_to_device(const char *path, int32_t device, DevBuf &d_bases, std::vector<uint64_t> &contig_starts, bool *handled)
@@ -439,6 +522,11 @@ static sh_status fasta_to_device(const char *path, int32_t device, DevBuf &d_bas
     SH_HIP(hipSetDevice(device));
     DevBuf d_raw;
     uint64_t n = 0;
+    bool inflated_on_device = false;
+    if (gz && shc::gunzip_device_wanted()) {
+        const sh_status st = fasta_bgzf_to_device(path, device, d_raw, n, &inflated_on_device);
+        if (st != SH_OK) return st;
+    }
     if (!gz) {
         const int fd = open(path, O_RDONLY);
         SH_CHECK(fd >= 0, SH_ERR_IO, "cannot open %s", path);
@@ -475,6 +563,13 @@ static sh_status fasta_to_device(const char *path, int32_t device, DevBuf &d_bas
         for (auto &t : thr) t.join();
         close(fd);
         SH_CHECK(!bad.load(), SH_ERR_IO, "error while reading %s into device memory", path);
+    } else if (inflated_on_device) {
+        char first[256];
+        const size_t fl = (size_t)std::min<uint64_t>(n, sizeof first);
+        SH_HIP(hipMemcpy(first, d_raw.p, fl, hipMemcpyDeviceToHost));
+        size_t q = 0;
+        while (q < fl && (first[q] == '\n' || first[q] == '\r')) ++q;
+        if (q >= fl || first[q] != '>') return SH_OK;
     } else {
         gzFile g = gzopen(path, "rb");
         SH_CHECK(g, SH_ERR_IO, "cannot open %s", path);
@@ -633,6 +728,7 @@ extern "C" sh_status sh_index_build_fasta(const char *path, const sh_opts *opts,
         }
     }
     if (const char *e = getenv("SCRUBBY_HIP_FASTA_HOST")) if (*e == '1') return shi_index_build_fasta_host(path, opts, device, out);
+    shc::GunzipRun gunzip_run(device);
     DevBuf d_bases;
     std::vector<uint64_t> cs;
     bool handled = false;

@@ -1278,6 +1278,7 @@ extern "C" sh_status sh_reads_run(const sh_reads_config *c, sh_reads_result *res
     SH_CHECK(c->n_files >= 1 && c->n_files <= 2, SH_ERR_BAD_ARG, "one or two input files are supported (got %u)", c->n_files);
     for (uint32_t i = 0; i < c->n_files; ++i) SH_CHECK(c->input[i] && c->output[i], SH_ERR_BAD_ARG, "input/output %u missing", i);
     SH_CHECK(c->index, SH_ERR_BAD_ARG, "MissingAlignmentIndex");
+    shc::GunzipRun gunzip_run(c->device);      // SCRUBBY_HIP_GUNZIP_DEVICE=1: the device of the run's inflaters, the run's counts
     if (const char *e = getenv("SCRUBBY_HIP_LEGACY_HOST")) if (*e == '1') return shi_reads_run_legacy(c, res);     // A/B switch for bench.py
     for (uint32_t i = 0; i < c->n_files; ++i) {
         bool exists;
@@ -1448,6 +1449,7 @@ extern "C" sh_status sh_kraken_run(const sh_kraken_config *c, sh_reads_result *r
     for (uint32_t i = 0; i < c->n_files; ++i) SH_CHECK(c->input[i] && c->output[i], SH_ERR_BAD_ARG, "input/output %u missing", i);
     SH_CHECK(c->db, SH_ERR_BAD_ARG, "MissingClassifierIndex");
     SH_CHECK(c->n_taxa + c->n_taxa_direct > 0, SH_ERR_BAD_ARG, "MissingTaxa: --taxa or --taxa-direct is required");
+    shc::GunzipRun gunzip_run(c->device);
     if (const char *e = getenv("SCRUBBY_HIP_LEGACY_HOST")) if (*e == '1') return shi_kraken_run_legacy(c, res);
     for (uint32_t i = 0; i < c->n_files; ++i) {
         bool exists;

@@ -133,6 +133,24 @@ class DeflateStats(C.Structure):
 
 SH_DEFLATE_LITERALS_ONLY = 1
 
+
+class GzMember(C.Structure):
+    _fields_ = [("file_off", C.c_uint64), ("in_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32),
+                ("crc32", C.c_uint32), ("status", C.c_uint32)]
+
+
+class InflateStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("n_stored_blocks", C.c_uint64), ("n_fixed_blocks", C.c_uint64), ("n_dynamic_blocks", C.c_uint64),
+                ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# a member's status (sh_gz_member.status)
+INFLATE_STATUS = ("ok", "bad block type", "bad code lengths", "invalid symbol", "distance too far back", "input overrun", "output overrun",
+                  "output short of ISIZE", "stored LEN/NLEN mismatch", "CRC mismatch")
+
 EXPORTS = [
     "sh_version", "sh_device_count", "sh_last_error", "sh_preset",
     "sh_index_build", "sh_index_build_device", "sh_index_build_fasta", "sh_index_save", "sh_index_load",
@@ -159,6 +177,7 @@ EXPORTS = [
     "sh_k2_distrib_count", "sh_k2_distrib_copy", "sh_k2_distrib_write", "sh_k2_distrib_read", "sh_k2_bracken_estimate", "sh_k2_bracken_write",
     "sh_k2_distrib_run", "sh_k2_bracken_run",
     "sh_deflate_bound", "sh_deflater_create", "sh_deflate_device", "sh_gzip_member", "sh_deflater_free",
+    "sh_bgzf_scan", "sh_inflater_create", "sh_inflate_members_device", "sh_gunzip_bgzf", "sh_inflater_free",
 ]
 
 _LIB = None
@@ -222,6 +241,11 @@ def load():
     L.sh_deflate_device.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), vp, C.POINTER(DeflateStats)]
     L.sh_gzip_member.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(DeflateStats)]
     L.sh_deflater_free.argtypes = [vp]
+    L.sh_bgzf_scan.argtypes = [vp, u64, C.POINTER(GzMember), u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
+    L.sh_inflater_create.argtypes = [i32, u64, u64, u64, C.POINTER(vp)]
+    L.sh_inflate_members_device.argtypes = [vp, vp, C.POINTER(GzMember), u64, vp, u64, vp, C.POINTER(InflateStats)]
+    L.sh_gunzip_bgzf.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateStats)]
+    L.sh_inflater_free.argtypes = [vp]
     for name in EXPORTS:
         if name not in ("sh_version", "sh_device_count", "sh_last_error", "sh_index_set_size", "sh_deflate_bound"):
             getattr(L, name).restype = i32
@@ -649,6 +673,60 @@ class Deflater:
     def close(self):
         if self.h:
             load().sh_deflater_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bgzf_scan(buf, cap=None):
+    """The BGZF members of `buf` (bytes, a window of a file) -> (list of GzMember, consumed, stopped); host only (sh_bgzf_scan).
+    stopped: 0 end of buffer, 1 incomplete member, 2 not BGZF."""
+    n = len(buf)
+    cap = n // 28 + 1 if cap is None else cap
+    arr = (GzMember * max(cap, 1))()
+    src = np.frombuffer(buf, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+    n_members, consumed, stopped = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+    check(load().sh_bgzf_scan(src.ctypes.data, n, arr, cap, C.byref(n_members), C.byref(consumed), C.byref(stopped)))
+    return [arr[i] for i in range(n_members.value)], consumed.value, stopped.value
+
+
+class Inflater:
+    """Owns an sh_inflater: BGZF members inflated on the device, calls of up to max_in_bytes / max_out_bytes / max_members."""
+
+    def __init__(self, max_in_bytes, max_out_bytes, max_members, device=0):
+        L = require_gpu()
+        self.h = C.c_void_p()
+        check(L.sh_inflater_create(device, max_in_bytes, max_out_bytes, max_members, C.byref(self.h)))
+
+    def inflate_members_device(self, d_in, members, d_out, out_cap=None):
+        """d_in / d_out: torch uint8 CUDA tensors; members: list of GzMember (their status is filled, also when the call raises) -> stats."""
+        arr = (GzMember * max(len(members), 1))(*members)
+        st = InflateStats()
+        cap = d_out.numel() if out_cap is None else out_cap
+        rc = load().sh_inflate_members_device(self.h, C.c_void_p(d_in.data_ptr()), arr, len(members), C.c_void_p(d_out.data_ptr()), cap, _stream_ptr(), C.byref(st))
+        for i, m in enumerate(members):
+            m.status = arr[i].status
+        check(rc)
+        return st.as_dict()
+
+    def gunzip(self, data, out_cap=None):
+        """BGZF bytes (whole members) in, (inflated bytes, stats) out (sh_gunzip_bgzf: host memory both ways)."""
+        n = len(data)
+        if out_cap is None:
+            out_cap = sum(m.out_len for m in bgzf_scan(data)[0])
+        src = np.frombuffer(data, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+        st, out_len = InflateStats(), C.c_uint64(0)
+        check(load().sh_gunzip_bgzf(self.h, src.ctypes.data, n, out.ctypes.data, out_cap, C.byref(out_len), C.byref(st)))
+        return out[:out_len.value].tobytes(), st.as_dict()
+
+    def close(self):
+        if self.h:
+            load().sh_inflater_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
