@@ -97,18 +97,21 @@ struct BatchScratch {
     std::string env;          // the environment switches a context captures when it is created
     uint64_t ctx_reads = 0, ctx_bases = 0;
     uint32_t ctx_len = 0;
-    uint8_t *d_bases = nullptr, *d_flags = nullptr;
-    uint64_t *d_off = nullptr;
-    sh_trace *d_tr = nullptr;
-    size_t cap_bases = 0, cap_reads = 0, cap_tr = 0;
+    DevBuf d_bases, d_flags, d_off, d_tr;      // device copies of the batch: freed with the set
+    size_t cap_bases = 0, cap_off = 0, cap_flags = 0, cap_tr = 0;      // elements each holds
     hipStream_t s = nullptr, us = nullptr;
-    void release()
+    // room for `need` elements of `elem` bytes: what the buffer holds is not kept
+    static hipError_t grow(DevBuf &b, size_t &cap, size_t need, size_t elem = 1)
+    {
+        if (need <= cap) return hipSuccess;
+        b.reset(); cap = 0;
+        const hipError_t e = b.alloc(need * elem);
+        if (e == hipSuccess) cap = need;
+        return e;
+    }
+    ~BatchScratch()      // the buffers go after this, by their own destructors (hipFree waits for the device)
     {
         if (ctx) sh_ctx_destroy(ctx);
-        if (d_bases) hipFree(d_bases);
-        if (d_flags) hipFree(d_flags);
-        if (d_off) hipFree(d_off);
-        if (d_tr) hipFree(d_tr);
         if (s) hipStreamDestroy(s);
         if (us) hipStreamDestroy(us);
     }
@@ -117,7 +120,7 @@ struct BatchScratch {
 void shi_batch_pool_release(sh_index *idx)
 {
     std::lock_guard<std::mutex> lk(idx->pool_mu);
-    for (void *p : idx->pool) { ((BatchScratch *)p)->release(); delete (BatchScratch *)p; }
+    for (void *p : idx->pool) delete (BatchScratch *)p;
     idx->pool.clear();
 }
 
@@ -149,7 +152,7 @@ extern "C" sh_status sh_classify_batch(const sh_index *idx, const sh_opts *opts,
     if (!B) { B = new BatchScratch; B->opts = *opts; B->env = env_sig; }
     auto give_back = [&](bool keep) {
         if (keep && !no_pool) { std::lock_guard<std::mutex> lk(idx->pool_mu); idx->pool.push_back(B); }
-        else { B->release(); delete B; }
+        else delete B;
     };
 #define CB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { sh_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); give_back(false); return e_ == hipErrorOutOfMemory ? SH_ERR_OOM : SH_ERR_HIP; } } while (0)
     sh_status st = SH_OK;
@@ -163,17 +166,12 @@ extern "C" sh_status sh_classify_batch(const sh_index *idx, const sh_opts *opts,
     }
     if (!B->s) CB_HIP(hipStreamCreate(&B->s));
     if (!B->us) CB_HIP(hipStreamCreateWithFlags(&B->us, hipStreamNonBlocking));
-    if (n_bases + 32 > B->cap_bases) { if (B->d_bases) hipFree(B->d_bases); B->d_bases = nullptr; B->cap_bases = n_bases + 32; CB_HIP(hipMalloc(&B->d_bases, B->cap_bases)); }
-    if (n_reads + 1 > B->cap_reads) {
-        if (B->d_off) hipFree(B->d_off);
-        if (B->d_flags) hipFree(B->d_flags);
-        B->d_off = nullptr; B->d_flags = nullptr; B->cap_reads = n_reads + 1;
-        CB_HIP(hipMalloc(&B->d_off, B->cap_reads * 8));
-        CB_HIP(hipMalloc(&B->d_flags, B->cap_reads));
-    }
-    if (out_trace && n_reads > B->cap_tr) { if (B->d_tr) hipFree(B->d_tr); B->d_tr = nullptr; B->cap_tr = n_reads; CB_HIP(hipMalloc(&B->d_tr, B->cap_tr * sizeof(sh_trace))); }
+    CB_HIP(BatchScratch::grow(B->d_bases, B->cap_bases, n_bases + 32));
+    CB_HIP(BatchScratch::grow(B->d_off, B->cap_off, n_reads + 1, 8));
+    CB_HIP(BatchScratch::grow(B->d_flags, B->cap_flags, n_reads + 1));
+    if (out_trace) CB_HIP(BatchScratch::grow(B->d_tr, B->cap_tr, n_reads, sizeof(sh_trace)));
     sh_ctx *ctx = B->ctx;
-    uint8_t *d_bases = B->d_bases, *d_flags = B->d_flags; uint64_t *d_off = B->d_off; sh_trace *d_tr = out_trace ? B->d_tr : nullptr;
+    uint8_t *d_bases = B->d_bases.as<uint8_t>(), *d_flags = B->d_flags.as<uint8_t>(); uint64_t *d_off = B->d_off.as<uint64_t>(); sh_trace *d_tr = out_trace ? B->d_tr.as<sh_trace>() : nullptr;
     hipStream_t s = B->s, us = B->us;
     // offsets are rebased so that d_bases[0] is the first base of the batch
     std::vector<uint64_t> off0;
@@ -405,14 +403,13 @@ __global__ void k_checksum(const uint64_t *w, uint64_t n, unsigned long long *ou
 
 static sh_status device_checksum(const void *d, uint64_t n_words, uint64_t *out)
 {
-    unsigned long long *d_acc = nullptr;
     *out = 0;
     if (n_words == 0) return SH_OK;
-    SH_HIP(hipMalloc(&d_acc, 8));
-    hipError_t e = hipMemset(d_acc, 0, 8);
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, 0, (const uint64_t *)d, n_words, d_acc); e = hipMemcpy(out, d_acc, 8, hipMemcpyDeviceToHost); }
-    hipFree(d_acc);
-    SH_HIP(e);
+    DevBuf acc;
+    SH_HIP(acc.alloc(8));
+    SH_HIP(hipMemset(acc.p, 0, 8));
+    hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, 0, (const uint64_t *)d, n_words, acc.as<unsigned long long>());
+    SH_HIP(hipMemcpy(out, acc.p, 8, hipMemcpyDeviceToHost));
     return SH_OK;
 }
 
@@ -702,10 +699,12 @@ extern "C" sh_status sh_bench_gather(const sh_index *idx, uint64_t n_probes, int
 {
     SH_CHECK(idx && out_gbs_useful && out_ms && iters > 0, SH_ERR_BAD_ARG, "sh_bench_gather: bad argument");
     SH_HIP(hipSetDevice(idx->device));
-    unsigned long long *sink = nullptr;
-    SH_HIP(hipMalloc(&sink, 8));
-    hipEvent_t e0, e1;
-    SH_HIP(hipEventCreate(&e0)); SH_HIP(hipEventCreate(&e1));
+    DevBuf b_sink;
+    SH_HIP(b_sink.alloc(8));
+    unsigned long long *const sink = b_sink.as<unsigned long long>();
+    DevEvent ev0, ev1;
+    SH_HIP(ev0.create()); SH_HIP(ev1.create());
+    const hipEvent_t e0 = ev0.e, e1 = ev1.e;
     hipLaunchKernelGGL(k_gather, dim3(256 * 16), dim3(256), 0, nullptr, (const uint4 *)idx->d_slots, idx->lg_slots, n_probes, 1ull, sink);
     SH_HIP(hipEventRecord(e0, nullptr));
     for (int it = 0; it < iters; ++it)
@@ -716,7 +715,6 @@ extern "C" sh_status sh_bench_gather(const sh_index *idx, uint64_t n_probes, int
     SH_HIP(hipEventElapsedTime(&ms, e0, e1));
     *out_ms = ms / iters;
     *out_gbs_useful = 16.0 * (double)n_probes / (*out_ms * 1e-3) / 1e9;
-    hipEventDestroy(e0); hipEventDestroy(e1); hipFree(sink);
     return SH_OK;
 }
 
@@ -819,16 +817,16 @@ extern "C" sh_status sh_dbg_rmq_trace(int32_t device, uint64_t seed, int32_t n_o
 {
     SH_CHECK(out && n_out && n_ops > 0 && key_range > 0 && cache >= 0, SH_ERR_BAD_ARG, "sh_dbg_rmq_trace: bad argument");
     SH_HIP(hipSetDevice(device));
-    RqNode *pool = nullptr; int32_t *ly = nullptr, *li = nullptr; long long *d_out = nullptr, *d_n = nullptr;
-    SH_HIP(hipMalloc(&pool, sizeof(RqNode) * ((size_t)n_ops + 4))); SH_HIP(hipMalloc(&ly, 4 * ((size_t)n_ops + 1))); SH_HIP(hipMalloc(&li, 4 * ((size_t)n_ops + 1)));
-    SH_HIP(hipMalloc(&d_out, 8 * (size_t)n_ops)); SH_HIP(hipMalloc(&d_n, 8));
-    hipLaunchKernelGGL(k_dbg_rmq_trace, dim3(1), dim3(64), 0, 0, seed, n_ops, key_range, fifo, cache, pool, ly, li, d_out, d_n);
+    DevBuf pool, ly, li, d_out, d_n;
+    SH_HIP(pool.alloc(sizeof(RqNode) * ((size_t)n_ops + 4))); SH_HIP(ly.alloc(4 * ((size_t)n_ops + 1))); SH_HIP(li.alloc(4 * ((size_t)n_ops + 1)));
+    SH_HIP(d_out.alloc(8 * (size_t)n_ops)); SH_HIP(d_n.alloc(8));
+    SH_HIP(hipMemset(d_out.p, 0, 8 * (size_t)n_ops));      // all n_ops words are copied back, the sequence may write fewer
+    hipLaunchKernelGGL(k_dbg_rmq_trace, dim3(1), dim3(64), 0, 0, seed, n_ops, key_range, fifo, cache, pool.as<RqNode>(), ly.as<int32_t>(), li.as<int32_t>(), d_out.as<long long>(), d_n.as<long long>());
     SH_HIP(hipDeviceSynchronize());
     long long n = 0;
-    SH_HIP(hipMemcpy(&n, d_n, 8, hipMemcpyDeviceToHost));
-    if (n > 0) SH_HIP(hipMemcpy(out, d_out, 8 * (size_t)n_ops, hipMemcpyDeviceToHost));
+    SH_HIP(hipMemcpy(&n, d_n.p, 8, hipMemcpyDeviceToHost));
+    if (n > 0) SH_HIP(hipMemcpy(out, d_out.p, 8 * (size_t)n_ops, hipMemcpyDeviceToHost));
     *n_out = n;
-    hipFree(pool); hipFree(ly); hipFree(li); hipFree(d_out); hipFree(d_n);
     return SH_OK;
 }
 
@@ -855,12 +853,11 @@ extern "C" sh_status sh_dbg_wave_ops(int32_t device, const int32_t *in32, const 
 {
     SH_CHECK(in32 && in64 && out32 && out64 && bcast_lane >= 0 && bcast_lane < 64, SH_ERR_BAD_ARG, "sh_dbg_wave_ops: bad argument");
     SH_HIP(hipSetDevice(device));
-    int32_t *d_i = nullptr, *d_o = nullptr; unsigned long long *d_i64 = nullptr, *d_o64 = nullptr;
-    SH_HIP(hipMalloc(&d_i, 256)); SH_HIP(hipMalloc(&d_i64, 512)); SH_HIP(hipMalloc(&d_o, 12 * 256)); SH_HIP(hipMalloc(&d_o64, 9 * 512));
-    SH_HIP(hipMemcpy(d_i, in32, 256, hipMemcpyHostToDevice)); SH_HIP(hipMemcpy(d_i64, in64, 512, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dbg_wave_ops, dim3(1), dim3(64), 0, 0, d_i, d_i64, bcast_lane, d_o, d_o64);
+    DevBuf d_i, d_i64, d_o, d_o64;
+    SH_HIP(d_i.alloc(256)); SH_HIP(d_i64.alloc(512)); SH_HIP(d_o.alloc(12 * 256)); SH_HIP(d_o64.alloc(9 * 512));
+    SH_HIP(hipMemcpy(d_i.p, in32, 256, hipMemcpyHostToDevice)); SH_HIP(hipMemcpy(d_i64.p, in64, 512, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_dbg_wave_ops, dim3(1), dim3(64), 0, 0, d_i.as<int32_t>(), d_i64.as<unsigned long long>(), bcast_lane, d_o.as<int32_t>(), d_o64.as<unsigned long long>());
     SH_HIP(hipDeviceSynchronize());
-    SH_HIP(hipMemcpy(out32, d_o, 12 * 256, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(out64, d_o64, 9 * 512, hipMemcpyDeviceToHost));
-    hipFree(d_i); hipFree(d_i64); hipFree(d_o); hipFree(d_o64);
+    SH_HIP(hipMemcpy(out32, d_o.p, 12 * 256, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(out64, d_o64.p, 9 * 512, hipMemcpyDeviceToHost));
     return SH_OK;
 }

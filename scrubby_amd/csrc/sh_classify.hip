@@ -46,8 +46,10 @@
 #include "sh_sketch.h"
 #include "sh_chain.h"
 #include "sh_long.h"
+#include "sh_ctx_layout.h"
 #include <algorithm>
 #include <chrono>
+#include <memory>
 
 #define SH_SPLIT ((sh_status)-2)      // internal: classify_chunk asks for smaller chunks
 #define K1_LIST_CAP 8           // ring of queued minimizers per lane (power of two; 4 KiB of LDS per wave); 4 are drained per W-step block
@@ -3360,7 +3362,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // ------------------------------------------------------------------------------------------------
 // host side: context
 // ------------------------------------------------------------------------------------------------
+static_assert(CL_SORT_CLS == N_SORT_CLS && CL_SINK_SHARDS == SINK_SHARDS && CL_LSEG == LSEG && CL_GT == GT, "sh_ctx_layout.h repeats these constants");
+static_assert(sizeof(ChainRec) == 40 && sizeof(SortItem) == 24 && sizeof(BigMeta) == 16 && sizeof(BigTables) == 96, "tests/ctx_layout_host.cpp stands in for these types");
+
+// Everything a context allocates - device and pinned memory, events, streams - is made through its owner and released by it: the members
+// of sh_ctx below are views.  What a call makes later (d_coop, d_lkind, the side streams) goes the same way.
+struct CtxOwner {
+    enum Kind : uint8_t { DEVICE, PINNED, EVENT, STREAM };
+    std::vector<std::pair<void *, Kind>> held;
+    CtxOwner() = default;
+    CtxOwner(const CtxOwner &) = delete;
+    CtxOwner &operator=(const CtxOwner &) = delete;
+    ~CtxOwner() { for (auto [p, kind] : held) release(p, kind); }
+    template <class T> hipError_t keep(hipError_t e, T *&p, Kind kind) { if (e == hipSuccess) held.push_back({(void *)p, kind}); else p = nullptr; return e; }
+    template <class T> hipError_t device(T *&p, size_t bytes) { return keep(hipMalloc((void **)&p, bytes), p, DEVICE); }
+    template <class T> hipError_t pinned(T *&p, size_t bytes) { return keep(hipHostMalloc((void **)&p, bytes), p, PINNED); }
+    hipError_t event(hipEvent_t &ev, unsigned flags = hipEventDefault) { return keep(hipEventCreateWithFlags(&ev, flags), ev, EVENT); }
+    hipError_t stream(hipStream_t &st, unsigned flags) { return keep(hipStreamCreateWithFlags(&st, flags), st, STREAM); }
+    template <class T> void drop(T *&p)      // one of them ahead of the others (a buffer about to be regrown)
+    {
+        for (size_t i = 0; i < held.size(); ++i) if (held[i].first == (void *)p) { release(p, held[i].second); held.erase(held.begin() + (long)i); break; }
+        p = nullptr;
+    }
+    static void release(void *p, Kind kind)
+    {
+        if (kind == DEVICE) hipFree(p);
+        else if (kind == PINNED) hipHostFree(p);
+        else if (kind == EVENT) hipEventDestroy((hipEvent_t)p);
+        else hipStreamDestroy((hipStream_t)p);
+    }
+};
+
 struct sh_ctx {
+    CtxOwner own;
     const sh_index *idx = nullptr;
     int idx_device = 0;
     sh_opts opts{};
@@ -3482,8 +3516,6 @@ static void fill_align_params(const sh_opts &o, AlignParams &A)
     A.lemma = 0; A.unc_max = 0;
 }
 
-static bool w_supported(int w) { return w == 5 || w == 10 || w == 11 || w == 19; }
-
 // A context built for one index serves another of the same shape (same device, k, w, occurrence thresholds resolved the same way):
 // only the index pointer and the occurrence cut-off taken from it change.  The streaming host path keeps its context between runs
 // this way (sh_stream.cpp): the reference rebuilds the index on every run, but re-creating ~35 GB of scratch each time means waiting
@@ -3517,7 +3549,8 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
              SH_ERR_BAD_ARG, "sh_ctx_create: the index derived mid_occ with other occurrence parameters (min %d, max %d, frac %g) than this preset's (min %d, max %d, frac %g): rebuild it for this preset",
              idx->o_min_mid_occ, idx->o_max_mid_occ, (double)idx->o_mid_occ_frac, opts->min_mid_occ, opts->max_mid_occ, (double)opts->mid_occ_frac);
     SH_HIP(hipSetDevice(idx->device));
-    sh_ctx *c = new sh_ctx();
+    std::unique_ptr<sh_ctx> guard(new sh_ctx());      // every way out but the last frees the context and what it owns by then
+    sh_ctx *c = guard.get();
     c->idx = idx; c->idx_device = idx->device; c->opts = *opts; c->max_reads = max_reads; c->max_bases = max_bases; c->max_read_len = max_read_len;
     const CtxSwitches &sw = c->sw = shi_ctx_switches();
     c->cs = shi_call_switches();      // for the [dbg] lines below: every call reads it afresh
@@ -3526,136 +3559,67 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
     fill_align_params(*opts, c->AP);
     c->AP.lemma = c->P.ext_lemma; c->AP.unc_max = c->P.ext_unc_max;
     fill_long_params(*opts, sw, mid_occ, c->LP);
-    c->ext = (opts->flags & SH_F_CIGAR) != 0;
-    c->ext_long = c->ext && !opts->is_sr;
+    // every capacity and the layout of every carved allocation: sh_ctx_layout.h
+    const CtxElem elem = {sizeof(ChainRec), sizeof(SortItem), sizeof(BigMeta), sizeof(BigTables)};
+    const CtxCaps K = ctx_caps(max_reads, max_bases, max_read_len, opts->k, opts->w, (opts->flags & SH_F_CIGAR) != 0, opts->is_sr != 0, sw.arena_bytes, sw.ext_bytes, elem);
+    c->ext = K.ext; c->ext_long = K.ext_long; c->use_k1 = K.use_k1; c->use_long = K.use_long;
+    c->arena_bytes = K.arena_bytes; c->legacy_bytes = K.legacy_bytes; c->max_segs = K.max_segs; c->mz_cap = K.mz_cap; c->larena_bytes = K.larena_bytes;
     if (c->ext) {
         SH_CHECK(idx->d_ref && idx->d_cstart, SH_ERR_INDEX, "sh_ctx_create: this index holds no reference bases, which the extension stage (SH_F_CIGAR) aligns against: rebuild it from FASTA");
         SH_CHECK(opts->a > 0 && opts->e > 0 && opts->q + opts->e < 100 && opts->q2 + opts->e2 < 100, SH_ERR_BAD_ARG, "sh_ctx_create: alignment scores out of the int8 range of ksw2");
     }
-    // K1 stages a tile of 64 reads in LDS; it needs k <= 23 (hash and position share 64 bits),
-    // read positions < 2^17 and a supported compile-time window
-    c->use_k1 = opts->k <= 23 && max_read_len <= 1024 && w_supported(opts->w);
     uint64_t tile_bytes = (uint64_t)64 * max_read_len + 32;
     c->lds_words = (uint32_t)((tile_bytes + 15) / 16);
-    const uint64_t n_tiles = (max_reads + 63) / 64;
     auto fail = [&](hipError_t e, const char *what) {
         size_t mf = 0, mt = 0;
         (void)hipMemGetInfo(&mf, &mt);
         sh_set_error("sh_ctx_create: %s: %s (device memory: %.1f of %.1f GB free)", what, hipGetErrorString(e), mf / 1e9, mt / 1e9);
-        sh_ctx_destroy(c);
         return e == hipErrorOutOfMemory ? SH_ERR_OOM : SH_ERR_HIP;
     };
+    CtxOwner &own = c->own;
     hipError_t e;
-    if ((e = hipMalloc(&c->d_records, (n_tiles * 64) * c->seed_cap * sizeof(uint4))) != hipSuccess) return fail(e, "records");
-    if ((e = hipMalloc(&c->d_k1info, max_reads * 4)) != hipSuccess) return fail(e, "k1info");
-    if ((e = hipMalloc(&c->d_work_small, max_reads * 4)) != hipSuccess) return fail(e, "work_small");
-    if ((e = hipMalloc(&c->d_work_small2, max_reads * 4)) != hipSuccess) return fail(e, "work_small2");
-    if ((e = hipMalloc(&c->d_work_resketch, max_reads * 4)) != hipSuccess) return fail(e, "work_resketch");
-    if ((e = hipMalloc(&c->d_work_defer, max_reads * 4)) != hipSuccess) return fail(e, "work_defer");
-    if ((e = hipMalloc(&c->d_work_defer2, max_reads * 4)) != hipSuccess) return fail(e, "work_defer2");
+    // (the order of the allocations is part of the sizes: two of them below ask what the device has left)
+    if ((e = own.device(c->d_records, (K.n_tiles * 64) * c->seed_cap * sizeof(uint4))) != hipSuccess) return fail(e, "records");
+    if ((e = own.device(c->d_k1info, max_reads * 4)) != hipSuccess) return fail(e, "k1info");
+    if ((e = own.device(c->d_work_small, max_reads * 4)) != hipSuccess) return fail(e, "work_small");
+    if ((e = own.device(c->d_work_small2, max_reads * 4)) != hipSuccess) return fail(e, "work_small2");
+    if ((e = own.device(c->d_work_resketch, max_reads * 4)) != hipSuccess) return fail(e, "work_resketch");
+    if ((e = own.device(c->d_work_defer, max_reads * 4)) != hipSuccess) return fail(e, "work_defer");
+    if ((e = own.device(c->d_work_defer2, max_reads * 4)) != hipSuccess) return fail(e, "work_defer2");
     for (int p = 0; p < 2; ++p) for (int q = 0; q < 2; ++q)
-        if ((e = hipMalloc(&c->d_big[p][q], max_reads * 4)) != hipSuccess) return fail(e, "big lists");
-    if ((e = hipMalloc(&c->d_ctr, sizeof(Counters))) != hipSuccess) return fail(e, "counters");
-    if ((e = hipHostMalloc(&c->h_ctr, sizeof(Counters))) != hipSuccess) return fail(e, "pinned counters");
-    // arena: anchors (+ sort buffer) and DP state of reads with > 64 anchors (36 B per anchor slot) + a slice for
-    // the legacy re-sketch path.  Default 4 KiB per read of the batch (~110 anchor slots per read; the CHM13-sized
-    // workload averages 72), at least 4 GiB; reads that find no room are deferred and re-run.
-    c->arena_bytes = std::max<uint64_t>(4ull << 30, max_reads * 4096ull);      // floor: a small batch still meets reads with 10^5 anchors (4 MB each); a starved arena means deferral rounds of ~1.5 ms
-    // without K1 every read takes the legacy path, whose sketch buffers and anchors live in the arena: ~48 B per base
-    if (!c->use_k1) c->arena_bytes = std::max<uint64_t>(c->arena_bytes, std::min<uint64_t>(max_reads * (uint64_t)max_read_len * 48ull, (c->ext_long ? 32ull : 64ull) << 30));      // long-read presets with the extension filter: the raw anchors have their own buffer (d_stage_*)
-    if (sw.arena_bytes != SW_UNSET) c->arena_bytes = (uint64_t)sw.arena_bytes;
-    if ((e = hipMalloc(&c->d_arena, c->arena_bytes)) != hipSuccess) return fail(e, "arena");
+        if ((e = own.device(c->d_big[p][q], max_reads * 4)) != hipSuccess) return fail(e, "big lists");
+    if ((e = own.device(c->d_ctr, sizeof(Counters))) != hipSuccess) return fail(e, "counters");
+    if ((e = own.pinned(c->h_ctr, sizeof(Counters))) != hipSuccess) return fail(e, "pinned counters");
+    if ((e = own.device(c->d_arena, c->arena_bytes)) != hipSuccess) return fail(e, "arena");
     {
-        const uint64_t big_min = (64ull << 20) + max_reads * 160;
-        const bool long_fe = !c->use_k1 && w_supported(opts->w);      // the long-read front end feeds the repeat path
-        c->legacy_bytes = (c->use_k1 || long_fe) ? std::min<uint64_t>(c->arena_bytes / 8, 1ull << 30)
-                                                 : (c->arena_bytes > 2 * big_min ? c->arena_bytes - big_min : c->arena_bytes / 2);
-        uint8_t *p = c->d_arena + c->legacy_bytes;
-        uint64_t left = c->arena_bytes - c->legacy_bytes;
-        // k_expand's waves reserve sort-list entries in chunks (<= 32): up to one abandoned chunk per wave and class
-        const uint64_t waves = 3 * std::min<uint64_t>(std::max<uint64_t>(n_tiles, 1), 256 * 8);      // k_expand's grid (big_pass)
-        const uint64_t sort_cap[N_SORT_CLS] = {max_reads + 32 * waves, max_reads + 32 * waves, max_reads + 8 * waves, max_reads + 8 * waves, max_reads + waves, max_reads + waves};
-        uint64_t sort_cap_sum = 0;
-        for (int i = 0; i < N_SORT_CLS; ++i) sort_cap_sum += sort_cap[i];
-        uint64_t fixed = 4 * 64 * sizeof(SortItem) + 4096 + max_reads * (sizeof(BigMeta) + 8 + 16) + sort_cap_sum * sizeof(SortItem) + sort_cap[N_SORT_CLS - 1] * 4 + 16384;
-        uint64_t per_anchor = 8 + 8 + 8 + 4 + 4 + 4 + 2 + (c->ext ? 8 + 3 : 0);   // ax bx az aq bq af (+ tile_split and cluster queue shares) (+ hz)
-        uint64_t cap = left > fixed ? (left - fixed) / per_anchor : 0;
-        cap &= ~15ull;
-        if (cap < 1024) { sh_set_error("sh_ctx_create: arena of %llu MiB is too small", (unsigned long long)(c->arena_bytes >> 20)); sh_ctx_destroy(c); return SH_ERR_OOM; }
+        SH_CHECK(K.anchor_cap >= 1024, SH_ERR_OOM, "sh_ctx_create: arena of %llu MiB is too small", (unsigned long long)(c->arena_bytes >> 20));
         BigBufs &B = c->B;
-        B.anchor_cap = cap;
-        auto take = [&](uint64_t bytes) { uint8_t *q = p; p += (bytes + 255) & ~255ull; return q; };
-        B.ax = (uint64_t *)take(cap * 8); B.bx = (uint64_t *)take(cap * 8); B.az = (uint64_t *)take(cap * 8);
-        B.aq = (uint32_t *)take(cap * 4); B.bq = (uint32_t *)take(cap * 4);
-        B.af = (int32_t *)take(cap * 4);
-        B.hz = c->ext ? (uint64_t *)take(cap * 8) : nullptr;
-        B.meta = (BigMeta *)take(max_reads * sizeof(BigMeta));
-        B.acc_nu = (int32_t *)take(max_reads * 4); B.acc_best = (int32_t *)take(max_reads * 4);
-        for (int i = 0; i < N_SORT_CLS; ++i) B.sort_items[i] = (SortItem *)take(sort_cap[i] * sizeof(SortItem));
-        B.tile_base = (uint32_t *)take((max_reads + 1) * 4);
-        B.giant_order = (uint32_t *)take(sort_cap[N_SORT_CLS - 1] * 4);
-        B.tile_split = (uint32_t *)take((cap / GT + max_reads + 2) * 12);      // three words per tile
-        {   // a cluster of class c has more than {4096, 1024, 256, 64} anchors
-            const uint64_t div[4] = {4096, 1024, 256, c->ext ? 8u : 64u};
-            for (int i = 0; i < 4; ++i) { B.cl_cap[i] = (uint32_t)std::min<uint64_t>(cap / div[i] + 64, UINT32_MAX); B.cl_items[i] = (SortItem *)take((uint64_t)B.cl_cap[i] * sizeof(SortItem)); }
-        }
-        {
-            BigTables h{};
-            for (int i = 0; i < N_SORT_CLS; ++i) h.sort_items[i] = B.sort_items[i];
-            for (int i = 0; i < 4; ++i) { h.cl_items[i] = B.cl_items[i]; h.cl_cap[i] = B.cl_cap[i]; }
-            BigTables *d_t = (BigTables *)take(sizeof(BigTables));
-            if (hipMemcpy(d_t, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) { sh_set_error("sh_ctx_create: class tables"); sh_ctx_destroy(c); return SH_ERR_HIP; }
-            B.tabs = d_t;
-        }
-        if ((uint64_t)(p - c->d_arena) > c->arena_bytes) {   // alignment slack: shrink
-            sh_set_error("sh_ctx_create: internal arena carve overflow"); sh_ctx_destroy(c); return SH_ERR_OOM;
-        }
+        Carve count, place{c->d_arena + c->legacy_bytes};
+        big_layout(count, B, K, max_reads, elem);
+        SH_CHECK(count.off <= c->arena_bytes - c->legacy_bytes, SH_ERR_OOM, "sh_ctx_create: internal arena carve overflow");
+        big_layout(place, B, K, max_reads, elem);
+        BigTables h{};
+        for (int i = 0; i < N_SORT_CLS; ++i) h.sort_items[i] = B.sort_items[i];
+        for (int i = 0; i < 4; ++i) { h.cl_items[i] = B.cl_items[i]; h.cl_cap[i] = B.cl_cap[i]; }
+        SH_CHECK(hipMemcpy((void *)B.tabs, &h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess, SH_ERR_HIP, "sh_ctx_create: class tables");
     }
-    c->use_long = !c->use_k1 && w_supported(opts->w);
     if (c->use_long) {
-        const uint64_t cb = std::min<uint64_t>(max_bases + 64, max_reads * (uint64_t)max_read_len + 64);     // bases of one chunk, at most
-        c->max_segs = cb / LSEG + max_reads + 2;
-        c->mz_cap = cb * 5 / (2 * ((uint64_t)opts->w + 1)) + 4096;   // minimizer density is ~2/(w+1), + 25 %; reads beyond the cap take the legacy path
-        auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-        c->long_bytes = al((max_reads + 1) * 4) + al(c->max_segs * 4) + al((c->max_segs + 1) * 8) + al((c->max_segs / 16384 + 2) * 8) + al(c->mz_cap * 8) + al(c->mz_cap * 4) + al(c->mz_cap * 16) + al(max_reads * 8);
-        if ((e = hipMalloc(&c->d_long, c->long_bytes)) != hipSuccess) return fail(e, "long-read buffers");
-        uint8_t *p = c->d_long;
-        auto take = [&](uint64_t b) { uint8_t *q = p; p += al(b); return q; };
-        c->d_seg_base = (uint32_t *)take((max_reads + 1) * 4); c->d_seg_cnt = (uint32_t *)take(c->max_segs * 4);
-        c->d_seg_off = (unsigned long long *)take((c->max_segs + 1) * 8); c->d_scan_tot = (unsigned long long *)take((c->max_segs / 16384 + 2) * 8); c->d_mz_hash = (uint64_t *)take(c->mz_cap * 8);
-        c->d_mz_y = (uint32_t *)take(c->mz_cap * 4); c->d_lrec = (uint4 *)take(c->mz_cap * 16); c->d_seed_off = (unsigned long long *)take(max_reads * 8);
+        Carve count, place;
+        long_layout(count, *c, K, max_reads);
+        c->long_bytes = count.off;
+        if ((e = own.device(c->d_long, c->long_bytes)) != hipSuccess) return fail(e, "long-read buffers");
+        place.base = c->d_long;
+        long_layout(place, *c, K, max_reads);
     }
     if (c->ext) {
-        // chain hand-over: 32-B records, 12 B per chain anchor, one list head per read; sized for ~2 chains and ~32 chain anchors per
-        // read of the chunk (a chunk that needs more is cut in two and re-run: classify_chunk returns SH_SPLIT)
-        uint64_t cap_recs = std::max<uint64_t>(1ull << 20, 2 * max_reads), cap_anch = std::max<uint64_t>(1ull << 24, 32 * max_reads);
-        if (c->ext_long) {      // a long read's chains hold most of its minimizers (~2 / (w + 1) per base), secondary chains as many again
-            // bases of one chunk: max_bases may describe a whole batch of many chunks; ~8 kb per read is what long-read sets average - a
-            // chunk that holds more is cut in two when its chains do not fit (SH_SPLIT)
-            const uint64_t cb = std::min<uint64_t>({max_bases + 64, max_reads * (uint64_t)max_read_len + 64, max_reads * 8192ull + (64ull << 20)});
-            // flag-only calls hand over the chains of the loci that can hold regs[0] (k_lr_locus: ~100 chain anchors and a dozen chains per read
-            // of the bench workload); a call with a trace hands over every chain (thousands of anchors, hundreds of chains per read) and is
-            // cut into smaller chunks when they do not fit
-            cap_anch = std::max<uint64_t>(cap_anch, cb / 8);
-            cap_recs = std::max<uint64_t>(cap_recs, std::min<uint64_t>(cb / 64, 1ull << 28) + 8 * max_reads);
-        }
-        if (sw.ext_bytes != SW_UNSET) { cap_anch = std::max<uint64_t>(1 << 16, (uint64_t)sw.ext_bytes / 16); cap_recs = std::max<uint64_t>(1 << 12, cap_anch / 16); }
-        cap_recs = std::min<uint64_t>((cap_recs + SINK_SHARDS - 1) / SINK_SHARDS, 0xfffffff0ull / SINK_SHARDS);      // per shard
-        cap_anch = (cap_anch + SINK_SHARDS - 1) / SINK_SHARDS;
-        auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-        c->ext_bytes = al(SINK_SHARDS * cap_recs * sizeof(ChainRec)) + al(SINK_SHARDS * cap_anch * 8) + al(SINK_SHARDS * cap_anch * 4) + 3 * al(max_reads * 4) + al(max_reads * 8) + al(max_reads * 4) + (c->ext_long ? 0 : 2 * al(max_reads * 4));
-        if ((e = hipMalloc(&c->d_ext, c->ext_bytes)) != hipSuccess) return fail(e, "extension-stage buffers");
-        uint8_t *p = c->d_ext;
-        auto take = [&](uint64_t b) { uint8_t *q = p; p += al(b); return q; };
-        c->sink.recs = (ChainRec *)take(SINK_SHARDS * cap_recs * sizeof(ChainRec)); c->sink.cap_recs = (uint32_t)cap_recs;
-        c->sink.cx = (uint64_t *)take(SINK_SHARDS * cap_anch * 8); c->sink.cq = (uint32_t *)take(SINK_SHARDS * cap_anch * 4); c->sink.cap_anch = cap_anch;
-        c->sink.head = (uint32_t *)take(max_reads * 4);
+        Carve count, place;
+        ext_layout(count, *c, K, max_reads, elem);
+        c->ext_bytes = count.off;
+        if ((e = own.device(c->d_ext, c->ext_bytes)) != hipSuccess) return fail(e, "extension-stage buffers");
+        place.base = c->d_ext;
+        ext_layout(place, *c, K, max_reads, elem);
+        c->sink.cap_recs = (uint32_t)K.cap_recs; c->sink.cap_anch = K.cap_anch;
         c->sink.trec = c->use_k1 ? c->d_records : nullptr; c->sink.tinfo = c->d_k1info; c->sink.tseed_cap = c->seed_cap;
-        c->d_ext_list = (uint32_t *)take(max_reads * 4);
-        c->d_ext_redo = (uint32_t *)take(max_reads * 4);
-        if (!c->ext_long) { c->d_ext_unres[0] = (uint32_t *)take(max_reads * 4); c->d_ext_unres[1] = (uint32_t *)take(max_reads * 4); }
-        c->sink.best = (unsigned long long *)take(max_reads * 8);
-        c->sink.tie = (uint32_t *)take(max_reads * 4);
         c->sink.n_recs = c->d_ctr->ext_n_recs; c->sink.n_anch = c->d_ctr->ext_n_anch; c->sink.overflow = &c->d_ctr->ext_overflow;
         c->ext_reg_cap = (uint32_t)sw.ext_reg_cap;
         if (!c->ext_long) {
@@ -3665,7 +3629,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
             // k_regs_align_top holds one chain and the few regions z-drops split off it in LDS: its share of the scratch needs no region arrays
             c->ext_scratch_per_wave_top = align_scratch_layout(max_read_len, 64, nullptr, nullptr, nullptr);
             c->ext_waves_top = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)256 * std::max<uint64_t>(1, (160u << 10) / (sizeof(AlignLdsTop) + 16)), budget / c->ext_scratch_per_wave_top, (max_reads + 3) / 4}));
-            if ((e = hipMalloc(&c->d_ext_scratch, std::max<uint64_t>((uint64_t)c->ext_waves * c->ext_scratch_per_wave, (uint64_t)c->ext_waves_top * c->ext_scratch_per_wave_top))) != hipSuccess) return fail(e, "extension-stage scratch");
+            if ((e = own.device(c->d_ext_scratch, std::max<uint64_t>((uint64_t)c->ext_waves * c->ext_scratch_per_wave, (uint64_t)c->ext_waves_top * c->ext_scratch_per_wave_top))) != hipSuccess) return fail(e, "extension-stage scratch");
         } else {
             // per-wave working memory of the two kernels (k_long_chains, k_regs_align_long), each in two sizes: every wave slot with room for
             // the usual read, and a few waves with room for the largest alignment minimap2 attempts (max_sw_mat = 10^8 cells) / for reads
@@ -3710,43 +3674,29 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
                 if (i == 0) { int dev = 0, ncu = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) c->n_cu = ncu; }
                 c->lext_waves[i] = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({wave_max[i], budget[i] / c->lext_per_wave[i], t ? std::max<uint64_t>(4, max_reads / 16) : max_reads}));
                 if (c->cs.dbg_set) fprintf(stderr, "[dbg] long-read stage working memory %d: %u waves x %.2f MB\n", i, c->lext_waves[i], c->lext_per_wave[i] / 1048576.0);
-                if ((e = hipMalloc(&c->d_lext[i], (uint64_t)c->lext_waves[i] * c->lext_per_wave[i])) != hipSuccess) return fail(e, "long-read extension-stage scratch");
+                if ((e = own.device(c->d_lext[i],(uint64_t)c->lext_waves[i] * c->lext_per_wave[i])) != hipSuccess) return fail(e, "long-read extension-stage scratch");
             }
-            if ((e = hipMalloc(&c->d_lext_big, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
-            if ((e = hipMalloc(&c->d_lext_big2, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
-            if ((e = hipMalloc(&c->d_lext_sorted, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
-            for (auto &q : c->d_lext_unres) if ((e = hipMalloc(&q, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
-            if ((e = hipMalloc(&c->d_lext_exact_list, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
-            if ((e = hipMalloc(&c->d_lext_exact_list2, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
-            if ((e = hipMalloc(&c->d_lext_esorted, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
+            for (uint32_t **q : {&c->d_lext_big, &c->d_lext_big2, &c->d_lext_sorted, &c->d_lext_unres[0], &c->d_lext_unres[1], &c->d_lext_exact_list, &c->d_lext_exact_list2, &c->d_lext_esorted})
+                if ((e = own.device(*q, max_reads * 4)) != hipSuccess) return fail(e, "long-read extension-stage list");
             for (int t = 1; t < 2; ++t) {   // the exact long join on the one-lane trees (E3): the second size of the chains kernel plus the node pools of the two trees; one wave per CU (LDS)
                 LongSizes q = t ? zb : z; q.phase = 2;
                 c->lext_exact_sz[t] = q;
                 c->lext_exact_per_wave[t] = long_ws_carve(nullptr, nullptr, q);
                 const uint64_t bud = (t ? 6ull << 30 : 1ull << 30) * (budget[0] + 1) / ((6ull << 30) + 1);      // scaled like the others
                 c->lext_exact_waves[t] = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({256, bud / c->lext_exact_per_wave[t], std::max<uint64_t>(4, max_reads / 16)}));
-                if ((e = hipMalloc(&c->d_lext_exact[t], (uint64_t)c->lext_exact_waves[t] * c->lext_exact_per_wave[t])) != hipSuccess) return fail(e, "long-read extension-stage scratch");
+                if ((e = own.device(c->d_lext_exact[t],(uint64_t)c->lext_exact_waves[t] * c->lext_exact_per_wave[t])) != hipSuccess) return fail(e, "long-read extension-stage scratch");
             }
-            // the chains between the two kernels: what the hand-over buffers can hold, twice (the long join re-orders, it adds nothing; a read
-            // with one chain kept may leave that chain beside the join's outcome: lr_chains_wave, `both`)
-            c->larena_bytes = SINK_SHARDS * cap_anch * 32 + SINK_SHARDS * cap_recs * 12 + max_reads * 48 + (1ull << 20);
-            if ((e = hipMalloc(&c->d_larena, c->larena_bytes)) != hipSuccess) return fail(e, "long-read extension-stage arena");
-            if ((e = hipMalloc(&c->d_lhdr, max_reads * sizeof(LongHdr))) != hipSuccess) return fail(e, "long-read extension-stage headers");
-            for (auto &q : c->d_locus) if ((e = hipMalloc(&q, max_reads * sizeof(SortItem))) != hipSuccess) return fail(e, "long-read locus lists");
-            if ((e = hipMalloc(&c->d_lr_drop, max_reads * 4)) != hipSuccess) return fail(e, "long-read locus table");
-            if ((e = hipMalloc(&c->d_lr_fb, max_reads * 4)) != hipSuccess) return fail(e, "long-read locus list");
-            {   // k_expand's raw anchors wait here for k_lr_locus (12 B each; ~1.1 anchors per base on a repeat-rich reference); reads that
-                // find no room come back in the pass's next iteration
-                const uint64_t cb = std::min<uint64_t>({max_bases + 64, max_reads * (uint64_t)max_read_len + 64, max_reads * 8192ull + (64ull << 20)});
-                c->stage_cap = std::min<uint64_t>(cb + cb / 4 + (1ull << 20), (64ull << 30) / 12);
-                {   // last of the context's allocations: at most 45 % of what the device still has (a million-read context fits that way - its
-                    // launches pay the stage's longest reads once where two half-size ones pay them twice; what finds no room is deferred)
-                    size_t fr = 0, tot = 0;
-                    if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->stage_cap = std::min<uint64_t>(c->stage_cap, std::max<uint64_t>(1ull << 20, (uint64_t)((double)fr * 0.45) / 12));
-                }
-                if (sw.stage_bytes != SW_UNSET) c->stage_cap = std::max<uint64_t>(1ull << 16, (uint64_t)sw.stage_bytes / 12);
-                if ((e = hipMalloc(&c->d_stage_x, c->stage_cap * 8)) != hipSuccess) return fail(e, "long-read anchor staging");
-                if ((e = hipMalloc(&c->d_stage_q, c->stage_cap * 4)) != hipSuccess) return fail(e, "long-read anchor staging");
+            if ((e = own.device(c->d_larena, c->larena_bytes)) != hipSuccess) return fail(e, "long-read extension-stage arena");
+            if ((e = own.device(c->d_lhdr, max_reads * sizeof(LongHdr))) != hipSuccess) return fail(e, "long-read extension-stage headers");
+            for (auto &q : c->d_locus) if ((e = own.device(q, max_reads * sizeof(SortItem))) != hipSuccess) return fail(e, "long-read locus lists");
+            if ((e = own.device(c->d_lr_drop, max_reads * 4)) != hipSuccess) return fail(e, "long-read locus table");
+            if ((e = own.device(c->d_lr_fb, max_reads * 4)) != hipSuccess) return fail(e, "long-read locus list");
+            {   // the raw anchors' staging, the last of the context's allocations: sized by what the device has left now (ctx_stage_cap)
+                size_t fr = 0, tot = 0;
+                const bool have = hipMemGetInfo(&fr, &tot) == hipSuccess;
+                c->stage_cap = ctx_stage_cap(max_reads, max_bases, max_read_len, have, fr, sw.stage_bytes);
+                if ((e = own.device(c->d_stage_x, c->stage_cap * 8)) != hipSuccess) return fail(e, "long-read anchor staging");
+                if ((e = own.device(c->d_stage_q, c->stage_cap * 4)) != hipSuccess) return fail(e, "long-read anchor staging");
             }
             {   // reference windows of 2^shift bases, at least as wide as the widest gap either chaining pass links across
                 const int32_t D = std::max({opts->max_gap, opts->max_gap_ref, opts->bw, opts->bw_long, 1});
@@ -3755,14 +3705,14 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
                 c->locus_shift = sh;
             }
         }
-        for (auto &ev : c->ev_ext) if ((e = hipEventCreate(&ev)) != hipSuccess) return fail(e, "event");
+        for (auto &ev : c->ev_ext) if ((e = own.event(ev)) != hipSuccess) return fail(e, "event");
     }
-    for (auto &ev : c->ev) if ((e = hipEventCreate(&ev)) != hipSuccess) return fail(e, "event");
-    for (auto &ev : c->evx) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
+    for (auto &ev : c->ev) if ((e = own.event(ev)) != hipSuccess) return fail(e, "event");
+    for (auto &ev : c->evx) if ((e = own.event(ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
     // (the side streams are created when a call first needs one: HIP deals its hardware queues - four by default - out to the streams that
     // exist, and a side stream that shares the caller's queue runs after it, not beside it)
     c->par = (int)sw.streams;
-    *out = c;
+    *out = guard.release();
     return SH_OK;
 }
 
@@ -3791,16 +3741,7 @@ extern "C" sh_status sh_ctx_debug_list(const sh_ctx *c, int32_t which, uint32_t 
 extern "C" sh_status sh_ctx_destroy(sh_ctx *c)
 {
     if (!c) return SH_OK;
-    hipFree(c->d_records); hipFree(c->d_k1info); hipFree(c->d_work_small); hipFree(c->d_work_small2); hipFree(c->d_work_resketch);
-    hipFree(c->d_work_defer); hipFree(c->d_work_defer2);
-    for (auto &pp : c->d_big) for (auto p : pp) hipFree(p);
-    hipFree(c->d_ctr); if (c->h_ctr) hipHostFree(c->h_ctr); hipFree(c->d_arena); hipFree(c->d_long);
-    hipFree(c->d_ext); hipFree(c->d_ext_scratch); for (auto q : c->d_lext) hipFree(q); hipFree(c->d_lext_big); hipFree(c->d_lext_big2); hipFree(c->d_lext_sorted); for (auto q : c->d_lext_unres) hipFree(q); hipFree(c->d_lext_exact_list); hipFree(c->d_lext_exact_list2); hipFree(c->d_lext_esorted); for (auto q : c->d_lext_exact) hipFree(q); hipFree(c->d_larena); hipFree(c->d_lhdr); for (auto q : c->d_locus) hipFree(q); hipFree(c->d_lr_drop); hipFree(c->d_lr_fb); hipFree(c->d_stage_x); hipFree(c->d_stage_q); hipFree(c->d_lkind); hipFree(c->d_coop);
-    for (auto ev : c->ev_ext) if (ev) hipEventDestroy(ev);
-    for (auto ev : c->ev) if (ev) hipEventDestroy(ev);
-    for (auto ev : c->evx) if (ev) hipEventDestroy(ev);
-    for (auto st : c->sx) if (st) hipStreamDestroy(st);
-    delete c;
+    delete c;      // ~CtxOwner releases what the context allocated
     return SH_OK;
 }
 
@@ -3825,7 +3766,7 @@ static void launch_long(const LongArgs &a, hipStream_t s)
 static sh_status ensure_side_streams(sh_ctx *c, int first, int last)
 {
     for (int i = first; i <= last; ++i)
-        if (!c->sx[i]) SH_HIP(hipStreamCreateWithFlags(&c->sx[i], hipStreamNonBlocking));
+        if (!c->sx[i]) SH_HIP(c->own.stream(c->sx[i], hipStreamNonBlocking));
     return SH_OK;
 }
 
@@ -3847,25 +3788,22 @@ static sh_status pick_side_streams(sh_ctx *c, hipStream_t s)
     if (es != SH_OK) return es;
     // SCRUBBY_HIP_SIDE_PICK=g,f pins the two streams (giants' launch, follower) and skips the probe
     if (c->cs.side_pick >= 0) { c->side_pick[0] = (int)c->cs.side_pick & 255; c->side_pick[1] = (int)c->cs.side_pick >> 8; c->side_probed = s; c->side_probed_done = true; return SH_OK; }
-    struct Events {      // destroyed on every way out
-        hipEvent_t t0 = nullptr, t1 = nullptr, e = nullptr;
-        ~Events() { if (t0) hipEventDestroy(t0); if (t1) hipEventDestroy(t1); if (e) hipEventDestroy(e); }
-    } ev;
-    SH_HIP(hipEventCreate(&ev.t0)); SH_HIP(hipEventCreate(&ev.t1)); SH_HIP(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+    DevEvent ev_t0, ev_t1, ev_e;      // destroyed on every way out
+    SH_HIP(ev_t0.create()); SH_HIP(ev_t1.create()); SH_HIP(ev_e.create(hipEventDisableTiming));
     float ms[3] = {1e9f, 1e9f, 1e9f};
     for (int i = 0; i < 3; ++i) {
         float rep[3] = {0, 0, 0};      // the median of three tries: one 0.2-ms timing is at the mercy of whatever else the device is doing
         for (int k = 0; k < 3; ++k) {
             SH_HIP(hipStreamSynchronize(s));
-            SH_HIP(hipEventRecord(ev.t0, s));
-            SH_HIP(hipStreamWaitEvent(c->sx[i], ev.t0, 0));
+            SH_HIP(hipEventRecord(ev_t0.e, s));
+            SH_HIP(hipStreamWaitEvent(c->sx[i], ev_t0.e, 0));
             hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, 20000ull);
             hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, c->sx[i], 20000ull);
-            SH_HIP(hipEventRecord(ev.e, c->sx[i]));
-            SH_HIP(hipStreamWaitEvent(s, ev.e, 0));
-            SH_HIP(hipEventRecord(ev.t1, s));
-            SH_HIP(hipEventSynchronize(ev.t1));
-            SH_HIP(hipEventElapsedTime(&rep[k], ev.t0, ev.t1));
+            SH_HIP(hipEventRecord(ev_e.e, c->sx[i]));
+            SH_HIP(hipStreamWaitEvent(s, ev_e.e, 0));
+            SH_HIP(hipEventRecord(ev_t1.e, s));
+            SH_HIP(hipEventSynchronize(ev_t1.e));
+            SH_HIP(hipEventElapsedTime(&rep[k], ev_t0.e, ev_t1.e));
         }
         std::sort(rep, rep + 3);
         ms[i] = rep[1];
@@ -4215,30 +4153,29 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             LongSizes q = phase == 2 ? c->lext_exact_sz[1] : c->lext_sz[phase * 2 + 1];
             int cur = 0;
             for (int round = 0; n_un > 0; ++round) {
-                uint8_t *buf = nullptr;
+                DevBuf buf;      // this round's working memory: gone at the end of the round, which sync_ctr has synchronised by then
                 unsigned long long per = 0; uint32_t waves = 0;
                 if (round < 5) {
                     q.cap_a = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_a * 4, 1u << 28); q.cap_u = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_u * 4, 1u << 26); q.cap_r = q.cap_u;
                     q.cap_m = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_m * 4, 1u << 26); q.cap_k = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_k * 4, 1u << 22);
                     q.cap_t = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_t * 4, 1u << 28); q.cap_p = std::min<uint64_t>(q.cap_p * 4, 4ull << 30);
                     per = long_ws_carve(nullptr, nullptr, q);
-                    for (waves = std::min<uint32_t>(n_un, 4); waves > 0 && hipMalloc(&buf, per * waves) != hipSuccess; waves >>= 1) { buf = nullptr; (void)hipGetLastError(); }
+                    for (waves = std::min<uint32_t>(n_un, 4); waves > 0 && buf.alloc(per * waves) != hipSuccess; waves >>= 1) (void)hipGetLastError();
                 }
-                if (!buf) {      // no memory to be had: counted, warned about, chain-level answer
+                if (!buf.p) {      // no memory to be had: counted, warned about, chain-level answer
                     hipLaunchKernelGGL(k_lext_giveup, dim3(16), dim3(256), 0, s, (const uint32_t *)c->d_lext_unres[cur], n_un, d_flags, d_trace, c->d_lhdr, c->d_ctr, x.kind);
                     SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_unres, 0, 4, s));
                     return sync_ctr();
                 }
                 const uint32_t zero2[4] = {0, 0, n_un, 0};
                 SH_HIP(hipMemcpyAsync(&c->d_ctr->lext_n_unres, zero2, 16, hipMemcpyHostToDevice, s));      // lext_n_unres, lext_ticket_unres, lext_n_unres_in
-                xa.scratch = buf; xa.scratch_per_wave = per; xa.sz = q;
+                xa.scratch = buf.as<uint8_t>(); xa.scratch_per_wave = per; xa.sz = q;
                 xa.list = c->d_lext_unres[cur]; xa.n_list = &c->d_ctr->lext_n_unres_in; xa.ticket = &c->d_ctr->lext_ticket_unres;
                 xa.big_list = nullptr; xa.n_big = nullptr; xa.part = 0; xa.unres_list = c->d_lext_unres[cur ^ 1]; xa.n_unres = &c->d_ctr->lext_n_unres;
                 if (phase == 0) hipLaunchKernelGGL((k_long_chains<4096, false, true>), dim3(waves), dim3(64), 0, s, xa);
                 else if (phase == 2) hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(waves), dim3(64), 0, s, xa);
                 else hipLaunchKernelGGL(k_regs_align_long, dim3(waves), dim3(64), 0, s, xa);
                 sh_status st = sync_ctr();
-                hipFree(buf);
                 if (st != SH_OK) return st;
                 if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
                 n_un = c->h_ctr->lext_n_unres; cur ^= 1;
@@ -4254,7 +4191,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             constexpr uint32_t QCAP = 65536, NDESC = 512;
             constexpr size_t off_desc = 256, off_ready = off_desc + NDESC * sizeof(LongCoopDesc), off_items = off_ready + QCAP * 4, region = off_items + QCAP * 16;
             static_assert(sizeof(LongCoopDesc) % 8 == 0 && off_items % 16 == 0 && region % 256 == 0, "coop layout");
-            if (!c->d_coop) SH_HIP(hipMalloc(&c->d_coop, 3 * region));
+            if (!c->d_coop) SH_HIP(c->own.device(c->d_coop, 3 * region));
             uint8_t *base = c->d_coop + (size_t)which * region;
             SH_HIP(hipMemsetAsync(base, 0, off_items, st));
             xx.coop.q_res = (uint32_t *)base; xx.coop.q_head = (uint32_t *)(base + 64); xx.coop.active = (uint32_t *)(base + 128); xx.coop.n_reads = (uint32_t *)(base + 192);
@@ -4533,12 +4470,14 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
             n_sr_ondemand += n_un;
             int cur = 0;
             while (n_un > 0) {
-                uint8_t *buf = nullptr; unsigned long long per = 0; uint32_t waves = 0;
+                DevBuf scratch;      // this round's working memory: gone at the end of the round, after the stream has been synchronised
+                unsigned long long per = 0; uint32_t waves = 0;
                 if (cap < (1u << 24)) {
                     cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 4, 1u << 24);
                     per = align_scratch_layout(c->max_read_len, cap, nullptr, nullptr, nullptr);
-                    for (waves = std::min<uint32_t>(n_un, 8); waves > 0 && hipMalloc(&buf, per * waves) != hipSuccess; waves >>= 1) { buf = nullptr; (void)hipGetLastError(); }
+                    for (waves = std::min<uint32_t>(n_un, 8); waves > 0 && scratch.alloc(per * waves) != hipSuccess; waves >>= 1) (void)hipGetLastError();
                 }
+                uint8_t *const buf = scratch.as<uint8_t>();
                 const uint32_t z4[4] = {0, 0, n_un, 0};      // ext_n_unres, ext_ticket_unres, ext_n_unres_in
                 SH_HIP(hipMemcpyAsync(&c->d_ctr->ext_n_unres, z4, 16, hipMemcpyHostToDevice, s));
                 xa.list = c->d_ext_unres[cur]; xa.n_list = &c->d_ctr->ext_n_unres_in; xa.ticket = &c->d_ctr->ext_ticket_unres;
@@ -4550,7 +4489,6 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
                 hipLaunchKernelGGL(k_regs_align, dim3(waves), dim3(64), 0, s, xa);
                 SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
                 SH_HIP(hipStreamSynchronize(s));
-                if (buf) hipFree(buf);
                 SH_HIP(hipGetLastError());
                 if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
                 SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
@@ -4703,9 +4641,8 @@ extern "C" sh_status sh_classify_device(sh_ctx *c, const uint8_t *d_bases, const
     if (stats) memset(stats, 0, sizeof(*stats));
     if (c->ext_long) {      // the stage's per-read path record of this call
         if (n_reads > c->lkind_cap) {
-            if (c->d_lkind) hipFree(c->d_lkind);
-            c->d_lkind = nullptr; c->lkind_cap = 0;
-            SH_HIP(hipMalloc(&c->d_lkind, n_reads + n_reads / 8 + 64));
+            c->own.drop(c->d_lkind); c->lkind_cap = 0;
+            SH_HIP(c->own.device(c->d_lkind, n_reads + n_reads / 8 + 64));
             c->lkind_cap = n_reads + n_reads / 8 + 64;
         }
         c->lkind_n = n_reads;
@@ -4743,77 +4680,73 @@ extern "C" sh_status sh_dbg_front_end(sh_ctx *c, const uint8_t *d_bases, const u
         SH_CHECK(off[r] <= off[r + 1] && off[r + 1] - off[r] <= c->max_read_len, SH_ERR_BAD_ARG, "sh_dbg_front_end: read %llu: offsets decrease or the read is longer than the context's %u", (unsigned long long)r, c->max_read_len);
     SH_CHECK(off[n_reads] <= n_bases, SH_ERR_BAD_ARG, "sh_dbg_front_end: offsets beyond n_bases");
     const hipStream_t s = nullptr;
-    uint8_t *d_flags = nullptr;
-    auto run = [&]() -> sh_status {
-        SH_HIP(hipMalloc(&d_flags, n_reads));
-        SH_HIP(hipMemsetAsync(d_flags, 0xff, n_reads, s));
-        SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
-        SH_HIP(hipMemsetAsync(c->d_k1info, 0, n_reads * 4, s));      // a read K1 hands on unsketched (tile beyond the LDS stage) has none
-        c->cur_reads = n_reads;
-        const sh_status st = launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, nullptr, s);
-        if (st != SH_OK) return st;
-        SH_HIP(hipGetLastError());
-        SH_HIP(hipStreamSynchronize(s));
-        Counters ctr;
-        SH_HIP(hipMemcpy(&ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
-        SH_HIP(hipMemcpy(k1info, c->d_k1info, n_reads * 4, hipMemcpyDeviceToHost));
-        info[0] = c->use_k1 ? 1 : c->use_long ? 2 : 0; info[1] = (int32_t)c->seed_cap; info[2] = (int32_t)ctr.n_small; info[3] = (int32_t)ctr.n_big[0]; info[4] = (int32_t)ctr.n_resketch;
-        // the route: which work list names the read (bit 0 work_small, 1 work_big, 2 work_resketch; bit 7: named twice by one list)
-        memset(route, 0, n_reads);
-        const uint32_t *lists[3] = {c->d_work_small, c->d_big[0][0], c->d_work_resketch};
-        const uint32_t cnt[3] = {ctr.n_small, ctr.n_big[0], ctr.n_resketch};
-        std::vector<uint32_t> h;
-        for (int l = 0; l < 3; ++l) {
-            SH_CHECK(cnt[l] <= n_reads, SH_ERR_HIP, "sh_dbg_front_end: work list %d holds %u of %llu reads", l, cnt[l], (unsigned long long)n_reads);
-            h.resize(cnt[l]);
-            if (cnt[l]) SH_HIP(hipMemcpy(h.data(), lists[l], 4 * (size_t)cnt[l], hipMemcpyDeviceToHost));
-            for (uint32_t r : h) {
-                SH_CHECK(r < n_reads, SH_ERR_HIP, "sh_dbg_front_end: work list %d names read %u of %llu", l, r, (unsigned long long)n_reads);
-                route[r] |= (route[r] >> l & 1) ? 0x80 : (uint8_t)(1 << l);
-            }
+    DevBuf b_flags;
+    SH_HIP(b_flags.alloc(n_reads));
+    uint8_t *const d_flags = b_flags.as<uint8_t>();
+    SH_HIP(hipMemsetAsync(d_flags, 0xff, n_reads, s));
+    SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
+    SH_HIP(hipMemsetAsync(c->d_k1info, 0, n_reads * 4, s));      // a read K1 hands on unsketched (tile beyond the LDS stage) has none
+    c->cur_reads = n_reads;
+    const sh_status st = launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, nullptr, s);
+    if (st != SH_OK) return st;
+    SH_HIP(hipGetLastError());
+    SH_HIP(hipStreamSynchronize(s));
+    Counters ctr;
+    SH_HIP(hipMemcpy(&ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
+    SH_HIP(hipMemcpy(k1info, c->d_k1info, n_reads * 4, hipMemcpyDeviceToHost));
+    info[0] = c->use_k1 ? 1 : c->use_long ? 2 : 0; info[1] = (int32_t)c->seed_cap; info[2] = (int32_t)ctr.n_small; info[3] = (int32_t)ctr.n_big[0]; info[4] = (int32_t)ctr.n_resketch;
+    // the route: which work list names the read (bit 0 work_small, 1 work_big, 2 work_resketch; bit 7: named twice by one list)
+    memset(route, 0, n_reads);
+    const uint32_t *lists[3] = {c->d_work_small, c->d_big[0][0], c->d_work_resketch};
+    const uint32_t cnt[3] = {ctr.n_small, ctr.n_big[0], ctr.n_resketch};
+    std::vector<uint32_t> h;
+    for (int l = 0; l < 3; ++l) {
+        SH_CHECK(cnt[l] <= n_reads, SH_ERR_HIP, "sh_dbg_front_end: work list %d holds %u of %llu reads", l, cnt[l], (unsigned long long)n_reads);
+        h.resize(cnt[l]);
+        if (cnt[l]) SH_HIP(hipMemcpy(h.data(), lists[l], 4 * (size_t)cnt[l], hipMemcpyDeviceToHost));
+        for (uint32_t r : h) {
+            SH_CHECK(r < n_reads, SH_ERR_HIP, "sh_dbg_front_end: work list %d names read %u of %llu", l, r, (unsigned long long)n_reads);
+            route[r] |= (route[r] >> l & 1) ? 0x80 : (uint8_t)(1 << l);
         }
-        uint64_t n_rec = 0, n_mz = 0;
-        if (c->use_k1) {
-            std::vector<uint4> hr(n_reads * c->seed_cap);
-            SH_HIP(hipMemcpy(hr.data(), c->d_records, hr.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-            for (uint64_t r = 0; r < n_reads; ++r) {
-                rec_off[r] = n_rec; mz_off[r] = 0;
-                const uint32_t n = std::min<uint32_t>((k1info[r] >> 16) & 0x7fffu, c->seed_cap);
-                SH_CHECK(n_rec + n <= rec_cap, SH_ERR_BAD_ARG, "sh_dbg_front_end: more than rec_cap = %llu seed records", (unsigned long long)rec_cap);
-                memcpy(records + 4 * n_rec, hr.data() + r * c->seed_cap, (size_t)n * sizeof(uint4));
-                n_rec += n;
-            }
-        } else if (c->use_long) {
-            std::vector<uint32_t> seg_base(n_reads + 1);
-            SH_HIP(hipMemcpy(seg_base.data(), c->d_seg_base, 4 * (n_reads + 1), hipMemcpyDeviceToHost));
-            const uint32_t n_segs = seg_base[n_reads];
-            SH_CHECK(n_segs == ctr.n_long_segs && n_segs <= c->max_segs, SH_ERR_HIP, "sh_dbg_front_end: segment table of %u segments (counter %u, room for %llu)", n_segs, ctr.n_long_segs, (unsigned long long)c->max_segs);
-            std::vector<unsigned long long> seg_off((size_t)n_segs + 1), seed_off(n_reads);
-            SH_HIP(hipMemcpy(seg_off.data(), c->d_seg_off, 8 * ((size_t)n_segs + 1), hipMemcpyDeviceToHost));
-            SH_HIP(hipMemcpy(seed_off.data(), c->d_seed_off, 8 * n_reads, hipMemcpyDeviceToHost));
-            const uint64_t tot = std::min<uint64_t>(seg_off[n_segs], c->mz_cap);
-            std::vector<uint64_t> hh(tot); std::vector<uint32_t> hy(tot); std::vector<uint4> hr(tot);
-            if (tot) {
-                SH_HIP(hipMemcpy(hh.data(), c->d_mz_hash, 8 * tot, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(hy.data(), c->d_mz_y, 4 * tot, hipMemcpyDeviceToHost));
-                SH_HIP(hipMemcpy(hr.data(), c->d_lrec, 16 * tot, hipMemcpyDeviceToHost));
-            }
-            for (uint64_t r = 0; r < n_reads; ++r) {
-                rec_off[r] = n_rec; mz_off[r] = n_mz;
-                const uint32_t nm = k1info[r] & 0xffffu, ns = k1info[r] >> 16;
-                const uint64_t mb = seg_off[seg_base[r]], sb = seed_off[r];
-                SH_CHECK(mb + nm <= tot && sb + ns <= tot && ns <= nm, SH_ERR_HIP, "sh_dbg_front_end: read %llu: %u minimizers at %llu, %u records at %llu, of %llu", (unsigned long long)r, nm, (unsigned long long)mb, ns, (unsigned long long)sb, (unsigned long long)tot);
-                SH_CHECK(n_rec + ns <= rec_cap && n_mz + nm <= mz_cap, SH_ERR_BAD_ARG, "sh_dbg_front_end: more than rec_cap = %llu seed records or mz_cap = %llu minimizers", (unsigned long long)rec_cap, (unsigned long long)mz_cap);
-                memcpy(records + 4 * n_rec, hr.data() + sb, (size_t)ns * sizeof(uint4));
-                memcpy(mz_hash + n_mz, hh.data() + mb, (size_t)nm * 8); memcpy(mz_y + n_mz, hy.data() + mb, (size_t)nm * 4);
-                n_rec += ns; n_mz += nm;
-            }
-        } else {
-            for (uint64_t r = 0; r < n_reads; ++r) { rec_off[r] = 0; mz_off[r] = 0; }
+    }
+    uint64_t n_rec = 0, n_mz = 0;
+    if (c->use_k1) {
+        std::vector<uint4> hr(n_reads * c->seed_cap);
+        SH_HIP(hipMemcpy(hr.data(), c->d_records, hr.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+        for (uint64_t r = 0; r < n_reads; ++r) {
+            rec_off[r] = n_rec; mz_off[r] = 0;
+            const uint32_t n = std::min<uint32_t>((k1info[r] >> 16) & 0x7fffu, c->seed_cap);
+            SH_CHECK(n_rec + n <= rec_cap, SH_ERR_BAD_ARG, "sh_dbg_front_end: more than rec_cap = %llu seed records", (unsigned long long)rec_cap);
+            memcpy(records + 4 * n_rec, hr.data() + r * c->seed_cap, (size_t)n * sizeof(uint4));
+            n_rec += n;
         }
-        rec_off[n_reads] = n_rec; mz_off[n_reads] = n_mz;
-        return SH_OK;
-    };
-    const sh_status st = run();
-    hipFree(d_flags);
-    return st;
+    } else if (c->use_long) {
+        std::vector<uint32_t> seg_base(n_reads + 1);
+        SH_HIP(hipMemcpy(seg_base.data(), c->d_seg_base, 4 * (n_reads + 1), hipMemcpyDeviceToHost));
+        const uint32_t n_segs = seg_base[n_reads];
+        SH_CHECK(n_segs == ctr.n_long_segs && n_segs <= c->max_segs, SH_ERR_HIP, "sh_dbg_front_end: segment table of %u segments (counter %u, room for %llu)", n_segs, ctr.n_long_segs, (unsigned long long)c->max_segs);
+        std::vector<unsigned long long> seg_off((size_t)n_segs + 1), seed_off(n_reads);
+        SH_HIP(hipMemcpy(seg_off.data(), c->d_seg_off, 8 * ((size_t)n_segs + 1), hipMemcpyDeviceToHost));
+        SH_HIP(hipMemcpy(seed_off.data(), c->d_seed_off, 8 * n_reads, hipMemcpyDeviceToHost));
+        const uint64_t tot = std::min<uint64_t>(seg_off[n_segs], c->mz_cap);
+        std::vector<uint64_t> hh(tot); std::vector<uint32_t> hy(tot); std::vector<uint4> hr(tot);
+        if (tot) {
+            SH_HIP(hipMemcpy(hh.data(), c->d_mz_hash, 8 * tot, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(hy.data(), c->d_mz_y, 4 * tot, hipMemcpyDeviceToHost));
+            SH_HIP(hipMemcpy(hr.data(), c->d_lrec, 16 * tot, hipMemcpyDeviceToHost));
+        }
+        for (uint64_t r = 0; r < n_reads; ++r) {
+            rec_off[r] = n_rec; mz_off[r] = n_mz;
+            const uint32_t nm = k1info[r] & 0xffffu, ns = k1info[r] >> 16;
+            const uint64_t mb = seg_off[seg_base[r]], sb = seed_off[r];
+            SH_CHECK(mb + nm <= tot && sb + ns <= tot && ns <= nm, SH_ERR_HIP, "sh_dbg_front_end: read %llu: %u minimizers at %llu, %u records at %llu, of %llu", (unsigned long long)r, nm, (unsigned long long)mb, ns, (unsigned long long)sb, (unsigned long long)tot);
+            SH_CHECK(n_rec + ns <= rec_cap && n_mz + nm <= mz_cap, SH_ERR_BAD_ARG, "sh_dbg_front_end: more than rec_cap = %llu seed records or mz_cap = %llu minimizers", (unsigned long long)rec_cap, (unsigned long long)mz_cap);
+            memcpy(records + 4 * n_rec, hr.data() + sb, (size_t)ns * sizeof(uint4));
+            memcpy(mz_hash + n_mz, hh.data() + mb, (size_t)nm * 8); memcpy(mz_y + n_mz, hy.data() + mb, (size_t)nm * 4);
+            n_rec += ns; n_mz += nm;
+        }
+    } else {
+        for (uint64_t r = 0; r < n_reads; ++r) { rec_off[r] = 0; mz_off[r] = 0; }
+    }
+    rec_off[n_reads] = n_rec; mz_off[n_reads] = n_mz;
+    return SH_OK;
 }

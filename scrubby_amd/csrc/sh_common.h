@@ -71,9 +71,10 @@ struct DevBuf {   // frees on scope exit
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) hipFree(p); }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) hipFree(p); p = nullptr; }
     template <class T> T *as() { return (T *)p; }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    hipError_t alloc(size_t bytes) { const hipError_t e = hipMalloc(&p, bytes ? bytes : 16); if (e != hipSuccess) p = nullptr; return e; }
 };
 struct DevEvent {   // destroyed on scope exit, if it was created
     hipEvent_t e = nullptr;
@@ -81,7 +82,7 @@ struct DevEvent {   // destroyed on scope exit, if it was created
     DevEvent(const DevEvent &) = delete;
     DevEvent &operator=(const DevEvent &) = delete;
     ~DevEvent() { if (e) hipEventDestroy(e); }
-    hipError_t create() { return hipEventCreate(&e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
 };
 
 // ---- device helpers --------------------------------------------------------------------------
