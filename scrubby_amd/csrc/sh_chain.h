@@ -592,11 +592,20 @@ __device__ __forceinline__ uint32_t pf_rank_sort(ParFillLds &L, uint32_t n, uint
 
 // Folds predecessor j, scoring sc against the anchor, into the anchor's maximum.  false: more than max_skip valid predecessors - the
 // anchor is dirty, no need to see the rest.
+// The second form takes f[j] already loaded (par_fill_tiled issues its loads ahead of the decisions).
 __device__ __forceinline__ bool pf_fold(int32_t sc, const int32_t *f, int32_t j, int32_t max_skip, int32_t &max_f, int32_t &max_j, int32_t &nv)
 {
     if (sc == SH_SC_NONE) return true;
     if (++nv > max_skip) return false;
     const int32_t c = sc + f[j];
+    if (c > max_f) { max_f = c; max_j = j; }
+    return true;
+}
+__device__ __forceinline__ bool pf_fold(int32_t sc, int32_t fj, int32_t j, int32_t max_skip, int32_t &max_f, int32_t &max_j, int32_t &nv)
+{
+    if (sc == SH_SC_NONE) return true;
+    if (++nv > max_skip) return false;
+    const int32_t c = sc + fj;
     if (c > max_f) { max_f = c; max_j = j; }
     return true;
 }
@@ -653,44 +662,58 @@ __device__ inline bool par_fill_block(PX x, PQ q, int32_t *f, int32_t *pt, uint3
 // completely in LDS (its own rank table, all rounds), with the last PFT_H anchors of the tile before it as a halo; f and (p, t = 0) go
 // out once, coalesced.  An anchor whose window is not inside tile + halo is dirty (so is one with PFT_H anchors within max_dist_x behind
 // it: the max_iter cut is not looked at any closer than that; needs max_iter >= PFT_H).  Same contract as par_fill_block.
+// A tile is 12 B per anchor (three blocks' worth fit a CU's LDS): q and f share one word, 16 bits each - q < qlen <= PF_MAX_Q with the
+// cluster-start mark in bit 15; comput_sc gives at most dq less a penalty, so k <= f[i] <= k + q_i, and a k that would not fit declines -
+// and p's slot holds dcs (below) until the anchor's own round writes p.  A look-back step was two dependent LDS round trips (x and q of the
+// predecessor, then f); a scan now loads x and q|f of PFT_B predecessors (one ds_read2 each) ahead of deciding about any of them (indices
+// clamped into the tile; what lies beyond an exit is loaded and dropped) and then takes them in the sequential order, through the same exits.
+// The kernel is bound by the instructions it issues, not by these waits: the batches save a fifth of the scalar bookkeeping.
 #define PFT_T 4096
 #define PFT_H 256
-struct PfTile { uint32_t x[PFT_H + PFT_T], q[PFT_H + PFT_T]; int32_t f[PFT_H + PFT_T]; uint16_t p[PFT_T], perm[PFT_T], dcs[PFT_H + PFT_T]; int32_t wtot[16], carry; };
+#define PFT_B 4
+#define PFT_QMARK 0x8000u
+// a batch's loads stay ahead of the decisions: without it the compiler sinks each load into the branch that uses it
+#define PFT_LOADED(X, QF) _Pragma("unroll") for (int32_t b_ = 0; b_ < PFT_B; ++b_) asm volatile("" : "+v"((X)[b_]), "+v"((QF)[b_]))
+struct PfTile { uint32_t x[PFT_H + PFT_T], qf[PFT_H + PFT_T]; uint16_t p[PFT_T], perm[PFT_T]; int32_t wtot[16], carry; };
+// three of k_giant_top's blocks per CU: a third of the 160 KiB, PfTile with the kernel's other LDS objects (sh_classify.hip asserts the sum)
+#define PFT_LDS_BUDGET (160 * 1024 / 3)
+static_assert(sizeof(PfTile) + sizeof(ParFillLds) <= PFT_LDS_BUDGET, "PfTile: three blocks per CU");
 
 __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int32_t *f, int32_t *pt, uint32_t n, int32_t qlen, const ChainParams &P, uint32_t tid, uint32_t nthr,
                                       ParFillLds &L, PfTile &T, uint32_t g_min = 32768u)
 {
     if (qlen > PF_MAX_Q || n >= 0x7ffffff0u || P.max_iter < PFT_H || nthr < PFT_H || nthr > 1024) return false;
+    if ((int64_t)P.k + PF_MAX_Q > 65535) return false;      // f in 16 bits
     const int32_t mdy = chain_max_dist_y(P, qlen), mdx = (int32_t)chain_max_dist_x(P, qlen);
     // The largest reads of a batch (10^5 anchors of a dense tandem array, hundreds of them inside every window) set the kernel's time however
     // small the batch: for those G = 8 lanes share an anchor, each taking every eighth predecessor (combined as the sequential scan would
     // have decided: largest sum, of equal sums the largest index).  Every lane must then know where its anchor's cluster starts without
     // walking there: dcs = distance to the cluster start, from a block-wide scan of the marks.
     const uint32_t G = n >= g_min ? 8u : 1u, sub = tid & (G - 1u), grp = tid / G, n_grp = nthr / G;
-    const uint32_t lane = tid & 63u, wave = tid >> 6, n_wave = nthr >> 6;
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
     if (tid == 0) L.n_dirty = 0;
     uint32_t h = 0;
     for (uint32_t t0 = 0; t0 < n; t0 += PFT_T) {
         const uint32_t tn = n - t0 < PFT_T ? n - t0 : PFT_T;
         if (tid == 0) T.carry = -1;
-        for (uint32_t k = tid; k < tn; k += nthr) { T.x[h + k] = (uint32_t)x[t0 + k]; T.q[h + k] = q[t0 + k]; }
-        if (G > 1) {      // dcs over halo + tile (an anchor whose cluster starts before the halo counts from index 0: the scan then runs out of halo)
-            __syncthreads();
+        for (uint32_t k = tid; k < tn; k += nthr) { const uint32_t qv = q[t0 + k]; T.x[h + k] = (uint32_t)x[t0 + k]; T.qf[h + k] = (qv & 0x7fffu) | ((qv >> 16) & PFT_QMARK); }
+        if (G > 1) {      // dcs over halo + tile (an anchor whose cluster starts before the halo counts from index 0: the scan then runs out of halo);
+            __syncthreads();      // kept for the tile's anchors only, in p's slots - an anchor's lanes read it before one of them writes p there
             for (uint32_t c0 = 0; c0 < h + tn; c0 += nthr) {
                 const uint32_t k = c0 + tid;
-                const int32_t v = k < h + tn && (T.q[k] >> 31) ? (int32_t)k : -1;
+                const int32_t v = k < h + tn && (T.qf[k] & PFT_QMARK) ? (int32_t)k : -1;
                 int32_t inc = wave_scan_max_incl(v);
                 if (lane == 63) T.wtot[wave] = inc;
                 __syncthreads();
                 int32_t before = T.carry;
                 for (uint32_t w = 0; w < wave; ++w) before = T.wtot[w] > before ? T.wtot[w] : before;
                 inc = inc > before ? inc : before;
-                if (k < h + tn) T.dcs[k] = (uint16_t)(inc < 0 ? k : k - (uint32_t)inc);
+                if (k >= h && k < h + tn) T.p[k - h] = (uint16_t)(inc < 0 ? k : k - (uint32_t)inc);
                 __syncthreads();
                 if (tid == nthr - 1) T.carry = inc;
             }
         }
-        const uint32_t R = pf_rank_sort(L, tn, tid, nthr, [&](uint32_t k) { return T.q[h + k] & 0x7fffffffu; }, [&](uint32_t slot, uint32_t k) { T.perm[slot] = (uint16_t)k; });
+        const uint32_t R = pf_rank_sort(L, tn, tid, nthr, [&](uint32_t k) { return T.qf[h + k] & 0x7fffu; }, [&](uint32_t slot, uint32_t k) { T.perm[slot] = (uint16_t)k; });
         if (R > PF_MAX_RANK) return false;
         for (uint32_t r = 0; r < R; ++r) {
             const uint32_t e = L.start[r + 1];
@@ -698,33 +721,47 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
                 const uint32_t idx = base + grp;
                 const bool on = idx < e;
                 const uint32_t kt = on ? T.perm[idx] : 0u, k = h + kt;
-                const uint32_t qraw = T.q[k], qi = qraw & 0x7fffffffu, xi = T.x[k];
+                const uint32_t qraw = T.qf[k] & 0xffffu, qi = qraw & 0x7fffu, xi = T.x[k];
                 int32_t max_f = P.k, max_j = -1, nv = 0;
                 bool bad = false;
-                if (on && !(qraw >> 31)) {
+                if (on && !(qraw & PFT_QMARK)) {
                     const uint32_t lim = min((uint32_t)mdx, qi + (uint32_t)P.bw);
                     if (sub == 0 && k >= PFT_H && xi - T.x[k - PFT_H] <= (uint32_t)mdx) bad = true;      // a window of PFT_H anchors or more: left to the sequential code
+                    // predecessor j as the sequential scan meets it (x and q|f already loaded); false: the scan ends at j
+                    auto take = [&](int32_t j, uint32_t xj, uint32_t qfj, bool at_mark) -> bool {
+                        if (xi - xj > lim) return false;
+                        const int32_t sc = comput_sc(xi, qi, xj, qfj & 0x7fffu, mdx, mdy, P);
+                        if (!pf_fold(sc, (int32_t)(qfj >> 16), j, P.max_skip, max_f, max_j, nv)) return false;
+                        return !(at_mark && (qfj & PFT_QMARK));
+                    };
+                    uint32_t bx[PFT_B], bqf[PFT_B];
+                    bool stop = false;
                     if (G == 1) {
-                        bool stop = false;
-                        for (int32_t j = (int32_t)k - 1; j >= 0; --j) {
-                            const uint32_t qj = T.q[j], xj = T.x[j];
-                            if (xi - xj > lim) { stop = true; break; }
-                            const int32_t sc = comput_sc(xi, qi, xj, qj & 0x7fffffffu, mdx, mdy, P);
-                            if (!pf_fold(sc, T.f, j, P.max_skip, max_f, max_j, nv)) { stop = true; break; }
-                            if (qj >> 31) { stop = true; break; }
+                        for (int32_t j = (int32_t)k - 1; j >= 0 && !stop; j -= PFT_B) {
+#pragma unroll
+                            for (int32_t b = 0; b < PFT_B; ++b) { const int32_t jb = j - b > 0 ? j - b : 0; bx[b] = T.x[jb]; bqf[b] = T.qf[jb]; }
+                            PFT_LOADED(bx, bqf);
+#pragma unroll
+                            for (int32_t b = 0; b < PFT_B; ++b) {
+                                if (j - b < 0) break;
+                                if (!take(j - b, bx[b], bqf[b], true)) { stop = true; break; }
+                            }
                         }
                         if (!stop && t0 > h) bad = true;      // ran out of halo
                     } else {
-                        const int32_t jmin = (int32_t)k - (int32_t)T.dcs[k];
-                        bool stop = false;
-                        for (int32_t j = (int32_t)k - 1 - (int32_t)sub; j >= jmin; j -= (int32_t)G) {
-                            const uint32_t xj = T.x[j];
-                            if (xi - xj > lim) { stop = true; break; }
-                            const int32_t sc = comput_sc(xi, qi, xj, T.q[j] & 0x7fffffffu, mdx, mdy, P);
-                            if (!pf_fold(sc, T.f, j, P.max_skip, max_f, max_j, nv)) { stop = true; break; }
+                        const int32_t jmin = (int32_t)k - (int32_t)T.p[kt], step = (int32_t)G;      // p[kt]: still dcs
+                        for (int32_t j = (int32_t)k - 1 - (int32_t)sub; j >= jmin && !stop; j -= step * PFT_B) {
+#pragma unroll
+                            for (int32_t b = 0; b < PFT_B; ++b) { const int32_t jb = j - step * b > jmin ? j - step * b : jmin; bx[b] = T.x[jb]; bqf[b] = T.qf[jb]; }
+                            PFT_LOADED(bx, bqf);
+#pragma unroll
+                            for (int32_t b = 0; b < PFT_B; ++b) {
+                                if (j - step * b < jmin) break;
+                                if (!take(j - step * b, bx[b], bqf[b], false)) { stop = true; break; }
+                            }
                         }
                         // the cluster starts before the halo and this lane never met the distance limit
-                        if (!stop && jmin == 0 && t0 > h && !(T.q[0] >> 31)) bad = true;
+                        if (!stop && jmin == 0 && t0 > h && !(T.qf[0] & PFT_QMARK)) bad = true;
                     }
                 }
                 if (G == 8u) {      // uniform: G is.  The eight lanes of an anchor combine over DPP (neighbour, other pair, other quad)
@@ -735,7 +772,7 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
 #undef PF_COMBINE
                 }
                 if (on && sub == 0) {
-                    T.f[k] = max_f; T.p[kt] = (uint16_t)(max_j < 0 ? 0 : (int32_t)k - max_j);
+                    T.qf[k] = qraw | (uint32_t)max_f << 16; T.p[kt] = (uint16_t)(max_j < 0 ? 0 : (int32_t)k - max_j);
                     if (bad || nv > P.max_skip) { const int32_t d = atomicAdd(&L.n_dirty, 1); if (d < PF_DIRTY_CAP) L.dirty[d] = t0 + kt; }
                 }
             }
@@ -744,15 +781,15 @@ __device__ inline bool par_fill_tiled(const uint64_t *x, const uint32_t *q, int3
         }
         for (uint32_t k = tid; k < tn; k += nthr) {
             const uint32_t g = t0 + k, d = T.p[k];
-            f[g] = T.f[h + k];
+            f[g] = (int32_t)(T.qf[h + k] >> 16);
             *(int2 *)(pt + 2 * (size_t)g) = make_int2(d ? (int32_t)(g - d) : -1, 0);
         }
         // the halo of the next tile: the last anchors of this one
         const uint32_t tot = h + tn, nh = tot < PFT_H ? tot : PFT_H;
-        uint32_t hx = 0, hq = 0; int32_t hf = 0;
-        if (tid < nh) { hx = T.x[tot - nh + tid]; hq = T.q[tot - nh + tid]; hf = T.f[tot - nh + tid]; }
+        uint32_t hx = 0, hqf = 0;
+        if (tid < nh) { hx = T.x[tot - nh + tid]; hqf = T.qf[tot - nh + tid]; }
         __syncthreads();
-        if (tid < nh) { T.x[tid] = hx; T.q[tid] = hq; T.f[tid] = hf; }
+        if (tid < nh) { T.x[tid] = hx; T.qf[tid] = hqf; }
         h = nh;
         __syncthreads();
     }

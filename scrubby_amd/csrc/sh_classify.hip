@@ -2401,7 +2401,12 @@ __global__ __launch_bounds__(NTHR) void k_sort_top(K3Args a)
 // The same for the giant reads, after their sort and ahead of k_giant_chain (anchors and DP state in the arena).  Also without
 // ChainSink::best (trace mode) it runs par_fill_block, so that k_giant_chain and k_cluster_dp only have the backtracks left: the read's
 // table entry then carries the mark (qlen bit 31).
-__global__ __launch_bounds__(512) void k_giant_top(K3Args a)
+// Three blocks per CU: 53.4 KB of LDS each (PFT_LDS_BUDGET) and, at 512 threads, 6 waves per SIMD - 80 VGPRs, which the compiler is held to
+// (it wants 88 and spills 7: 32 B of scratch a lane): 171.0 ms a step against 175.6 with two blocks.  256-thread blocks get three resident
+// without the cap and lose as much again on twice the trips through a tile's load, sort and store sweeps and the eight-lane rounds.
+#define GIANT_TOP_NTHR 512
+static_assert(sizeof(ParFillLds) + sizeof(PfTile) + sizeof(long long[18]) + 2 * sizeof(uint32_t[TOPBT_MAX]) + 4 * sizeof(uint32_t) + 64 <= PFT_LDS_BUDGET, "k_giant_top: three blocks per CU");
+__global__ __launch_bounds__(GIANT_TOP_NTHR, 6) void k_giant_top(K3Args a)
 {
     __shared__ ParFillLds s_pf;
     __shared__ PfTile s_tile;
@@ -3874,7 +3879,7 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     }
     // flag-only hand-over (t_mode): the big clusters first (k_cluster_dp), then the small ones against the best score those gave
     const bool two_phase = k.t_mode && k.sink.best != nullptr;
-    if (use_pf) hipLaunchKernelGGL(k_giant_top, dim3(1024), dim3(512), 0, g, k);
+    if (use_pf) hipLaunchKernelGGL(k_giant_top, dim3(1024), dim3(GIANT_TOP_NTHR), 0, g, k);
     hipLaunchKernelGGL(k_giant_chain, dim3(1024), dim3(512), 0, g, k, two_phase ? 0 : -1);
     if (side && k.cl_lds) {      // the LDS classes feed k_cluster_dp's queue too - all of them: the 512 class runs on the main stream
         SH_HIP(hipEventRecord(c->evx[1], c->sx[0])); SH_HIP(hipStreamWaitEvent(g, c->evx[1], 0));
