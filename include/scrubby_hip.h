@@ -699,6 +699,14 @@ typedef struct sh_dbg_chain_case {
 typedef struct sh_dbg_chain_result { int32_t ret, bt_ret, n_u, best, n_emit, pad; } sh_dbg_chain_result;
 sh_status sh_dbg_chain(int32_t device, const uint64_t *x, const uint32_t *q, uint64_t n_total, const sh_dbg_chain_case *cases, int32_t n_cases,
                        const int32_t *f_in, const int32_t *p_in, sh_dbg_chain_result *out, int32_t *f, int32_t *p, int32_t *t, int32_t *chains);
+/* Test aid: the stable block sort of the repeat path (block_merge_sort in csrc/sh_wave.h: the LDS sort classes, the giant reads' tiles and the
+ * group probe share it), called directly (csrc/sh_dbg_chain.hip; tests/test_block_sort_gpu.py compares with numpy's stable argsort).  One block
+ * of nthr threads (64, 128, 256 or 512) per case sorts the n pairs (x[off + i], q[off + i]), 1 <= n <= 4096, by x in LDS, equal x in input
+ * order, and stores them at the same place in out_x / out_q; one launch per thread count.  Pairs no case covers come back as (0, ~0u).  Another
+ * n or thread count, or a case outside the arrays: SH_ERR_BAD_ARG before any launch. */
+typedef struct sh_dbg_sort_case { uint64_t off; int32_t n, nthr; } sh_dbg_sort_case;
+sh_status sh_dbg_block_sort(int32_t device, const uint64_t *x, const uint32_t *q, uint64_t n_total, const sh_dbg_sort_case *cases, int32_t n_cases,
+                            uint64_t *out_x, uint32_t *out_q);
 
 /* Test aid: the three minimizer state machines of csrc/sh_sketch.h, called directly (csrc/sh_dbg_sketch.hip; tests/test_sketch_gpu.py compares
  * them with the oracle's mmo_sketch, integers only).  One lane per sequence, one launch per call.  bases / offsets: host arrays, sequence i is

@@ -1000,23 +1000,6 @@ __global__ void k_pair_swap(Counters *ctr)
     ctr->n_big_defer[0] = 0;
 }
 
-// stable sort of the first n lanes' (x, q) by x: rank by comparison with every broadcast key, then push
-__device__ inline void wave_rank_sort(uint64_t &x, uint32_t &q, uint32_t n, uint32_t lane)
-{
-    uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
-    uint32_t rank = 0;
-    for (uint32_t b = 0; b < n; ++b) {
-        uint64_t xb = (uint64_t)rdlane(xh, b) << 32 | rdlane(xl, b);
-        rank += (xb < x) || (xb == x && b < lane);
-    }
-    if (lane >= n) rank = lane;
-    int addr = (int)(rank * 4);
-    xl = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)xl);
-    xh = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)xh);
-    q = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)q);
-    x = (uint64_t)xh << 32 | xl;
-}
-
 // SH_F_CIGAR, flag-only (ChainParams::ext_*): the cluster(s) around a read's singleton seeds, alone.
 // One wave per read of the repeat path's list, one lane per seed.  A read with unique seeds has its true locus there; the other
 // occurrences of its repeated seeds - hundreds of loci - need not be expanded, sorted and chained if they cannot matter:
@@ -2072,53 +2055,6 @@ __global__ __launch_bounds__(256) void k_lr_locus(K3Args a, int lc)
         __syncthreads();
     }
     if (tid == 0 && st_in) { atomicAdd(&a.ctr->lr_locus_in, st_in); atomicAdd(&a.ctr->lr_locus_kept, st_kept); if (st_reads) atomicAdd(&a.ctr->lr_locus_reads, st_reads); }
-}
-
-// stable block merge sort: 64-element tiles ranked in registers (one tile per wave at a time), then merge-path
-// rounds between (sx,sq) and (dx,dq), C outputs per thread and step.  Returns true if the result ended in the
-// second buffer.  Every thread of the block must call.
-template <class PX, class PQ>
-__device__ inline bool block_merge_sort(PX sx, PQ sq, PX dx, PQ dq, uint32_t n)
-{
-    const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
-    for (uint32_t base = wave * 64; base < n; base += nwave * 64) {
-        const uint32_t cnt = n - base < 64 ? n - base : 64;
-        uint64_t x = lane < cnt ? sx[base + lane] : ~0ull;
-        uint32_t q = lane < cnt ? sq[base + lane] : 0u;
-        uint64_t xp = wave_shr1_u64(x, 0ull);
-        if (__ballot(lane > 0 && lane < cnt && x < xp) != 0) {
-            wave_rank_sort(x, q, cnt, lane);
-            if (lane < cnt) { sx[base + lane] = x; sq[base + lane] = q; }
-        }
-    }
-    __syncthreads();
-    const uint32_t C = n >= 16 * nthr ? 16 : (n >= 8 * nthr ? 8 : 4);     // outputs per thread and step (divides 128)
-    const uint32_t n_chunks = (n + C - 1) / C;
-    bool flipped = false;
-    for (uint32_t width = 64; width < n; width <<= 1) {
-        for (uint32_t c = tid; c < n_chunks; c += nthr) {
-            const uint32_t o0 = c * C, o1 = o0 + C < n ? o0 + C : n;
-            const uint32_t pb = o0 / (2 * width) * (2 * width);
-            const uint32_t L0 = pb, L1 = pb + width < n ? pb + width : n, R1 = pb + 2 * width < n ? pb + 2 * width : n;
-            const uint32_t lenL = L1 - L0, lenR = R1 - L1, d = o0 - pb;
-            uint32_t lo = d > lenR ? d - lenR : 0, hi = d < lenL ? d : lenL;
-            while (lo < hi) {
-                uint32_t mid = (lo + hi) >> 1;
-                if (sx[L0 + mid] <= sx[L1 + (d - 1 - mid)]) lo = mid + 1; else hi = mid;
-            }
-            uint32_t ia = L0 + lo, ib = L1 + (d - lo);
-            uint64_t va = ia < L1 ? sx[ia] : ~0ull, vb = ib < R1 ? sx[ib] : ~0ull;
-            for (uint32_t o = o0; o < o1; ++o) {
-                const bool takeL = ia < L1 && (ib >= R1 || va <= vb);
-                if (takeL) { dx[o] = va; dq[o] = sq[ia]; ++ia; va = ia < L1 ? sx[ia] : ~0ull; }
-                else { dx[o] = vb; dq[o] = sq[ib]; ++ib; vb = ib < R1 ? sx[ib] : ~0ull; }
-            }
-        }
-        __syncthreads();
-        PX tx = sx; sx = dx; dx = tx; PQ tq = sq; sq = dq; dq = tq;
-        flipped = !flipped;
-    }
-    return flipped;
 }
 
 // block reduction of the per-thread chain results of one read; thread 0 stores them
@@ -3452,7 +3388,7 @@ struct sh_ctx {
     int side_pick[2] = {0, 1};       // long reads: the side streams of the giants' launch and of the follower (pick_side_streams)
     hipStream_t side_probed = nullptr; bool side_probed_done = false;
     int par = 1;                     // CtxSwitches::streams
-    hipEvent_t evx[8] = {};
+    hipEvent_t evx[14] = {};         // 8..12: behind k_sort_top of each LDS class, 13: the end of the leftovers' stream (big_pass)
 };
 
 static void fill_chain_params(const sh_opts &o, const CtxSwitches &sw, int32_t mid_occ, ChainParams &P)
@@ -3842,11 +3778,15 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     }
     // the sort classes run one after the other.  Side by side (streams sx[0..2]) measured 9 % slower when they carried the whole repeat
     // path (they fight for LDS); that mode predates k_group_probe, which the class-4 and giant kernels must follow: it stays off.
+    // That holds for the heavy kernels.  What k_sort_top leaves to k_sort_lds is a few reads per class (about 10 k of 730 k a step of the
+    // bench): a kernel that is all tail, one or two reads in a busy block while the rest of the device waits.  Those five launches go aside
+    // (`aside` below), the k_sort_top kernels stay in order on the caller's stream.
     const int64_t side_env = c->cs.side;
     // small batches (an eighth of the bench's records on each of 8 GPUs): every class kernel is mostly tail, side by side they overlap:
-    // 39.3 -> 36.6 ms at 2.5 M records; at 20 M it costs 2 % (SCRUBBY_HIP_SIDE=0 / 1 forces either)
+    // 39.3 -> 36.6 ms at 2.5 M records; at 20 M it costs 2 % (SCRUBBY_HIP_SIDE=0 / 1 forces either; 0 also keeps the leftovers on
+    // the caller's stream, the order before they went aside; 2: no class side by side, the leftovers aside whatever the batch size)
     const bool gp = k.flag_only && k.P.flag_stop != INT32_MAX && !(k.dbg & DBG_NO_GROUP_PROBE);      // k_group_probe runs (chain-level decision): the class-4 and giant kernels must follow it
-    const bool side = side_env > 0 || (side_env < 0 && !gp && c->cur_reads <= 3000000ull);
+    const bool side = side_env == 1 || (side_env < 0 && !gp && c->cur_reads <= 3000000ull);
     if (side) { sh_status es = ensure_side_streams(c, 0, 2); if (es != SH_OK) return es; }
     hipStream_t s0 = side ? c->sx[0] : s, s1 = side ? c->sx[1] : s, g = side ? c->sx[2] : s;
     const bool use_pf = (k.emit || !k.flag_only) && !(k.dbg & DBG_NO_PARFILL);
@@ -3860,17 +3800,44 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
         hipLaunchKernelGGL(k_group_probe, dim3(256 * 3), dim3(256), 0, s, k, 4);
         hipLaunchKernelGGL(k_group_probe, dim3(256 * 3), dim3(256), 0, s, k, (int)SORT_CLS_GIANT);
     }
-    // each class: the read-level pass (k_sort_top), then the cluster path for what it left (k_sort_lds), on the class's stream
+    // The leftovers aside (wherever the classes are not side by side; SCRUBBY_HIP_SIDE=0: not at all): k_sort_lds<c> only needs k_sort_top<c> (which empties the table entries of the
+    // reads it settles) and nothing before k_finalize needs k_sort_lds - unless it queues clusters for k_cluster_dp (cl_lds).  So each goes to
+    // ONE side stream, behind an event recorded after its k_sort_top, and runs beside k_sort_top<c + 1>, the last one beside the giant kernels;
+    // the stream is joined ahead of k_finalize.  Reads are disjoint between the kernels, the sink's cursors, best[] and the sh_* counters are
+    // atomics (K2 on sx[3] writes them concurrently as it is), acc_nu / acc_best are per read.  With K2 that makes three streams at work.
+    const bool aside = use_top && !side && !k.cl_lds && side_env != 0;
+    hipStream_t sa = s;
+    if (aside) {      // a stream that runs BESIDE the caller's, not one that shares its hardware queue
+        sh_status ps = pick_side_streams(c, s);
+        if (ps != SH_OK) return ps;
+        sa = c->sx[c->side_pick[0]];
+    }
+    auto lds_stream = [&](int cls, hipStream_t own, hipStream_t &out) -> sh_status {      // where k_sort_lds of the class goes, ordered behind its k_sort_top
+        out = own;
+        if (!aside) return SH_OK;
+        SH_HIP(hipEventRecord(c->evx[8 + cls], own));
+        SH_HIP(hipStreamWaitEvent(sa, c->evx[8 + cls], 0));
+        out = sa;
+        return SH_OK;
+    };
+    hipStream_t sl = s;
+    sh_status ls = SH_OK;
+    // each class: the read-level pass (k_sort_top), then the cluster path for what it left (k_sort_lds), on the class's stream or aside
     if (use_top) hipLaunchKernelGGL((k_sort_top<256, 0, 64>), dim3(grid * 2), dim3(64), 0, s, k);
-    hipLaunchKernelGGL((k_sort_lds<256, 0, 64>), dim3(grid * 2), dim3(64), 0, s, k);
+    if ((ls = lds_stream(0, s, sl)) != SH_OK) return ls;
+    hipLaunchKernelGGL((k_sort_lds<256, 0, 64>), dim3(grid * 2), dim3(64), 0, sl, k);
     if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_A, 1, 128>), dim3(grid * 2), dim3(128), 0, s, k);
-    hipLaunchKernelGGL((k_sort_lds<SORT_LDS_A, 1, 128>), dim3(grid * 2), dim3(128), 0, s, k);
+    if ((ls = lds_stream(1, s, sl)) != SH_OK) return ls;
+    hipLaunchKernelGGL((k_sort_lds<SORT_LDS_A, 1, 128>), dim3(grid * 2), dim3(128), 0, sl, k);
     if (use_top) hipLaunchKernelGGL((k_sort_top<1024, 2, 256>), dim3(256 * 6), dim3(256), 0, s0, k);
-    hipLaunchKernelGGL((k_sort_lds<1024, 2, 256>), dim3(256 * 6), dim3(256), 0, s0, k);
+    if ((ls = lds_stream(2, s0, sl)) != SH_OK) return ls;
+    hipLaunchKernelGGL((k_sort_lds<1024, 2, 256>), dim3(256 * 6), dim3(256), 0, sl, k);
     if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_B, 3, 256>), dim3(256 * 3), dim3(256), 0, s0, k);
-    hipLaunchKernelGGL((k_sort_lds<SORT_LDS_B, 3, 256>), dim3(256 * 3), dim3(256), 0, s0, k);
+    if ((ls = lds_stream(3, s0, sl)) != SH_OK) return ls;
+    hipLaunchKernelGGL((k_sort_lds<SORT_LDS_B, 3, 256>), dim3(256 * 3), dim3(256), 0, sl, k);
     if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_C, 4, 512>), dim3(256), dim3(512), 0, s1, k);
-    hipLaunchKernelGGL((k_sort_lds<SORT_LDS_C, 4, 512>), dim3(256), dim3(512), 0, s1, k);
+    if ((ls = lds_stream(4, s1, sl)) != SH_OK) return ls;
+    hipLaunchKernelGGL((k_sort_lds<SORT_LDS_C, 4, 512>), dim3(256), dim3(512), 0, sl, k);
     hipLaunchKernelGGL(k_giant_scan, dim3(1), dim3(1024), 0, g, k);
     hipLaunchKernelGGL(k_giant_chunksort, dim3(256 * 3), dim3(256), 0, g, k);
     for (uint32_t pass = 0; pass < (k.giant_fanin == 4 ? 4u : 8u); ++pass) {      // run widths GT, 4 GT, ... (fan-in 2: GT << pass): up to 2^19 anchors per read
@@ -3892,6 +3859,7 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
         hipLaunchKernelGGL(k_giant_chain, dim3(1024), dim3(512), 0, g, k, 1);
     }
     if (side) for (int i = 0; i < 3; ++i) { SH_HIP(hipEventRecord(c->evx[1 + i], c->sx[i])); SH_HIP(hipStreamWaitEvent(s, c->evx[1 + i], 0)); }
+    if (aside) { SH_HIP(hipEventRecord(c->evx[13], sa)); SH_HIP(hipStreamWaitEvent(s, c->evx[13], 0)); }
     hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, s, k);
     return SH_OK;
 }

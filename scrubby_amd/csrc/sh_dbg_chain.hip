@@ -265,3 +265,69 @@ extern "C" sh_status sh_dbg_chain(int32_t device, const uint64_t *x, const uint3
     hipFree(d_p2); hipFree(d_t2); hipFree(d_z); hipFree(d_of); hipFree(d_op); hipFree(d_ot); hipFree(d_ch);
     return st;
 }
+
+// ---- the block sort of the repeat path (block_merge_sort, sh_wave.h), called directly (tests/test_block_sort_gpu.py) ----
+// One block per case with the LDS buffers of k_sort_lds<SORT_LDS_C>: load, sort, store whichever buffer the result ended in.
+#define DBGS_MAX_N 4096               // SORT_LDS_C
+
+struct DbgSortBufs { const sh_dbg_sort_case *cases; const uint32_t *order; const uint64_t *x; const uint32_t *q; uint64_t *ox; uint32_t *oq; };
+
+template <int NTHR>
+__global__ void __launch_bounds__(NTHR) k_dbg_block_sort(DbgSortBufs B)
+{
+    __shared__ uint64_t s_x[2][DBGS_MAX_N];
+    __shared__ uint32_t s_q[2][DBGS_MAX_N];
+    const sh_dbg_sort_case c = B.cases[B.order[blockIdx.x]];
+    const uint32_t tid = threadIdx.x, n = (uint32_t)c.n;      // 1 <= n <= DBGS_MAX_N: checked before the launch
+    for (uint32_t i = tid; i < n; i += NTHR) { s_x[0][i] = B.x[c.off + i]; s_q[0][i] = B.q[c.off + i]; }
+    __syncthreads();
+    const bool fl = block_merge_sort(&s_x[0][0], &s_q[0][0], &s_x[1][0], &s_q[1][0], n);
+    const uint64_t *rx = fl ? s_x[1] : s_x[0]; const uint32_t *rq = fl ? s_q[1] : s_q[0];
+    for (uint32_t i = tid; i < n; i += NTHR) { B.ox[c.off + i] = rx[i]; B.oq[c.off + i] = rq[i]; }
+}
+
+extern "C" sh_status sh_dbg_block_sort(int32_t device, const uint64_t *x, const uint32_t *q, uint64_t n_total, const sh_dbg_sort_case *cases, int32_t n_cases,
+                                       uint64_t *out_x, uint32_t *out_q)
+{
+    SH_CHECK(x && q && cases && out_x && out_q && n_cases > 0 && n_cases <= DBGC_MAX_CASES && n_total > 0, SH_ERR_BAD_ARG, "sh_dbg_block_sort: bad argument");
+    static const int32_t nthr_of[4] = {64, 128, 256, 512};
+    std::vector<uint32_t> order[4];
+    for (int32_t i = 0; i < n_cases; ++i) {
+        const sh_dbg_sort_case &c = cases[i];
+        SH_CHECK(c.n >= 1 && c.n <= DBGS_MAX_N && c.off <= n_total && (uint64_t)c.n <= n_total - c.off, SH_ERR_BAD_ARG, "sh_dbg_block_sort: case %d: 1..%d pairs inside the arrays, not %d at %llu", i, DBGS_MAX_N, c.n, (unsigned long long)c.off);
+        int v = 0;
+        while (v < 4 && nthr_of[v] != c.nthr) ++v;
+        SH_CHECK(v < 4, SH_ERR_BAD_ARG, "sh_dbg_block_sort: case %d: 64, 128, 256 or 512 threads, not %d", i, c.nthr);
+        order[v].push_back((uint32_t)i);
+    }
+    SH_HIP(hipSetDevice(device));
+    uint64_t *d_x = nullptr, *d_ox = nullptr; uint32_t *d_q = nullptr, *d_oq = nullptr, *d_order = nullptr; sh_dbg_sort_case *d_cases = nullptr;
+    auto run = [&]() -> sh_status {
+        const size_t nt = (size_t)n_total;
+        SH_HIP(hipMalloc(&d_x, 8 * nt)); SH_HIP(hipMalloc(&d_ox, 8 * nt)); SH_HIP(hipMalloc(&d_q, 4 * nt)); SH_HIP(hipMalloc(&d_oq, 4 * nt));
+        SH_HIP(hipMalloc(&d_order, 4 * (size_t)n_cases)); SH_HIP(hipMalloc(&d_cases, sizeof(sh_dbg_sort_case) * (size_t)n_cases));
+        SH_HIP(hipMemcpy(d_x, x, 8 * nt, hipMemcpyHostToDevice)); SH_HIP(hipMemcpy(d_q, q, 4 * nt, hipMemcpyHostToDevice));
+        SH_HIP(hipMemcpy(d_cases, cases, sizeof(sh_dbg_sort_case) * (size_t)n_cases, hipMemcpyHostToDevice));
+        SH_HIP(hipMemset(d_ox, 0, 8 * nt)); SH_HIP(hipMemset(d_oq, 0xff, 4 * nt));      // pairs no case covers come back as (0, ~0u)
+        DbgSortBufs B{d_cases, nullptr, d_x, d_q, d_ox, d_oq};
+        uint32_t at = 0;
+        for (int v = 0; v < 4; ++v) {      // one launch per thread count
+            const uint32_t m = (uint32_t)order[v].size();
+            if (!m) continue;
+            SH_HIP(hipMemcpy(d_order + at, order[v].data(), 4 * (size_t)m, hipMemcpyHostToDevice));
+            B.order = d_order + at;
+            if (v == 0) hipLaunchKernelGGL(k_dbg_block_sort<64>, dim3(m), dim3(64), 0, 0, B);
+            else if (v == 1) hipLaunchKernelGGL(k_dbg_block_sort<128>, dim3(m), dim3(128), 0, 0, B);
+            else if (v == 2) hipLaunchKernelGGL(k_dbg_block_sort<256>, dim3(m), dim3(256), 0, 0, B);
+            else hipLaunchKernelGGL(k_dbg_block_sort<512>, dim3(m), dim3(512), 0, 0, B);
+            SH_HIP(hipGetLastError());
+            at += m;
+        }
+        SH_HIP(hipDeviceSynchronize());
+        SH_HIP(hipMemcpy(out_x, d_ox, 8 * nt, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(out_q, d_oq, 4 * nt, hipMemcpyDeviceToHost));
+        return SH_OK;
+    };
+    const sh_status st = run();
+    hipFree(d_x); hipFree(d_ox); hipFree(d_q); hipFree(d_oq); hipFree(d_order); hipFree(d_cases);
+    return st;
+}

@@ -82,7 +82,7 @@ static const SwDef<CallSwitches> SW_CALL[] = {
     {"SCRUBBY_HIP_GIANT_BINS_DOWN", 'I', 0, SW_ANY, &CallSwitches::giant_bins_down},           // A/B: size bins more that go to the giants' launch
     {"SCRUBBY_HIP_GIANT_WAVES", 'I', SW_UNSET, 1, INT64_MAX, &CallSwitches::giant_waves},      // A/B: waves of the giants' launch (default 64)
     {"SCRUBBY_HIP_SIDE_PICK", '2', -1, SW_ANY, &CallSwitches::side_pick},                      // pins the side streams of the giants' launch and the follower, no probe
-    {"SCRUBBY_HIP_SIDE", 'I', -1, SW_ANY, &CallSwitches::side},                                // 1 / 0: the sort classes side by side, or never (default: by chunk size)
+    {"SCRUBBY_HIP_SIDE", 'I', -1, SW_ANY, &CallSwitches::side},                                // 1 / 0: the sort classes side by side, or nothing of them beside the caller's stream; 2: only the leftover k_sort_lds kernels aside (default: by chunk size, 1 or 2)
     {"SCRUBBY_HIP_K2_LATE", 'I', -1, SW_ANY, &CallSwitches::k2_late},                          // 1: K2 starts beside the second pass's giant kernels
     {"SCRUBBY_HIP_NO_COOP", 'P', 0, SW_ANY, &CallSwitches::no_coop},                           // A/B: no long join shared among waves (lr_coop_fill)
     {"SCRUBBY_HIP_GIANTS_PLAIN", 'P', 0, SW_ANY, &CallSwitches::giants_plain},                 // A/B: the giants on the plain instance of the chains kernel, and no lr_coop_fill

@@ -78,3 +78,69 @@ __device__ inline int32_t wave_bcast(int32_t v, int l) { return __builtin_amdgcn
 __device__ inline unsigned long long wave_bcast_u64(unsigned long long v, int l) { return wave_readlane_u64(v, __builtin_amdgcn_readfirstlane(l)); }
 // lane l receives lane l-1's 64-bit value, lane 0 receives `fill`
 __device__ inline unsigned long long wave_shr1_u64(unsigned long long v, unsigned long long fill) { return dpp_mov_u64<0x138, 0xf>(fill, v); }
+
+// ---- the repeat path's sorts (k_sort_top / k_sort_lds, k_giant_chunksort, group_probe; sh_dbg_block_sort calls the block sort directly) ----
+
+// stable sort of the first n lanes' (x, q) by x: rank by comparison with every broadcast key, then push
+__device__ inline void wave_rank_sort(uint64_t &x, uint32_t &q, uint32_t n, uint32_t lane)
+{
+    uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+    uint32_t rank = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        uint64_t xb = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)xh, (int)b) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)xl, (int)b);
+        rank += (xb < x) || (xb == x && b < lane);
+    }
+    if (lane >= n) rank = lane;
+    int addr = (int)(rank * 4);
+    xl = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)xl);
+    xh = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)xh);
+    q = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)q);
+    x = (uint64_t)xh << 32 | xl;
+}
+
+// stable block merge sort: 64-element tiles ranked in registers (one tile per wave at a time), then merge-path
+// rounds between (sx,sq) and (dx,dq), C outputs per thread and step.  Returns true if the result ended in the
+// second buffer.  Every thread of the block must call.
+template <class PX, class PQ>
+__device__ inline bool block_merge_sort(PX sx, PQ sq, PX dx, PQ dq, uint32_t n)
+{
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
+    for (uint32_t base = wave * 64; base < n; base += nwave * 64) {
+        const uint32_t cnt = n - base < 64 ? n - base : 64;
+        uint64_t x = lane < cnt ? sx[base + lane] : ~0ull;
+        uint32_t q = lane < cnt ? sq[base + lane] : 0u;
+        uint64_t xp = wave_shr1_u64(x, 0ull);
+        if (__ballot(lane > 0 && lane < cnt && x < xp) != 0) {
+            wave_rank_sort(x, q, cnt, lane);
+            if (lane < cnt) { sx[base + lane] = x; sq[base + lane] = q; }
+        }
+    }
+    __syncthreads();
+    const uint32_t C = n >= 16 * nthr ? 16 : (n >= 8 * nthr ? 8 : 4);     // outputs per thread and step (divides 128)
+    const uint32_t n_chunks = (n + C - 1) / C;
+    bool flipped = false;
+    for (uint32_t width = 64; width < n; width <<= 1) {
+        for (uint32_t c = tid; c < n_chunks; c += nthr) {
+            const uint32_t o0 = c * C, o1 = o0 + C < n ? o0 + C : n;
+            const uint32_t pb = o0 / (2 * width) * (2 * width);
+            const uint32_t L0 = pb, L1 = pb + width < n ? pb + width : n, R1 = pb + 2 * width < n ? pb + 2 * width : n;
+            const uint32_t lenL = L1 - L0, lenR = R1 - L1, d = o0 - pb;
+            uint32_t lo = d > lenR ? d - lenR : 0, hi = d < lenL ? d : lenL;
+            while (lo < hi) {
+                uint32_t mid = (lo + hi) >> 1;
+                if (sx[L0 + mid] <= sx[L1 + (d - 1 - mid)]) lo = mid + 1; else hi = mid;
+            }
+            uint32_t ia = L0 + lo, ib = L1 + (d - lo);
+            uint64_t va = ia < L1 ? sx[ia] : ~0ull, vb = ib < R1 ? sx[ib] : ~0ull;
+            for (uint32_t o = o0; o < o1; ++o) {
+                const bool takeL = ia < L1 && (ib >= R1 || va <= vb);
+                if (takeL) { dx[o] = va; dq[o] = sq[ia]; ++ia; va = ia < L1 ? sx[ia] : ~0ull; }
+                else { dx[o] = vb; dq[o] = sq[ib]; ++ib; vb = ib < R1 ? sx[ib] : ~0ull; }
+            }
+        }
+        __syncthreads();
+        PX tx = sx; sx = dx; dx = tx; PQ tq = sq; sq = dq; dq = tq;
+        flipped = !flipped;
+    }
+    return flipped;
+}
