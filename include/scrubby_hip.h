@@ -79,6 +79,9 @@ typedef struct sh_opts {
     float   rmq_rescue_ratio;
 } sh_opts;
 #define SH_F_CIGAR 1
+/* A/B and tests: k_expand writes the anchors of every repeat-path read to the arena and the sort kernels read them back, instead of
+ * building them in the LDS sort buffer of the kernel that sorts them (late anchors).  Results do not depend on it. */
+#define SH_F_NO_LATE_ANCHORS 2
 
 /* Per-read decision trace (optional output; used by the parity tests). */
 typedef struct sh_trace {
@@ -136,6 +139,8 @@ typedef struct sh_stats {
     uint64_t n_rmq_open;       /* ... reads that met such a tie and kept the scan's choice (smallest index): 0 by default since round 5 (every tied read takes the tree); only with SCRUBBY_HIP_RMQ_EXACT_MAX = N >= 0, for reads of more than N chain anchors */
     uint64_t n_ext_ondemand;   /* reads beyond the extension stage's prepared working-memory sizes, redone with memory allocated for them (visits, both kernels) */
     uint64_t n_lc_filtered;    /* SH_F_CIGAR flag-only, counted with SCRUBBY_HIP_DBG & 16 only: reads k_local_cluster decided although a seed of theirs lies above mid_occ (part of n_ext_shortcut) */
+    uint64_t n_late_reads;     /* table entries of the sort classes whose anchors the sort kernels build themselves (late anchors; 0 with SH_F_NO_LATE_ANCHORS) */
+    uint64_t n_deferred;       /* times a repeat-path read found no arena room and was put off to the pass's next iteration */
 } sh_stats;
 
 typedef struct sh_index sh_index;
@@ -707,6 +712,18 @@ sh_status sh_dbg_chain(int32_t device, const uint64_t *x, const uint32_t *q, uin
 typedef struct sh_dbg_sort_case { uint64_t off; int32_t n, nthr; } sh_dbg_sort_case;
 sh_status sh_dbg_block_sort(int32_t device, const uint64_t *x, const uint32_t *q, uint64_t n_total, const sh_dbg_sort_case *cases, int32_t n_cases,
                             uint64_t *out_x, uint32_t *out_q);
+/* Test aid: stage_anchors of csrc/sh_chain.h - the anchors of a short read built in the LDS sort buffer of the kernel that sorts them - called
+ * directly (csrc/sh_dbg_chain.hip; tests/test_stage_anchors_gpu.py).  records: 16-byte seed records as four u32 (.x,.y = position word or
+ * slot << 28 | n, .z = occurrences, .w = qpos << 1 | strand); positions: the occurrence lists.  Case i is a read of n_seed (1..64) records from
+ * rec_off with qlen bases and the range [c0, c0 + m), 1 <= m <= 4096, of its anchors in generation order, staged by one block of nthr threads
+ * (64, 128, 256 or 512) into out_x / out_q [out_off, out_off + m); ref_x / ref_q get the same range from a plain loop of one thread over the
+ * seeds seed_filter keeps (make_anchor per occurrence), total[i] the read's anchor count.  The filter is the occurrence cut at max_occ with
+ * mm_seed_select's streaks (occ_dist, max_max_occ; occ_dist = 0: the plain cut).  A range that reaches past total[i] is not staged; pairs no
+ * case covers come back as (0, ~0u).  A case or an occurrence list outside its array: SH_ERR_BAD_ARG before any launch. */
+typedef struct sh_dbg_stage_case { uint64_t rec_off, out_off; int32_t n_seed, qlen, nthr, pad; uint32_t c0, m; } sh_dbg_stage_case;
+sh_status sh_dbg_stage_anchors(int32_t device, const uint32_t *records, uint64_t n_records, const uint64_t *positions, uint64_t n_positions,
+                               int32_t k, int32_t max_occ, int32_t max_max_occ, int32_t occ_dist, const sh_dbg_stage_case *cases, int32_t n_cases,
+                               uint64_t n_out, uint64_t *out_x, uint32_t *out_q, uint64_t *ref_x, uint32_t *ref_q, uint32_t *total);
 
 /* Test aid: the three minimizer state machines of csrc/sh_sketch.h, called directly (csrc/sh_dbg_sketch.hip; tests/test_sketch_gpu.py compares
  * them with the oracle's mmo_sketch, integers only).  One lane per sequence, one launch per call.  bases / offsets: host arrays, sequence i is

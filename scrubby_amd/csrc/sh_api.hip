@@ -207,7 +207,7 @@ extern "C" sh_status sh_classify_batch(const sh_index *idx, const sh_opts *opts,
                 stats->n_ext_fallback += ps.n_ext_fallback; stats->ms_ext_fallback += ps.ms_ext_fallback; stats->n_ext_unresolved += ps.n_ext_unresolved; stats->n_rmq_rechained += ps.n_rmq_rechained; stats->n_rmq_tied += ps.n_rmq_tied;
                 stats->n_dp_parallel += ps.n_dp_parallel; stats->n_dp_dirty += ps.n_dp_dirty; stats->n_top_settled += ps.n_top_settled;
                 stats->n_locus_reads += ps.n_locus_reads; stats->n_locus_redone += ps.n_locus_redone; stats->n_rmq_exact += ps.n_rmq_exact; stats->n_ext_ondemand += ps.n_ext_ondemand; stats->n_rmq_open += ps.n_rmq_open;
-                stats->n_lc_filtered += ps.n_lc_filtered;
+                stats->n_lc_filtered += ps.n_lc_filtered; stats->n_late_reads += ps.n_late_reads; stats->n_deferred += ps.n_deferred;
             }
         }
     });

@@ -199,6 +199,104 @@ __device__ inline void make_anchor(uint64_t r, uint32_t qposz, int32_t qlen, int
     }
 }
 
+// The occurrence filter of seed tile t of a read, one seed per lane of ONE wave (every lane calls): mm_seed_select's streak rule by ballots
+// where a streak can keep a seed, the plain cut otherwise.  my_n = anchors this lane's seed contributes (0: filtered or absent).
+// general_mt: the streaks were decided across seed tiles beforehand and sit in bit 31 of .z (k_expand<true>'s select_multi_tile).
+__device__ inline void seed_tile_filter(const uint4 *recb, uint32_t n_seed, int32_t qlen, int32_t max_occ, const ChainParams &P, bool general_mt,
+                                        uint32_t t, uint32_t lane, uint4 &rec, uint32_t &my_n, bool &flt, bool &have)
+{
+    const bool plain_cut = !(P.occ_dist > 0 && P.max_max_occ > max_occ);
+    const uint32_t n_st = (n_seed + 63) / 64;
+    const uint32_t sidx = t * 64 + lane;
+    have = sidx < n_seed;
+    rec = have ? recb[sidx] : make_uint4(0, 0, 0, 0);
+    const uint32_t occ = rec.z & SH_REC_OCC_MASK, qposz = rec.w;
+    const bool high = have && occ > (uint32_t)max_occ;
+    flt = false;
+    if (plain_cut) flt = high;
+    else if (general_mt) flt = (rec.z >> 31) != 0;
+    else if (n_st > 1) flt = high && n_seed >= 2;      // the caller made sure that no streak keeps a seed (max_high_occ == 0)
+    else {
+        const uint64_t hm = __ballot(high);
+        if (n_seed >= 2 && hm != 0) {
+            const uint64_t low = __ballot(have && !high);
+            const uint64_t below = low & ((1ULL << lane) - 1);
+            const uint64_t above = lane >= 63 ? 0 : low & ~((2ULL << lane) - 1);
+            const int32_t last0 = below ? 63 - __clzll((unsigned long long)below) : -1;
+            const int32_t nxt = above ? __ffsll((unsigned long long)above) - 1 : (int32_t)n_seed;
+            const uint32_t qp_last = (uint32_t)__shfl((int)qposz, last0 < 0 ? 0 : last0);
+            const uint32_t qp_next = (uint32_t)__shfl((int)qposz, nxt >= (int32_t)n_seed ? 0 : nxt);
+            const int32_t ps = last0 < 0 ? 0 : (int32_t)(qp_last >> 1);
+            const int32_t pe = nxt >= (int32_t)n_seed ? qlen : (int32_t)(qp_next >> 1);
+            int32_t od = P.occ_dist;
+            asm volatile("" : "+v"(od));      // the divisor's reciprocal is worked out here, not ahead of the caller's loop over its reads (registers held across the sort kernels' peak)
+            int32_t mho = (int32_t)((double)(pe - ps) / (double)od + .499);
+            if (mho > 128) mho = 128;
+            int32_t rank = 0;
+            if (__ballot(high && mho > 0) != 0) {
+                for (uint32_t u = 0; u < n_seed; ++u) {
+                    uint32_t ot = rdlane(occ, u);
+                    bool in = (int32_t)u > last0 && (int32_t)u < nxt;
+                    rank += in && (ot < occ || (ot == occ && u < lane));
+                }
+            }
+            if (high) {
+                flt = !(mho > 0 && rank < mho);
+                if (occ > (uint32_t)P.max_max_occ) flt = true;
+            }
+        }
+    }
+    my_n = (have && !flt) ? occ : 0u;
+}
+
+// Anchors [c0, c0 + m) of a read of at most 64 seeds, in generation order (seed order, then occurrence order), built where they are wanted:
+// dst_x / dst_q [0, m), LDS.  Every thread of the block calls; the caller's barrier follows.  Wave 0 filters the seeds (seed_tile_filter)
+// and leaves per seed the exclusive prefix sum of its anchors, its slot or position word and its query word in scr (STAGE_SCRATCH_U32
+// dwords of LDS that nobody else uses until that barrier); then a thread takes anchors c0 + tid, c0 + tid + nthr, ...: a 6-step search
+// over the prefix sums for the anchor's seed, one load from positions[] (none for a singleton), make_anchor.  The loads of four anchors are
+// issued before the first of them is used.
+#define STAGE_SCRATCH_U32 (65 + 3 * 64)
+template <class PX, class PQ>
+__device__ inline void stage_anchors(const uint4 *recb, uint32_t n_seed, int32_t qlen, const uint64_t *__restrict__ positions, int32_t max_occ, const ChainParams &P,
+                                     uint32_t c0, uint32_t m, PX dst_x, PQ dst_q, uint32_t tid, uint32_t nthr, uint32_t *scr)
+{
+    asm volatile("" : "+v"(tid));      // what is worked out from the thread's index stays here: hoisted out of the caller's loop over its reads it stayed in registers across the sort and the DP, ten of them
+    uint32_t *const s_ex = scr, *const s_qz = scr + 65, *const s_lo = scr + 129, *const s_hi = scr + 193;
+    if (tid < 64) {
+        uint4 rec; uint32_t my_n; bool flt, have;
+        seed_tile_filter(recb, n_seed, qlen, max_occ, P, false, 0u, tid, rec, my_n, flt, have);
+        const uint32_t incl = (uint32_t)wave_scan_add_incl((int32_t)my_n);
+        s_ex[tid] = incl - my_n;
+        if (tid == 63) s_ex[64] = incl;
+        s_qz[tid] = rec.w; s_lo[tid] = rec.x; s_hi[tid] = rec.y;
+    }
+    __syncthreads();
+    constexpr uint32_t U = 4;
+    for (uint32_t b = tid; b < m; b += U * nthr) {
+        uint64_t rp[U]; uint32_t qz[U];
+#pragma unroll
+        for (uint32_t j = 0; j < U; ++j) {
+            const uint32_t o = b + j * nthr;
+            rp[j] = 0; qz[j] = 0;
+            if (o < m) {
+                const uint32_t i = c0 + o;
+                uint32_t s = 0;      // the last seed whose prefix sum is <= i: empty seeds behind it start above i
+#pragma unroll
+                for (uint32_t step = 32; step > 0; step >>= 1) if (s_ex[s + step] <= i) s += step;
+                const uint32_t ex = s_ex[s], cnt = s_ex[s + 1] - ex;
+                const uint64_t w1 = (uint64_t)s_hi[s] << 32 | s_lo[s];
+                qz[j] = s_qz[s];
+                rp[j] = cnt == 1 ? w1 : positions[(w1 >> SH_SLOT_NBITS) + (i - ex)];
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < U; ++j) {
+            const uint32_t o = b + j * nthr;
+            if (o < m) { uint64_t x; uint32_t q; make_anchor(rp[j], qz[j], qlen, P.k, x, q); dst_x[o] = x; dst_q[o] = q; }
+        }
+    }
+}
+
 // ---- pair score (mg_lchain_dp's comput_sc, single segment, not cDNA) ---------------------------
 __device__ inline float sh_mg_log2(float x)
 {

@@ -98,6 +98,7 @@ struct Counters {
     unsigned long long sort_tot[N_SORT_CLS + 1], sort_anchor_tot[N_SORT_CLS + 1];    // SCRUBBY_HIP_DBG & 16: reads / anchors per sort class (4 = chained inside k_expand)     // statistics of k_cluster_dp by size class (whole chunk)
     unsigned long long sh_mini[64], sh_anchors[64];     // sharded sums
     uint32_t sh_host[64], sh_clusters[64], sh_pair[64];      // sh_pair: reads decided by the pair test
+    uint32_t sh_late[64], sh_deferred[64];                   // k_expand: table entries left to the sort kernels (late anchors), reads put off for want of arena room
     uint32_t sh_pf_reads[64], sh_pf_dirty[64], sh_top[64];   // reads chained by par_fill_block / _tiled, their dirty anchors, reads settled by backtrack_block_top
     uint32_t sh_lemma[64];       // SH_F_CIGAR flag-only: reads decided inside a chaining kernel (top chain + chain_lemma)
     // long-read presets, flag-only: anchors pre-selected by locus (k_lr_locus) - reads listed per table size, reads with anchors dropped,
@@ -399,17 +400,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     if (lane == 0) atomicAdd(&a.ctr->sh_mini[SHARD()], (unsigned long long)msum);
 }
 
-// ---- wave helpers ------------------------------------------------------------------------------------
-__device__ inline uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ inline uint32_t wave_sum_u32(uint32_t v)
-{
-    return (uint32_t)wave_all_add((int32_t)v);
-}
-__device__ inline uint32_t wave_excl_scan_u32(uint32_t v, uint32_t lane)
-{
-    return (uint32_t)wave_scan_add_incl((int32_t)v) - v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // long reads (any length): segment-parallel sketch, then per read thinning screen + probe + compaction
 // ------------------------------------------------------------------------------------------------
@@ -700,7 +690,12 @@ __global__ void k_route_all(uint64_t n_reads, uint32_t *work_resketch, Counters 
 // K2 / K3
 // ------------------------------------------------------------------------------------------------
 struct BigMeta { uint32_t r, n_a; int32_t rep_len; uint32_t state; };   // state: 0 expanded, 1 deferred
-struct SortItem { uint32_t w, n, qlen, pad; unsigned long long off; };
+struct SortItem { uint32_t w, n, qlen, pad; unsigned long long off; };      // pad in a sort class: 0, or late_item() when the arena slots at off hold no anchors yet (k_expand's `late`)
+#define LATE_MAX_READ (1u << 26)      // pad: bits 0..25 = read + 1, bits 26..31 = seeds - 1
+__device__ inline uint32_t late_item(uint32_t r, uint32_t n_seed) { return (r + 1u) | (n_seed - 1u) << 26; }
+// The class of 513 .. 1024 anchors keeps its anchors in the arena: with the staging code k_sort_lds<1024, 2, 256> takes 130 VGPRs where it took
+// 128 (the compiler then no longer holds it to four waves per SIMD: three), and its k_sort_top shares the reads
+__host__ __device__ constexpr bool late_class(int cls) { return cls != 2; }      // by sort class: k_expand asks it with the class it lists the read in, the kernels with their own
 // The class tables once more, in HBM: a kernel that indexes an array INSIDE its argument struct with a run-time value (the sort class a
 // read falls into, the size class of a cluster) gets the whole struct copied to scratch, and every later a.X becomes a scratch load - the
 // ISA of k_cluster_dp had five of them per chunk of predecessors.  Run-time indices go through BigBufs::tabs; compile-time ones keep the copy.
@@ -1536,6 +1531,7 @@ struct K3Args {
     uint64_t *stage_x; uint32_t *stage_q; unsigned long long stage_cap;      // where k_expand leaves those reads' anchors (generation order)
     int32_t locus_min_qlen;            // reads shorter than this are not thinned out (mm_map_frag's rescue test could depend on what is left out)
     int32_t cl_lds;                    // k_sort_lds queues its big clusters for k_cluster_dp (long-read presets handing over every chain)
+    int32_t late;                      // k_expand leaves the anchors of short reads with more than 64 of them to the kernel that sorts them (stage_anchors)
     uint32_t giant_fanin;              // runs a giant-read merge pass merges into one: 4, or 2 (SCRUBBY_HIP_GIANT_FANIN, A/B and tests); decides the passes a read takes and so the buffer it ends in
 };
 
@@ -1631,7 +1627,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const ChainSink sink_l = a.sink;
     const bool plain_cut = !(P.occ_dist > 0 && P.max_max_occ > a.max_occ);
     WaveAlloc al_sort[N_SORT_CLS];
-    uint32_t n_clusters = 0, n_pair = 0, n_lemma = 0;
+    uint32_t n_clusters = 0, n_pair = 0, n_lemma = 0, n_late = 0, n_deferred = 0;
     unsigned long long anchors_wave = 0, a_cur = 0, a_end = 0, s_cur = 0, s_end = 0;      // wave-local slices of the anchor arena / the staging buffer
     __shared__ uint64_t e_x[64];
     __shared__ uint32_t e_q[64];
@@ -1668,44 +1664,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         uint4 *recb = a.records + (LONG ? (size_t)a.seed_off[r] : (size_t)r * a.seed_cap);
         // occurrence filter of seed tile t: my_n = anchors this lane's seed contributes (0 if filtered / absent)
         auto eval = [&](uint32_t t, uint4 &rec, uint32_t &my_n, bool &flt, bool &have) {
-            const uint32_t sidx = t * 64 + lane;
-            have = sidx < n_seed;
-            rec = have ? recb[sidx] : make_uint4(0, 0, 0, 0);
-            const uint32_t occ = rec.z & SH_REC_OCC_MASK, qposz = rec.w;
-            const bool high = have && occ > (uint32_t)a.max_occ;
-            flt = false;
-            if (plain_cut) flt = high;
-            else if (general_mt) flt = (rec.z >> 31) != 0;      // decided by select_multi_tile below
-            else if (n_st > 1) flt = high && n_seed >= 2;      // no_keep holds
-            else {
-                const uint64_t hm = __ballot(high);
-                if (n_seed >= 2 && hm != 0) {
-                    const uint64_t low = __ballot(have && !high);
-                    const uint64_t below = low & ((1ULL << lane) - 1);
-                    const uint64_t above = lane >= 63 ? 0 : low & ~((2ULL << lane) - 1);
-                    const int32_t last0 = below ? 63 - __clzll((unsigned long long)below) : -1;
-                    const int32_t nxt = above ? __ffsll((unsigned long long)above) - 1 : (int32_t)n_seed;
-                    const uint32_t qp_last = (uint32_t)__shfl((int)qposz, last0 < 0 ? 0 : last0);
-                    const uint32_t qp_next = (uint32_t)__shfl((int)qposz, nxt >= (int32_t)n_seed ? 0 : nxt);
-                    const int32_t ps = last0 < 0 ? 0 : (int32_t)(qp_last >> 1);
-                    const int32_t pe = nxt >= (int32_t)n_seed ? qlen : (int32_t)(qp_next >> 1);
-                    int32_t mho = (int32_t)((double)(pe - ps) / (double)P.occ_dist + .499);
-                    if (mho > 128) mho = 128;
-                    int32_t rank = 0;
-                    if (__ballot(high && mho > 0) != 0) {
-                        for (uint32_t u = 0; u < n_seed; ++u) {
-                            uint32_t ot = rdlane(occ, u);
-                            bool in = (int32_t)u > last0 && (int32_t)u < nxt;
-                            rank += in && (ot < occ || (ot == occ && u < lane));
-                        }
-                    }
-                    if (high) {
-                        flt = !(mho > 0 && rank < mho);
-                        if (occ > (uint32_t)P.max_max_occ) flt = true;
-                    }
-                }
-            }
-            my_n = (have && !flt) ? occ : 0u;
+            seed_tile_filter(recb, n_seed, qlen, a.max_occ, P, general_mt, t, lane, rec, my_n, flt, have);
         };
         if (general_mt) {
             // mm_seed_select over more than 64 seeds.  Forward sweep: index of the nearest low-occurrence seed before
@@ -1822,7 +1781,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             a.B.meta[w] = m; a.B.acc_nu[w] = 0; a.B.acc_best[w] = 0;
             if (defer) { uint32_t di = atomicAdd(a.defer_count, 1u); a.defer_list[di] = r; }
         }
-        if (defer) { if (to_stage) s_cur = s_end = 0; else a_cur = a_end = 0; continue; }
+        if (defer) { if (to_stage) s_cur = s_end = 0; else a_cur = a_end = 0; ++n_deferred; continue; }
         if (n_a == 0) continue;
         if (to_stage) s_cur += n_a; else if (!in_lds) a_cur += n_a;
         anchors_wave += n_a;
@@ -1830,8 +1789,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         uint32_t *const gq = in_lds ? e_q : (to_stage ? a.stage_q + off : a.B.aq + off);
 
         // ---- pass 2: anchors in generation order (seed order, then occurrence order) ----
+        // A short read bound for a sort class or the giant path keeps its arena slots but gets no anchors here: the kernel that sorts them
+        // builds them in its LDS sort buffer (stage_anchors; SortItem::pad carries the read)
+        const int cls = n_a <= 256 ? 0 : (n_a <= SORT_LDS_A ? 1 : (n_a <= 1024 ? 2 : (n_a <= SORT_LDS_B ? 3 : (n_a <= SORT_LDS_C ? 4 : SORT_CLS_GIANT))));      // the sort class, for a read that gets one
+        const bool late = !LONG && a.late && n_st == 1 && !in_lds && !to_stage && r < LATE_MAX_READ - 1u && late_class(cls);
         uint32_t run = 0;
-        for (uint32_t t = 0; t < n_st; ++t) {
+        for (uint32_t t = 0; t < (late ? 0u : n_st); ++t) {
             uint4 rec = rec0; uint32_t my_n = my_n0; bool flt = flt0, have = have0;
             if (t > 0) eval(t, rec, my_n, flt, have);
             // one lane per ANCHOR: anchor a of this seed tile belongs to the seed s with start[s] <= a < start[s] + my_n[s];
@@ -1917,12 +1880,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             const int lc = n_a <= LOCUS_N0 ? 0 : (n_a <= LOCUS_N1 ? 1 : 2);
             if (lane == 0) { const uint32_t li = atomicAdd(&a.ctr->n_locus[lc], 1u); SortItem it{w, n_a, (uint32_t)qlen, 0, off}; a.locus_items[lc][li] = it; }
         } else {
-            const int cls = n_a <= 256 ? 0 : (n_a <= SORT_LDS_A ? 1 : (n_a <= 1024 ? 2 : (n_a <= SORT_LDS_B ? 3 : (n_a <= SORT_LDS_C ? 4 : SORT_CLS_GIANT))));
             uint32_t lo, hi;
             const uint32_t si = al_sort[cls].take(&a.ctr->n_sort[cls], 1, cls <= 1 ? 32u : (cls <= 3 ? 8u : 1u), lo, hi);
             SortItem *const items = a.B.tabs->sort_items[cls];
             for (uint32_t i = lo + lane; i < hi; i += 64) items[i].n = 0;
-            if (lane == 0) { SortItem it{w, n_a, (uint32_t)qlen, 0, off}; items[si] = it; }
+            if (lane == 0) { SortItem it{w, n_a, (uint32_t)qlen, late ? late_item(r, n_seed) : 0u, off}; items[si] = it; }
+            n_late += late;
             if ((a.dbg & DBG_STATS) && lane == 0) { atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_a); }
         }
     }
@@ -1932,6 +1895,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     n_clusters = wave_sum_u32(n_clusters);
     if (lane == 0 && n_clusters) atomicAdd(&a.ctr->sh_clusters[SHARD()], n_clusters);
     if (lane == 0 && n_pair) atomicAdd(&a.ctr->sh_pair[SHARD()], n_pair);
+    if (lane == 0 && n_late && !a.quiet) atomicAdd(&a.ctr->sh_late[SHARD()], n_late);
+    if (lane == 0 && n_deferred) atomicAdd(&a.ctr->sh_deferred[SHARD()], n_deferred);
     if (lane == 0 && n_lemma) atomicAdd(&a.ctr->sh_lemma[SHARD()], n_lemma);
 }
 
@@ -2055,6 +2020,24 @@ __global__ __launch_bounds__(256) void k_lr_locus(K3Args a, int lc)
         __syncthreads();
     }
     if (tid == 0 && st_in) { atomicAdd(&a.ctr->lr_locus_in, st_in); atomicAdd(&a.ctr->lr_locus_kept, st_kept); if (st_reads) atomicAdd(&a.ctr->lr_locus_reads, st_reads); }
+}
+
+// A read k_expand left to its sort kernel (SortItem::pad = late_item(r, n_seed)): anchors [c0, c0 + m) into the block's first sort buffer, with
+// the filter of this pass (max_occ).  scr: the second sort buffer, idle until the sort's first merge round.
+// Only for kernels whose one parameter is K3Args: what the staging needs of it (records, positions, max_occ and three fields of P, eleven
+// scalar registers) is read from the kernel-argument segment HERE, behind a pointer the compiler cannot see through.  Taken from `a` these
+// were loaded at kernel entry and held across the sort and the DP, where the sort kernels have no scalar register left: the spills cost
+// k_sort_lds<1024> its fourth wave per SIMD.
+__device__ inline void late_anchors(uint32_t pad, int32_t qlen, uint32_t c0, uint32_t m, uint64_t *dst_x, uint32_t *dst_q, uint32_t tid, uint32_t nthr, uint32_t *scr)
+{
+    typedef const __attribute__((address_space(4))) K3Args *KernArgs;
+    KernArgs ka = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    pad = (uint32_t)__builtin_amdgcn_readfirstlane((int)pad);      // the same on every lane: the item came through LDS, which hides that
+    const uint32_t r = (pad & (LATE_MAX_READ - 1u)) - 1u, n_seed = (pad >> 26) + 1u;
+    ChainParams P{};      // what seed_tile_filter and make_anchor read
+    P.k = ka->P.k; P.occ_dist = ka->P.occ_dist; P.max_max_occ = ka->P.max_max_occ;
+    stage_anchors(ka->records + (size_t)r * ka->seed_cap, n_seed, qlen, ka->positions, ka->max_occ, P, c0, m, dst_x, dst_q, tid, nthr, scr);
 }
 
 // block reduction of the per-thread chain results of one read; thread 0 stores them
@@ -2199,7 +2182,8 @@ __global__ __launch_bounds__(NTHR) void k_sort_lds(K3Args a)
         const uint32_t n = si.n;
         if (n == 0) continue;
         const uint64_t *gx = a.B.ax + si.off; const uint32_t *gq = a.B.aq + si.off;
-        for (uint32_t i = tid; i < n; i += NTHR) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
+        if (late_class(CLS) && si.pad) late_anchors(si.pad, (int32_t)si.qlen, 0u, n, &s_x[0][0], &s_q[0][0], tid, NTHR, (uint32_t *)&s_x[1][0]);
+        else for (uint32_t i = tid; i < n; i += NTHR) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
         if (tid == 0) s_found = 0;
         __syncthreads();
         if (a.flag_only && !a.emit && a.P.flag_stop != INT32_MAX && n >= 96 && !(a.dbg & DBG_NO_GROUP_PROBE)) {
@@ -2306,7 +2290,8 @@ __global__ __launch_bounds__(NTHR) void k_sort_top(K3Args a)
         if (n == 0) continue;
         const int32_t qlen = (int32_t)si.qlen;
         const uint64_t *gx = a.B.ax + si.off; const uint32_t *gq = a.B.aq + si.off;
-        for (uint32_t i = tid; i < n; i += NTHR) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
+        if (late_class(CLS) && si.pad) late_anchors(si.pad, qlen, 0u, n, &s_x[0][0], &s_q[0][0], tid, NTHR, (uint32_t *)&s_x[1][0]);
+        else for (uint32_t i = tid; i < n; i += NTHR) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
         __syncthreads();
         const bool fl = block_merge_sort(&s_x[0][0], &s_q[0][0], &s_x[1][0], &s_q[1][0], n);
         uint64_t *rx = fl ? s_x[1] : s_x[0]; uint32_t *rq = fl ? s_q[1] : s_q[0];
@@ -2443,7 +2428,8 @@ __global__ __launch_bounds__(256) void k_giant_chunksort(K3Args a)
         const SortItem si = a.B.sort_items[SORT_CLS_GIANT][it];
         const uint32_t c0 = (t - a.B.tile_base[it]) * GT, m = si.n - c0 < GT ? si.n - c0 : GT;
         uint64_t *gx = a.B.ax + si.off + c0; uint32_t *gq = a.B.aq + si.off + c0;
-        for (uint32_t i = tid; i < m; i += 256) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
+        if (late_class(SORT_CLS_GIANT) && si.pad) late_anchors(si.pad, (int32_t)si.qlen, c0, m, &s_x[0][0], &s_q[0][0], tid, 256u, (uint32_t *)&s_x[1][0]);
+        else for (uint32_t i = tid; i < m; i += 256) { s_x[0][i] = gx[i]; s_q[0][i] = gq[i]; }
         __syncthreads();
         const bool fl = block_merge_sort(&s_x[0][0], &s_q[0][0], &s_x[1][0], &s_q[1][0], m);
         const uint64_t *rx = fl ? s_x[1] : s_x[0]; const uint32_t *rq = fl ? s_q[1] : s_q[0];
@@ -3768,6 +3754,7 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     SH_HIP(hipMemsetAsync(&ctr->expand_ticket, 0, 4, s));
     SH_HIP(hipMemsetAsync(&ctr->n_cl[0], 0, 4 * 6, s));
     // 6144 waves for 4096 resident (103 VGPRs: 4 per SIMD): measured best; 4096 or 5120 waves, or 5 waves per SIMD at 96 VGPRs, are 0-3 % slower
+    if (k.flag_only && k.P.flag_stop != INT32_MAX && !(k.dbg & DBG_NO_GROUP_PROBE)) k.late = 0;      // `gp` below: k_group_probe and k_sort_lds's own probe read the anchors from the arena
     if (k.locus) { SH_HIP(hipMemsetAsync(&ctr->n_locus[0], 0, 4 * 6, s)); SH_HIP(hipMemsetAsync(&ctr->stage_cursor, 0, 8, s)); }
     if (k.seed_off) hipLaunchKernelGGL(k_expand<true>, dim3(grid * 3), dim3(64), 0, s, k);
     else hipLaunchKernelGGL(k_expand<false>, dim3(grid * 3), dim3(64), 0, s, k);
@@ -3979,6 +3966,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     k.top_max = (int32_t)cs.top_max; k.pft_gmin = (uint32_t)cs.pft_gmin;
     SH_CHECK(cs.giant_fanin != 0, SH_ERR_BAD_ARG, "SCRUBBY_HIP_GIANT_FANIN must be 2 or 4, not '%s'", shi_call_switch_text(&CallSwitches::giant_fanin));
     k.giant_fanin = (uint32_t)cs.giant_fanin;
+    k.late = !k.seed_off && !(c->opts.flags & SH_F_NO_LATE_ANCHORS);      // big_pass drops it where k_group_probe reads the unsorted anchors; k.locus needs k.seed_off
     k.resketch_list = c->d_work_resketch;
     // long-read presets, flag-only: the anchors that cannot hold regs[0] never reach the sort classes (k_lr_locus).  Needs the probe (a read
     // with anchors left out is only ever proven mapped by it), a single chaining pass (max_occ <= mid_occ: whether mm_map_frag chains again
@@ -4589,6 +4577,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
         for (int i = 0; i < 64; ++i) sum_lemma += c->h_ctr->sh_lemma[i];
         stats->n_ext_shortcut += sum_lemma;
         stats->n_lc_filtered += c->h_ctr->lc_why[LC_DECIDED_FILTERED];
+        for (int i = 0; i < 64; ++i) { stats->n_late_reads += c->h_ctr->sh_late[i]; stats->n_deferred += c->h_ctr->sh_deferred[i]; }
         for (int i = 0; i < 64; ++i) { sum_host += c->h_ctr->sh_host[i]; sum_mini += c->h_ctr->sh_mini[i]; sum_anchors += c->h_ctr->sh_anchors[i]; sum_clusters += c->h_ctr->sh_clusters[i]; sum_pair += c->h_ctr->sh_pair[i]; sum_pf += c->h_ctr->sh_pf_reads[i]; sum_pfd += c->h_ctr->sh_pf_dirty[i]; sum_top += c->h_ctr->sh_top[i]; }
         stats->n_reads += n_reads; stats->n_bases += n_bases;
         stats->n_host += sum_host - ext_dropped - c->h_ctr->lr_fb_had;

@@ -331,3 +331,117 @@ extern "C" sh_status sh_dbg_block_sort(int32_t device, const uint64_t *x, const 
     hipFree(d_x); hipFree(d_ox); hipFree(d_q); hipFree(d_oq); hipFree(d_order); hipFree(d_cases);
     return st;
 }
+
+// ---- the repeat path's late anchors (stage_anchors, sh_chain.h), called directly (tests/test_stage_anchors_gpu.py) ----
+// Per case a read of 1..64 seed records and a range [c0, c0 + m) of its anchors.  First the definition: one thread per case runs seed_filter
+// on a copy of the records and walks the seeds in order, make_anchor per occurrence (what gen_anchors does), keeping the range; it also leaves
+// the read's anchor count.  Then one block of nthr threads per case stages the range into the first LDS sort buffer, scratch in the second,
+// as the sort kernels do, and stores it.  A range that reaches past the read's anchors is not staged.
+struct DbgStageBufs {
+    const sh_dbg_stage_case *cases; const uint32_t *order; const uint4 *rec; uint4 *rec_copy; const uint64_t *pos;
+    uint64_t *ox, *rx; uint32_t *oq, *rq, *total; ChainParams P; int32_t max_occ;
+};
+
+__global__ void __launch_bounds__(64) k_dbg_stage_ref(DbgStageBufs B)
+{
+    if (threadIdx.x != 0) return;
+    const sh_dbg_stage_case c = B.cases[blockIdx.x];
+    uint4 *mine = B.rec_copy + 64 * (size_t)blockIdx.x;
+    for (int32_t i = 0; i < c.n_seed; ++i) { uint4 r = B.rec[c.rec_off + i]; r.z &= SH_REC_OCC_MASK; mine[i] = r; }
+    const SeedView sv{mine, 1u, (uint32_t)c.n_seed};
+    int64_t n_a = 0; int32_t rep_len = 0;
+    seed_filter(sv, c.qlen, B.max_occ, B.P, n_a, rep_len);
+    B.total[blockIdx.x] = n_a > 0xffffffffll ? 0xffffffffu : (uint32_t)n_a;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < sv.n; ++i) {
+        const uint4 s = sv.get(i);
+        if (s.z >> 31) continue;
+        const uint32_t occ = s.z & SH_REC_OCC_MASK;
+        const uint64_t w1 = (uint64_t)s.y << 32 | s.x;
+        for (uint32_t t = 0; t < occ; ++t, ++at) {
+            if (at < c.c0 || at >= (uint64_t)c.c0 + c.m) continue;
+            uint64_t x; uint32_t q;
+            make_anchor(occ == 1 ? w1 : B.pos[(w1 >> SH_SLOT_NBITS) + t], s.w, c.qlen, B.P.k, x, q);
+            B.rx[c.out_off + (at - c.c0)] = x; B.rq[c.out_off + (at - c.c0)] = q;
+        }
+    }
+}
+
+template <int NTHR>
+__global__ void __launch_bounds__(NTHR) k_dbg_stage(DbgStageBufs B)
+{
+    __shared__ uint64_t s_x[2][DBGS_MAX_N];
+    __shared__ uint32_t s_q[2][DBGS_MAX_N];
+    static_assert(STAGE_SCRATCH_U32 * 4 <= 8 * 256, "the scratch fits the second sort buffer of the smallest class");
+    const uint32_t ci = B.order[blockIdx.x];
+    const sh_dbg_stage_case c = B.cases[ci];
+    const uint32_t tid = threadIdx.x;
+    if ((uint64_t)c.c0 + c.m > B.total[ci]) return;      // uniform
+    stage_anchors(B.rec + c.rec_off, (uint32_t)c.n_seed, c.qlen, B.pos, B.max_occ, B.P, c.c0, c.m, &s_x[0][0], &s_q[0][0], tid, (uint32_t)NTHR, (uint32_t *)&s_x[1][0]);
+    __syncthreads();
+    for (uint32_t i = tid; i < c.m; i += NTHR) { B.ox[c.out_off + i] = s_x[0][i]; B.oq[c.out_off + i] = s_q[0][i]; }
+}
+
+extern "C" sh_status sh_dbg_stage_anchors(int32_t device, const uint32_t *records, uint64_t n_records, const uint64_t *positions, uint64_t n_positions,
+                                          int32_t k, int32_t max_occ, int32_t max_max_occ, int32_t occ_dist, const sh_dbg_stage_case *cases, int32_t n_cases,
+                                          uint64_t n_out, uint64_t *out_x, uint32_t *out_q, uint64_t *ref_x, uint32_t *ref_q, uint32_t *total)
+{
+    SH_CHECK(records && positions && cases && out_x && out_q && ref_x && ref_q && total && n_cases > 0 && n_cases <= DBGC_MAX_CASES && n_records > 0 &&
+             n_positions > 0 && n_out > 0 && k > 0 && k <= 31 && max_occ >= 0, SH_ERR_BAD_ARG, "sh_dbg_stage_anchors: bad argument");
+    static const int32_t nthr_of[4] = {64, 128, 256, 512};
+    std::vector<uint32_t> order[4];
+    for (int32_t i = 0; i < n_cases; ++i) {
+        const sh_dbg_stage_case &c = cases[i];
+        SH_CHECK(c.n_seed >= 1 && c.n_seed <= 64 && c.rec_off <= n_records && (uint64_t)c.n_seed <= n_records - c.rec_off, SH_ERR_BAD_ARG, "sh_dbg_stage_anchors: case %d: 1..64 seed records inside the array, not %d at %llu", i, c.n_seed, (unsigned long long)c.rec_off);
+        SH_CHECK(c.m >= 1 && c.m <= DBGS_MAX_N && c.c0 <= (1u << 30) && c.out_off <= n_out && (uint64_t)c.m <= n_out - c.out_off && c.qlen > 0, SH_ERR_BAD_ARG, "sh_dbg_stage_anchors: case %d: 1..%d anchors from %u inside the outputs, not %u at %llu", i, DBGS_MAX_N, c.c0, c.m, (unsigned long long)c.out_off);
+        uint64_t sum = 0;
+        for (int32_t j = 0; j < c.n_seed; ++j) {      // every occurrence list inside positions[]
+            const uint32_t *r = records + 4 * (c.rec_off + (uint64_t)j);
+            const uint64_t w1 = (uint64_t)r[1] << 32 | r[0], occ = r[2] & SH_REC_OCC_MASK, slot = w1 >> SH_SLOT_NBITS;
+            SH_CHECK(occ >= 1 && (occ == 1 || (slot <= n_positions && occ <= n_positions - slot)), SH_ERR_BAD_ARG, "sh_dbg_stage_anchors: case %d, seed %d: %llu occurrences at %llu of %llu", i, j, (unsigned long long)occ, (unsigned long long)slot, (unsigned long long)n_positions);
+            sum += occ;
+        }
+        SH_CHECK(sum <= (1u << 24), SH_ERR_BAD_ARG, "sh_dbg_stage_anchors: case %d: %llu occurrences", i, (unsigned long long)sum);
+        int v = 0;
+        while (v < 4 && nthr_of[v] != c.nthr) ++v;
+        SH_CHECK(v < 4, SH_ERR_BAD_ARG, "sh_dbg_stage_anchors: case %d: 64, 128, 256 or 512 threads, not %d", i, c.nthr);
+        order[v].push_back((uint32_t)i);
+    }
+    SH_HIP(hipSetDevice(device));
+    uint4 *d_rec = nullptr, *d_copy = nullptr; uint64_t *d_pos = nullptr, *d_ox = nullptr, *d_rx = nullptr; uint32_t *d_oq = nullptr, *d_rq = nullptr, *d_total = nullptr, *d_order = nullptr;
+    sh_dbg_stage_case *d_cases = nullptr;
+    auto run = [&]() -> sh_status {
+        const size_t no = (size_t)n_out, nc = (size_t)n_cases;
+        SH_HIP(hipMalloc(&d_rec, 16 * (size_t)n_records)); SH_HIP(hipMalloc(&d_copy, 16 * 64 * nc)); SH_HIP(hipMalloc(&d_pos, 8 * (size_t)n_positions));
+        SH_HIP(hipMalloc(&d_ox, 8 * no)); SH_HIP(hipMalloc(&d_rx, 8 * no)); SH_HIP(hipMalloc(&d_oq, 4 * no)); SH_HIP(hipMalloc(&d_rq, 4 * no));
+        SH_HIP(hipMalloc(&d_total, 4 * nc)); SH_HIP(hipMalloc(&d_order, 4 * nc)); SH_HIP(hipMalloc(&d_cases, sizeof(sh_dbg_stage_case) * nc));
+        SH_HIP(hipMemcpy(d_rec, records, 16 * (size_t)n_records, hipMemcpyHostToDevice)); SH_HIP(hipMemcpy(d_pos, positions, 8 * (size_t)n_positions, hipMemcpyHostToDevice));
+        SH_HIP(hipMemcpy(d_cases, cases, sizeof(sh_dbg_stage_case) * nc, hipMemcpyHostToDevice));
+        SH_HIP(hipMemset(d_ox, 0, 8 * no)); SH_HIP(hipMemset(d_rx, 0, 8 * no)); SH_HIP(hipMemset(d_oq, 0xff, 4 * no)); SH_HIP(hipMemset(d_rq, 0xff, 4 * no));      // what no case covers: (0, ~0u)
+        DbgStageBufs B{d_cases, nullptr, d_rec, d_copy, d_pos, d_ox, d_rx, d_oq, d_rq, d_total, ChainParams{}, max_occ};
+        B.P.k = k; B.P.max_occ = max_occ; B.P.max_max_occ = max_max_occ; B.P.occ_dist = occ_dist;      // what the filter and make_anchor read
+        hipLaunchKernelGGL(k_dbg_stage_ref, dim3((uint32_t)n_cases), dim3(64), 0, 0, B);
+        SH_HIP(hipGetLastError());
+        uint32_t at = 0;
+        for (int v = 0; v < 4; ++v) {      // one launch per thread count
+            const uint32_t m = (uint32_t)order[v].size();
+            if (!m) continue;
+            SH_HIP(hipMemcpy(d_order + at, order[v].data(), 4 * (size_t)m, hipMemcpyHostToDevice));
+            B.order = d_order + at;
+            if (v == 0) hipLaunchKernelGGL(k_dbg_stage<64>, dim3(m), dim3(64), 0, 0, B);
+            else if (v == 1) hipLaunchKernelGGL(k_dbg_stage<128>, dim3(m), dim3(128), 0, 0, B);
+            else if (v == 2) hipLaunchKernelGGL(k_dbg_stage<256>, dim3(m), dim3(256), 0, 0, B);
+            else hipLaunchKernelGGL(k_dbg_stage<512>, dim3(m), dim3(512), 0, 0, B);
+            SH_HIP(hipGetLastError());
+            at += m;
+        }
+        SH_HIP(hipDeviceSynchronize());
+        SH_HIP(hipMemcpy(out_x, d_ox, 8 * no, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(out_q, d_oq, 4 * no, hipMemcpyDeviceToHost));
+        SH_HIP(hipMemcpy(ref_x, d_rx, 8 * no, hipMemcpyDeviceToHost)); SH_HIP(hipMemcpy(ref_q, d_rq, 4 * no, hipMemcpyDeviceToHost));
+        SH_HIP(hipMemcpy(total, d_total, 4 * nc, hipMemcpyDeviceToHost));
+        return SH_OK;
+    };
+    const sh_status st = run();
+    hipFree(d_rec); hipFree(d_copy); hipFree(d_pos); hipFree(d_ox); hipFree(d_rx); hipFree(d_oq); hipFree(d_rq); hipFree(d_total); hipFree(d_order); hipFree(d_cases);
+    return st;
+}

@@ -79,6 +79,16 @@ __device__ inline unsigned long long wave_bcast_u64(unsigned long long v, int l)
 // lane l receives lane l-1's 64-bit value, lane 0 receives `fill`
 __device__ inline unsigned long long wave_shr1_u64(unsigned long long v, unsigned long long fill) { return dpp_mov_u64<0x138, 0xf>(fill, v); }
 
+__device__ inline uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
+__device__ inline uint32_t wave_sum_u32(uint32_t v)
+{
+    return (uint32_t)wave_all_add((int32_t)v);
+}
+__device__ inline uint32_t wave_excl_scan_u32(uint32_t v, uint32_t lane)
+{
+    return (uint32_t)wave_scan_add_incl((int32_t)v) - v;
+}
+
 // ---- the repeat path's sorts (k_sort_top / k_sort_lds, k_giant_chunksort, group_probe; sh_dbg_block_sort calls the block sort directly) ----
 
 // stable sort of the first n lanes' (x, q) by x: rank by comparison with every broadcast key, then push
