@@ -3377,6 +3377,22 @@ struct sh_ctx {
     hipEvent_t evx[14] = {};         // 8..12: behind k_sort_top of each LDS class, 13: the end of the leftovers' stream (big_pass)
 };
 
+// One chunk of a call on its way through the stages of classify_chunk: what the call passed in, the two argument templates the stages
+// copy and vary, the state one stage leaves for the next, and the totals add_chunk_stats files at the end.
+struct Chunk {
+    const uint8_t *d_bases; const uint64_t *d_offsets; uint64_t n_reads, n_bases; uint8_t *d_flags; sh_trace *d_trace; hipStream_t s; sh_stats *stats;
+    uint32_t grid = 0;               // blocks of the kernels that take one tile of 64 reads per wave
+    K2Args b{};                      // K2, k_pair_pass, k_local_cluster, k_chain_large
+    K3Args k{};                      // the repeat path
+    bool pair_pass = false, k2_late = false;
+    bool first = true;               // no pass of the repeat path has been read back yet
+    Counters snap{};                 // the counters after that first pass: the routing of the front end
+    uint32_t resk_done = 0;          // reads of the re-sketch list k_chain_large has taken
+    uint32_t ext_list = 0, ext_regions = 0, ext_dropped = 0; float ms_ext = 0;
+    uint32_t n_big_a = 0, n_exact_reads = 0, n_ondemand = 0;      // long reads: second working-memory size, exact long join; either stage: memory on demand
+    uint32_t n_fallback = 0; double ms_fallback = 0;              // short reads: the third pass
+};
+
 static void fill_chain_params(const sh_opts &o, const CtxSwitches &sw, int32_t mid_occ, ChainParams &P)
 {
     P.k = o.k; P.is_sr = o.is_sr;
@@ -3564,7 +3580,7 @@ extern "C" sh_status sh_ctx_create(const sh_index *idx, const sh_opts *opts, uin
             const uint64_t L = std::max<uint32_t>(max_read_len, 64);
             // Sizes: every wave slot takes the usual read (16 Ki chain anchors - with the anchors pre-selected by locus a read brings ~1000 -,
             // 8 MB of direction bytes: an end extension of max_gap bases at the band of the long-read presets); a few hundred slots take a
-            // read of 256 Ki chain anchors or an alignment of 32 MB; beyond that memory is allocated for the reads that need it (ext_round)
+            // read of 256 Ki chain anchors or an alignment of 32 MB; beyond that memory is allocated for the reads that need it (on_demand)
             LongSizes z{};
             z.cap_q = (uint32_t)((L + 31) & ~15ull);
             z.cap_k = (uint32_t)std::min<uint64_t>(32768, ((2 * L + 1024) + 15) & ~15ull);
@@ -3900,68 +3916,123 @@ static sh_status launch_front_end(sh_ctx *c, const uint8_t *d_bases, const uint6
     return SH_OK;
 }
 
-static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
-                                uint8_t *d_flags, sh_trace *d_trace, hipStream_t s, sh_stats *stats)
+// ------------------------------------------------------------------------------------------------
+// host side: the driver of one chunk.  Every stage is a function of the context and the chunk (plus a copy of the kernel arguments where
+// it varies them); classify_chunk at the end of the section is the list of stages.  DESIGN.md §3.5 maps stage -> kernels -> read-back.
+// ------------------------------------------------------------------------------------------------
+#define SH_TRY(call) do { const sh_status st_ = (call); if (st_ != SH_OK) return st_; } while (0)
+
+// The device's counters in h_ctr as they stand once everything queued on `s` has run; an error of those launches surfaces here.
+static sh_status read_counters(sh_ctx *c, hipStream_t s)
+{
+    SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    SH_HIP(hipStreamSynchronize(s));
+    SH_HIP(hipGetLastError());
+    return SH_OK;
+}
+
+// ---- [dbg] lines (scripts/ and profiles/ parse them: the format strings stay as they are) ----
+static void print_repeat_pass(const Counters &h, int iter)      // DBG_STATS, after each iteration of run_repeat_path
+{
+    fprintf(stderr, "[dbg] iter %d resketch %u reasons %u %u %u pair tests between two singletons (dbg) %u segs %u big %u/%u defer %u/%u\n", iter, h.n_resketch, h.n_leg_reason[0], h.n_leg_reason[1], h.n_leg_reason[2], h.n_leg_reason[3], h.n_long_segs, h.n_big[0], h.n_big[1], h.n_big_defer[0], h.n_big_defer[1]);
+    fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", h.cl_tot[0], h.cl_tot[1], h.cl_tot[2], h.cl_tot[3], h.cl_anchor_tot[0], h.cl_anchor_tot[1], h.cl_anchor_tot[2], h.cl_anchor_tot[3]);
+    fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", h.sort_tot[6], h.sort_anchor_tot[6], h.sort_tot[0], h.sort_anchor_tot[0], h.sort_tot[1], h.sort_anchor_tot[1], h.sort_tot[2], h.sort_anchor_tot[2], h.sort_tot[3], h.sort_anchor_tot[3], h.sort_tot[4], h.sort_anchor_tot[4], h.sort_tot[5], h.sort_anchor_tot[5]);
+    fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", h.pair_mid[0], h.pair_mid[1], h.pair_mid[2], h.pair_mid[3]);
+    static const char *const lc_name[] = {"tried", "no singleton", "a seed above mid_occ", "singletons apart", "window grew / too many", "K size", "no margin over U_out", "lemma / no chain / tie", "decided", "decided, seeds filtered", "seeds not 2..64"};
+    fprintf(stderr, "[dbg] local-cluster shortcut, reads (anchors the occurrence filter admits):");
+    for (int i = 0; i <= LC_N_SEED; ++i) fprintf(stderr, "%s %s %u (%llu)", i ? "," : "", lc_name[i], h.lc_why[i], h.lc_anchors[i]);
+    fprintf(stderr, "\n");
+    fprintf(stderr, "[dbg] ring DP: chunks in window %llu, beyond %llu, far rescans %llu; clusters %llu (anchors %llu), with a max_skip break %llu (anchors %llu), widest window %llu, anchors of clusters with a window > 64: %llu, > 128: %llu\n", h.cl_dbg[0], h.cl_dbg[1], h.cl_dbg[2], h.cl_dbg[3], h.cl_dbg[6], h.cl_dbg[4], h.cl_dbg[5], h.cl_dbg[7], h.cl_dbg[8], h.cl_dbg[9]);
+    fprintf(stderr, "[dbg] parallel fill: reads done %llu (anchors %llu), not applicable %llu (anchors %llu), dirty anchors %llu; k_cluster_dp clusters prefilled %llu, sequential %llu (anchors %llu); read-level backtracks tried %llu, candidates listed %llu, given up (too many) %llu, chains visited %llu\n", h.pf_dbg[0], h.pf_dbg[3], h.pf_dbg[1], h.pf_dbg[4], h.pf_dbg[2], h.pf_dbg[5], h.pf_dbg[6], h.pf_dbg[7], h.pf_dbg[8], h.pf_dbg[11], h.pf_dbg[12], h.pf_dbg[10]);
+}
+
+static void print_first_round(const Counters &h, bool locus, uint32_t n_fb)      // long reads, after the first round of the stage
+{
+    if (locus) fprintf(stderr, "[dbg] anchors by locus: %u reads thinned out (%llu of %llu anchors kept); %u reads redone with every anchor (one chain and more possible %u, short read %u, top score within reach of what was left out %u, no chain after the join %u, probe undecided %u, no probe %u, no chain among the anchors kept %u)\n",
+                       h.lr_locus_reads, h.lr_locus_kept, h.lr_locus_in, n_fb, h.lr_fb_why[0], h.lr_fb_why[1], h.lr_fb_why[2], h.lr_fb_why[3], h.lr_fb_why[4], h.lr_fb_why[5], h.lr_fb_why[6]);
+    fprintf(stderr, "[dbg] probes that gave up (first round): region %u, window %u, filling over 4 M cells %u, direction bytes %u, z-drop / empty %u, CIGAR room %u, no proof within six fillings %u\n",
+            h.lr_probe_why[1], h.lr_probe_why[2], h.lr_probe_why[3], h.lr_probe_why[4], h.lr_probe_why[5], h.lr_probe_why[6], h.lr_probe_why[7]);
+}
+
+static void print_long_stage(const Counters &h, const Chunk &ch, const ChainSink &sink)      // long reads, at the end of the stage
+{
+    fprintf(stderr, "[dbg] long-read extension stage: %u reads with chains, %u re-chained (RMQ), %u with tied RMQ priorities, %u needed the large scratch, %u regions aligned, %u reads dropped\n",
+            ch.ext_list, h.lext_rechained, h.lext_rmq_tie, ch.n_big_a, h.ext_regions, h.ext_dropped);
+    unsigned long long tot = 0, mr = 0, ma = 0, sr = 0, sa = 0;
+    for (int i = 0; i < LR_NCLK; ++i) tot += h.lext_clk[i];
+    fprintf(stderr, "[dbg] long-read extension stage, share of wave time: gather %.1f  rmq-sort %.1f  rmq-fill %.1f  backtrack+compact %.1f  gen_regs %.1f  parent/select %.1f  squeeze %.1f  region set-up %.1f  ksw %.1f  z-drop test %.1f  update_extra %.1f  staging %.1f %%  (total %.1f wave-s at 100 MHz)\n",
+            100. * h.lext_clk[0] / (tot + 1), 100. * h.lext_clk[1] / (tot + 1), 100. * h.lext_clk[2] / (tot + 1), 100. * h.lext_clk[3] / (tot + 1), 100. * h.lext_clk[4] / (tot + 1), 100. * h.lext_clk[5] / (tot + 1),
+            100. * h.lext_clk[6] / (tot + 1), 100. * h.lext_clk[7] / (tot + 1), 100. * h.lext_clk[8] / (tot + 1), 100. * h.lext_clk[9] / (tot + 1), 100. * h.lext_clk[10] / (tot + 1), 100. * h.lext_clk[11] / (tot + 1), tot / 1e8);
+    fprintf(stderr, "[dbg] RMQ: %llu reads, %llu anchors (largest read %llu), per anchor: %.2f ring blocks, %.3f trips behind the ring with %.2f old blocks, list length %.1f, %.2f inner chunks\n",
+            h.lext_d[6], h.lext_d[0], h.lext_d[7], (double)h.lext_d[1] / (h.lext_d[0] + 1), (double)h.lext_d[2] / (h.lext_d[0] + 1),
+            (double)h.lext_d[3] / (h.lext_d[0] + 1), (double)h.lext_d[4] / (h.lext_d[0] + 1), (double)h.lext_d[5] / (h.lext_d[0] + 1));
+    fprintf(stderr, "[dbg] chains kernel: slowest read %.1f ms (%llu chains after the long join; read %llu of the chunk, %llu bases), all reads %.1f wave-ms\n", (h.lext_slow >> 24) / 1e5, h.lext_slow & 0xffffff,
+            h.lext_slow3 & 0xffffffffull, h.lext_slow2 & 0xffffffffull, h.lext_kernel_sum / 1e5);
+    { unsigned long long tb = 0; for (int i = 0; i < LR_NCLK; ++i) tb += h.lext_clk_big[i];
+      fprintf(stderr, "[dbg] regions kernel, second size: gen_regs %.1f  parent/select %.1f  squeeze %.1f  set-up %.1f  ksw %.1f  z-drop %.1f  update_extra %.1f  staging %.1f %% of %.1f wave-s\n", 100. * h.lext_clk_big[4] / (tb + 1), 100. * h.lext_clk_big[5] / (tb + 1), 100. * h.lext_clk_big[6] / (tb + 1), 100. * h.lext_clk_big[7] / (tb + 1), 100. * h.lext_clk_big[8] / (tb + 1), 100. * h.lext_clk_big[9] / (tb + 1), 100. * h.lext_clk_big[10] / (tb + 1), 100. * h.lext_clk_big[11] / (tb + 1), tb / 1e8); }
+    { unsigned long long tg = h.lext_clk_big[0] + h.lext_clk_big[1] + h.lext_clk_big[2] + h.lext_clk_big[3];
+      fprintf(stderr, "[dbg] giants rmq-fill sections (wave-s): insert %.2f  trim %.2f  query %.2f  tally %.2f  score+inner %.2f\n", h.lext_clk_big[4] / 1e8, h.lext_clk_big[5] / 1e8, h.lext_clk_big[6] / 1e8, h.lext_clk_big[7] / 1e8, h.lext_clk_big[8] / 1e8);
+      fprintf(stderr, "[dbg] all rmq-fill sections (wave-s): insert %.2f  trim %.2f  query %.2f  tally %.2f  score+inner %.2f\n", h.lext_clk[4] / 1e8, h.lext_clk[5] / 1e8, h.lext_clk[6] / 1e8, h.lext_clk[7] / 1e8, h.lext_clk[8] / 1e8);
+      fprintf(stderr, "[dbg] chains kernel, the giants: gather %.1f  rmq-sort %.1f  rmq-fill %.1f  backtrack+compact %.1f %% of %.2f wave-s\n", 100. * h.lext_clk_big[0] / (tg + 1), 100. * h.lext_clk_big[1] / (tg + 1), 100. * h.lext_clk_big[2] / (tg + 1), 100. * h.lext_clk_big[3] / (tg + 1), tg / 1e8); }
+    { const unsigned long long *dd = h.lext_d_big;
+      fprintf(stderr, "[dbg] RMQ, the giants: %llu reads, %llu anchors (largest read %llu), per anchor: %.2f ring blocks, %.3f trips behind the ring with %.2f old blocks, list length %.1f, %.2f inner chunks\n",
+              dd[6], dd[0], dd[7], (double)dd[1] / (dd[0] + 1), (double)dd[2] / (dd[0] + 1), (double)dd[3] / (dd[0] + 1), (double)dd[4] / (dd[0] + 1), (double)dd[5] / (dd[0] + 1)); }
+    fprintf(stderr, "[dbg] regions kernel, second size: slowest read %.1f ms (%llu bases), all reads %.1f wave-ms\n", (h.lext_slow_part[3] >> 32) / 1e5, h.lext_slow_part[3] & 0xffffffffull, h.lext_sum_part[3] / 1e5);
+    fprintf(stderr, "[dbg] regions kernel, second size, largest per-read time of each step (ms): gen_regs %.1f  parent/select %.1f  squeeze %.1f  set-up %.1f  ksw %.1f  z-drop %.1f  update_extra %.1f  staging %.1f\n", h.lext_phase_max[4] / 1e5, h.lext_phase_max[5] / 1e5, h.lext_phase_max[6] / 1e5, h.lext_phase_max[7] / 1e5, h.lext_phase_max[8] / 1e5, h.lext_phase_max[9] / 1e5, h.lext_phase_max[10] / 1e5, h.lext_phase_max[11] / 1e5);
+    for (int pp = 0; pp < 3; ++pp) fprintf(stderr, "[dbg] chains kernel, part %d (0 lists of later passes, 1 all but the giants, 2 the giants): slowest read %.1f ms, all reads %.1f wave-ms\n", pp, (h.lext_slow_part[pp] >> 32) / 1e5, h.lext_sum_part[pp] / 1e5);
+    for (int i = 0; i < SINK_SHARDS; ++i) { sr += h.ext_n_recs[i]; sa += h.ext_n_anch[i]; mr = std::max<unsigned long long>(mr, h.ext_n_recs[i]); ma = std::max<unsigned long long>(ma, h.ext_n_anch[i]); }
+    fprintf(stderr, "[dbg] chain hand-over: %llu chains, %llu anchors; fullest shard %llu / %u chains, %llu / %llu anchors\n", sr, sa, mr, sink.cap_recs, ma, sink.cap_anch);
+}
+
+static void print_align_top(const Counters &h, uint32_t waves_top)      // short reads, DBG_STATS: the clocks and histograms of k_regs_align_top_stats
+{
+    unsigned long long tot = 0;
+    for (int i = 0; i < ACLK_N; ++i) tot += h.ext_clk[i];
+    fprintf(stderr, "[dbg] k_regs_align_top, %u waves: ksw fill %.1f  ksw backtrack %.1f  staging %.1f  lane-0 walks %.1f  other %.1f %% of %.3f wave-s; %u reads, %u ksw_extd2 calls (%u with T16 <= 256, Q16 <= 336 and the exact maximum)\n",
+            waves_top, 100. * h.ext_clk[0] / (tot + 1), 100. * h.ext_clk[1] / (tot + 1), 100. * h.ext_clk[2] / (tot + 1), 100. * h.ext_clk[3] / (tot + 1), 100. * h.ext_clk[4] / (tot + 1), tot / 1e8, h.ext_hist[22], h.ext_hist[20], h.ext_hist[21]);
+    fprintf(stderr, "[dbg] ksw_extd2 calls by T16 (<= 16, 32, 64, 128, 256, 448, more): %u %u %u %u %u %u %u; anti-diagonals: %llu %llu %llu %llu %llu %llu %llu\n", h.ext_hist[0], h.ext_hist[1], h.ext_hist[2], h.ext_hist[3], h.ext_hist[4], h.ext_hist[5], h.ext_hist[6],
+            h.ext_diag[0], h.ext_diag[1], h.ext_diag[2], h.ext_diag[3], h.ext_diag[4], h.ext_diag[5], h.ext_diag[6]);
+    fprintf(stderr, "[dbg] ksw_extd2 calls by Q16 (<= 16, 32, 64, 128, 256, 336, more): %u %u %u %u %u %u %u; by direction bytes (<= 4096, <= 9840, <= 32768, more): %u %u %u %u\n", h.ext_hist[8], h.ext_hist[9], h.ext_hist[10], h.ext_hist[11], h.ext_hist[12], h.ext_hist[13], h.ext_hist[14],
+            h.ext_hist[16], h.ext_hist[17], h.ext_hist[18], h.ext_hist[19]);
+}
+
+// ---- the front of the chunk: argument templates, K2, the flag-only shortcuts ----
+// The argument templates of the chunk: ch.b (K2, k_pair_pass, k_local_cluster, k_chain_large) and ch.k (the repeat path), ch.grid and
+// the two switches the stages read.  No launch.
+static sh_status fill_chunk_args(sh_ctx *c, Chunk &ch)
 {
     const sh_index *idx = c->idx;
-    c->cur_reads = n_reads;
-    SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
-    if (c->ext) { SH_HIP(hipMemsetAsync(c->sink.head, 0xff, n_reads * 4, s)); SH_HIP(hipMemsetAsync(c->sink.best, 0, n_reads * 8, s)); SH_HIP(hipMemsetAsync(c->sink.tie, 0, n_reads * 4, s)); }
-    SH_HIP(hipEventRecord(c->ev[0], s));
-    const uint32_t n_tiles = (uint32_t)((n_reads + 63) / 64);
-    { sh_status st = launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, d_trace, s); if (st != SH_OK) return st; }
-    SH_HIP(hipEventRecord(c->ev[1], s));
-
+    const CallSwitches &cs = c->cs;
     // flag-only shortcuts over the seed records: the pair test (chain-level decision), or with SH_F_CIGAR mode 2 (co-diagonal singletons)
-    const bool pair_pass = d_trace == nullptr && (c->P.pair_dq_max > 0 || c->P.ext_s1) && c->use_k1;
-    const int pair_mode_small = c->ext ? 2 : 0, pair_mode_big = c->ext ? 2 : 1;
-    K2Args b{};
-    b.offsets = d_offsets; b.bases = d_bases; b.n_reads = n_reads;
+    ch.pair_pass = ch.d_trace == nullptr && (c->P.pair_dq_max > 0 || c->P.ext_s1) && c->use_k1;
+    K2Args &b = ch.b;
+    b.offsets = ch.d_offsets; b.bases = ch.d_bases; b.n_reads = ch.n_reads;
     b.slots = (const uint4 *)idx->d_slots; b.lg_slots = idx->lg_slots; b.w = idx->w;
     b.positions = idx->d_positions;
     b.records = c->d_records; b.seed_cap = c->seed_cap;
-    b.k1info = c->d_k1info; b.flags = d_flags; b.trace = d_trace;
+    b.k1info = c->d_k1info; b.flags = ch.d_flags; b.trace = ch.d_trace;
     b.work_big = c->d_big[0][0];
     b.work_defer = c->d_work_defer; b.ctr = c->d_ctr;
     b.arena = c->d_arena; b.arena_bytes = c->legacy_bytes;
     b.P = c->P;
     b.sink = c->sink; b.emit = c->ext ? 1 : 0;
-    b.BC = BaseCtx{idx->d_ref, idx->d_cstart, d_bases};
-    const CallSwitches &cs = c->cs;
+    b.BC = BaseCtx{idx->d_ref, idx->d_cstart, ch.d_bases};
     b.dbg = (int32_t)cs.dbg;
-    if (c->ext && (d_trace != nullptr || c->ext_long)) { b.sink.best = nullptr; b.sink.tie = nullptr; }      // trace mode / long-read presets: every chain is handed over
-    const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(n_tiles, 1), 256 * 8);
+    if (c->ext && (ch.d_trace != nullptr || c->ext_long)) { b.sink.best = nullptr; b.sink.tie = nullptr; }      // trace mode / long-read presets: every chain is handed over
+    const uint32_t n_tiles = (uint32_t)((ch.n_reads + 63) / 64);
+    ch.grid = std::min<uint32_t>(std::max<uint32_t>(n_tiles, 1), 256 * 8);
     // K2 only needs K1's output and nothing waits for it before the end of the call: it runs on a side stream, beside k_local_cluster /
     // k_expand / the sort classes.  Starting it late instead, beside the giant reads' DP kernels of the second pass (SCRUBBY_HIP_K2_LATE=1),
     // was measured with the extension filter on: K2 itself 64 -> 22 ms, but the step 408 -> 428 ms - it does not find room beside those
     // persistent grids and ends up serialised.
-    const bool k2_late = c->use_k1 && (c->par & 1) && cs.k2_late > 0;
-    K2Args kb = b;
-    auto launch_k2 = [&]() -> sh_status {
-        if (c->par & 1) { sh_status es = ensure_side_streams(c, 3, 3); if (es != SH_OK) return es; }
-        hipStream_t sk = (c->par & 1) ? c->sx[3] : s;
-        SH_HIP(hipEventRecord(c->evx[4], s));
-        SH_HIP(hipStreamWaitEvent(sk, c->evx[4], 0));
-        kb.work = c->d_work_small; kb.work_count = &c->d_ctr->n_small; kb.work_begin = 0;
-        if (pair_pass) {      // flag-only: pair pass over all reads of the path, then the undecided ones, dense
-            kb.leftover = c->d_work_small2; kb.leftover_count = &c->d_ctr->n_small2;
-            hipLaunchKernelGGL(k_pair_pass, dim3(grid * 2), dim3(64), 0, sk, kb, pair_mode_small);
-            kb.work = c->d_work_small2; kb.work_count = &c->d_ctr->n_small2;
-        }
-        hipLaunchKernelGGL(k_chain_small<K2_CAP>, dim3(grid), dim3(64), 0, sk, kb);
-        SH_HIP(hipEventRecord(c->ev[2], sk));
-        SH_HIP(hipEventRecord(c->evx[5], sk));
-        return SH_OK;
-    };
-    if (c->use_k1 && !k2_late) { sh_status st = launch_k2(); if (st != SH_OK) return st; }
-    else if (!c->use_k1) SH_HIP(hipEventRecord(c->ev[2], s));
+    ch.k2_late = c->use_k1 && (c->par & 1) && cs.k2_late > 0;
 
-    K3Args k{};
-    k.offsets = d_offsets; k.positions = idx->d_positions; k.records = c->use_long ? c->d_lrec : c->d_records; k.seed_cap = c->seed_cap;
+    K3Args &k = ch.k;
+    k.offsets = ch.d_offsets; k.positions = idx->d_positions; k.records = c->use_long ? c->d_lrec : c->d_records; k.seed_cap = c->seed_cap;
     k.seed_off = c->use_long ? c->d_seed_off : nullptr; k.sel_scratch = c->use_long ? (uint32_t *)c->d_mz_hash : nullptr;
-    k.k1info = c->d_k1info; k.flags = d_flags; k.trace = d_trace; k.ctr = c->d_ctr; k.B = c->B; k.P = c->P;
-    k.flag_only = d_trace == nullptr && !c->ext;      // SH_F_CIGAR: every chain is needed, no early exit
-    k.sink = b.sink; k.emit = c->ext ? 1 : 0; k.BC = b.BC; k.t_mode = (c->ext && !c->ext_long && d_trace == nullptr) ? 1 : 0;
+    k.k1info = c->d_k1info; k.flags = ch.d_flags; k.trace = ch.d_trace; k.ctr = c->d_ctr; k.B = c->B; k.P = c->P;
+    k.flag_only = ch.d_trace == nullptr && !c->ext;      // SH_F_CIGAR: every chain is needed, no early exit
+    k.sink = b.sink; k.emit = c->ext ? 1 : 0; k.BC = b.BC; k.t_mode = (c->ext && !c->ext_long && ch.d_trace == nullptr) ? 1 : 0;
     k.dbg = (int32_t)cs.dbg;
     k.top_max = (int32_t)cs.top_max; k.pft_gmin = (uint32_t)cs.pft_gmin;
     SH_CHECK(cs.giant_fanin != 0, SH_ERR_BAD_ARG, "SCRUBBY_HIP_GIANT_FANIN must be 2 or 4, not '%s'", shi_call_switch_text(&CallSwitches::giant_fanin));
@@ -3971,7 +4042,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     // long-read presets, flag-only: the anchors that cannot hold regs[0] never reach the sort classes (k_lr_locus).  Needs the probe (a read
     // with anchors left out is only ever proven mapped by it), a single chaining pass (max_occ <= mid_occ: whether mm_map_frag chains again
     // must not hinge on chains left out) and windows narrow enough to tell loci apart
-    k.locus = c->ext_long && c->use_long && d_trace == nullptr && !cs.no_locus && !cs.no_probe &&
+    k.locus = c->ext_long && c->use_long && ch.d_trace == nullptr && !cs.no_locus && !cs.no_probe &&
               c->opts.max_clip_ratio >= 1.0f && c->P.max_occ <= c->P.mid_occ && c->locus_shift <= 20 && c->opts.min_cnt >= 1;
     {   // the shortest read for which `qlen - span > rmq_rescue_size || span > qlen * rmq_rescue_ratio` holds whatever the span (lr_chains_wave)
         int32_t q = 1;
@@ -3981,615 +4052,682 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     k.cl_lds = c->ext_long && c->P.max_iter <= RING_TMAX_ITER && !cs.no_cl_lds;
     k.locus_shift = c->locus_shift; k.lr_drop = c->d_lr_drop; k.stage_x = c->d_stage_x; k.stage_q = c->d_stage_q; k.stage_cap = c->stage_cap;
     for (int i = 0; i < 3; ++i) k.locus_items[i] = c->d_locus[i];
-    if (c->ext_long) SH_HIP(hipMemsetAsync(c->d_lr_drop, 0, n_reads * 4, s));
-    uint32_t resk_done = 0;
-    // pass 0 (mid_occ) over the reads K2 routed, pass 1 (max_occ) over the reads pass 0 could not chain;
-    // reads that found no arena room come back in the next iteration
-    int cur0 = 0, cur1 = 0;
-    if (pair_pass) {      // the repeat path's list: reads two singleton seeds decide never reach k_expand; the rest moves to the other list
-        K2Args pb = b;
+    return SH_OK;
+}
+
+// K2 over the LDS path's list, behind K1 on a side stream (flag-only: the pair pass first, K2 over what it leaves)
+static sh_status launch_k2(sh_ctx *c, Chunk &ch)
+{
+    const hipStream_t s = ch.s;
+    if (c->par & 1) SH_TRY(ensure_side_streams(c, 3, 3));
+    hipStream_t sk = (c->par & 1) ? c->sx[3] : s;
+    SH_HIP(hipEventRecord(c->evx[4], s));
+    SH_HIP(hipStreamWaitEvent(sk, c->evx[4], 0));
+    K2Args kb = ch.b;      // (as fill_chunk_args left it: the repeat path varies ch.b only after this launch)
+    kb.work = c->d_work_small; kb.work_count = &c->d_ctr->n_small; kb.work_begin = 0;
+    if (ch.pair_pass) {      // flag-only: pair pass over all reads of the path, then the undecided ones, dense
+        kb.leftover = c->d_work_small2; kb.leftover_count = &c->d_ctr->n_small2;
+        hipLaunchKernelGGL(k_pair_pass, dim3(ch.grid * 2), dim3(64), 0, sk, kb, c->ext ? 2 : 0);
+        kb.work = c->d_work_small2; kb.work_count = &c->d_ctr->n_small2;
+    }
+    hipLaunchKernelGGL(k_chain_small<K2_CAP>, dim3(ch.grid), dim3(64), 0, sk, kb);
+    SH_HIP(hipEventRecord(c->ev[2], sk));
+    SH_HIP(hipEventRecord(c->evx[5], sk));
+    return SH_OK;
+}
+
+// Flag-only shortcuts over the repeat path's list d_big[0][0]: what a shortcut decides never reaches k_expand, the rest moves to the
+// other list of the pair.  Returns the side the repeat path starts from.
+static int repeat_list_shortcuts(sh_ctx *c, Chunk &ch)
+{
+    const hipStream_t s = ch.s;
+    int cur0 = 0;
+    if (ch.pair_pass) {      // the repeat path's list: reads two singleton seeds decide never reach k_expand; the rest moves to the other list
+        K2Args pb = ch.b;
         pb.work = c->d_big[0][0]; pb.work_count = &c->d_ctr->n_big[0];
         pb.leftover = c->d_big[0][1]; pb.leftover_count = &c->d_ctr->n_big_defer[0]; pb.dbg_slot = 2;
-        hipLaunchKernelGGL(k_pair_pass, dim3(grid * 2), dim3(64), 0, s, pb, pair_mode_big);
+        hipLaunchKernelGGL(k_pair_pass, dim3(ch.grid * 2), dim3(64), 0, s, pb, c->ext ? 2 : 1);
         hipLaunchKernelGGL(k_pair_swap, dim3(1), dim3(1), 0, s, c->d_ctr);
         cur0 = 1;
     }
-    if (k.t_mode && c->P.ext_lemma && c->use_k1 && !c->use_long && !(k.dbg & DBG_NO_LOCAL_CLUSTER)) {      // reads whose singleton seeds' locus settles them
-        K2Args pb = b;
+    if (ch.k.t_mode && c->P.ext_lemma && c->use_k1 && !c->use_long && !(ch.k.dbg & DBG_NO_LOCAL_CLUSTER)) {      // reads whose singleton seeds' locus settles them
+        K2Args pb = ch.b;
         pb.work = c->d_big[0][cur0]; pb.work_count = &c->d_ctr->n_big[0];
         pb.leftover = c->d_big[0][cur0 ^ 1]; pb.leftover_count = &c->d_ctr->n_big_defer[0];
-        if (k.dbg & DBG_STATS) hipLaunchKernelGGL(k_local_cluster<true>, dim3(256 * 32), dim3(64), 0, s, pb);
+        if (ch.k.dbg & DBG_STATS) hipLaunchKernelGGL(k_local_cluster<true>, dim3(256 * 32), dim3(64), 0, s, pb);
         else hipLaunchKernelGGL(k_local_cluster<false>, dim3(256 * 32), dim3(64), 0, s, pb);      // latency-bound list probes: every wave slot
         hipLaunchKernelGGL(k_pair_swap, dim3(1), dim3(1), 0, s, c->d_ctr);
         cur0 ^= 1;
     }
-    bool first = true;
-    Counters snap{};
-    // the repeat path over the lists d_big[0][cur0] (pass 0, mid_occ) -> d_big[1][cur1] (pass 1, max_occ), until no read is deferred any more
-    auto run_repeat_path = [&](K3Args &k, K2Args &b, int &cur0, int &cur1, uint32_t &resk_done) -> sh_status {
-        for (int iter = 0;; ++iter) {
-            SH_CHECK(iter < 256, SH_ERR_OOM, "chain arena (%llu MiB) too small; set SCRUBBY_HIP_ARENA_MB", (unsigned long long)(c->arena_bytes >> 20));
-            k.pass = 0; k.max_occ = c->P.mid_occ;
-            k.list = c->d_big[0][cur0]; k.list_count = &c->d_ctr->n_big[0];
-            k.defer_list = c->d_big[0][cur0 ^ 1]; k.defer_count = &c->d_ctr->n_big_defer[0];
-            k.next_list = c->d_big[1][cur1]; k.next_count = &c->d_ctr->n_big[1];
-            sh_status st = big_pass(c, k, grid, s);
-            if (st != SH_OK) return st;
-            if (first && k2_late) { st = launch_k2(); if (st != SH_OK) return st; }
-            k.pass = 1; k.max_occ = c->P.max_occ;
-            k.list = c->d_big[1][cur1]; k.list_count = &c->d_ctr->n_big[1];
-            k.defer_list = c->d_big[1][cur1 ^ 1]; k.defer_count = &c->d_ctr->n_big_defer[1];
-            k.next_list = nullptr; k.next_count = nullptr;
-            st = big_pass(c, k, grid, s);
-            if (st != SH_OK) return st;
-            // the rare reads K1 or k_expand could not take
-            b.work = c->d_work_resketch; b.work_count = &c->d_ctr->n_resketch; b.work_begin = resk_done;
-            hipLaunchKernelGGL(k_chain_large, dim3(grid), dim3(64), 0, s, b);
-            if (first && c->use_k1) SH_HIP(hipStreamWaitEvent(s, c->evx[5], 0));
-            SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-            SH_HIP(hipStreamSynchronize(s));
-            SH_HIP(hipGetLastError());
-            if (first) { snap = *c->h_ctr; first = false; c->dbg_ptr[0] = c->d_big[1][cur1]; c->dbg_n[0] = snap.n_big[1]; c->dbg_ptr[1] = c->dbg_ptr[2] = nullptr; c->dbg_n[1] = c->dbg_n[2] = 0; }
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] iter %d resketch %u reasons %u %u %u pair tests between two singletons (dbg) %u segs %u big %u/%u defer %u/%u\n", iter, c->h_ctr->n_resketch, c->h_ctr->n_leg_reason[0], c->h_ctr->n_leg_reason[1], c->h_ctr->n_leg_reason[2], c->h_ctr->n_leg_reason[3], c->h_ctr->n_long_segs, c->h_ctr->n_big[0], c->h_ctr->n_big[1], c->h_ctr->n_big_defer[0], c->h_ctr->n_big_defer[1]);
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", c->h_ctr->cl_tot[0], c->h_ctr->cl_tot[1], c->h_ctr->cl_tot[2], c->h_ctr->cl_tot[3], c->h_ctr->cl_anchor_tot[0], c->h_ctr->cl_anchor_tot[1], c->h_ctr->cl_anchor_tot[2], c->h_ctr->cl_anchor_tot[3]);
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", c->h_ctr->sort_tot[6], c->h_ctr->sort_anchor_tot[6], c->h_ctr->sort_tot[0], c->h_ctr->sort_anchor_tot[0], c->h_ctr->sort_tot[1], c->h_ctr->sort_anchor_tot[1], c->h_ctr->sort_tot[2], c->h_ctr->sort_anchor_tot[2], c->h_ctr->sort_tot[3], c->h_ctr->sort_anchor_tot[3], c->h_ctr->sort_tot[4], c->h_ctr->sort_anchor_tot[4], c->h_ctr->sort_tot[5], c->h_ctr->sort_anchor_tot[5]);
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", c->h_ctr->pair_mid[0], c->h_ctr->pair_mid[1], c->h_ctr->pair_mid[2], c->h_ctr->pair_mid[3]);
-            if (k.dbg & DBG_STATS) {
-                const Counters &h = *c->h_ctr;
-                static const char *const lc_name[] = {"tried", "no singleton", "a seed above mid_occ", "singletons apart", "window grew / too many", "K size", "no margin over U_out", "lemma / no chain / tie", "decided", "decided, seeds filtered", "seeds not 2..64"};
-                fprintf(stderr, "[dbg] local-cluster shortcut, reads (anchors the occurrence filter admits):");
-                for (int i = 0; i <= LC_N_SEED; ++i) fprintf(stderr, "%s %s %u (%llu)", i ? "," : "", lc_name[i], h.lc_why[i], h.lc_anchors[i]);
-                fprintf(stderr, "\n");
-            }
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] ring DP: chunks in window %llu, beyond %llu, far rescans %llu; clusters %llu (anchors %llu), with a max_skip break %llu (anchors %llu), widest window %llu, anchors of clusters with a window > 64: %llu, > 128: %llu\n", c->h_ctr->cl_dbg[0], c->h_ctr->cl_dbg[1], c->h_ctr->cl_dbg[2], c->h_ctr->cl_dbg[3], c->h_ctr->cl_dbg[6], c->h_ctr->cl_dbg[4], c->h_ctr->cl_dbg[5], c->h_ctr->cl_dbg[7], c->h_ctr->cl_dbg[8], c->h_ctr->cl_dbg[9]);
-            if (k.dbg & DBG_STATS) fprintf(stderr, "[dbg] parallel fill: reads done %llu (anchors %llu), not applicable %llu (anchors %llu), dirty anchors %llu; k_cluster_dp clusters prefilled %llu, sequential %llu (anchors %llu); read-level backtracks tried %llu, candidates listed %llu, given up (too many) %llu, chains visited %llu\n", c->h_ctr->pf_dbg[0], c->h_ctr->pf_dbg[3], c->h_ctr->pf_dbg[1], c->h_ctr->pf_dbg[4], c->h_ctr->pf_dbg[2], c->h_ctr->pf_dbg[5], c->h_ctr->pf_dbg[6], c->h_ctr->pf_dbg[7], c->h_ctr->pf_dbg[8], c->h_ctr->pf_dbg[11], c->h_ctr->pf_dbg[12], c->h_ctr->pf_dbg[10]);
-            resk_done = c->h_ctr->n_resketch;
-            const uint32_t d0 = c->h_ctr->n_big_defer[0], d1 = c->h_ctr->n_big_defer[1];
-            if (d0 == 0 && d1 == 0) break;
-            // a read deferred when it was alone in the arena can never fit
-            SH_CHECK(!(d0 == c->h_ctr->n_big[0] && c->h_ctr->n_big[0] == 1 && d1 == 0) && !(d1 == c->h_ctr->n_big[1] && c->h_ctr->n_big[1] == 1 && d0 == 0),
-                     SH_ERR_OOM, "chain arena (%llu MiB) too small for one read; set SCRUBBY_HIP_ARENA_MB", (unsigned long long)(c->arena_bytes >> 20));
-            Counters z = *c->h_ctr;
-            z.n_big[0] = d0; z.n_big[1] = d1; z.n_big_defer[0] = z.n_big_defer[1] = 0;
-            SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
-            cur0 ^= 1; cur1 ^= 1;
-        }
-        return SH_OK;
-    };
-    { sh_status st = run_repeat_path(k, b, cur0, cur1, resk_done); if (st != SH_OK) return st; }
-    SH_HIP(hipEventRecord(c->ev[3], s));
+    return cur0;
+}
 
-    // legacy path deferrals: reads of k_chain_large that found no room in its arena slice come back alone
-    auto legacy_defers = [&](K2Args &bb) -> sh_status {
-        uint32_t n_defer = c->h_ctr->n_defer;
-        int rounds = 0;
-        while (n_defer > 0) {
-            SH_CHECK(++rounds < 64, SH_ERR_OOM, "re-sketch arena too small; set SCRUBBY_HIP_ARENA_MB");
-            std::swap(c->d_work_defer, c->d_work_defer2);
-            Counters z = *c->h_ctr;
-            z.n_defer = 0; z.arena_cursor = 0; z.n_resketch = n_defer;
-            SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
-            bb.work = c->d_work_defer2; bb.work_count = &c->d_ctr->n_resketch; bb.work_begin = 0; bb.work_defer = c->d_work_defer;
-            hipLaunchKernelGGL(k_chain_large, dim3(grid), dim3(64), 0, s, bb);
-            SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-            SH_HIP(hipStreamSynchronize(s));
-            uint32_t nd = c->h_ctr->n_defer;
-            SH_CHECK(nd < n_defer, SH_ERR_OOM, "re-sketch arena too small; set SCRUBBY_HIP_ARENA_MB");
-            n_defer = nd;
-        }
-        return SH_OK;
-    };
-    { sh_status st = legacy_defers(b); if (st != SH_OK) return st; }
-    uint32_t ext_list = 0, ext_regions = 0, ext_dropped = 0;
-    float ms_ext = 0;
-    if (c->ext_long) {
-        ExtLongArgs x{};
-        x.I.in.ref = idx->d_ref; x.I.in.cstart = idx->d_cstart; x.I.in.n_contigs = idx->n_contigs;
-        x.I.in.bases = d_bases; x.I.in.offsets = d_offsets; x.I.in.cx = c->sink.cx; x.I.in.cq = c->sink.cq; x.I.in.recs = c->sink.recs; x.I.in.head = c->sink.head;
-        x.I.rec = c->use_long ? c->d_lrec : c->d_records; x.I.k1info = c->d_k1info; x.I.seed_off = c->use_long ? c->d_seed_off : nullptr; x.I.seed_cap = c->seed_cap;
-        x.P = c->LP; x.AP = c->AP; x.CP = c->P;
-        x.AR.base = c->d_larena; x.AR.cap = c->larena_bytes; x.AR.cursor = &c->d_ctr->arena_cursor; x.AR.hdr = c->d_lhdr;
-        x.list = c->d_ext_list; x.n_list = &c->d_ctr->ext_n_list; x.ctr = c->d_ctr; x.flags = d_flags; x.trace = d_trace; x.flag_only = d_trace == nullptr;
-        x.clk = cs.dbg_set ? (cs.dbg_exact ? 3 : 1) : 0; x.probe = cs.no_probe ? 0 : 1;
-        x.drop = k.locus ? c->d_lr_drop : nullptr; x.fb_list = c->d_lr_fb; x.n_fb = &c->d_ctr->lr_n_fb;
-        x.exact_list = c->d_lext_exact_list; x.n_exact = &c->d_ctr->lext_n_exact;
-        x.exact_list2 = c->d_lext_exact_list2; x.n_exact2 = &c->d_ctr->lext_n_exact2;
-        x.kind = c->d_lkind ? c->d_lkind + c->lkind_r0 : nullptr;
-        { sh_status ps = pick_side_streams(c, s); if (ps != SH_OK) return ps; }
-        SH_HIP(hipEventRecord(c->ev_ext[0], s));
-        auto sync_ctr = [&]() -> sh_status {
-            SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-            SH_HIP(hipStreamSynchronize(s));
-            SH_HIP(hipGetLastError());
-            return SH_OK;
-        };
-        uint32_t n_big_a = 0, n_exact_reads = 0, n_ondemand = 0;
-        // Reads that outgrew the second size of a kernel's working memory too (minimap2 has no such limits): memory is allocated for them,
-        // four times the size before, until they fit (a chain-anchor count in the millions, an alignment of max_sw_mat cells); only when
-        // the device cannot give it do they keep their chain-level answer, counted and named in a warning.  xa: the arguments of the
-        // second-size pass; h_ctr holds its counters.
-        auto on_demand = [&](int phase, ExtLongArgs xa) -> sh_status {      // phase: 0 chains, 1 regions / alignment, 2 chains with the exact long join
-            uint32_t n_un = c->h_ctr->lext_n_unres;
-            n_ondemand += n_un;
-            LongSizes q = phase == 2 ? c->lext_exact_sz[1] : c->lext_sz[phase * 2 + 1];
-            int cur = 0;
-            for (int round = 0; n_un > 0; ++round) {
-                DevBuf buf;      // this round's working memory: gone at the end of the round, which sync_ctr has synchronised by then
-                unsigned long long per = 0; uint32_t waves = 0;
-                if (round < 5) {
-                    q.cap_a = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_a * 4, 1u << 28); q.cap_u = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_u * 4, 1u << 26); q.cap_r = q.cap_u;
-                    q.cap_m = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_m * 4, 1u << 26); q.cap_k = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_k * 4, 1u << 22);
-                    q.cap_t = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_t * 4, 1u << 28); q.cap_p = std::min<uint64_t>(q.cap_p * 4, 4ull << 30);
-                    per = long_ws_carve(nullptr, nullptr, q);
-                    for (waves = std::min<uint32_t>(n_un, 4); waves > 0 && buf.alloc(per * waves) != hipSuccess; waves >>= 1) (void)hipGetLastError();
-                }
-                if (!buf.p) {      // no memory to be had: counted, warned about, chain-level answer
-                    hipLaunchKernelGGL(k_lext_giveup, dim3(16), dim3(256), 0, s, (const uint32_t *)c->d_lext_unres[cur], n_un, d_flags, d_trace, c->d_lhdr, c->d_ctr, x.kind);
-                    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_unres, 0, 4, s));
-                    return sync_ctr();
-                }
-                const uint32_t zero2[4] = {0, 0, n_un, 0};
-                SH_HIP(hipMemcpyAsync(&c->d_ctr->lext_n_unres, zero2, 16, hipMemcpyHostToDevice, s));      // lext_n_unres, lext_ticket_unres, lext_n_unres_in
-                xa.scratch = buf.as<uint8_t>(); xa.scratch_per_wave = per; xa.sz = q;
-                xa.list = c->d_lext_unres[cur]; xa.n_list = &c->d_ctr->lext_n_unres_in; xa.ticket = &c->d_ctr->lext_ticket_unres;
-                xa.big_list = nullptr; xa.n_big = nullptr; xa.part = 0; xa.unres_list = c->d_lext_unres[cur ^ 1]; xa.n_unres = &c->d_ctr->lext_n_unres;
-                if (phase == 0) hipLaunchKernelGGL((k_long_chains<4096, false, true>), dim3(waves), dim3(64), 0, s, xa);
-                else if (phase == 2) hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(waves), dim3(64), 0, s, xa);
-                else hipLaunchKernelGGL(k_regs_align_long, dim3(waves), dim3(64), 0, s, xa);
-                sh_status st = sync_ctr();
-                if (st != SH_OK) return st;
-                if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-                n_un = c->h_ctr->lext_n_unres; cur ^= 1;
-            }
-            return SH_OK;
-        };
-        // One round of the stage: round 0 over every read with a chain; round 1 - flag-only calls whose anchors k_lr_locus thinned out - over the
-        // reads whose answer could depend on what was left out, after the repeat path has chained them again with every anchor
-        // lr_coop_fill's queue, counters and descriptors for one launch of an EXACT instance (three regions: the giants, E2a, E1 - launches that
-        // may run side by side); zeroed on the launch's stream
-        const bool coop = !cs.giants_plain && !cs.no_coop;
-        auto coop_setup = [&](ExtLongArgs &xx, int which, hipStream_t st, uint32_t n_blocks) -> sh_status {
-            constexpr uint32_t QCAP = 65536, NDESC = 512;
-            constexpr size_t off_desc = 256, off_ready = off_desc + NDESC * sizeof(LongCoopDesc), off_items = off_ready + QCAP * 4, region = off_items + QCAP * 16;
-            static_assert(sizeof(LongCoopDesc) % 8 == 0 && off_items % 16 == 0 && region % 256 == 0, "coop layout");
-            if (!c->d_coop) SH_HIP(c->own.device(c->d_coop, 3 * region));
-            uint8_t *base = c->d_coop + (size_t)which * region;
-            SH_HIP(hipMemsetAsync(base, 0, off_items, st));
-            xx.coop.q_res = (uint32_t *)base; xx.coop.q_head = (uint32_t *)(base + 64); xx.coop.active = (uint32_t *)(base + 128); xx.coop.n_reads = (uint32_t *)(base + 192);
-            xx.coop.desc = (LongCoopDesc *)(base + off_desc); xx.coop.ready = (uint32_t *)(base + off_ready); xx.coop.items = (uint4 *)(base + off_items);
-            xx.coop.cap = QCAP; xx.coop_on = n_blocks <= NDESC;
-            return SH_OK;
-        };
-        auto ext_round = [&](int round) -> sh_status {
-            SH_HIP(hipMemsetAsync(&c->d_ctr->arena_cursor, 0, 8, s));
-            {
-                ExtArgs xl{};
-                xl.in = x.I.in; xl.list = c->d_ext_list; xl.n_list = x.n_list; xl.n_reads = n_reads; xl.ctr = c->d_ctr;
-                if (round == 0) hipLaunchKernelGGL(k_lext_list, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, s, xl, x.drop, (uint32_t)std::max(1, c->LP.min_cnt), x.fb_list, x.n_fb);
-                else hipLaunchKernelGGL(k_lext_list_from, dim3(256), dim3(256), 0, s, xl, (const uint32_t *)c->d_lr_fb, (const uint32_t *)&c->d_ctr->lr_n_fb);
-                // largest reads first (d_ext_redo: bin of each list entry; d_lext_big2: the ordered list, free until the second kernel's first pass ends)
-                hipLaunchKernelGGL(k_lext_bins, dim3(256), dim3(256), 0, s, c->sink.recs, c->sink.head, c->d_ext_list, &c->d_ctr->ext_n_list, c->d_ext_redo, c->d_ctr->lext_hist, d_offsets);
-                hipLaunchKernelGGL(k_lext_scan, dim3(1), dim3(1), 0, s, c->d_ctr->lext_hist);
-                hipLaunchKernelGGL(k_lext_scatter, dim3(256), dim3(256), 0, s, c->d_ext_list, &c->d_ctr->ext_n_list, c->d_ext_redo, c->d_ctr->lext_hist, c->d_lext_sorted);
-                x.list = c->d_lext_sorted;
-            }
-            // first kernel: final chains (tier 0, then the reads that outgrew it with the large working memory)
-            {
-                ExtLongArgs xa = x;
-                xa.scratch = c->d_lext[0]; xa.scratch_per_wave = c->lext_per_wave[0]; xa.sz = c->lext_sz[0];
-                xa.ticket = &c->d_ctr->ext_ticket; xa.big_list = c->d_lext_big; xa.n_big = &c->d_ctr->lext_n_big;
-                // reads whose chain anchors outgrow the first size go straight to the large working memory, on a side stream beside the rest
-                int bin_cut = 0;
-                while (bin_cut < 31 && (2ull << bin_cut) <= c->lext_sz[0].cap_a) ++bin_cut;      // bin b holds totals in [2^b, 2^(b+1))
-                bin_cut = std::max(1, bin_cut - (int)cs.giant_bins_down);
-                xa.hist = c->d_ctr->lext_hist; xa.bin_cut = bin_cut; xa.part = 1;
-                ExtLongArgs xg = xa;
-                xg.scratch = c->d_lext[1]; xg.scratch_per_wave = c->lext_per_wave[1]; xg.sz = c->lext_sz[1];
-                xg.ticket = &c->d_ctr->lext_ticket_g; xg.part = 2;
-                // The giants - a dozen reads per half million, 10^5 chain anchors each, half a second and more of one wave apiece - are the pair's
-                // critical path.  With the 512-anchor ring their window reaches back into HBM at nearly every step, and those trips take several
-                // times longer while the main grid loads the memory system; so they get the 4096-anchor ring (99 KB of LDS a wave, no trip
-                // behind it), and because a CU the main grid has filled has no such room left, the main grid is held back until the giants'
-                // blocks have begun (k_wait_started: bounded, ~2 ms at most).  The main grid's blocks (13 KB) fit beside them.
-                uint32_t g_waves = std::min<uint32_t>(c->lext_waves[1], 64u);
-                if (cs.giant_waves != SW_UNSET) g_waves = std::min<uint32_t>(c->lext_waves[1], (uint32_t)cs.giant_waves);
-                xg.started = &c->d_ctr->lext_started;
-                SH_HIP(hipMemsetAsync(&c->d_ctr->lext_started, 0, 4, s));
-                SH_HIP(hipEventRecord(c->evx[0], s));
-                hipStream_t sg = c->sx[c->side_pick[0]];
-                SH_HIP(hipStreamWaitEvent(sg, c->evx[0], 0));
-                const uint32_t m_waves = c->lext_waves[0];
-                // (the giants on the EXACT instance at once: the tree is only kept over the stretches that ask it, lr_rmq_fill - a giant with a tie
-                // is not chained twice, and the exact passes lose their longest reads)
-                const bool giants_exact = !cs.giants_plain;
-                if (coop) { sh_status cs = coop_setup(xg, 0, sg, g_waves); if (cs != SH_OK) return cs; }      // the giants' waves share the long join of the launch's largest reads (lr_coop_fill, sh_long.h)
-                if (giants_exact) hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(g_waves), dim3(64), 0, sg, xg);
-                else hipLaunchKernelGGL((k_long_chains<4096, false, false>), dim3(g_waves), dim3(64), 0, sg, xg);
-                SH_HIP(hipEventRecord(c->evx[1], sg));
-                hipLaunchKernelGGL(k_wait_started, dim3(1), dim3(64), 0, s, (const uint32_t *)&c->d_ctr->lext_started, g_waves, 2000u);
-                hipLaunchKernelGGL((k_long_chains<512, false, false>), dim3(m_waves), dim3(64), 0, s, xa);
-                SH_HIP(hipStreamWaitEvent(s, c->evx[1], 0));
-                sh_status st = sync_ctr(); if (st != SH_OK) return st;
-                if (coop && cs.dbg_set) {
-                    uint32_t h[64] = {};
-                    SH_HIP(hipMemcpy(h, c->d_coop, sizeof(h), hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[dbg] long join shared among the giants' waves: %u reads in %u runs (%u taken off the queue)\n", h[48], h[0], h[16]);
-                }
-                if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;       // hand-over buffers or arena full: the caller cuts the chunk in two
-                if (c->h_ctr->lext_n_big > 0) {
-                    xa.scratch = c->d_lext[1]; xa.scratch_per_wave = c->lext_per_wave[1]; xa.sz = c->lext_sz[1];
-                    xa.list = c->d_lext_big; xa.n_list = &c->d_ctr->lext_n_big; xa.ticket = &c->d_ctr->lext_ticket_big; xa.big_list = nullptr; xa.n_big = nullptr; xa.part = 0;
-                    xa.unres_list = c->d_lext_unres[0]; xa.n_unres = &c->d_ctr->lext_n_unres;
-                    hipLaunchKernelGGL((k_long_chains<4096, false, true>), dim3(c->lext_waves[1]), dim3(64), 0, s, xa);
-                    st = sync_ctr(); if (st != SH_OK) return st;
-                    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-                    st = on_demand(0, xa); if (st != SH_OK) return st;
-                }
-            }
-            n_big_a += c->h_ctr->lext_n_big;
-            if (c->h_ctr->lext_n_exact + c->h_ctr->lext_n_exact2 > 0) {
-                // The long join of these reads met two candidates of equal priority in a way that can change the chains: once more with
-                // upstream's main tree beside the scan (sh_rmq_tree.h), maintained by the whole wave and asked at the ties.  The tree holds the
-                // look-back window only and lives in LDS, so the passes run on the ordinary working memory of the chains kernel:
-                //   E1   the 1024-anchor ring + a 1664-node tree (79 KB of LDS a wave, two waves to a CU), first size, largest reads first;
-                //   E2a  the reads that needed the 4096-anchor ring in the first pass already, and those whose join holds more than 60 000 anchors: that ring + a 1792-node tree (156 KB, one wave to a
-                //        CU), second size - on a side stream BESIDE E1 (launched first, so that its few blocks find their LDS);
-                //   E2b  what outgrew E1's ring or working memory after all: the same instance, after E1;
-                //   E3   (SCRUBBY_HIP_RMQ_ONE_LANE=1) what outgrew E2's ring or tree: both trees on one lane over node pools in the wave's scratch
-                //        (lr_rmq_fill_tree) - the literal mg_lchain_rmq, for windows no LDS holds; then memory on demand for what outgrew the sizes.
-                const uint32_t n_e1 = c->h_ctr->lext_n_exact, n_e2a = c->h_ctr->lext_n_exact2;
-                n_exact_reads += n_e1 + n_e2a;
-                const auto t_ex = std::chrono::steady_clock::now();
-                ExtLongArgs xe = x;
-                xe.part = 0; xe.exact_list = nullptr; xe.n_exact = nullptr; xe.exact_list2 = nullptr; xe.n_exact2 = nullptr;
-                SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big, 0, 8, s));       // lext_n_big, lext_ticket_big: E1's list of deferred reads
-                SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big2, 0, 8, s));      // lext_n_big2, lext_ticket_big2 (the regions kernel's list: free until it starts): E2's
-                hipStream_t se = c->sx[c->side_pick[0]];
-                if (n_e2a > 0) {
-                    ExtLongArgs x2 = xe;
-                    x2.scratch = c->d_lext[1]; x2.scratch_per_wave = c->lext_per_wave[1]; x2.sz = c->lext_sz[1];
-                    x2.list = c->d_lext_exact_list2; x2.n_list = &c->d_ctr->lext_n_exact2; x2.ticket = &c->d_ctr->lext_ticket_exact2;
-                    x2.big_list = c->d_lext_big2; x2.n_big = &c->d_ctr->lext_n_big2; x2.unres_list = nullptr; x2.n_unres = nullptr;
-                    x2.started = &c->d_ctr->lext_started;
-                    const uint32_t w2 = std::min<uint32_t>({c->lext_waves[1], (uint32_t)c->n_cu / 2u, n_e2a});      // half of the CUs at most: E1's blocks need the others
-                    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_started, 0, 4, s));
-                    SH_HIP(hipEventRecord(c->evx[0], s));
-                    SH_HIP(hipStreamWaitEvent(se, c->evx[0], 0));
-                    if (coop) { sh_status cs = coop_setup(x2, 1, se, w2); if (cs != SH_OK) return cs; }
-                    hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(w2), dim3(64), 0, se, x2);
-                    SH_HIP(hipEventRecord(c->evx[1], se));
-                    hipLaunchKernelGGL(k_wait_started, dim3(1), dim3(64), 0, s, (const uint32_t *)&c->d_ctr->lext_started, w2, 2000u);
-                }
-                if (n_e1 > 0) {
-                    xe.scratch = c->d_lext[0]; xe.scratch_per_wave = c->lext_per_wave[0]; xe.sz = c->lext_sz[0];
-                    // largest first, like every list of the stage: the pass ends with its slowest read (a read of 10^5 chain anchors is more than a second of one wave)
-                    SH_HIP(hipMemsetAsync(c->d_ctr->lext_hist, 0, sizeof(c->d_ctr->lext_hist), s));
-                    hipLaunchKernelGGL(k_lext_bins, dim3(64), dim3(256), 0, s, c->sink.recs, c->sink.head, c->d_lext_exact_list, &c->d_ctr->lext_n_exact, c->d_ext_redo, c->d_ctr->lext_hist, d_offsets);
-                    hipLaunchKernelGGL(k_lext_scan, dim3(1), dim3(1), 0, s, c->d_ctr->lext_hist);
-                    hipLaunchKernelGGL(k_lext_scatter, dim3(64), dim3(256), 0, s, c->d_lext_exact_list, &c->d_ctr->lext_n_exact, c->d_ext_redo, c->d_ctr->lext_hist, c->d_lext_esorted);
-                    xe.list = c->d_lext_esorted; xe.n_list = &c->d_ctr->lext_n_exact; xe.ticket = &c->d_ctr->lext_ticket_exact;
-                    xe.big_list = c->d_lext_big; xe.n_big = &c->d_ctr->lext_n_big; xe.unres_list = nullptr; xe.n_unres = nullptr;
-                    const uint32_t w1 = std::min<uint32_t>({c->lext_waves[0], 2u * (uint32_t)c->n_cu, n_e1});
-                    ExtLongArgs x1 = xe;
-                    if (coop) { sh_status cs = coop_setup(x1, 2, s, w1); if (cs != SH_OK) return cs; }
-                    hipLaunchKernelGGL((k_long_chains<1024, true, false>), dim3(w1), dim3(64), 0, s, x1);
-                }
-                if (n_e2a > 0) SH_HIP(hipStreamWaitEvent(s, c->evx[1], 0));
-                sh_status st = sync_ctr(); if (st != SH_OK) return st;
-                if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-                const uint32_t n_e2b = c->h_ctr->lext_n_big;
-                if (n_e2b > 0) {
-                    xe.scratch = c->d_lext[1]; xe.scratch_per_wave = c->lext_per_wave[1]; xe.sz = c->lext_sz[1];
-                    xe.list = c->d_lext_big; xe.n_list = &c->d_ctr->lext_n_big; xe.ticket = &c->d_ctr->lext_ticket_big;
-                    xe.big_list = c->d_lext_big2; xe.n_big = &c->d_ctr->lext_n_big2; xe.unres_list = nullptr; xe.n_unres = nullptr; xe.started = nullptr;
-                    hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(std::min<uint32_t>({c->lext_waves[1], (uint32_t)c->n_cu, n_e2b})), dim3(64), 0, s, xe);
-                    st = sync_ctr(); if (st != SH_OK) return st;
-                    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-                }
-                const uint32_t n_e3 = c->h_ctr->lext_n_big2;
-                if (n_e3 > 0) {      // (only with SCRUBBY_HIP_RMQ_ONE_LANE, or reads beyond the second working-memory size)
-                    xe.scratch = c->d_lext_exact[1]; xe.scratch_per_wave = c->lext_exact_per_wave[1]; xe.sz = c->lext_exact_sz[1];
-                    xe.list = c->d_lext_big2; xe.n_list = &c->d_ctr->lext_n_big2; xe.ticket = &c->d_ctr->lext_ticket_big2; xe.big_list = nullptr; xe.n_big = nullptr; xe.started = nullptr;
-                    xe.unres_list = c->d_lext_unres[0]; xe.n_unres = &c->d_ctr->lext_n_unres;
-                    hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(std::min<uint32_t>(c->lext_exact_waves[1], (uint32_t)c->n_cu)), dim3(64), 0, s, xe);
-                    st = sync_ctr(); if (st != SH_OK) return st;
-                    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-                    if (c->h_ctr->lext_n_unres > 0) { st = on_demand(2, xe); if (st != SH_OK) return st; }
-                }
-                SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big2, 0, 8, s));
-                if (cs.dbg_set) fprintf(stderr, "[dbg] exact long join: %u reads on the 1024-anchor ring beside %u on the 4096-anchor ring (%u with tied priorities so far), %u more on the large ring afterwards, %u beyond it, %.1f ms\n", n_e1, n_e2a, c->h_ctr->lext_rmq_tie, n_e2b, n_e3,
-                                                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ex).count());
-            }
-            SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "long-read extension stage: internal overflow code %u", c->h_ctr->ext_overflow);
-            ext_list += c->h_ctr->ext_n_list;
-            // second kernel: regions and alignment
-            {
-                ExtLongArgs xb = x;
-                xb.scratch = c->d_lext[2]; xb.scratch_per_wave = c->lext_per_wave[2]; xb.sz = c->lext_sz[2];
-                xb.ticket = &c->d_ctr->lext_ticket_b; xb.big_list = c->d_lext_big2; xb.n_big = &c->d_ctr->lext_n_big2;
-                // The launch of the second size runs BESIDE the first (side stream), taking reads off the list as the first launch puts them
-                // there: the pass used to begin when the first had ended, and it is one alignment of ~4 * 10^8 cells on one wave - a third of a
-                // second during which nothing else ran.  Both grids are resident together (two waves per SIMD each: 8 per CU); what the
-                // follower leaves (it gives up after a bounded number of looks) the launch after the first one takes, as before.
-                // (both grids must be RESIDENT together - a follower that holds the slot a block of the first launch waits for would wait for that
-                // launch to end: the first launch gives up the slots the follower needs; its reads are drawn by ticket, so fewer blocks lose nothing)
-                const uint32_t slots = 8u * (uint32_t)c->n_cu;
-                const bool follow = !cs.no_follow && c->lext_waves[3] <= slots / 4;
-                const uint32_t w_first = follow ? std::min<uint32_t>(c->lext_waves[2], slots - c->lext_waves[3]) : c->lext_waves[2];
-                if (follow) {
-                    SH_HIP(hipMemsetAsync(c->d_lext_big2, 0xff, (size_t)n_reads * 4, s));
-                    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_t0_done, 0, 4, s));
-                    SH_HIP(hipEventRecord(c->evx[2], s));
-                }
-                hipLaunchKernelGGL(k_regs_align_long, dim3(w_first), dim3(64), 0, s, xb);
-                if (follow) {
-                    // submitted in this order - first launch, its end mark, then the follower: two streams may share a hardware queue, and
-                    // a follower submitted ahead of the launch it follows would then sit in front of it until its looks ran out
-                    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(64), 0, s, &c->d_ctr->lext_t0_done, 1u);
-                    ExtLongArgs xf = xb;
-                    xf.scratch = c->d_lext[3]; xf.scratch_per_wave = c->lext_per_wave[3]; xf.sz = c->lext_sz[3];
-                    xf.list = c->d_lext_big2; xf.n_list = &c->d_ctr->lext_n_big2; xf.ticket = &c->d_ctr->lext_ticket_big2; xf.big_list = nullptr; xf.n_big = nullptr;
-                    xf.unres_list = c->d_lext_unres[0]; xf.n_unres = &c->d_ctr->lext_n_unres; xf.follow_done = &c->d_ctr->lext_t0_done;
-                    hipStream_t sf = c->sx[c->side_pick[1]];
-                    SH_HIP(hipStreamWaitEvent(sf, c->evx[2], 0));
-                    hipLaunchKernelGGL(k_regs_align_long, dim3(c->lext_waves[3]), dim3(64), 0, sf, xf);
-                    SH_HIP(hipEventRecord(c->evx[3], sf));
-                    SH_HIP(hipStreamWaitEvent(s, c->evx[3], 0));
-                }
-                sh_status st = sync_ctr(); if (st != SH_OK) return st;
-                if (c->h_ctr->lext_n_big2 > 0) {
-                    xb.scratch = c->d_lext[3]; xb.scratch_per_wave = c->lext_per_wave[3]; xb.sz = c->lext_sz[3];
-                    xb.list = c->d_lext_big2; xb.n_list = &c->d_ctr->lext_n_big2; xb.ticket = &c->d_ctr->lext_ticket_big2; xb.big_list = nullptr; xb.n_big = nullptr;
-                    xb.unres_list = c->d_lext_unres[0]; xb.n_unres = &c->d_ctr->lext_n_unres;
-                    hipLaunchKernelGGL(k_regs_align_long, dim3(c->lext_waves[3]), dim3(64), 0, s, xb);
-                    st = sync_ctr(); if (st != SH_OK) return st;
-                    st = on_demand(1, xb); if (st != SH_OK) return st;
-                }
-                n_big_a += c->h_ctr->lext_n_big2;
-            }
-            return SH_OK;
-        };
-        { sh_status st = ext_round(0); if (st != SH_OK) return st; }
-        const uint32_t n_fb = c->h_ctr->lr_n_fb;
-        if (k.locus && cs.dbg_set) fprintf(stderr, "[dbg] anchors by locus: %u reads thinned out (%llu of %llu anchors kept); %u reads redone with every anchor (one chain and more possible %u, short read %u, top score within reach of what was left out %u, no chain after the join %u, probe undecided %u, no probe %u, no chain among the anchors kept %u)\n",
-                                                        c->h_ctr->lr_locus_reads, c->h_ctr->lr_locus_kept, c->h_ctr->lr_locus_in, n_fb, c->h_ctr->lr_fb_why[0], c->h_ctr->lr_fb_why[1], c->h_ctr->lr_fb_why[2], c->h_ctr->lr_fb_why[3], c->h_ctr->lr_fb_why[4], c->h_ctr->lr_fb_why[5], c->h_ctr->lr_fb_why[6]);
-        if (cs.dbg_set) fprintf(stderr, "[dbg] probes that gave up (first round): region %u, window %u, filling over 4 M cells %u, direction bytes %u, z-drop / empty %u, CIGAR room %u, no proof within six fillings %u\n",
-                                               c->h_ctr->lr_probe_why[1], c->h_ctr->lr_probe_why[2], c->h_ctr->lr_probe_why[3], c->h_ctr->lr_probe_why[4], c->h_ctr->lr_probe_why[5], c->h_ctr->lr_probe_why[6], c->h_ctr->lr_probe_why[7]);
-        if (stats && k.locus) { stats->n_locus_reads += c->h_ctr->lr_locus_reads; stats->n_locus_redone += n_fb; }
-        if (n_fb > 0) {
-            // the reads whose answer could depend on the anchors left out: the repeat path once more with every anchor, then the stage again.
-            // Hand-over buffers, arena and lists start over; their first visit is forgotten (chain lists emptied, lr_drop cleared).
-            Counters z = *c->h_ctr;
-            memset(z.ext_n_recs, 0, sizeof(z.ext_n_recs)); memset(z.ext_n_anch, 0, sizeof(z.ext_n_anch)); memset(z.lext_hist, 0, sizeof(z.lext_hist));
-            z.n_defer = 0; z.arena_cursor = 0;
-            z.n_big[0] = n_fb; z.n_big[1] = 0; z.n_big_defer[0] = z.n_big_defer[1] = 0;
-            z.ext_n_list = 0; z.ext_ticket = 0; z.lext_ticket_g = 0; z.lext_n_big = 0; z.lext_ticket_big = 0; z.lext_n_big2 = 0; z.lext_ticket_big2 = 0; z.lext_ticket_b = 0; z.lext_n_unres = 0; z.lext_ticket_unres = 0; z.lext_n_exact = 0; z.lext_ticket_exact = 0; z.lext_n_exact2 = 0; z.lext_ticket_exact2 = 0;
-            SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_lext_forget, dim3(64), dim3(256), 0, s, (const uint32_t *)c->d_lr_fb, n_fb, c->sink.head, c->d_lr_drop, &c->d_ctr->lr_fb_had);
-            SH_HIP(hipMemcpyAsync(c->d_big[0][0], c->d_lr_fb, (size_t)n_fb * 4, hipMemcpyDeviceToDevice, s));
-            K3Args kf = k; kf.locus = 0; kf.quiet = 2;      // their chain-level count was taken back (k_lext_forget); the other statistics stay as they are
-            K2Args rb = b; rb.quiet = 2;
-            int f0 = 0, f1 = 0;
-            { sh_status st = run_repeat_path(kf, rb, f0, f1, resk_done); if (st != SH_OK) return st; }
-            rb.work_defer = c->d_work_defer;
-            { sh_status st = legacy_defers(rb); if (st != SH_OK) return st; }
-            x.drop = nullptr;
-            { sh_status st = ext_round(1); if (st != SH_OK) return st; }
-        }
-        if (c->h_ctr->lext_unresolved) {
-            static bool warned = false;
-            if (!warned) { warned = true; fprintf(stderr, "[scrubby-hip] WARNING: %u read(s) outgrew the extension stage's largest working memory (e.g. read %u of its batch, code %u: 18 chains, 20 read length, 21 chain anchors, 22 RMQ window, 23 seeds, 24 regions, 27-30 alignment window, 32 direction bytes); they keep their chain-level answer (mapped)\n", c->h_ctr->lext_unresolved, c->h_ctr->lext_err_read, c->h_ctr->lext_err_code); }
-        }
-        if (cs.dbg_set) fprintf(stderr, "[dbg] long-read extension stage: %u reads with chains, %u re-chained (RMQ), %u with tied RMQ priorities, %u needed the large scratch, %u regions aligned, %u reads dropped\n",
-                                               ext_list, c->h_ctr->lext_rechained, c->h_ctr->lext_rmq_tie, n_big_a, c->h_ctr->ext_regions, c->h_ctr->ext_dropped);
-        if (cs.dbg_set) {
-            unsigned long long tot = 0, mr = 0, ma = 0, sr = 0, sa = 0;
-            for (int i = 0; i < LR_NCLK; ++i) tot += c->h_ctr->lext_clk[i];
-            fprintf(stderr, "[dbg] long-read extension stage, share of wave time: gather %.1f  rmq-sort %.1f  rmq-fill %.1f  backtrack+compact %.1f  gen_regs %.1f  parent/select %.1f  squeeze %.1f  region set-up %.1f  ksw %.1f  z-drop test %.1f  update_extra %.1f  staging %.1f %%  (total %.1f wave-s at 100 MHz)\n",
-                    100. * c->h_ctr->lext_clk[0] / (tot + 1), 100. * c->h_ctr->lext_clk[1] / (tot + 1), 100. * c->h_ctr->lext_clk[2] / (tot + 1), 100. * c->h_ctr->lext_clk[3] / (tot + 1), 100. * c->h_ctr->lext_clk[4] / (tot + 1), 100. * c->h_ctr->lext_clk[5] / (tot + 1),
-                    100. * c->h_ctr->lext_clk[6] / (tot + 1), 100. * c->h_ctr->lext_clk[7] / (tot + 1), 100. * c->h_ctr->lext_clk[8] / (tot + 1), 100. * c->h_ctr->lext_clk[9] / (tot + 1), 100. * c->h_ctr->lext_clk[10] / (tot + 1), 100. * c->h_ctr->lext_clk[11] / (tot + 1), tot / 1e8);
-            fprintf(stderr, "[dbg] RMQ: %llu reads, %llu anchors (largest read %llu), per anchor: %.2f ring blocks, %.3f trips behind the ring with %.2f old blocks, list length %.1f, %.2f inner chunks\n",
-                    c->h_ctr->lext_d[6], c->h_ctr->lext_d[0], c->h_ctr->lext_d[7], (double)c->h_ctr->lext_d[1] / (c->h_ctr->lext_d[0] + 1), (double)c->h_ctr->lext_d[2] / (c->h_ctr->lext_d[0] + 1),
-                    (double)c->h_ctr->lext_d[3] / (c->h_ctr->lext_d[0] + 1), (double)c->h_ctr->lext_d[4] / (c->h_ctr->lext_d[0] + 1), (double)c->h_ctr->lext_d[5] / (c->h_ctr->lext_d[0] + 1));
-            fprintf(stderr, "[dbg] chains kernel: slowest read %.1f ms (%llu chains after the long join; read %llu of the chunk, %llu bases), all reads %.1f wave-ms\n", (c->h_ctr->lext_slow >> 24) / 1e5, c->h_ctr->lext_slow & 0xffffff,
-                    c->h_ctr->lext_slow3 & 0xffffffffull, c->h_ctr->lext_slow2 & 0xffffffffull, c->h_ctr->lext_kernel_sum / 1e5);
-            { unsigned long long tb = 0; for (int i = 0; i < LR_NCLK; ++i) tb += c->h_ctr->lext_clk_big[i];
-              fprintf(stderr, "[dbg] regions kernel, second size: gen_regs %.1f  parent/select %.1f  squeeze %.1f  set-up %.1f  ksw %.1f  z-drop %.1f  update_extra %.1f  staging %.1f %% of %.1f wave-s\n", 100. * c->h_ctr->lext_clk_big[4] / (tb + 1), 100. * c->h_ctr->lext_clk_big[5] / (tb + 1), 100. * c->h_ctr->lext_clk_big[6] / (tb + 1), 100. * c->h_ctr->lext_clk_big[7] / (tb + 1), 100. * c->h_ctr->lext_clk_big[8] / (tb + 1), 100. * c->h_ctr->lext_clk_big[9] / (tb + 1), 100. * c->h_ctr->lext_clk_big[10] / (tb + 1), 100. * c->h_ctr->lext_clk_big[11] / (tb + 1), tb / 1e8); }
-            { unsigned long long tg = c->h_ctr->lext_clk_big[0] + c->h_ctr->lext_clk_big[1] + c->h_ctr->lext_clk_big[2] + c->h_ctr->lext_clk_big[3];
-              fprintf(stderr, "[dbg] giants rmq-fill sections (wave-s): insert %.2f  trim %.2f  query %.2f  tally %.2f  score+inner %.2f\n", c->h_ctr->lext_clk_big[4] / 1e8, c->h_ctr->lext_clk_big[5] / 1e8, c->h_ctr->lext_clk_big[6] / 1e8, c->h_ctr->lext_clk_big[7] / 1e8, c->h_ctr->lext_clk_big[8] / 1e8);
-              fprintf(stderr, "[dbg] all rmq-fill sections (wave-s): insert %.2f  trim %.2f  query %.2f  tally %.2f  score+inner %.2f\n", c->h_ctr->lext_clk[4] / 1e8, c->h_ctr->lext_clk[5] / 1e8, c->h_ctr->lext_clk[6] / 1e8, c->h_ctr->lext_clk[7] / 1e8, c->h_ctr->lext_clk[8] / 1e8);
-              fprintf(stderr, "[dbg] chains kernel, the giants: gather %.1f  rmq-sort %.1f  rmq-fill %.1f  backtrack+compact %.1f %% of %.2f wave-s\n", 100. * c->h_ctr->lext_clk_big[0] / (tg + 1), 100. * c->h_ctr->lext_clk_big[1] / (tg + 1), 100. * c->h_ctr->lext_clk_big[2] / (tg + 1), 100. * c->h_ctr->lext_clk_big[3] / (tg + 1), tg / 1e8); }
-            { const unsigned long long *dd = c->h_ctr->lext_d_big;
-              fprintf(stderr, "[dbg] RMQ, the giants: %llu reads, %llu anchors (largest read %llu), per anchor: %.2f ring blocks, %.3f trips behind the ring with %.2f old blocks, list length %.1f, %.2f inner chunks\n",
-                      dd[6], dd[0], dd[7], (double)dd[1] / (dd[0] + 1), (double)dd[2] / (dd[0] + 1), (double)dd[3] / (dd[0] + 1), (double)dd[4] / (dd[0] + 1), (double)dd[5] / (dd[0] + 1)); }
-            fprintf(stderr, "[dbg] regions kernel, second size: slowest read %.1f ms (%llu bases), all reads %.1f wave-ms\n", (c->h_ctr->lext_slow_part[3] >> 32) / 1e5, c->h_ctr->lext_slow_part[3] & 0xffffffffull, c->h_ctr->lext_sum_part[3] / 1e5);
-            fprintf(stderr, "[dbg] regions kernel, second size, largest per-read time of each step (ms): gen_regs %.1f  parent/select %.1f  squeeze %.1f  set-up %.1f  ksw %.1f  z-drop %.1f  update_extra %.1f  staging %.1f\n", c->h_ctr->lext_phase_max[4] / 1e5, c->h_ctr->lext_phase_max[5] / 1e5, c->h_ctr->lext_phase_max[6] / 1e5, c->h_ctr->lext_phase_max[7] / 1e5, c->h_ctr->lext_phase_max[8] / 1e5, c->h_ctr->lext_phase_max[9] / 1e5, c->h_ctr->lext_phase_max[10] / 1e5, c->h_ctr->lext_phase_max[11] / 1e5);
-            for (int pp = 0; pp < 3; ++pp) fprintf(stderr, "[dbg] chains kernel, part %d (0 lists of later passes, 1 all but the giants, 2 the giants): slowest read %.1f ms, all reads %.1f wave-ms\n", pp, (c->h_ctr->lext_slow_part[pp] >> 32) / 1e5, c->h_ctr->lext_sum_part[pp] / 1e5);
-            for (int i = 0; i < SINK_SHARDS; ++i) { sr += c->h_ctr->ext_n_recs[i]; sa += c->h_ctr->ext_n_anch[i]; mr = std::max<unsigned long long>(mr, c->h_ctr->ext_n_recs[i]); ma = std::max<unsigned long long>(ma, c->h_ctr->ext_n_anch[i]); }
-            fprintf(stderr, "[dbg] chain hand-over: %llu chains, %llu anchors; fullest shard %llu / %u chains, %llu / %llu anchors\n", sr, sa, mr, c->sink.cap_recs, ma, c->sink.cap_anch);
-        }
-        SH_HIP(hipEventRecord(c->ev_ext[1], s));
-        SH_HIP(hipEventSynchronize(c->ev_ext[1]));
-        ext_regions = c->h_ctr->ext_regions; ext_dropped = c->h_ctr->ext_dropped;
-        if (stats) { stats->n_ext_unresolved += c->h_ctr->lext_unresolved; stats->n_rmq_rechained += c->h_ctr->lext_rechained; stats->n_rmq_tied += c->h_ctr->lext_rmq_tie; stats->n_rmq_exact += n_exact_reads + c->h_ctr->lext_exact_direct; stats->n_ext_ondemand += n_ondemand; stats->n_rmq_open += c->h_ctr->lext_rmq_open; }
-        hipEventElapsedTime(&ms_ext, c->ev_ext[0], c->ev_ext[1]);
-    } else if (c->ext) {
-        ExtArgs x{};
-        x.in.ref = idx->d_ref; x.in.cstart = idx->d_cstart; x.in.n_contigs = idx->n_contigs;
-        x.in.bases = d_bases; x.in.offsets = d_offsets; x.in.cx = c->sink.cx; x.in.cq = c->sink.cq; x.in.recs = c->sink.recs; x.in.head = c->sink.head;
-        x.P = c->AP; x.scratch = c->d_ext_scratch; x.scratch_per_wave = c->ext_scratch_per_wave; x.max_read_len = c->max_read_len; x.reg_cap = c->ext_reg_cap;
-        x.list = c->d_ext_list; x.n_list = &c->d_ctr->ext_n_list; x.ticket = &c->d_ctr->ext_ticket;
-        x.ctr = c->d_ctr; x.flags = d_flags; x.trace = d_trace; x.flag_only = d_trace == nullptr; x.n_reads = n_reads;
-        x.best = c->sink.best; x.tie = c->sink.tie; x.redo = c->d_ext_redo;
-        x.unres_list = c->d_ext_unres[0]; x.n_unres = &c->d_ctr->ext_n_unres;
-        uint32_t n_sr_ondemand = 0;
-        // minimap2 has no limit on a read's chains or regions; k_regs_align's per-wave working memory has (ext_reg_cap).  Reads beyond it are
-        // listed and redone with memory allocated for them, four times the last size per round, until none is left; only when the device
-        // cannot give it do they keep their chain-level answer (counted: sh_stats.n_ext_unresolved).  h_ctr holds the last launch's counters.
-        auto sr_on_demand = [&](ExtArgs xa) -> sh_status {
-            uint32_t n_un = c->h_ctr->ext_n_unres, cap = c->ext_reg_cap;
-            n_sr_ondemand += n_un;
-            int cur = 0;
-            while (n_un > 0) {
-                DevBuf scratch;      // this round's working memory: gone at the end of the round, after the stream has been synchronised
-                unsigned long long per = 0; uint32_t waves = 0;
-                if (cap < (1u << 24)) {
-                    cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 4, 1u << 24);
-                    per = align_scratch_layout(c->max_read_len, cap, nullptr, nullptr, nullptr);
-                    for (waves = std::min<uint32_t>(n_un, 8); waves > 0 && scratch.alloc(per * waves) != hipSuccess; waves >>= 1) (void)hipGetLastError();
-                }
-                uint8_t *const buf = scratch.as<uint8_t>();
-                const uint32_t z4[4] = {0, 0, n_un, 0};      // ext_n_unres, ext_ticket_unres, ext_n_unres_in
-                SH_HIP(hipMemcpyAsync(&c->d_ctr->ext_n_unres, z4, 16, hipMemcpyHostToDevice, s));
-                xa.list = c->d_ext_unres[cur]; xa.n_list = &c->d_ctr->ext_n_unres_in; xa.ticket = &c->d_ctr->ext_ticket_unres;
-                if (buf) { xa.scratch = buf; xa.scratch_per_wave = per; xa.reg_cap = cap; xa.unres_list = c->d_ext_unres[cur ^ 1]; xa.n_unres = &c->d_ctr->ext_n_unres; }
-                else {      // no memory to be had: counted, chain-level answer (on the context's own working memory: the last round's is freed)
-                    xa.unres_list = nullptr; xa.n_unres = nullptr; waves = std::min<uint32_t>(c->ext_waves, n_un);
-                    xa.scratch = c->d_ext_scratch; xa.scratch_per_wave = c->ext_scratch_per_wave; xa.reg_cap = c->ext_reg_cap;
-                }
-                hipLaunchKernelGGL(k_regs_align, dim3(waves), dim3(64), 0, s, xa);
-                SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-                SH_HIP(hipStreamSynchronize(s));
-                SH_HIP(hipGetLastError());
-                if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-                SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
-                if (!buf) break;
-                n_un = c->h_ctr->ext_n_unres; cur ^= 1;
-            }
-            return SH_OK;
-        };
-        SH_HIP(hipEventRecord(c->ev_ext[0], s));
-        hipLaunchKernelGGL(k_ext_list, dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_reads + 4 * EXT_SLAB - 1) / (4 * EXT_SLAB), 1), EXT_LIST_BLOCKS)), dim3(256), 0, s, x);
-        if (d_trace != nullptr) {
-            // trace mode: every read that handed over a chain goes through mm_gen_regs .. mm_filter_regs (one wave per read)
-            hipLaunchKernelGGL(k_regs_align, dim3(c->ext_waves), dim3(64), 0, s, x);
-        } else {
-            // flag-only: the lists hold each read's candidates for regs[0]; the top chain settles nearly every read (one lane each)
-            hipLaunchKernelGGL(k_ext_top, dim3(grid * 4), dim3(64), 0, s, x);
-        }
-        SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-        SH_HIP(hipStreamSynchronize(s));
-        SH_HIP(hipGetLastError());
-        if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;       // hand-over buffers full: the caller cuts the chunk in two
-        SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u: 2 chains, 3 primaries, 4 read length, 5 window, 6 regions)", c->h_ctr->ext_overflow);
-        ext_list = c->h_ctr->ext_n_list;
-        if (d_trace != nullptr && c->h_ctr->ext_n_unres > 0) { const uint32_t keep = ext_list; sh_status st = sr_on_demand(x); if (st != SH_OK) return st; ext_list = keep; }
-        const uint32_t n_redo = c->h_ctr->ext_n_redo;
-        if (d_trace == nullptr) { c->dbg_ptr[1] = c->d_ext_redo; c->dbg_n[1] = n_redo; }
-        if (cs.dbg_set) fprintf(stderr, "[dbg] extension stage: %u reads handed over chains, %u not settled by their top chain (tie %u, missing %u, short stretch %u, z-drop %u)\n", ext_list, n_redo, c->h_ctr->ext_reason[1], c->h_ctr->ext_reason[2], c->h_ctr->ext_reason[3], c->h_ctr->ext_reason[4]);
-        uint32_t n_redo2 = 0;
-        if (d_trace == nullptr && n_redo > 0) {
-            // second pass: regs[0] of the reads its max stretch could not vouch for goes through mm_align1 (one wave per read)
-            ExtArgs x1 = x;
-            x1.list = c->d_ext_redo; x1.n_list = &c->d_ctr->ext_n_redo; x1.ticket = &c->d_ctr->ext_ticket2; x1.top_only = 1; x1.redo2 = c->d_ext_list;     // the first list is spent
-            x1.scratch_per_wave = c->ext_scratch_per_wave_top; x1.reg_cap = 64;
-            x1.stats = (cs.dbg & DBG_STATS) != 0;
-            if (x1.stats) {
-                SH_HIP(hipMemsetAsync(c->d_ctr->ext_clk, 0, sizeof(c->d_ctr->ext_clk) + sizeof(c->d_ctr->ext_diag) + sizeof(c->d_ctr->ext_hist), s));
-                hipLaunchKernelGGL(k_regs_align_top_stats, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
-            } else hipLaunchKernelGGL(k_regs_align_top, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
-            SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-            SH_HIP(hipStreamSynchronize(s));
-            SH_HIP(hipGetLastError());
-            SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
-            n_redo2 = c->h_ctr->ext_n_redo2;
-            c->dbg_ptr[2] = c->d_ext_list; c->dbg_n[2] = n_redo2;
-            if (x1.stats) {
-                const Counters &h = *c->h_ctr;
-                unsigned long long tot = 0;
-                for (int i = 0; i < ACLK_N; ++i) tot += h.ext_clk[i];
-                fprintf(stderr, "[dbg] k_regs_align_top, %u waves: ksw fill %.1f  ksw backtrack %.1f  staging %.1f  lane-0 walks %.1f  other %.1f %% of %.3f wave-s; %u reads, %u ksw_extd2 calls (%u with T16 <= 256, Q16 <= 336 and the exact maximum)\n",
-                        c->ext_waves_top, 100. * h.ext_clk[0] / (tot + 1), 100. * h.ext_clk[1] / (tot + 1), 100. * h.ext_clk[2] / (tot + 1), 100. * h.ext_clk[3] / (tot + 1), 100. * h.ext_clk[4] / (tot + 1), tot / 1e8, h.ext_hist[22], h.ext_hist[20], h.ext_hist[21]);
-                fprintf(stderr, "[dbg] ksw_extd2 calls by T16 (<= 16, 32, 64, 128, 256, 448, more): %u %u %u %u %u %u %u; anti-diagonals: %llu %llu %llu %llu %llu %llu %llu\n", h.ext_hist[0], h.ext_hist[1], h.ext_hist[2], h.ext_hist[3], h.ext_hist[4], h.ext_hist[5], h.ext_hist[6],
-                        h.ext_diag[0], h.ext_diag[1], h.ext_diag[2], h.ext_diag[3], h.ext_diag[4], h.ext_diag[5], h.ext_diag[6]);
-                fprintf(stderr, "[dbg] ksw_extd2 calls by Q16 (<= 16, 32, 64, 128, 256, 336, more): %u %u %u %u %u %u %u; by direction bytes (<= 4096, <= 9840, <= 32768, more): %u %u %u %u\n", h.ext_hist[8], h.ext_hist[9], h.ext_hist[10], h.ext_hist[11], h.ext_hist[12], h.ext_hist[13], h.ext_hist[14],
-                        h.ext_hist[16], h.ext_hist[17], h.ext_hist[18], h.ext_hist[19]);
-            }
-        }
-        uint32_t n_fallback = 0; double ms_fallback = 0;
-        if (n_redo2 > 0) {
-            n_fallback = n_redo2;
-            const auto t_fb = std::chrono::steady_clock::now();
-            // third pass, reads whose top chain does not survive: all their chains, then the complete procedure.  They take the repeat path
-            // again (wave-parallel expansion, sort classes, cluster DP) with nothing filtered; the legacy lane-per-read kernel that used to
-            // carry this pass spent 130 ms on 507 reads of the sr-div workload.  The hand-over buffers start over.
-            Counters z = *c->h_ctr;
-            memset(z.ext_n_recs, 0, sizeof(z.ext_n_recs)); memset(z.ext_n_anch, 0, sizeof(z.ext_n_anch));
-            z.n_defer = 0; z.arena_cursor = 0; z.ext_n_list2 = n_redo2; z.ext_ticket3 = 0;
-            z.n_big[0] = n_redo2; z.n_big[1] = 0; z.n_big_defer[0] = z.n_big_defer[1] = 0;
-            SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
-            ExtArgs x2 = x;
-            x2.list = c->d_ext_list; x2.n_list = &c->d_ctr->ext_n_list2; x2.ticket = &c->d_ctr->ext_ticket3;
-            hipLaunchKernelGGL(k_ext_reset, dim3(64), dim3(256), 0, s, x2);
-            SH_HIP(hipMemcpyAsync(c->d_big[0][0], c->d_ext_list, (size_t)n_redo2 * 4, hipMemcpyDeviceToDevice, s));
-            K3Args kf = k;
-            kf.sink.best = nullptr; kf.sink.tie = nullptr; kf.t_mode = 0; kf.flag_only = 0; kf.quiet = 1;
-            K2Args rb = b;
-            rb.sink.best = nullptr; rb.sink.tie = nullptr; rb.quiet = 1;
-            int f0 = 0, f1 = c->dbg_ptr[0] == c->d_big[1][0] ? 1 : 0;      // not over the first pass's list of re-chained reads (sh_ctx_debug_list)
-            { sh_status st = run_repeat_path(kf, rb, f0, f1, resk_done); if (st != SH_OK) return st; }
-            // reads the repeat path handed to the legacy kernel and that found no room there
-            rb.work_defer = c->d_work_defer;
-            uint32_t left = c->h_ctr->n_defer;
-            int rounds2 = 0;
-            while (left > 0) {
-                SH_CHECK(++rounds2 < 64, SH_ERR_OOM, "re-sketch arena too small for the extension stage's last pass; set SCRUBBY_HIP_ARENA_MB");
-                std::swap(c->d_work_defer, c->d_work_defer2);
-                Counters z2 = *c->h_ctr;
-                z2.n_defer = 0; z2.arena_cursor = 0; z2.n_resketch = left;
-                SH_HIP(hipMemcpyAsync(c->d_ctr, &z2, sizeof(Counters), hipMemcpyHostToDevice, s));
-                rb.work = c->d_work_defer2; rb.work_count = &c->d_ctr->n_resketch; rb.work_begin = 0; rb.work_defer = c->d_work_defer;
-                hipLaunchKernelGGL(k_chain_large, dim3(grid), dim3(64), 0, s, rb);
-                SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-                SH_HIP(hipStreamSynchronize(s));
-                const uint32_t nd = c->h_ctr->n_defer;
-                SH_CHECK(nd < left, SH_ERR_OOM, "re-sketch arena too small for the extension stage's last pass; set SCRUBBY_HIP_ARENA_MB");
-                left = nd;
-            }
-            if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-            hipLaunchKernelGGL(k_regs_align, dim3(c->ext_waves), dim3(64), 0, s, x2);
-            SH_HIP(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-            SH_HIP(hipStreamSynchronize(s));
-            SH_HIP(hipGetLastError());
-            if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
-            SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
-            if (c->h_ctr->ext_n_unres > 0) { sh_status st = sr_on_demand(x2); if (st != SH_OK) return st; }
-            ms_fallback = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fb).count();
-        }
-        if (stats) { stats->n_ext_fallback += n_fallback; stats->ms_ext_fallback += ms_fallback; stats->n_ext_unresolved += c->h_ctr->lext_unresolved; stats->n_ext_ondemand += n_sr_ondemand; }
-        if (c->h_ctr->lext_unresolved) {
-            static bool warned_sr = false;
-            if (!warned_sr) { warned_sr = true; fprintf(stderr, "[scrubby-hip] WARNING: %u read(s) outgrew the extension stage's working memory (e.g. read %u of its batch, code %u: 2 chains, 3 primaries, 6 regions); they keep their chain-level answer (mapped)\n", c->h_ctr->lext_unresolved, c->h_ctr->lext_err_read, c->h_ctr->lext_err_code); }
-        }
-        SH_HIP(hipEventRecord(c->ev_ext[1], s));
-        SH_HIP(hipEventSynchronize(c->ev_ext[1]));
-        ext_regions = c->h_ctr->ext_regions; ext_dropped = c->h_ctr->ext_dropped;
-        if (d_trace == nullptr) ext_list = n_redo;      // reads that needed base-level alignment
-        hipEventElapsedTime(&ms_ext, c->ev_ext[0], c->ev_ext[1]);
+// ---- the repeat path ----
+// The repeat path over the lists d_big[0][cur0] (pass 0, mid_occ) -> d_big[1][cur1] (pass 1, max_occ), then k_chain_large over the rare
+// reads K1 or k_expand could not take, until no read is deferred any more: reads that found no arena room come back in the next iteration.
+// k and b are ch.k and ch.b, or a caller's varied copies of them (rechain_list).  Reads the counters back after every iteration.
+static sh_status run_repeat_path(sh_ctx *c, Chunk &ch, K3Args &k, K2Args &b, int &cur0, int &cur1)
+{
+    const hipStream_t s = ch.s;
+    for (int iter = 0;; ++iter) {
+        SH_CHECK(iter < 256, SH_ERR_OOM, "chain arena (%llu MiB) too small; set SCRUBBY_HIP_ARENA_MB", (unsigned long long)(c->arena_bytes >> 20));
+        k.pass = 0; k.max_occ = c->P.mid_occ;
+        k.list = c->d_big[0][cur0]; k.list_count = &c->d_ctr->n_big[0];
+        k.defer_list = c->d_big[0][cur0 ^ 1]; k.defer_count = &c->d_ctr->n_big_defer[0];
+        k.next_list = c->d_big[1][cur1]; k.next_count = &c->d_ctr->n_big[1];
+        SH_TRY(big_pass(c, k, ch.grid, s));
+        if (ch.first && ch.k2_late) SH_TRY(launch_k2(c, ch));
+        k.pass = 1; k.max_occ = c->P.max_occ;
+        k.list = c->d_big[1][cur1]; k.list_count = &c->d_ctr->n_big[1];
+        k.defer_list = c->d_big[1][cur1 ^ 1]; k.defer_count = &c->d_ctr->n_big_defer[1];
+        k.next_list = nullptr; k.next_count = nullptr;
+        SH_TRY(big_pass(c, k, ch.grid, s));
+        // the rare reads K1 or k_expand could not take
+        b.work = c->d_work_resketch; b.work_count = &c->d_ctr->n_resketch; b.work_begin = ch.resk_done;
+        hipLaunchKernelGGL(k_chain_large, dim3(ch.grid), dim3(64), 0, s, b);
+        if (ch.first && c->use_k1) SH_HIP(hipStreamWaitEvent(s, c->evx[5], 0));
+        SH_TRY(read_counters(c, s));
+        const Counters &h = *c->h_ctr;
+        if (ch.first) { ch.snap = h; ch.first = false; c->dbg_ptr[0] = c->d_big[1][cur1]; c->dbg_n[0] = ch.snap.n_big[1]; c->dbg_ptr[1] = c->dbg_ptr[2] = nullptr; c->dbg_n[1] = c->dbg_n[2] = 0; }
+        if (k.dbg & DBG_STATS) print_repeat_pass(h, iter);
+        ch.resk_done = h.n_resketch;
+        const uint32_t d0 = h.n_big_defer[0], d1 = h.n_big_defer[1];
+        if (d0 == 0 && d1 == 0) break;
+        // a read deferred when it was alone in the arena can never fit
+        SH_CHECK(!(d0 == h.n_big[0] && h.n_big[0] == 1 && d1 == 0) && !(d1 == h.n_big[1] && h.n_big[1] == 1 && d0 == 0),
+                 SH_ERR_OOM, "chain arena (%llu MiB) too small for one read; set SCRUBBY_HIP_ARENA_MB", (unsigned long long)(c->arena_bytes >> 20));
+        Counters z = h;
+        z.n_big[0] = d0; z.n_big[1] = d1; z.n_big_defer[0] = z.n_big_defer[1] = 0;
+        SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
+        cur0 ^= 1; cur1 ^= 1;
     }
+    return SH_OK;
+}
+
+// legacy path deferrals: reads of k_chain_large that found no room in its arena slice come back alone, until none is left.  h_ctr holds
+// the counters of the launch that deferred them; `of_what` completes the error text ("" or which pass ran out).
+static sh_status legacy_defers(sh_ctx *c, Chunk &ch, K2Args &bb, const char *of_what)
+{
+    const hipStream_t s = ch.s;
+    uint32_t n_defer = c->h_ctr->n_defer;
+    int rounds = 0;
+    while (n_defer > 0) {
+        SH_CHECK(++rounds < 64, SH_ERR_OOM, "re-sketch arena too small%s; set SCRUBBY_HIP_ARENA_MB", of_what);
+        std::swap(c->d_work_defer, c->d_work_defer2);
+        Counters z = *c->h_ctr;
+        z.n_defer = 0; z.arena_cursor = 0; z.n_resketch = n_defer;
+        SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
+        bb.work = c->d_work_defer2; bb.work_count = &c->d_ctr->n_resketch; bb.work_begin = 0; bb.work_defer = c->d_work_defer;
+        hipLaunchKernelGGL(k_chain_large, dim3(ch.grid), dim3(64), 0, s, bb);
+        SH_TRY(read_counters(c, s));
+        const uint32_t nd = c->h_ctr->n_defer;
+        SH_CHECK(nd < n_defer, SH_ERR_OOM, "re-sketch arena too small%s; set SCRUBBY_HIP_ARENA_MB", of_what);
+        n_defer = nd;
+    }
+    return SH_OK;
+}
+
+// A list of n reads through the repeat path once more, with the caller's varied arguments (kf, rb: `quiet` set, so that the reads are not
+// counted twice), starting from the sides f0 / f1 of the ping-pong lists.  The caller has reset the device's counters for it (each caller
+// clears its own fields: n_big[0] = n among them) and queued what forgets the reads' first visit.
+static sh_status rechain_list(sh_ctx *c, Chunk &ch, const uint32_t *list, uint32_t n, K3Args kf, K2Args rb, int f0, int f1, const char *of_what)
+{
+    SH_HIP(hipMemcpyAsync(c->d_big[0][f0], list, (size_t)n * 4, hipMemcpyDeviceToDevice, ch.s));
+    SH_TRY(run_repeat_path(c, ch, kf, rb, f0, f1));
+    rb.work_defer = c->d_work_defer;
+    return legacy_defers(c, ch, rb, of_what);
+}
+
+// ---- the extension stage, long-read presets ----
+// The two things every pass of the stage selects in its copy of ExtLongArgs.
+// Working memory: tier i of the context ([phase * 2 + size]), or a buffer of the caller's.
+static void ext_memory(ExtLongArgs &x, uint8_t *scratch, unsigned long long per_wave, const LongSizes &sz) { x.scratch = scratch; x.scratch_per_wave = per_wave; x.sz = sz; }
+static void ext_tier(ExtLongArgs &x, const sh_ctx *c, int i) { ext_memory(x, c->d_lext[i], c->lext_per_wave[i], c->lext_sz[i]); }
+// Lists: the one a pass takes its reads from (ids, count, ticket), the one it spills the reads that outgrow its working memory to, and
+// the one for reads that outgrow the largest (either may be none: {}).  What belongs to one launch only - the part of a size-ordered
+// list with its histogram, the started / follow_done words - is cleared: a pass that wants one sets it after this call.
+struct ExtList { uint32_t *ids = nullptr, *n = nullptr, *ticket = nullptr; };
+static void ext_lists(ExtLongArgs &x, ExtList from, ExtList spill, ExtList unres)
+{
+    x.list = from.ids; x.n_list = from.n; x.ticket = from.ticket;
+    x.big_list = spill.ids; x.n_big = spill.n;
+    x.unres_list = unres.ids; x.n_unres = unres.n;
+    x.hist = nullptr; x.bin_cut = 0; x.part = 0; x.started = nullptr; x.follow_done = nullptr;
+}
+static ExtList lext_big(const sh_ctx *c) { return {c->d_lext_big, &c->d_ctr->lext_n_big, &c->d_ctr->lext_ticket_big}; }
+static ExtList lext_big2(const sh_ctx *c) { return {c->d_lext_big2, &c->d_ctr->lext_n_big2, &c->d_ctr->lext_ticket_big2}; }
+static ExtList lext_unres(const sh_ctx *c, int side) { return {c->d_lext_unres[side], &c->d_ctr->lext_n_unres, nullptr}; }
+static bool lext_coop(const sh_ctx *c) { return !c->cs.giants_plain && !c->cs.no_coop; }
+
+// The arguments every pass of the stage starts from: the whole list of reads with chains, no working memory chosen yet.
+static ExtLongArgs long_ext_args(const sh_ctx *c, const Chunk &ch)
+{
+    const sh_index *idx = c->idx;
+    const CallSwitches &cs = c->cs;
+    ExtLongArgs x{};
+    x.I.in.ref = idx->d_ref; x.I.in.cstart = idx->d_cstart; x.I.in.n_contigs = idx->n_contigs;
+    x.I.in.bases = ch.d_bases; x.I.in.offsets = ch.d_offsets; x.I.in.cx = c->sink.cx; x.I.in.cq = c->sink.cq; x.I.in.recs = c->sink.recs; x.I.in.head = c->sink.head;
+    x.I.rec = c->use_long ? c->d_lrec : c->d_records; x.I.k1info = c->d_k1info; x.I.seed_off = c->use_long ? c->d_seed_off : nullptr; x.I.seed_cap = c->seed_cap;
+    x.P = c->LP; x.AP = c->AP; x.CP = c->P;
+    x.AR.base = c->d_larena; x.AR.cap = c->larena_bytes; x.AR.cursor = &c->d_ctr->arena_cursor; x.AR.hdr = c->d_lhdr;
+    x.list = c->d_ext_list; x.n_list = &c->d_ctr->ext_n_list; x.ctr = c->d_ctr; x.flags = ch.d_flags; x.trace = ch.d_trace; x.flag_only = ch.d_trace == nullptr;
+    x.clk = cs.dbg_set ? (cs.dbg_exact ? 3 : 1) : 0; x.probe = cs.no_probe ? 0 : 1;
+    x.drop = ch.k.locus ? c->d_lr_drop : nullptr; x.fb_list = c->d_lr_fb; x.n_fb = &c->d_ctr->lr_n_fb;
+    x.exact_list = c->d_lext_exact_list; x.n_exact = &c->d_ctr->lext_n_exact;
+    x.exact_list2 = c->d_lext_exact_list2; x.n_exact2 = &c->d_ctr->lext_n_exact2;
+    x.kind = c->d_lkind ? c->d_lkind + c->lkind_r0 : nullptr;
+    return x;
+}
+
+// Reads that outgrew the second size of a kernel's working memory too (minimap2 has no such limits): memory is allocated for them,
+// four times the size before, until they fit (a chain-anchor count in the millions, an alignment of max_sw_mat cells); only when
+// the device cannot give it do they keep their chain-level answer, counted and named in a warning.  xa: the arguments of the
+// second-size pass; h_ctr holds its counters.  Reads the counters back after every round.
+static sh_status on_demand(sh_ctx *c, Chunk &ch, int phase, ExtLongArgs xa)      // phase: 0 chains, 1 regions / alignment, 2 chains with the exact long join
+{
+    const hipStream_t s = ch.s;
+    uint32_t n_un = c->h_ctr->lext_n_unres;
+    ch.n_ondemand += n_un;
+    LongSizes q = phase == 2 ? c->lext_exact_sz[1] : c->lext_sz[phase * 2 + 1];
+    int cur = 0;
+    for (int round = 0; n_un > 0; ++round) {
+        DevBuf buf;      // this round's working memory: gone at the end of the round, which read_counters has synchronised by then
+        unsigned long long per = 0; uint32_t waves = 0;
+        if (round < 5) {
+            q.cap_a = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_a * 4, 1u << 28); q.cap_u = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_u * 4, 1u << 26); q.cap_r = q.cap_u;
+            q.cap_m = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_m * 4, 1u << 26); q.cap_k = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_k * 4, 1u << 22);
+            q.cap_t = (uint32_t)std::min<uint64_t>((uint64_t)q.cap_t * 4, 1u << 28); q.cap_p = std::min<uint64_t>(q.cap_p * 4, 4ull << 30);
+            per = long_ws_carve(nullptr, nullptr, q);
+            for (waves = std::min<uint32_t>(n_un, 4); waves > 0 && buf.alloc(per * waves) != hipSuccess; waves >>= 1) (void)hipGetLastError();
+        }
+        if (!buf.p) {      // no memory to be had: counted, warned about, chain-level answer
+            hipLaunchKernelGGL(k_lext_giveup, dim3(16), dim3(256), 0, s, (const uint32_t *)c->d_lext_unres[cur], n_un, ch.d_flags, ch.d_trace, c->d_lhdr, c->d_ctr, xa.kind);
+            SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_unres, 0, 4, s));
+            return read_counters(c, s);
+        }
+        const uint32_t zero2[4] = {0, 0, n_un, 0};
+        SH_HIP(hipMemcpyAsync(&c->d_ctr->lext_n_unres, zero2, 16, hipMemcpyHostToDevice, s));      // lext_n_unres, lext_ticket_unres, lext_n_unres_in
+        ext_memory(xa, buf.as<uint8_t>(), per, q);
+        ext_lists(xa, {c->d_lext_unres[cur], &c->d_ctr->lext_n_unres_in, &c->d_ctr->lext_ticket_unres}, {}, lext_unres(c, cur ^ 1));
+        if (phase == 0) hipLaunchKernelGGL((k_long_chains<4096, false, true>), dim3(waves), dim3(64), 0, s, xa);
+        else if (phase == 2) hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(waves), dim3(64), 0, s, xa);
+        else hipLaunchKernelGGL(k_regs_align_long, dim3(waves), dim3(64), 0, s, xa);
+        SH_TRY(read_counters(c, s));
+        if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+        n_un = c->h_ctr->lext_n_unres; cur ^= 1;
+    }
+    return SH_OK;
+}
+
+// lr_coop_fill's queue, counters and descriptors for one launch of an EXACT instance (three regions: the giants, E2a, E1 - launches that
+// may run side by side); zeroed on the launch's stream
+static sh_status coop_setup(sh_ctx *c, ExtLongArgs &xx, int which, hipStream_t st, uint32_t n_blocks)
+{
+    constexpr uint32_t QCAP = 65536, NDESC = 512;
+    constexpr size_t off_desc = 256, off_ready = off_desc + NDESC * sizeof(LongCoopDesc), off_items = off_ready + QCAP * 4, region = off_items + QCAP * 16;
+    static_assert(sizeof(LongCoopDesc) % 8 == 0 && off_items % 16 == 0 && region % 256 == 0, "coop layout");
+    if (!c->d_coop) SH_HIP(c->own.device(c->d_coop, 3 * region));
+    uint8_t *base = c->d_coop + (size_t)which * region;
+    SH_HIP(hipMemsetAsync(base, 0, off_items, st));
+    xx.coop.q_res = (uint32_t *)base; xx.coop.q_head = (uint32_t *)(base + 64); xx.coop.active = (uint32_t *)(base + 128); xx.coop.n_reads = (uint32_t *)(base + 192);
+    xx.coop.desc = (LongCoopDesc *)(base + off_desc); xx.coop.ready = (uint32_t *)(base + off_ready); xx.coop.items = (uint4 *)(base + off_items);
+    xx.coop.cap = QCAP; xx.coop_on = n_blocks <= NDESC;
+    return SH_OK;
+}
+
+// Largest reads first, like every list of the stage: a pass ends with its slowest read (a read of 10^5 chain anchors is more than a second
+// of one wave).  d_ext_redo takes the bin of each list entry, lext_hist - zero on entry - the bins' sizes, then their cursors.
+static void lext_order(sh_ctx *c, Chunk &ch, uint32_t blocks, const uint32_t *list, const uint32_t *n_list, uint32_t *out)
+{
+    uint32_t *const hist = c->d_ctr->lext_hist;
+    hipLaunchKernelGGL(k_lext_bins, dim3(blocks), dim3(256), 0, ch.s, c->sink.recs, c->sink.head, list, n_list, c->d_ext_redo, hist, ch.d_offsets);
+    hipLaunchKernelGGL(k_lext_scan, dim3(1), dim3(1), 0, ch.s, hist);
+    hipLaunchKernelGGL(k_lext_scatter, dim3(blocks), dim3(256), 0, ch.s, list, n_list, c->d_ext_redo, hist, out);
+}
+
+// first kernel: final chains - the giants aside, the main grid, then the reads that outgrew the first size with the large working memory
+static sh_status lext_chains_pass(sh_ctx *c, Chunk &ch, const ExtLongArgs &x)
+{
+    const hipStream_t s = ch.s;
+    const CallSwitches &cs = c->cs;
+    ExtLongArgs xa = x;
+    ext_tier(xa, c, 0);
+    ext_lists(xa, {x.list, x.n_list, &c->d_ctr->ext_ticket}, lext_big(c), {});
+    // reads whose chain anchors outgrow the first size go straight to the large working memory, on a side stream beside the rest
+    int bin_cut = 0;
+    while (bin_cut < 31 && (2ull << bin_cut) <= c->lext_sz[0].cap_a) ++bin_cut;      // bin b holds totals in [2^b, 2^(b+1))
+    bin_cut = std::max(1, bin_cut - (int)cs.giant_bins_down);
+    xa.hist = c->d_ctr->lext_hist; xa.bin_cut = bin_cut; xa.part = 1;
+    ExtLongArgs xg = xa;      // the giants: the same list, histogram, cut and spill list; their part of it, a ticket and the second size of their own
+    ext_tier(xg, c, 1);
+    xg.ticket = &c->d_ctr->lext_ticket_g; xg.part = 2;
+    // The giants - a dozen reads per half million, 10^5 chain anchors each, half a second and more of one wave apiece - are the pair's
+    // critical path.  With the 512-anchor ring their window reaches back into HBM at nearly every step, and those trips take several
+    // times longer while the main grid loads the memory system; so they get the 4096-anchor ring (99 KB of LDS a wave, no trip
+    // behind it), and because a CU the main grid has filled has no such room left, the main grid is held back until the giants'
+    // blocks have begun (k_wait_started: bounded, ~2 ms at most).  The main grid's blocks (13 KB) fit beside them.
+    uint32_t g_waves = std::min<uint32_t>(c->lext_waves[1], 64u);
+    if (cs.giant_waves != SW_UNSET) g_waves = std::min<uint32_t>(c->lext_waves[1], (uint32_t)cs.giant_waves);
+    xg.started = &c->d_ctr->lext_started;
+    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_started, 0, 4, s));
+    SH_HIP(hipEventRecord(c->evx[0], s));
+    hipStream_t sg = c->sx[c->side_pick[0]];
+    SH_HIP(hipStreamWaitEvent(sg, c->evx[0], 0));
+    const uint32_t m_waves = c->lext_waves[0];
+    // (the giants on the EXACT instance at once: the tree is only kept over the stretches that ask it, lr_rmq_fill - a giant with a tie
+    // is not chained twice, and the exact passes lose their longest reads)
+    const bool giants_exact = !cs.giants_plain;
+    if (lext_coop(c)) SH_TRY(coop_setup(c, xg, 0, sg, g_waves));      // the giants' waves share the long join of the launch's largest reads (lr_coop_fill, sh_long.h)
+    if (giants_exact) hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(g_waves), dim3(64), 0, sg, xg);
+    else hipLaunchKernelGGL((k_long_chains<4096, false, false>), dim3(g_waves), dim3(64), 0, sg, xg);
+    SH_HIP(hipEventRecord(c->evx[1], sg));
+    hipLaunchKernelGGL(k_wait_started, dim3(1), dim3(64), 0, s, (const uint32_t *)&c->d_ctr->lext_started, g_waves, 2000u);
+    hipLaunchKernelGGL((k_long_chains<512, false, false>), dim3(m_waves), dim3(64), 0, s, xa);
+    SH_HIP(hipStreamWaitEvent(s, c->evx[1], 0));
+    SH_TRY(read_counters(c, s));
+    if (lext_coop(c) && cs.dbg_set) {
+        uint32_t h[64] = {};
+        SH_HIP(hipMemcpy(h, c->d_coop, sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[dbg] long join shared among the giants' waves: %u reads in %u runs (%u taken off the queue)\n", h[48], h[0], h[16]);
+    }
+    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;       // hand-over buffers or arena full: the caller cuts the chunk in two
+    if (c->h_ctr->lext_n_big > 0) {
+        ext_tier(xa, c, 1);
+        ext_lists(xa, lext_big(c), {}, lext_unres(c, 0));
+        hipLaunchKernelGGL((k_long_chains<4096, false, true>), dim3(c->lext_waves[1]), dim3(64), 0, s, xa);
+        SH_TRY(read_counters(c, s));
+        if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+        SH_TRY(on_demand(c, ch, 0, xa));
+    }
+    ch.n_big_a += c->h_ctr->lext_n_big;
+    return SH_OK;
+}
+
+// The long join of these reads met two candidates of equal priority in a way that can change the chains: once more with
+// upstream's main tree beside the scan (sh_rmq_tree.h), maintained by the whole wave and asked at the ties.  The tree holds the
+// look-back window only and lives in LDS, so the passes run on the ordinary working memory of the chains kernel:
+//   E1   the 1024-anchor ring + a 1664-node tree (79 KB of LDS a wave, two waves to a CU), first size, largest reads first;
+//   E2a  the reads that needed the 4096-anchor ring in the first pass already, and those whose join holds more than 60 000 anchors: that ring + a 1792-node tree (156 KB, one wave to a
+//        CU), second size - on a side stream BESIDE E1 (launched first, so that its few blocks find their LDS);
+//   E2b  what outgrew E1's ring or working memory after all: the same instance, after E1;
+//   E3   (SCRUBBY_HIP_RMQ_ONE_LANE=1) what outgrew E2's ring or tree: both trees on one lane over node pools in the wave's scratch
+//        (lr_rmq_fill_tree) - the literal mg_lchain_rmq, for windows no LDS holds; then memory on demand for what outgrew the sizes.
+// h_ctr holds the counters of the chains pass (the two lists' lengths).
+static sh_status lext_exact_passes(sh_ctx *c, Chunk &ch, const ExtLongArgs &x)
+{
+    const hipStream_t s = ch.s;
+    const bool coop = lext_coop(c);
+    const uint32_t n_e1 = c->h_ctr->lext_n_exact, n_e2a = c->h_ctr->lext_n_exact2;
+    ch.n_exact_reads += n_e1 + n_e2a;
+    const auto t_ex = std::chrono::steady_clock::now();
+    ExtLongArgs xe = x;
+    xe.exact_list = nullptr; xe.n_exact = nullptr; xe.exact_list2 = nullptr; xe.n_exact2 = nullptr;
+    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big, 0, 8, s));       // lext_n_big, lext_ticket_big: E1's list of deferred reads
+    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big2, 0, 8, s));      // lext_n_big2, lext_ticket_big2 (the regions kernel's list: free until it starts): E2's
+    hipStream_t se = c->sx[c->side_pick[0]];
+    if (n_e2a > 0) {
+        ExtLongArgs x2 = xe;
+        ext_tier(x2, c, 1);
+        ext_lists(x2, {c->d_lext_exact_list2, &c->d_ctr->lext_n_exact2, &c->d_ctr->lext_ticket_exact2}, lext_big2(c), {});
+        x2.started = &c->d_ctr->lext_started;
+        const uint32_t w2 = std::min<uint32_t>({c->lext_waves[1], (uint32_t)c->n_cu / 2u, n_e2a});      // half of the CUs at most: E1's blocks need the others
+        SH_HIP(hipMemsetAsync(&c->d_ctr->lext_started, 0, 4, s));
+        SH_HIP(hipEventRecord(c->evx[0], s));
+        SH_HIP(hipStreamWaitEvent(se, c->evx[0], 0));
+        if (coop) SH_TRY(coop_setup(c, x2, 1, se, w2));
+        hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(w2), dim3(64), 0, se, x2);
+        SH_HIP(hipEventRecord(c->evx[1], se));
+        hipLaunchKernelGGL(k_wait_started, dim3(1), dim3(64), 0, s, (const uint32_t *)&c->d_ctr->lext_started, w2, 2000u);
+    }
+    if (n_e1 > 0) {
+        ExtLongArgs x1 = xe;
+        ext_tier(x1, c, 0);
+        SH_HIP(hipMemsetAsync(c->d_ctr->lext_hist, 0, sizeof(c->d_ctr->lext_hist), s));
+        lext_order(c, ch, 64, c->d_lext_exact_list, &c->d_ctr->lext_n_exact, c->d_lext_esorted);
+        ext_lists(x1, {c->d_lext_esorted, &c->d_ctr->lext_n_exact, &c->d_ctr->lext_ticket_exact}, lext_big(c), {});
+        const uint32_t w1 = std::min<uint32_t>({c->lext_waves[0], 2u * (uint32_t)c->n_cu, n_e1});
+        if (coop) SH_TRY(coop_setup(c, x1, 2, s, w1));
+        hipLaunchKernelGGL((k_long_chains<1024, true, false>), dim3(w1), dim3(64), 0, s, x1);
+    }
+    if (n_e2a > 0) SH_HIP(hipStreamWaitEvent(s, c->evx[1], 0));
+    SH_TRY(read_counters(c, s));
+    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+    const uint32_t n_e2b = c->h_ctr->lext_n_big;
+    if (n_e2b > 0) {
+        ext_tier(xe, c, 1);
+        ext_lists(xe, lext_big(c), lext_big2(c), {});
+        hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(std::min<uint32_t>({c->lext_waves[1], (uint32_t)c->n_cu, n_e2b})), dim3(64), 0, s, xe);
+        SH_TRY(read_counters(c, s));
+        if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+    }
+    const uint32_t n_e3 = c->h_ctr->lext_n_big2;
+    if (n_e3 > 0) {      // (only with SCRUBBY_HIP_RMQ_ONE_LANE, or reads beyond the second working-memory size)
+        ext_memory(xe, c->d_lext_exact[1], c->lext_exact_per_wave[1], c->lext_exact_sz[1]);
+        ext_lists(xe, lext_big2(c), {}, lext_unres(c, 0));
+        hipLaunchKernelGGL((k_long_chains<4096, true, false>), dim3(std::min<uint32_t>(c->lext_exact_waves[1], (uint32_t)c->n_cu)), dim3(64), 0, s, xe);
+        SH_TRY(read_counters(c, s));
+        if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+        if (c->h_ctr->lext_n_unres > 0) SH_TRY(on_demand(c, ch, 2, xe));
+    }
+    SH_HIP(hipMemsetAsync(&c->d_ctr->lext_n_big2, 0, 8, s));
+    if (c->cs.dbg_set) fprintf(stderr, "[dbg] exact long join: %u reads on the 1024-anchor ring beside %u on the 4096-anchor ring (%u with tied priorities so far), %u more on the large ring afterwards, %u beyond it, %.1f ms\n", n_e1, n_e2a, c->h_ctr->lext_rmq_tie, n_e2b, n_e3,
+                               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ex).count());
+    return SH_OK;
+}
+
+// second kernel: regions and alignment, with the follower of the second size beside the first launch
+static sh_status lext_regions_pass(sh_ctx *c, Chunk &ch, const ExtLongArgs &x)
+{
+    const hipStream_t s = ch.s;
+    ExtLongArgs xb = x;
+    ext_tier(xb, c, 2);
+    ext_lists(xb, {x.list, x.n_list, &c->d_ctr->lext_ticket_b}, lext_big2(c), {});
+    // The launch of the second size runs BESIDE the first (side stream), taking reads off the list as the first launch puts them
+    // there: the pass used to begin when the first had ended, and it is one alignment of ~4 * 10^8 cells on one wave - a third of a
+    // second during which nothing else ran.  Both grids are resident together (two waves per SIMD each: 8 per CU); what the
+    // follower leaves (it gives up after a bounded number of looks) the launch after the first one takes, as before.
+    // (both grids must be RESIDENT together - a follower that holds the slot a block of the first launch waits for would wait for that
+    // launch to end: the first launch gives up the slots the follower needs; its reads are drawn by ticket, so fewer blocks lose nothing)
+    const uint32_t slots = 8u * (uint32_t)c->n_cu;
+    const bool follow = !c->cs.no_follow && c->lext_waves[3] <= slots / 4;
+    const uint32_t w_first = follow ? std::min<uint32_t>(c->lext_waves[2], slots - c->lext_waves[3]) : c->lext_waves[2];
+    if (follow) {
+        SH_HIP(hipMemsetAsync(c->d_lext_big2, 0xff, (size_t)ch.n_reads * 4, s));
+        SH_HIP(hipMemsetAsync(&c->d_ctr->lext_t0_done, 0, 4, s));
+        SH_HIP(hipEventRecord(c->evx[2], s));
+    }
+    hipLaunchKernelGGL(k_regs_align_long, dim3(w_first), dim3(64), 0, s, xb);
+    // what the first launch spilled: the second size, reads beyond it listed for on_demand
+    ext_tier(xb, c, 3);
+    ext_lists(xb, lext_big2(c), {}, lext_unres(c, 0));
+    if (follow) {
+        // submitted in this order - first launch, its end mark, then the follower: two streams may share a hardware queue, and
+        // a follower submitted ahead of the launch it follows would then sit in front of it until its looks ran out
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(64), 0, s, &c->d_ctr->lext_t0_done, 1u);
+        ExtLongArgs xf = xb;
+        xf.follow_done = &c->d_ctr->lext_t0_done;
+        hipStream_t sf = c->sx[c->side_pick[1]];
+        SH_HIP(hipStreamWaitEvent(sf, c->evx[2], 0));
+        hipLaunchKernelGGL(k_regs_align_long, dim3(c->lext_waves[3]), dim3(64), 0, sf, xf);
+        SH_HIP(hipEventRecord(c->evx[3], sf));
+        SH_HIP(hipStreamWaitEvent(s, c->evx[3], 0));
+    }
+    SH_TRY(read_counters(c, s));
+    if (c->h_ctr->lext_n_big2 > 0) {
+        hipLaunchKernelGGL(k_regs_align_long, dim3(c->lext_waves[3]), dim3(64), 0, s, xb);
+        SH_TRY(read_counters(c, s));
+        SH_TRY(on_demand(c, ch, 1, xb));
+    }
+    ch.n_big_a += c->h_ctr->lext_n_big2;
+    return SH_OK;
+}
+
+// One round of the stage: round 0 over every read with a chain; round 1 - flag-only calls whose anchors k_lr_locus thinned out - over the
+// reads whose answer could depend on what was left out, after the repeat path has chained them again with every anchor
+static sh_status ext_round(sh_ctx *c, Chunk &ch, ExtLongArgs &x, int round)
+{
+    const hipStream_t s = ch.s;
+    SH_HIP(hipMemsetAsync(&c->d_ctr->arena_cursor, 0, 8, s));
+    ExtArgs xl{};
+    xl.in = x.I.in; xl.list = c->d_ext_list; xl.n_list = x.n_list; xl.n_reads = ch.n_reads; xl.ctr = c->d_ctr;
+    if (round == 0) hipLaunchKernelGGL(k_lext_list, dim3((uint32_t)((ch.n_reads + 255) / 256)), dim3(256), 0, s, xl, x.drop, (uint32_t)std::max(1, c->LP.min_cnt), x.fb_list, x.n_fb);
+    else hipLaunchKernelGGL(k_lext_list_from, dim3(256), dim3(256), 0, s, xl, (const uint32_t *)c->d_lr_fb, (const uint32_t *)&c->d_ctr->lr_n_fb);
+    // largest reads first (d_lext_sorted: the ordered list, every pass of the round reads it through x.list)
+    lext_order(c, ch, 256, c->d_ext_list, &c->d_ctr->ext_n_list, c->d_lext_sorted);
+    x.list = c->d_lext_sorted;
+    SH_TRY(lext_chains_pass(c, ch, x));
+    if (c->h_ctr->lext_n_exact + c->h_ctr->lext_n_exact2 > 0) SH_TRY(lext_exact_passes(c, ch, x));
+    SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "long-read extension stage: internal overflow code %u", c->h_ctr->ext_overflow);
+    ch.ext_list += c->h_ctr->ext_n_list;
+    return lext_regions_pass(c, ch, x);
+}
+
+// The reads whose answer could depend on the anchors k_lr_locus left out (d_lr_fb, n_fb of them): the repeat path once more with every
+// anchor, then the stage again.  Hand-over buffers, arena and lists start over; their first visit is forgotten (chain lists emptied,
+// lr_drop cleared).
+static sh_status lext_second_round(sh_ctx *c, Chunk &ch, ExtLongArgs &x, uint32_t n_fb)
+{
+    const hipStream_t s = ch.s;
+    Counters z = *c->h_ctr;
+    memset(z.ext_n_recs, 0, sizeof(z.ext_n_recs)); memset(z.ext_n_anch, 0, sizeof(z.ext_n_anch)); memset(z.lext_hist, 0, sizeof(z.lext_hist));
+    z.n_defer = 0; z.arena_cursor = 0;
+    z.n_big[0] = n_fb; z.n_big[1] = 0; z.n_big_defer[0] = z.n_big_defer[1] = 0;
+    z.ext_n_list = 0; z.ext_ticket = 0; z.lext_ticket_g = 0; z.lext_n_big = 0; z.lext_ticket_big = 0; z.lext_n_big2 = 0; z.lext_ticket_big2 = 0; z.lext_ticket_b = 0; z.lext_n_unres = 0; z.lext_ticket_unres = 0; z.lext_n_exact = 0; z.lext_ticket_exact = 0; z.lext_n_exact2 = 0; z.lext_ticket_exact2 = 0;
+    SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_lext_forget, dim3(64), dim3(256), 0, s, (const uint32_t *)c->d_lr_fb, n_fb, c->sink.head, c->d_lr_drop, &c->d_ctr->lr_fb_had);
+    K3Args kf = ch.k; kf.locus = 0; kf.quiet = 2;      // their chain-level count was taken back (k_lext_forget); the other statistics stay as they are
+    K2Args rb = ch.b; rb.quiet = 2;
+    SH_TRY(rechain_list(c, ch, c->d_lr_fb, n_fb, kf, rb, 0, 0, ""));
+    x.drop = nullptr;
+    return ext_round(c, ch, x, 1);
+}
+
+static sh_status long_ext_stage(sh_ctx *c, Chunk &ch)
+{
+    const hipStream_t s = ch.s;
+    ExtLongArgs x = long_ext_args(c, ch);
+    SH_TRY(pick_side_streams(c, s));
+    SH_HIP(hipEventRecord(c->ev_ext[0], s));
+    SH_TRY(ext_round(c, ch, x, 0));
+    const uint32_t n_fb = c->h_ctr->lr_n_fb;
+    if (c->cs.dbg_set) print_first_round(*c->h_ctr, ch.k.locus, n_fb);
+    if (ch.stats && ch.k.locus) { ch.stats->n_locus_reads += c->h_ctr->lr_locus_reads; ch.stats->n_locus_redone += n_fb; }
+    if (n_fb > 0) SH_TRY(lext_second_round(c, ch, x, n_fb));
+    if (c->h_ctr->lext_unresolved) {
+        static bool warned = false;
+        if (!warned) { warned = true; fprintf(stderr, "[scrubby-hip] WARNING: %u read(s) outgrew the extension stage's largest working memory (e.g. read %u of its batch, code %u: 18 chains, 20 read length, 21 chain anchors, 22 RMQ window, 23 seeds, 24 regions, 27-30 alignment window, 32 direction bytes); they keep their chain-level answer (mapped)\n", c->h_ctr->lext_unresolved, c->h_ctr->lext_err_read, c->h_ctr->lext_err_code); }
+    }
+    if (c->cs.dbg_set) print_long_stage(*c->h_ctr, ch, c->sink);
+    SH_HIP(hipEventRecord(c->ev_ext[1], s));
+    SH_HIP(hipEventSynchronize(c->ev_ext[1]));
+    ch.ext_regions = c->h_ctr->ext_regions; ch.ext_dropped = c->h_ctr->ext_dropped;
+    hipEventElapsedTime(&ch.ms_ext, c->ev_ext[0], c->ev_ext[1]);
+    return SH_OK;
+}
+
+// ---- the extension stage, short reads ----
+static ExtArgs sr_ext_args(const sh_ctx *c, const Chunk &ch)
+{
+    const sh_index *idx = c->idx;
+    ExtArgs x{};
+    x.in.ref = idx->d_ref; x.in.cstart = idx->d_cstart; x.in.n_contigs = idx->n_contigs;
+    x.in.bases = ch.d_bases; x.in.offsets = ch.d_offsets; x.in.cx = c->sink.cx; x.in.cq = c->sink.cq; x.in.recs = c->sink.recs; x.in.head = c->sink.head;
+    x.P = c->AP; x.scratch = c->d_ext_scratch; x.scratch_per_wave = c->ext_scratch_per_wave; x.max_read_len = c->max_read_len; x.reg_cap = c->ext_reg_cap;
+    x.list = c->d_ext_list; x.n_list = &c->d_ctr->ext_n_list; x.ticket = &c->d_ctr->ext_ticket;
+    x.ctr = c->d_ctr; x.flags = ch.d_flags; x.trace = ch.d_trace; x.flag_only = ch.d_trace == nullptr; x.n_reads = ch.n_reads;
+    x.best = c->sink.best; x.tie = c->sink.tie; x.redo = c->d_ext_redo;
+    x.unres_list = c->d_ext_unres[0]; x.n_unres = &c->d_ctr->ext_n_unres;
+    return x;
+}
+
+// minimap2 has no limit on a read's chains or regions; k_regs_align's per-wave working memory has (ext_reg_cap).  Reads beyond it are
+// listed and redone with memory allocated for them, four times the last size per round, until none is left; only when the device
+// cannot give it do they keep their chain-level answer (counted: sh_stats.n_ext_unresolved).  h_ctr holds the last launch's counters.
+// Reads the counters back after every round.
+static sh_status sr_on_demand(sh_ctx *c, Chunk &ch, ExtArgs xa)
+{
+    const hipStream_t s = ch.s;
+    uint32_t n_un = c->h_ctr->ext_n_unres, cap = c->ext_reg_cap;
+    ch.n_ondemand += n_un;
+    int cur = 0;
+    while (n_un > 0) {
+        DevBuf scratch;      // this round's working memory: gone at the end of the round, after the stream has been synchronised
+        unsigned long long per = 0; uint32_t waves = 0;
+        if (cap < (1u << 24)) {
+            cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 4, 1u << 24);
+            per = align_scratch_layout(c->max_read_len, cap, nullptr, nullptr, nullptr);
+            for (waves = std::min<uint32_t>(n_un, 8); waves > 0 && scratch.alloc(per * waves) != hipSuccess; waves >>= 1) (void)hipGetLastError();
+        }
+        uint8_t *const buf = scratch.as<uint8_t>();
+        const uint32_t z4[4] = {0, 0, n_un, 0};      // ext_n_unres, ext_ticket_unres, ext_n_unres_in
+        SH_HIP(hipMemcpyAsync(&c->d_ctr->ext_n_unres, z4, 16, hipMemcpyHostToDevice, s));
+        xa.list = c->d_ext_unres[cur]; xa.n_list = &c->d_ctr->ext_n_unres_in; xa.ticket = &c->d_ctr->ext_ticket_unres;
+        if (buf) { xa.scratch = buf; xa.scratch_per_wave = per; xa.reg_cap = cap; xa.unres_list = c->d_ext_unres[cur ^ 1]; xa.n_unres = &c->d_ctr->ext_n_unres; }
+        else {      // no memory to be had: counted, chain-level answer (on the context's own working memory: the last round's is freed)
+            xa.unres_list = nullptr; xa.n_unres = nullptr; waves = std::min<uint32_t>(c->ext_waves, n_un);
+            xa.scratch = c->d_ext_scratch; xa.scratch_per_wave = c->ext_scratch_per_wave; xa.reg_cap = c->ext_reg_cap;
+        }
+        hipLaunchKernelGGL(k_regs_align, dim3(waves), dim3(64), 0, s, xa);
+        SH_TRY(read_counters(c, s));
+        if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+        SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
+        if (!buf) break;
+        n_un = c->h_ctr->ext_n_unres; cur ^= 1;
+    }
+    return SH_OK;
+}
+
+// first pass over the reads that handed over a chain.  Trace mode: every one of them goes through mm_gen_regs .. mm_filter_regs (one
+// wave per read).  Flag-only: the lists hold each read's candidates for regs[0]; the top chain settles nearly every read (one lane each)
+static sh_status sr_top_pass(sh_ctx *c, Chunk &ch, const ExtArgs &x)
+{
+    const hipStream_t s = ch.s;
+    hipLaunchKernelGGL(k_ext_list, dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>((ch.n_reads + 4 * EXT_SLAB - 1) / (4 * EXT_SLAB), 1), EXT_LIST_BLOCKS)), dim3(256), 0, s, x);
+    if (ch.d_trace != nullptr) hipLaunchKernelGGL(k_regs_align, dim3(c->ext_waves), dim3(64), 0, s, x);
+    else hipLaunchKernelGGL(k_ext_top, dim3(ch.grid * 4), dim3(64), 0, s, x);
+    SH_TRY(read_counters(c, s));
+    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;       // hand-over buffers full: the caller cuts the chunk in two
+    SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u: 2 chains, 3 primaries, 4 read length, 5 window, 6 regions)", c->h_ctr->ext_overflow);
+    ch.ext_list = c->h_ctr->ext_n_list;
+    if (ch.d_trace != nullptr && c->h_ctr->ext_n_unres > 0) SH_TRY(sr_on_demand(c, ch, x));
+    return SH_OK;
+}
+
+// second pass (flag-only): regs[0] of the reads its max stretch could not vouch for goes through mm_align1 (one wave per read).  Leaves
+// the reads whose top chain does not survive in d_ext_list (the first list is spent); h_ctr->ext_n_redo2 counts them.
+static sh_status sr_align1_pass(sh_ctx *c, Chunk &ch, const ExtArgs &x)
+{
+    const hipStream_t s = ch.s;
+    ExtArgs x1 = x;
+    x1.list = c->d_ext_redo; x1.n_list = &c->d_ctr->ext_n_redo; x1.ticket = &c->d_ctr->ext_ticket2; x1.top_only = 1; x1.redo2 = c->d_ext_list;
+    x1.scratch_per_wave = c->ext_scratch_per_wave_top; x1.reg_cap = 64;
+    x1.stats = (c->cs.dbg & DBG_STATS) != 0;
+    if (x1.stats) {
+        SH_HIP(hipMemsetAsync(c->d_ctr->ext_clk, 0, sizeof(c->d_ctr->ext_clk) + sizeof(c->d_ctr->ext_diag) + sizeof(c->d_ctr->ext_hist), s));
+        hipLaunchKernelGGL(k_regs_align_top_stats, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
+    } else hipLaunchKernelGGL(k_regs_align_top, dim3(c->ext_waves_top), dim3(64), 0, s, x1);
+    SH_TRY(read_counters(c, s));
+    SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
+    c->dbg_ptr[2] = c->d_ext_list; c->dbg_n[2] = c->h_ctr->ext_n_redo2;
+    if (x1.stats) print_align_top(*c->h_ctr, c->ext_waves_top);
+    return SH_OK;
+}
+
+// third pass, reads whose top chain does not survive (d_ext_list, n_redo2 of them): all their chains, then the complete procedure.  They
+// take the repeat path again (wave-parallel expansion, sort classes, cluster DP) with nothing filtered; the legacy lane-per-read kernel
+// that used to carry this pass spent 130 ms on 507 reads of the sr-div workload.  The hand-over buffers start over.
+static sh_status sr_third_pass(sh_ctx *c, Chunk &ch, const ExtArgs &x, uint32_t n_redo2)
+{
+    const hipStream_t s = ch.s;
+    ch.n_fallback = n_redo2;
+    const auto t_fb = std::chrono::steady_clock::now();
+    Counters z = *c->h_ctr;
+    memset(z.ext_n_recs, 0, sizeof(z.ext_n_recs)); memset(z.ext_n_anch, 0, sizeof(z.ext_n_anch));
+    z.n_defer = 0; z.arena_cursor = 0; z.ext_n_list2 = n_redo2; z.ext_ticket3 = 0;
+    z.n_big[0] = n_redo2; z.n_big[1] = 0; z.n_big_defer[0] = z.n_big_defer[1] = 0;
+    SH_HIP(hipMemcpyAsync(c->d_ctr, &z, sizeof(Counters), hipMemcpyHostToDevice, s));
+    ExtArgs x2 = x;
+    x2.list = c->d_ext_list; x2.n_list = &c->d_ctr->ext_n_list2; x2.ticket = &c->d_ctr->ext_ticket3;
+    hipLaunchKernelGGL(k_ext_reset, dim3(64), dim3(256), 0, s, x2);
+    K3Args kf = ch.k;
+    kf.sink.best = nullptr; kf.sink.tie = nullptr; kf.t_mode = 0; kf.flag_only = 0; kf.quiet = 1;
+    K2Args rb = ch.b;
+    rb.sink.best = nullptr; rb.sink.tie = nullptr; rb.quiet = 1;
+    const int f1 = c->dbg_ptr[0] == c->d_big[1][0] ? 1 : 0;      // not over the first pass's list of re-chained reads (sh_ctx_debug_list)
+    // (with the reads the repeat path handed to the legacy kernel and that found no room there)
+    SH_TRY(rechain_list(c, ch, c->d_ext_list, n_redo2, kf, rb, 0, f1, " for the extension stage's last pass"));
+    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+    hipLaunchKernelGGL(k_regs_align, dim3(c->ext_waves), dim3(64), 0, s, x2);
+    SH_TRY(read_counters(c, s));
+    if (c->h_ctr->ext_overflow == 1) return SH_SPLIT;
+    SH_CHECK(c->h_ctr->ext_overflow == 0, SH_ERR_OOM, "extension stage: a read exceeds the per-wave working memory (code %u)", c->h_ctr->ext_overflow);
+    if (c->h_ctr->ext_n_unres > 0) SH_TRY(sr_on_demand(c, ch, x2));
+    ch.ms_fallback = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fb).count();
+    return SH_OK;
+}
+
+static sh_status sr_ext_stage(sh_ctx *c, Chunk &ch)
+{
+    const hipStream_t s = ch.s;
+    const bool flag_only = ch.d_trace == nullptr;
+    const ExtArgs x = sr_ext_args(c, ch);
+    SH_HIP(hipEventRecord(c->ev_ext[0], s));
+    SH_TRY(sr_top_pass(c, ch, x));
+    const uint32_t n_redo = c->h_ctr->ext_n_redo;
+    if (flag_only) { c->dbg_ptr[1] = c->d_ext_redo; c->dbg_n[1] = n_redo; }
+    if (c->cs.dbg_set) fprintf(stderr, "[dbg] extension stage: %u reads handed over chains, %u not settled by their top chain (tie %u, missing %u, short stretch %u, z-drop %u)\n", ch.ext_list, n_redo, c->h_ctr->ext_reason[1], c->h_ctr->ext_reason[2], c->h_ctr->ext_reason[3], c->h_ctr->ext_reason[4]);
+    uint32_t n_redo2 = 0;
+    if (flag_only && n_redo > 0) { SH_TRY(sr_align1_pass(c, ch, x)); n_redo2 = c->h_ctr->ext_n_redo2; }
+    if (n_redo2 > 0) SH_TRY(sr_third_pass(c, ch, x, n_redo2));
+    if (c->h_ctr->lext_unresolved) {
+        static bool warned_sr = false;
+        if (!warned_sr) { warned_sr = true; fprintf(stderr, "[scrubby-hip] WARNING: %u read(s) outgrew the extension stage's working memory (e.g. read %u of its batch, code %u: 2 chains, 3 primaries, 6 regions); they keep their chain-level answer (mapped)\n", c->h_ctr->lext_unresolved, c->h_ctr->lext_err_read, c->h_ctr->lext_err_code); }
+    }
+    SH_HIP(hipEventRecord(c->ev_ext[1], s));
+    SH_HIP(hipEventSynchronize(c->ev_ext[1]));
+    ch.ext_regions = c->h_ctr->ext_regions; ch.ext_dropped = c->h_ctr->ext_dropped;
+    if (flag_only) ch.ext_list = n_redo;      // reads that needed base-level alignment
+    hipEventElapsedTime(&ch.ms_ext, c->ev_ext[0], c->ev_ext[1]);
+    return SH_OK;
+}
+
+// ---- the chunk ----
+// What the chunk adds to the call's statistics: h_ctr holds the counters of the last read-back, ch.snap those of the first.
+static void add_chunk_stats(sh_ctx *c, const Chunk &ch)
+{
+    sh_stats *const stats = ch.stats;
+    const Counters &h = *c->h_ctr, &snap = ch.snap;
+    if (c->ext_long) { stats->n_ext_unresolved += h.lext_unresolved; stats->n_rmq_rechained += h.lext_rechained; stats->n_rmq_tied += h.lext_rmq_tie; stats->n_rmq_exact += ch.n_exact_reads + h.lext_exact_direct; stats->n_ext_ondemand += ch.n_ondemand; stats->n_rmq_open += h.lext_rmq_open; }
+    else if (c->ext) { stats->n_ext_fallback += ch.n_fallback; stats->ms_ext_fallback += ch.ms_fallback; stats->n_ext_unresolved += h.lext_unresolved; stats->n_ext_ondemand += ch.n_ondemand; }
+    float t01 = 0, t12 = 0, t23 = 0, t04 = 0;
+    hipEventElapsedTime(&t01, c->ev[0], c->ev[1]); hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+    hipEventElapsedTime(&t23, c->ev[1], c->ev[3]); hipEventElapsedTime(&t04, c->ev[0], c->ev[4]);
+    uint64_t sum_host = 0, sum_mini = 0, sum_anchors = 0, sum_clusters = 0, sum_pair = 0, sum_lemma = 0, sum_pf = 0, sum_pfd = 0, sum_top = 0;
+    for (int i = 0; i < 64; ++i) sum_lemma += h.sh_lemma[i];
+    stats->n_ext_shortcut += sum_lemma;
+    stats->n_lc_filtered += h.lc_why[LC_DECIDED_FILTERED];
+    for (int i = 0; i < 64; ++i) { stats->n_late_reads += h.sh_late[i]; stats->n_deferred += h.sh_deferred[i]; }
+    for (int i = 0; i < 64; ++i) { sum_host += h.sh_host[i]; sum_mini += h.sh_mini[i]; sum_anchors += h.sh_anchors[i]; sum_clusters += h.sh_clusters[i]; sum_pair += h.sh_pair[i]; sum_pf += h.sh_pf_reads[i]; sum_pfd += h.sh_pf_dirty[i]; sum_top += h.sh_top[i]; }
+    stats->n_reads += ch.n_reads; stats->n_bases += ch.n_bases;
+    stats->n_host += sum_host - ch.ext_dropped - h.lr_fb_had;
+    stats->n_ext_reads += ch.ext_list; stats->n_ext_regions += ch.ext_regions; stats->n_ext_dropped += ch.ext_dropped; stats->ms_ext += ch.ms_ext;
+    const uint32_t n_big0 = snap.n_big_total ? snap.n_big_total : snap.n_big[0];
+    stats->n_no_seed += ch.n_reads - snap.n_small - n_big0 - snap.n_resketch;
+    uint64_t nl = (uint64_t)snap.n_resketch + n_big0;
+    stats->n_chain_large += nl; stats->n_chain_small += snap.n_small;
+    stats->n_minimizers += sum_mini;
+    stats->n_anchors += sum_anchors; stats->n_clusters += sum_clusters; stats->n_resketch += ch.resk_done; stats->n_pair_decided += sum_pair;
+    stats->n_dp_parallel += sum_pf; stats->n_dp_dirty += sum_pfd; stats->n_top_settled += sum_top;
+    stats->ms_sketch_probe += t01; stats->ms_chain_small += t12; stats->ms_chain_large += t23; stats->ms_total += t04;
+}
+
+static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                uint8_t *d_flags, sh_trace *d_trace, hipStream_t s, sh_stats *stats)
+{
+    Chunk ch{d_bases, d_offsets, n_reads, n_bases, d_flags, d_trace, s, stats};
+    c->cur_reads = n_reads;
+    SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
+    if (c->ext) { SH_HIP(hipMemsetAsync(c->sink.head, 0xff, n_reads * 4, s)); SH_HIP(hipMemsetAsync(c->sink.best, 0, n_reads * 8, s)); SH_HIP(hipMemsetAsync(c->sink.tie, 0, n_reads * 4, s)); }
+    SH_HIP(hipEventRecord(c->ev[0], s));
+    SH_TRY(launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, d_trace, s));
+    SH_HIP(hipEventRecord(c->ev[1], s));
+
+    SH_TRY(fill_chunk_args(c, ch));
+    if (c->use_k1 && !ch.k2_late) SH_TRY(launch_k2(c, ch));      // K2 aside (late: run_repeat_path launches it behind its first pass)
+    else if (!c->use_k1) SH_HIP(hipEventRecord(c->ev[2], s));
+    if (c->ext_long) SH_HIP(hipMemsetAsync(c->d_lr_drop, 0, n_reads * 4, s));
+
+    // pass 0 (mid_occ) over the reads K1 routed to the repeat path and the shortcuts left, pass 1 (max_occ) over the reads pass 0 could not chain
+    int cur0 = repeat_list_shortcuts(c, ch), cur1 = 0;
+    SH_TRY(run_repeat_path(c, ch, ch.k, ch.b, cur0, cur1));
+    SH_HIP(hipEventRecord(c->ev[3], s));
+    SH_TRY(legacy_defers(c, ch, ch.b, ""));
+
+    if (c->ext_long) SH_TRY(long_ext_stage(c, ch));
+    else if (c->ext) SH_TRY(sr_ext_stage(c, ch));
     SH_HIP(hipEventRecord(c->ev[4], s));
     SH_HIP(hipEventSynchronize(c->ev[4]));
-    if (stats) {
-        float t01 = 0, t12 = 0, t23 = 0, t04 = 0;
-        hipEventElapsedTime(&t01, c->ev[0], c->ev[1]); hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-        hipEventElapsedTime(&t23, c->ev[1], c->ev[3]); hipEventElapsedTime(&t04, c->ev[0], c->ev[4]);
-        uint64_t sum_host = 0, sum_mini = 0, sum_anchors = 0, sum_clusters = 0, sum_pair = 0, sum_lemma = 0, sum_pf = 0, sum_pfd = 0, sum_top = 0;
-        for (int i = 0; i < 64; ++i) sum_lemma += c->h_ctr->sh_lemma[i];
-        stats->n_ext_shortcut += sum_lemma;
-        stats->n_lc_filtered += c->h_ctr->lc_why[LC_DECIDED_FILTERED];
-        for (int i = 0; i < 64; ++i) { stats->n_late_reads += c->h_ctr->sh_late[i]; stats->n_deferred += c->h_ctr->sh_deferred[i]; }
-        for (int i = 0; i < 64; ++i) { sum_host += c->h_ctr->sh_host[i]; sum_mini += c->h_ctr->sh_mini[i]; sum_anchors += c->h_ctr->sh_anchors[i]; sum_clusters += c->h_ctr->sh_clusters[i]; sum_pair += c->h_ctr->sh_pair[i]; sum_pf += c->h_ctr->sh_pf_reads[i]; sum_pfd += c->h_ctr->sh_pf_dirty[i]; sum_top += c->h_ctr->sh_top[i]; }
-        stats->n_reads += n_reads; stats->n_bases += n_bases;
-        stats->n_host += sum_host - ext_dropped - c->h_ctr->lr_fb_had;
-        stats->n_ext_reads += ext_list; stats->n_ext_regions += ext_regions; stats->n_ext_dropped += ext_dropped; stats->ms_ext += ms_ext; const uint32_t n_big0 = snap.n_big_total ? snap.n_big_total : snap.n_big[0];
-        stats->n_no_seed += n_reads - snap.n_small - n_big0 - snap.n_resketch;
-        uint64_t nl = (uint64_t)snap.n_resketch + n_big0;
-        stats->n_chain_large += nl; stats->n_chain_small += snap.n_small;
-        stats->n_minimizers += sum_mini;
-        stats->n_anchors += sum_anchors; stats->n_clusters += sum_clusters; stats->n_resketch += resk_done; stats->n_pair_decided += sum_pair;
-        stats->n_dp_parallel += sum_pf; stats->n_dp_dirty += sum_pfd; stats->n_top_settled += sum_top;
-        stats->ms_sketch_probe += t01; stats->ms_chain_small += t12; stats->ms_chain_large += t23; stats->ms_total += t04;
-    }
+    if (stats) add_chunk_stats(c, ch);
     return SH_OK;
 }
 

@@ -82,6 +82,23 @@ def test_edge_reads_trace_and_flag_only(S, oracle, cfg1, gpu_index, cpu_index):
     assert np.array_equal(gf0, of0)
 
 
+def test_edge_reads_third_pass_with_a_small_arena(S, oracle, cfg1, gpu_index, cpu_index, monkeypatch):
+    """Flag-only, reads whose top chain does not survive take the repeat path again (the third pass: sh_stats.n_ext_fallback); with a
+    chain arena too small for the batch the deferral loops run as well, and neither the flags nor the third pass's reads may change.
+    32 MB is the largest power of two at which these reads defer (n_deferred: 0 at 64 MB, 11 at 32, 89 at 16)."""
+    ref = cfg1[2]
+    recs, bases, offs = AC.edge_reads(ref, 4000)
+    of, _ = cpu_index.classify(oracle.preset("sr"), bases, offs, threads=8, want_trace=False)
+    gf, _, st, rc = gpu_index.classify(bases, offs, want_trace=False)
+    assert rc == 0 and np.array_equal(gf, of)
+    assert st["n_ext_fallback"] > 0, "the cases are meant to contain reads that reach the third pass"
+    monkeypatch.setenv("SCRUBBY_HIP_ARENA_MB", "32")
+    gf2, _, st2, rc2 = gpu_index.classify(bases, offs, want_trace=False)
+    assert rc2 == 0 and np.array_equal(gf2, of)
+    assert st2["n_ext_fallback"] == st["n_ext_fallback"]
+    assert st2["n_deferred"] > 0
+
+
 def test_flag_only_shortcut_decides_most_clean_reads(S, oracle, cfg1, gpu_index, cpu_index):
     P, R, ref, seqs, reads, off = cfg1
     gf, _, st, _ = gpu_index.classify(reads, off, want_trace=False)
