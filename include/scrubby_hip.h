@@ -931,6 +931,43 @@ sh_status sh_inflate_members_device(sh_inflater *inf, const uint8_t *d_in, sh_gz
 sh_status sh_gunzip_bgzf(sh_inflater *inf, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_len, sh_inflate_stats *stats);
 sh_status sh_inflater_free(sh_inflater *inf);
 
+/* ---- any gzip stream on the device (sh_gunzip_*): what gzip, pigz or a sequencer writes, one long member as well as many ----
+ * The window of compressed bytes a feed is given is cut into chunks of chunk_bytes at fixed offsets.  k_gz_find looks for a DEFLATE
+ * block start in every chunk, k_gz_size decodes from each start to the first block boundary past the chunk's end and counts, the host
+ * walks the chain of end bits (a chunk that does not start where its predecessor ended is decoded again from there, at most 8 rounds),
+ * k_gz_markers decodes the chain's spans once more to 16-bit symbols in which a reference to the 32 KiB before the span is a marker,
+ * k_gz_tails settles the windows behind spans whose last 32 KiB hold no marker, k_gz_windows passes the 32 KiB along the rest of the
+ * chain and k_gz_resolve replaces the markers and takes the CRC-32 in pieces.
+ * A feed
+ *   - decodes as many whole chunks as out_cap (and the inflater's max_out_bytes) holds; *consumed is the count of whole input bytes the
+ *     caller may drop: it presents the rest again, in front of new bytes.  n may not exceed the inflater's max_in_bytes;
+ *   - with last != 0 wants the stream to end at a member end (what follows a member and is no gzip member is ignored, as gzread
+ *     ignores it), else SH_ERR_IO naming the file offset;
+ *   - returns SH_ERR_BAD_ARG naming the size when out_cap is below what the first chunk needs;
+ *   - returns SH_ERR_IO with the member's file offset and the status for data that does not decode, a CRC-32 or ISIZE (modulo 2^32)
+ *     that does not hold, or a distance too far back: never a short or wrong output;
+ *   - returns SH_GUNZIP_FALLBACK when 8 rounds leave a chunk open (a stream of fixed blocks has no block start to find) or more than
+ *     four members end in one chunk's span: *consumed and *out_len then cover what was decoded before, which is right, and the
+ *     caller reads the file another way.
+ * After any status but SH_OK the sh_gunzip takes no further feed.  One call at a time per inflater; sh_gunzip_close before
+ * sh_inflater_free.  The scratch (2 B per byte of max_out_bytes, 32 KiB per chunk of max_in_bytes) is the inflater's and is allocated
+ * by the first sh_gunzip_open, so an inflater that only sees BGZF takes what it took before. */
+#define SH_GUNZIP_FALLBACK 10
+typedef struct sh_gunzip sh_gunzip;   /* one gzip file being read: resume bit, last 32 KiB of output, the open member's CRC-32 and length so far */
+typedef struct sh_gunzip_stats { uint64_t n_chunks, n_skipped, n_redone, n_rounds, n_members, n_marker_symbols, n_window_steps, in_bytes, out_bytes;
+                                 float ms_find, ms_size, ms_markers, ms_windows, ms_resolve, ms; } sh_gunzip_stats;
+sh_status sh_gunzip_open(sh_inflater *inf, uint32_t chunk_bytes /* 1 KiB .. 1 MiB, 0: the default */, sh_gunzip **out);
+sh_status sh_gunzip_feed_device(sh_gunzip *gz, const uint8_t *d_in, uint64_t n, int32_t last, uint8_t *d_out, uint64_t out_cap,
+                                uint64_t *consumed, uint64_t *out_len, void *stream, sh_gunzip_stats *stats);
+sh_status sh_gunzip_feed(sh_gunzip *gz, const uint8_t *in, uint64_t n, int32_t last, uint8_t *out, uint64_t out_cap,
+                         uint64_t *consumed, uint64_t *out_len, sh_gunzip_stats *stats);      /* host memory through the inflater's pinned staging */
+sh_status sh_gunzip_close(sh_gunzip *gz);
+/* test aid: one feed (last != 0) of a whole stream in HBM in which the caller names the chunk starts instead of k_gz_find: starts[j],
+ * j >= 1, is a bit position of the stream or ~0 for none (n_starts = the number of chunks, else SH_ERR_BAD_ARG); a start outside its
+ * chunk counts as none.  Wrong starts cost rounds, never bytes. */
+sh_status sh_dbg_gunzip_starts(sh_inflater *inf, uint32_t chunk_bytes, const uint8_t *d_in, uint64_t n, const uint64_t *starts, uint64_t n_starts,
+                               uint8_t *d_out, uint64_t out_cap, uint64_t *out_len, void *stream, sh_gunzip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 // libraries without their headers, so the few entry points and the two stream structs are declared here as their ABI has them).
 // A host without one of the libraries gets an error that names it when such a file is met - nothing else depends on them.
 #pragma once
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -30,7 +31,14 @@ constexpr uint64_t GUNZIP_OUT_BYTES = 192ull << 20;        // inflated bytes per
 constexpr uint64_t GUNZIP_MAX_MEMBERS = 1ull << 18;
 constexpr uint64_t GUNZIP_READER_MEMBERS = 1ull << 15;     // members a reader takes per fill (1 MiB of descriptors); a window with more is served in several fills
 constexpr uint64_t GUNZIP_FIRST_WINDOW_BYTES = 256ull << 10;      // the first window of a file is small: file_is_empty opens every input for one byte
-bool gunzip_device_wanted();                      // the switch, read at every call: only "1" turns it on
+int gunzip_device_level();                        // the switch, read at every call: 1 = BGZF members on the device, 2 = any gzip stream as well, else 0
+inline bool gunzip_device_wanted() { return gunzip_device_level() >= 1; }
+// A reader of a general gzip stream (level 2) feeds windows of 16 MiB and takes a whole inflater call's output per feed: one feed drains
+// a window up to a ratio of 12, so the window is not found and sized again for the part a smaller output would have cut off.
+constexpr uint64_t GUNZIP_ANY_WINDOW_BYTES = 16ull << 20;
+constexpr uint64_t GUNZIP_ANY_OUT_BYTES = GUNZIP_OUT_BYTES;
+void gunzip_count_any(uint64_t chunks, uint64_t redone, uint64_t bytes);
+void gunzip_time_any(double ms_read, double ms_feed, const sh_gunzip_stats &st);
 int gunzip_reader_device();                       // the open run's device, else the calling thread's current one
 sh_inflater *gunzip_pool_acquire(int device);     // an idle inflater of that device, else a new one on it; nullptr: no device or no memory
 void gunzip_pool_release(sh_inflater *inf);
@@ -153,7 +161,16 @@ class In {
     uint64_t foff_ = 0;
     size_t win_n_ = 0, served_ = 0;
     std::vector<uint8_t> inflated_;
+    size_t inflated_n_ = 0;      // inflated_[served_, inflated_n_) is what is left to serve
     std::vector<sh_gz_member> members_;
+    // SCRUBBY_HIP_GUNZIP_DEVICE=2 and a gzip member that is not BGZF (the file's first, or one behind BGZF members): the same window of
+    // the file is fed to a sh_gunzip on a pooled inflater, which the reader keeps until the file is closed.  served_total_ counts what
+    // the reader has handed out, for the fallback: zlib then reads the file again from its start and passes over that many bytes.
+    bool any_ = false;
+    sh_inflater *any_inf_ = nullptr;
+    sh_gunzip *any_gz_ = nullptr;
+    uint64_t served_total_ = 0;
+    size_t any_window_ = (size_t)GUNZIP_ANY_WINDOW_BYTES;
 
     // what gzread does for the plain and gzip files: -1 = error
     long read_gz(void *buf, size_t n)
@@ -187,7 +204,68 @@ class In {
         gzbuffer(gz_, 1 << 20);
         return 1;
     }
-    // the next window: 1 = inflated_ holds bytes, 2 = handed to zlib, 0 = end of the file, -1 = error
+    void any_release()
+    {
+        if (any_gz_) { sh_gunzip_close(any_gz_); any_gz_ = nullptr; }
+        if (any_inf_) { gunzip_pool_release(any_inf_); any_inf_ = nullptr; }
+    }
+    // the whole file goes through zlib, which passes over what was served.  2 = gz_ reads on, -1 = error
+    int any_to_zlib(const char *why)
+    {
+        any_release();
+        any_ = false;
+        if (fp_) { fclose(fp_); fp_ = nullptr; }
+        gunzip_note_zlib(path_.c_str(), foff_, why);
+        gz_ = gzopen(path_.c_str(), "rb");
+        if (!gz_) { error = "cannot open " + path_; return -1; }
+        gzbuffer(gz_, 1 << 20);
+        std::vector<char> skip(1 << 20);
+        for (uint64_t left = served_total_; left;) {
+            const int got = gzread(gz_, skip.data(), (unsigned)std::min<uint64_t>(left, skip.size()));
+            if (got <= 0) { error = "read error: " + path_ + " does not hold again what was read from it"; return -1; }
+            left -= (uint64_t)got;
+        }
+        return 2;
+    }
+    // the next window of a general gzip stream: as bgzf_fill
+    int any_fill()
+    {
+        if (!any_gz_) {
+            any_inf_ = gunzip_pool_acquire(gunzip_reader_device());
+            if (!any_inf_ || sh_gunzip_open(any_inf_, 0, &any_gz_) != SH_OK) return any_to_zlib("no device inflater");
+            shi_gunzip_set_offset(any_gz_, foff_);
+        }
+        if (inflated_.size() < GUNZIP_ANY_OUT_BYTES) inflated_.resize((size_t)GUNZIP_ANY_OUT_BYTES);
+        for (;;) {
+            const size_t want = first_window_ ? (size_t)GUNZIP_FIRST_WINDOW_BYTES : any_window_;
+            if (in_.size() < want) in_.resize(want);
+            const auto t0 = std::chrono::steady_clock::now();
+            while (win_n_ < want && !src_eof_) {
+                const size_t got = fread(in_.data() + win_n_, 1, want - win_n_, fp_);
+                if (got == 0) { if (ferror(fp_)) { error = "read error"; return -1; } src_eof_ = true; }
+                win_n_ += got;
+            }
+            uint64_t consumed = 0, out_len = 0;
+            sh_gunzip_stats st;
+            const auto t1 = std::chrono::steady_clock::now();
+            const sh_status rc = sh_gunzip_feed(any_gz_, in_.data(), win_n_, src_eof_ ? 1 : 0, inflated_.data(), GUNZIP_ANY_OUT_BYTES, &consumed, &out_len, &st);
+            if (rc == SH_GUNZIP_FALLBACK) return any_to_zlib("a gzip stream the device finds no block starts in");
+            if (rc == SH_ERR_BAD_ARG) return any_to_zlib("a chunk that holds more than a reader takes");
+            if (rc != SH_OK) { error = std::string("read error: ") + sh_last_error(); return -1; }
+            gunzip_count_any(st.n_chunks, st.n_redone, out_len);
+            gunzip_time_any(std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count(), st);
+            memmove(in_.data(), in_.data() + consumed, win_n_ - consumed);
+            win_n_ -= consumed; foff_ += consumed;
+            served_ = 0; inflated_n_ = out_len;
+            if (out_len) { first_window_ = false; return 1; }
+            if (src_eof_) { end_ = true; return 0; }      // a last feed that gives nothing and no error: the stream is over
+            if (consumed) continue;
+            if (first_window_) { first_window_ = false; continue; }      // a block larger than the first window
+            if (any_window_ < (size_t)GUNZIP_WINDOW_BYTES) { any_window_ = (size_t)GUNZIP_WINDOW_BYTES; continue; }      // or than 16 MiB: all an inflater takes
+            return any_to_zlib("a block larger than the window");
+        }
+    }
+    // the next window: 1 = inflated_ holds bytes, 2 = handed to zlib, 3 = what follows is for any_fill, 0 = end of the file, -1 = error
     int bgzf_fill()
     {
         for (;;) {
@@ -211,6 +289,7 @@ class In {
             if (n_members == 0) {
                 if (stopped == 1 && src_eof_) { error = "read error: truncated BGZF member at file offset " + std::to_string(foff_); return -1; }
                 if (stopped == 1) { first_window_ = false; continue; }      // a member larger than the first window
+                if (gunzip_device_level() == 2 && win_n_ >= 2 && in_[0] == 0x1f && in_[1] == 0x8b) { bgzf_ = false; any_ = true; served_ = inflated_n_ = 0; return 3; }
                 const int r = bgzf_to_zlib("a gzip member that is not BGZF");
                 return r > 0 ? 2 : r;
             }
@@ -225,6 +304,7 @@ class In {
             memmove(in_.data(), in_.data() + consumed, win_n_ - consumed);
             win_n_ -= consumed; foff_ += consumed;
             first_window_ = false;
+            inflated_n_ = inflated_.size();
             if (!inflated_.empty()) return 1;
         }
     }
@@ -252,8 +332,12 @@ public:
             uint64_t n_members = 0, consumed = 0;
             const int stopped = shin_bgzf_scan(in_.data(), win_n_, (ShinMember *)&first, 1, &n_members, &consumed);
             if (n_members == 1 || stopped == 1) {      // the first member is BGZF (or the beginning of one): the inflater is taken at the first read
-                fp_ = f; path_ = path; bgzf_ = true; first_window_ = true; foff_ = 0; served_ = 0;
+                fp_ = f; path_ = path; bgzf_ = true; first_window_ = true; foff_ = 0; served_ = 0; inflated_n_ = 0; served_total_ = 0;
                 inflated_.clear();
+                return true;
+            }
+            if (gunzip_device_level() == 2) {      // an ordinary gzip file: the sh_gunzip is taken at the first read
+                fp_ = f; path_ = path; any_ = true; first_window_ = true; foff_ = 0; served_ = 0; inflated_n_ = 0; served_total_ = 0;
                 return true;
             }
             win_n_ = 0;
@@ -287,18 +371,20 @@ public:
     long read(void *buf, size_t n)
     {
         if (n == 0) return 0;
-        if (bgzf_) {
+        if (bgzf_ || any_) {
             size_t done = 0;
             while (done < n) {
-                if (served_ == inflated_.size()) {
-                    const int r = bgzf_fill();
+                if (served_ == inflated_n_) {
+                    if (end_) break;
+                    const int r = bgzf_ ? bgzf_fill() : any_fill();
                     if (r < 0) return -1;
                     if (r == 0) break;
                     if (r == 2) { const long g = read_gz((char *)buf + done, n - done); return g < 0 ? -1 : (long)done + g; }
+                    if (r == 3) continue;
                 }
-                const size_t k = std::min(n - done, inflated_.size() - served_);
+                const size_t k = std::min(n - done, inflated_n_ - served_);
                 memcpy((char *)buf + done, inflated_.data() + served_, k);
-                done += k; served_ += k;
+                done += k; served_ += k; served_total_ += k;
             }
             return (long)done;
         }
@@ -349,7 +435,8 @@ public:
         if (codec_open_) { if (kind_ == Kind::Bzip2) Bz2Api::get().DecompressEnd(&bz_); else if (kind_ == Kind::Xz) LzmaApi::get().end(&xz_); codec_open_ = false; }
         if (fp_) { fclose(fp_); fp_ = nullptr; }
         src_eof_ = end_ = false;
-        bgzf_ = false; win_n_ = 0; served_ = 0; foff_ = 0;
+        any_release();
+        bgzf_ = any_ = false; win_n_ = 0; served_ = 0; inflated_n_ = 0; foff_ = 0; served_total_ = 0;
         inflated_.clear();
     }
 };

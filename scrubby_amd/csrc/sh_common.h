@@ -132,5 +132,6 @@ void shi_deflater_stage_ms(const sh_deflater *df, double ms3[3]);
 
 // sh_inflate.hip: the members of a host buffer (in_off relative to `in`, n bytes; file_off as the caller wants it named) inflated into
 // host memory through the inflater's pinned staging; d_out != nullptr: the bytes stay on the device there and `out` is not written
+void shi_gunzip_set_offset(sh_gunzip *gz, uint64_t file_off);      // sh_inflate.hip: where a sh_gunzip's stream begins in its file, before its first feed
 sh_status shi_gunzip_members(sh_inflater *inf, const uint8_t *in, uint64_t n, sh_gz_member *members, uint64_t n_members, uint8_t *out, uint8_t *d_out, uint64_t out_cap,
                              uint64_t *out_len, sh_inflate_stats *stats);

@@ -571,24 +571,38 @@ static sh_status fasta_to_device(const char *path, int32_t device, DevBuf &d_bas
         while (q < fl && (first[q] == '\n' || first[q] == '\r')) ++q;
         if (q >= fl || first[q] != '>') return SH_OK;
     } else {
-        gzFile g = gzopen(path, "rb");
-        SH_CHECK(g, SH_ERR_IO, "cannot open %s", path);
-        gzbuffer(g, 1 << 20);
         const size_t BLK = 64u << 20;
         std::vector<std::unique_ptr<char[]>> blocks;
         std::vector<size_t> lens;
-        for (;;) {
-            std::unique_ptr<char[]> b(new char[BLK]);
-            const int r = gzread(g, b.get(), (unsigned)BLK);
-            if (r < 0) { gzclose(g); sh_set_error("read error in %s", path); return SH_ERR_IO; }
-            if (r == 0) break;
-            n += (uint64_t)r; lens.push_back((size_t)r); blocks.push_back(std::move(b));
+        if (shc::gunzip_device_level() == 2) {
+            // SCRUBBY_HIP_GUNZIP_DEVICE=2: an ordinary .gz is inflated on this device through the reader every input goes through
+            // (shc::In over a sh_gunzip).  The total size is not known before the end, so the text is staged through the host.
+            shc::In in;
+            SH_CHECK(in.open(path), SH_ERR_IO, "%s", in.error.c_str());
+            for (;;) {
+                std::unique_ptr<char[]> b(new char[BLK]);
+                const long r = in.read(b.get(), BLK);
+                SH_CHECK(r >= 0, SH_ERR_IO, "%s: %s", path, in.error.c_str());
+                if (r == 0) break;
+                n += (uint64_t)r; lens.push_back((size_t)r); blocks.push_back(std::move(b));
+            }
+        } else {
+            gzFile g = gzopen(path, "rb");
+            SH_CHECK(g, SH_ERR_IO, "cannot open %s", path);
+            gzbuffer(g, 1 << 20);
+            for (;;) {
+                std::unique_ptr<char[]> b(new char[BLK]);
+                const int r = gzread(g, b.get(), (unsigned)BLK);
+                if (r < 0) { gzclose(g); sh_set_error("read error in %s", path); return SH_ERR_IO; }
+                if (r == 0) break;
+                n += (uint64_t)r; lens.push_back((size_t)r); blocks.push_back(std::move(b));
+            }
+            // a short read is only the end of the file if zlib says so: a truncated or corrupt stream is an error, not a short reference
+            int zerr = Z_OK;
+            gzerror(g, &zerr);
+            const int zc = gzclose(g);
+            SH_CHECK((zerr == Z_OK || zerr == Z_STREAM_END) && zc == Z_OK, SH_ERR_IO, "%s: gzip stream is truncated or corrupt", path);
         }
-        // a short read is only the end of the file if zlib says so: a truncated or corrupt stream is an error, not a short reference
-        int zerr = Z_OK;
-        gzerror(g, &zerr);
-        const int zc = gzclose(g);
-        SH_CHECK((zerr == Z_OK || zerr == Z_STREAM_END) && zc == Z_OK, SH_ERR_IO, "%s: gzip stream is truncated or corrupt", path);
         size_t q = 0;
         while (!blocks.empty() && q < lens[0] && (blocks[0][q] == '\n' || blocks[0][q] == '\r')) ++q;
         if (blocks.empty() || q >= lens[0] || blocks[0][q] != '>') return SH_OK;

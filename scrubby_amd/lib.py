@@ -17,7 +17,7 @@ SH_OK = 0
 STATUS_NAMES = {
     0: "SH_OK", 1: "SH_ERR_BAD_ARG", 2: "SH_ERR_PRESET_UNKNOWN", 3: "SH_ERR_PRESET_UNSUPPORTED",
     4: "SH_ERR_NO_DEVICE", 5: "SH_ERR_OOM", 6: "SH_ERR_HIP", 7: "SH_ERR_IO", 8: "SH_ERR_EMPTY_READ",
-    9: "SH_ERR_INDEX",
+    9: "SH_ERR_INDEX", 10: "SH_GUNZIP_FALLBACK",
 }
 SH_ERR_PRESET_UNKNOWN, SH_ERR_PRESET_UNSUPPORTED, SH_ERR_EMPTY_READ = 2, 3, 8
 
@@ -148,9 +148,19 @@ class InflateStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-# a member's status (sh_gz_member.status)
+class GunzipStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_chunks", "n_skipped", "n_redone", "n_rounds", "n_members", "n_marker_symbols", "n_window_steps", "in_bytes", "out_bytes")] + \
+               [(n, C.c_float) for n in ("ms_find", "ms_size", "ms_markers", "ms_windows", "ms_resolve", "ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# a member's status (sh_gz_member.status), and what a span of a general gzip stream ends with besides
 INFLATE_STATUS = ("ok", "bad block type", "bad code lengths", "invalid symbol", "distance too far back", "input overrun", "output overrun",
-                  "output short of ISIZE", "stored LEN/NLEN mismatch", "CRC mismatch")
+                  "output short of ISIZE", "stored LEN/NLEN mismatch", "CRC mismatch", "end of the stream", "too many members in one span",
+                  "bad gzip header", "second decode differs from the first", "ISIZE mismatch")
+SH_GUNZIP_FALLBACK = 10
 
 EXPORTS = [
     "sh_version", "sh_device_count", "sh_last_error", "sh_preset",
@@ -179,6 +189,7 @@ EXPORTS = [
     "sh_k2_distrib_run", "sh_k2_bracken_run",
     "sh_deflate_bound", "sh_deflater_create", "sh_deflate_device", "sh_gzip_member", "sh_deflater_free",
     "sh_bgzf_scan", "sh_inflater_create", "sh_inflate_members_device", "sh_gunzip_bgzf", "sh_inflater_free",
+    "sh_gunzip_open", "sh_gunzip_feed_device", "sh_gunzip_feed", "sh_gunzip_close", "sh_dbg_gunzip_starts",
 ]
 
 _LIB = None
@@ -249,6 +260,11 @@ def load():
     L.sh_inflate_members_device.argtypes = [vp, vp, C.POINTER(GzMember), u64, vp, u64, vp, C.POINTER(InflateStats)]
     L.sh_gunzip_bgzf.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateStats)]
     L.sh_inflater_free.argtypes = [vp]
+    L.sh_gunzip_open.argtypes = [vp, u32, C.POINTER(vp)]
+    L.sh_gunzip_feed_device.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(GunzipStats)]
+    L.sh_gunzip_feed.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(GunzipStats)]
+    L.sh_gunzip_close.argtypes = [vp]
+    L.sh_dbg_gunzip_starts.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(GunzipStats)]
     for name in EXPORTS:
         if name not in ("sh_version", "sh_device_count", "sh_last_error", "sh_index_set_size", "sh_deflate_bound"):
             getattr(L, name).restype = i32
@@ -727,9 +743,64 @@ class Inflater:
         check(load().sh_gunzip_bgzf(self.h, src.ctypes.data, n, out.ctypes.data, out_cap, C.byref(out_len), C.byref(st)))
         return out[:out_len.value].tobytes(), st.as_dict()
 
+    def gunzip_open(self, chunk_bytes=0):
+        """A Gunzip over this inflater: any gzip stream, fed in windows (sh_gunzip_open).  Close it before the inflater."""
+        return Gunzip(self, chunk_bytes)
+
+    def gunzip_starts(self, d_in, starts, d_out, chunk_bytes=0, out_cap=None):
+        """Test aid (sh_dbg_gunzip_starts): a whole stream in HBM in one feed, the chunk starts (bit positions, ~0 = none) given -> (out_len, stats)."""
+        arr = np.ascontiguousarray(starts, dtype=np.uint64)
+        st, out_len = GunzipStats(), C.c_uint64(0)
+        cap = d_out.numel() if out_cap is None else out_cap
+        check(load().sh_dbg_gunzip_starts(self.h, chunk_bytes, C.c_void_p(d_in.data_ptr()), d_in.numel(), arr.ctypes.data, len(arr), C.c_void_p(d_out.data_ptr()), cap,
+                                          C.byref(out_len), _stream_ptr(), C.byref(st)))
+        return out_len.value, st.as_dict()
+
     def close(self):
         if self.h:
             load().sh_inflater_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Gunzip:
+    """Owns an sh_gunzip: one gzip file being read through an Inflater.  A feed returns (status, consumed, bytes or out_len, stats);
+    status is SH_OK or SH_GUNZIP_FALLBACK (what was decoded before is returned), anything else raises."""
+
+    def __init__(self, inflater, chunk_bytes=0):
+        self.inflater = inflater
+        self.h = C.c_void_p()
+        check(load().sh_gunzip_open(inflater.h, chunk_bytes, C.byref(self.h)))
+
+    def feed_device(self, d_in, n, last, d_out, out_cap=None):
+        """d_in / d_out: torch uint8 CUDA tensors; the first n bytes of d_in -> (status, consumed, out_len, stats)"""
+        st, consumed, out_len = GunzipStats(), C.c_uint64(0), C.c_uint64(0)
+        cap = d_out.numel() if out_cap is None else out_cap
+        rc = load().sh_gunzip_feed_device(self.h, C.c_void_p(d_in.data_ptr()), n, int(last), C.c_void_p(d_out.data_ptr()), cap, C.byref(consumed), C.byref(out_len),
+                                          _stream_ptr(), C.byref(st))
+        if rc != SH_GUNZIP_FALLBACK:
+            check(rc)
+        return rc, consumed.value, out_len.value, st.as_dict()
+
+    def feed(self, data, last, out_cap):
+        """host bytes in -> (status, consumed, the bytes, stats) (sh_gunzip_feed)"""
+        n = len(data)
+        src = np.frombuffer(data, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+        st, consumed, out_len = GunzipStats(), C.c_uint64(0), C.c_uint64(0)
+        rc = load().sh_gunzip_feed(self.h, src.ctypes.data, n, int(last), out.ctypes.data, out_cap, C.byref(consumed), C.byref(out_len), C.byref(st))
+        if rc != SH_GUNZIP_FALLBACK:
+            check(rc)
+        return rc, consumed.value, out[:out_len.value].tobytes(), st.as_dict()
+
+    def close(self):
+        if self.h:
+            load().sh_gunzip_close(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
