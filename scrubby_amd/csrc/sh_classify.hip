@@ -43,6 +43,7 @@
 #include "sh_common.h"
 #include "sh_wave.h"
 #include "sh_merge4.h"
+#include "sh_sort_rungs.h"
 #include "sh_sketch.h"
 #include "sh_chain.h"
 #include "sh_long.h"
@@ -60,6 +61,7 @@
 #define SORT_LDS_C 4096         // ... 96 KiB; larger ones: 4096-anchor chunks in LDS, then merge rounds in the arena
 #define N_SORT_CLS 6             // LDS classes <= 256, 512, 1024, 2048, 4096 anchors (block LDS sized to the class: occupancy), then giant
 #define SORT_CLS_GIANT 5
+#define RUNG_HIST_BINS ((SORT_LDS_C - 1024) / 64)      // tables 3 and 4 by 64 anchors
 #define GT 2048u                 // tile of the giant-read merge sort
 // k_lr_locus (long-read presets, flag-only): reads of up to LOCUS_N0 / LOCUS_N1 / LOCUS_MAX_N anchors count their anchors per reference
 // window in 2^12 / 2^14 / 2^15 sixteen-bit counters of LDS; a run of more than LOCUS_RUN_MAX occupied windows is kept whatever it holds
@@ -77,7 +79,8 @@ struct Counters {
     uint32_t n_big_total, pad1;   // repeat-path reads before the pair pass took its share (0: no pair pass)
     uint32_t n_sort[N_SORT_CLS], n_giant_tiles, n_giant_passes;
     uint32_t expand_ticket, lc_ticket;     // k_expand / k_local_cluster: next read of the pass's list
-    uint32_t top_ticket[N_SORT_CLS];       // k_sort_top / k_giant_top: likewise
+    uint32_t top_ticket[N_SORT_CLS];       // k_giant_top: likewise ([SORT_CLS_GIANT]; k_sort_top draws from rung_ticket)
+    uint32_t rung_ticket[SORT_N_RUNGS + (SORT_N_RUNGS & 1)];      // k_sort_top: next item of the rung's table, one word per launch (sh_sort_rungs.h)
     uint32_t sort_ticket[N_SORT_CLS];      // k_sort_lds: next item of the class (blocks draw reads one by one: their costs differ a hundredfold)
     uint32_t n_long_segs, pad2;
     uint32_t ext_reason[8];       // why the top chain did not settle a read (k_ext_top)
@@ -110,6 +113,8 @@ struct Counters {
     unsigned long long lext_slow2, lext_slow3, lext_slow_part[4], lext_sum_part[4], lext_clk_big[LR_NCLK], lext_d_big[8], lext_phase_max[LR_NCLK];
     uint32_t lext_started, lext_t0_done;      // SCRUBBY_HIP_DBG: the slowest read of the chains kernel (time << 32 | read length / read)
     unsigned long long stage_cursor;      // k_expand's raw anchors of the reads k_lr_locus will thin out (their own buffer: 12 B per anchor)
+    // SCRUBBY_HIP_DBG & 16: reads / anchors k_expand lists in tables 3 and 4, per pass and per 64-anchor bin of n (bin 0: 1025 .. 1088)
+    unsigned long long rung_hist_reads[2][RUNG_HIST_BINS], rung_hist_anchors[2][RUNG_HIST_BINS];
 };
 #define SHARD() ((blockIdx.x + (blockIdx.x >> 6)) & 63)
 
@@ -1886,7 +1891,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             for (uint32_t i = lo + lane; i < hi; i += 64) items[i].n = 0;
             if (lane == 0) { SortItem it{w, n_a, (uint32_t)qlen, late ? late_item(r, n_seed) : 0u, off}; items[si] = it; }
             n_late += late;
-            if ((a.dbg & DBG_STATS) && lane == 0) { atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_a); }
+            if ((a.dbg & DBG_STATS) && lane == 0) {
+                atomicAdd(&a.ctr->sort_tot[cls], 1ull); atomicAdd(&a.ctr->sort_anchor_tot[cls], (unsigned long long)n_a);
+                if (cls == 3 || cls == 4) { const uint32_t bin = (n_a - 1025u) >> 6; atomicAdd(&a.ctr->rung_hist_reads[a.pass & 1][bin], 1ull); atomicAdd(&a.ctr->rung_hist_anchors[a.pass & 1][bin], (unsigned long long)n_a); }
+            }
         }
     }
     for (int cls = 0; cls < N_SORT_CLS; ++cls)
@@ -2266,9 +2274,13 @@ __device__ inline bool fix_dirty_clusters(PX x, PQ q, int32_t *f, int32_t *pt, u
 // mg_chain_backtrack's first candidates over the whole read (backtrack_block_top) - no cluster is visited.  A read it settles is emptied in
 // its class table, so k_sort_lds skips it; the others (many candidates at the top score; par_fill_block not applicable) are left untouched.
 // Its own kernel: inside k_sort_lds the extra code cost 80 VGPRs and half the occupancy.
-template <int NMAX, int CLS, int NTHR>
+// One launch per rung of sh_sort_rungs.h: the block's LDS is sized to NMAX, and of table CLS it takes the reads with NMIN < n <= NMAX -
+// those of the table's other rungs are passed over untouched.  Every rung draws its own tickets over the whole table.
+template <int NMIN, int NMAX, int CLS, int NTHR>
 __global__ __launch_bounds__(NTHR) void k_sort_top(K3Args a)
 {
+    constexpr int RUNG = sort_rung_of(NMAX);
+    static_assert(RUNG >= 0 && SORT_RUNGS[RUNG].cls == CLS && SORT_RUNGS[RUNG].nmin == NMIN && SORT_RUNGS[RUNG].nmax == NMAX && SORT_RUNGS[RUNG].nthr == NTHR, "k_sort_top is instantiated from SORT_RUNGS");
     __shared__ uint64_t s_x[2][NMAX];
     __shared__ uint32_t s_q[2][NMAX];
     __shared__ ParFillLds s_pf;
@@ -2280,14 +2292,22 @@ __global__ __launch_bounds__(NTHR) void k_sort_top(K3Args a)
     const uint32_t n_items = a.ctr->n_sort[CLS];
     unsigned long long *const dbg = (a.dbg & DBG_STATS) ? a.ctr->pf_dbg : nullptr;
     for (;;) {
-        if (tid == 0) s_it = atomicAdd(&a.ctr->top_ticket[CLS], 1u);
+        if (tid == 0) s_it = atomicAdd(&a.ctr->rung_ticket[RUNG], 1u);
         __syncthreads();
         const uint32_t it = s_it;
         __syncthreads();
         if (it >= n_items) break;
         const SortItem si = a.B.sort_items[CLS][it];
         const uint32_t n = si.n;
-        if (n == 0) continue;
+        if (n == 0) continue;      // settled earlier
+        if constexpr (!sort_rung_alone(RUNG)) {
+            // another rung's read: passed over.  Asked of a copy the compiler cannot see through: told that NMIN < n <= NMAX it compiles the
+            // loops over n below differently and every instance takes four more VGPRs (79 -> 83; with the test in the single-rung kernels
+            // too, <512> and <1024> 79 / 78 -> 83 / 82 and five waves per SIMD for six).
+            uint32_t nn = n;
+            asm volatile("" : "+v"(nn));
+            if (nn <= (uint32_t)NMIN || nn > (uint32_t)NMAX) continue;
+        }
         const int32_t qlen = (int32_t)si.qlen;
         const uint64_t *gx = a.B.ax + si.off; const uint32_t *gq = a.B.aq + si.off;
         if (late_class(CLS) && si.pad) late_anchors(si.pad, qlen, 0u, n, &s_x[0][0], &s_q[0][0], tid, NTHR, (uint32_t *)&s_x[1][0]);
@@ -3759,6 +3779,43 @@ static sh_status pick_side_streams(sh_ctx *c, hipStream_t s)
     return SH_OK;
 }
 
+// k_sort_top over the rungs of tables 3 and 4 (sh_sort_rungs.h; tables 0-2 keep the grids they had): a grid of the blocks the runtime says
+// are resident - what the rung's LDS was cut for, if the compiled kernel reaches it.
+struct RungGrids { uint32_t per_cu[SORT_N_RUNGS], blocks[SORT_N_RUNGS]; bool ok; };
+
+template <int I = 0>
+static void rung_grids_fill(RungGrids &g)
+{
+    if constexpr (I < SORT_N_RUNGS) {
+        if constexpr (SORT_RUNGS[I].cls >= 3) {
+            int per_cu = 0;
+            const auto kern = &k_sort_top<SORT_RUNGS[I].nmin, SORT_RUNGS[I].nmax, SORT_RUNGS[I].cls, SORT_RUNGS[I].nthr>;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, SORT_RUNGS[I].nthr, 0) != hipSuccess || per_cu <= 0) { g.ok = false; per_cu = 0; }
+            g.per_cu[I] = (uint32_t)per_cu; g.blocks[I] = 256u * (uint32_t)per_cu;
+        }
+        rung_grids_fill<I + 1>(g);
+    }
+}
+
+static RungGrids rung_grids()
+{
+    RungGrids g{};
+    g.ok = true;
+    rung_grids_fill(g);
+    return g;
+}
+
+// every rung of table CLS, in the ladder's order, on stream s
+template <int CLS, int I = 0>
+static void launch_rungs(const RungGrids &g, hipStream_t s, const K3Args &k)
+{
+    if constexpr (I < SORT_N_RUNGS) {
+        if constexpr (SORT_RUNGS[I].cls == CLS)
+            hipLaunchKernelGGL((k_sort_top<SORT_RUNGS[I].nmin, SORT_RUNGS[I].nmax, SORT_RUNGS[I].cls, SORT_RUNGS[I].nthr>), dim3(g.blocks[I]), dim3(SORT_RUNGS[I].nthr), 0, s, k);
+        launch_rungs<CLS, I + 1>(g, s, k);
+    }
+}
+
 // one pass of the repeat path over list[*count]: expand -> sort -> DP -> finalize
 static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
 {
@@ -3795,6 +3852,14 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     const bool use_pf = (k.emit || !k.flag_only) && !(k.dbg & DBG_NO_PARFILL);
     const bool use_top = use_pf && k.emit && k.sink.best != nullptr && !(k.dbg & DBG_NO_TOPBT);
     if (use_pf) SH_HIP(hipMemsetAsync(&ctr->top_ticket[0], 0, 4 * N_SORT_CLS, s));
+    if (use_top) SH_HIP(hipMemsetAsync(&ctr->rung_ticket[0], 0, 4 * SORT_N_RUNGS, s));
+    static const RungGrids rungs = rung_grids();      // the device's answer is the same for every context of the process
+    SH_CHECK(!use_top || rungs.ok, SH_ERR_HIP, "k_sort_top: a rung has no resident block");
+    if ((k.dbg & DBG_STATS) && use_top && k.pass == 0) {
+        fprintf(stderr, "[dbg] k_sort_top rungs of tables 3 and 4, resident blocks per CU (cut for):");
+        for (int i = 0; i < SORT_N_RUNGS; ++i) if (SORT_RUNGS[i].cls >= 3) fprintf(stderr, " (%d, %d] %u (%d)", SORT_RUNGS[i].nmin, SORT_RUNGS[i].nmax, rungs.per_cu[i], SORT_RUNGS[i].blocks);
+        fprintf(stderr, "\n");
+    }
     if (side) {
         SH_HIP(hipEventRecord(c->evx[0], s));
         for (int i = 0; i < 3; ++i) SH_HIP(hipStreamWaitEvent(c->sx[i], c->evx[0], 0));
@@ -3826,19 +3891,20 @@ static sh_status big_pass(sh_ctx *c, K3Args k, uint32_t grid, hipStream_t s)
     hipStream_t sl = s;
     sh_status ls = SH_OK;
     // each class: the read-level pass (k_sort_top), then the cluster path for what it left (k_sort_lds), on the class's stream or aside
-    if (use_top) hipLaunchKernelGGL((k_sort_top<256, 0, 64>), dim3(grid * 2), dim3(64), 0, s, k);
+    // (tables 3 and 4: one k_sort_top per rung, in order on the table's stream; the leftovers take the whole table behind the last rung)
+    if (use_top) hipLaunchKernelGGL((k_sort_top<64, 256, 0, 64>), dim3(grid * 2), dim3(64), 0, s, k);
     if ((ls = lds_stream(0, s, sl)) != SH_OK) return ls;
     hipLaunchKernelGGL((k_sort_lds<256, 0, 64>), dim3(grid * 2), dim3(64), 0, sl, k);
-    if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_A, 1, 128>), dim3(grid * 2), dim3(128), 0, s, k);
+    if (use_top) hipLaunchKernelGGL((k_sort_top<256, SORT_LDS_A, 1, 128>), dim3(grid * 2), dim3(128), 0, s, k);
     if ((ls = lds_stream(1, s, sl)) != SH_OK) return ls;
     hipLaunchKernelGGL((k_sort_lds<SORT_LDS_A, 1, 128>), dim3(grid * 2), dim3(128), 0, sl, k);
-    if (use_top) hipLaunchKernelGGL((k_sort_top<1024, 2, 256>), dim3(256 * 6), dim3(256), 0, s0, k);
+    if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_A, 1024, 2, 256>), dim3(256 * 6), dim3(256), 0, s0, k);
     if ((ls = lds_stream(2, s0, sl)) != SH_OK) return ls;
     hipLaunchKernelGGL((k_sort_lds<1024, 2, 256>), dim3(256 * 6), dim3(256), 0, sl, k);
-    if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_B, 3, 256>), dim3(256 * 3), dim3(256), 0, s0, k);
+    if (use_top) launch_rungs<3>(rungs, s0, k);
     if ((ls = lds_stream(3, s0, sl)) != SH_OK) return ls;
     hipLaunchKernelGGL((k_sort_lds<SORT_LDS_B, 3, 256>), dim3(256 * 3), dim3(256), 0, sl, k);
-    if (use_top) hipLaunchKernelGGL((k_sort_top<SORT_LDS_C, 4, 512>), dim3(256), dim3(512), 0, s1, k);
+    if (use_top) launch_rungs<4>(rungs, s1, k);
     if ((ls = lds_stream(4, s1, sl)) != SH_OK) return ls;
     hipLaunchKernelGGL((k_sort_lds<SORT_LDS_C, 4, 512>), dim3(256), dim3(512), 0, sl, k);
     hipLaunchKernelGGL(k_giant_scan, dim3(1), dim3(1024), 0, g, k);
@@ -3937,6 +4003,11 @@ static void print_repeat_pass(const Counters &h, int iter)      // DBG_STATS, af
     fprintf(stderr, "[dbg] iter %d resketch %u reasons %u %u %u pair tests between two singletons (dbg) %u segs %u big %u/%u defer %u/%u\n", iter, h.n_resketch, h.n_leg_reason[0], h.n_leg_reason[1], h.n_leg_reason[2], h.n_leg_reason[3], h.n_long_segs, h.n_big[0], h.n_big[1], h.n_big_defer[0], h.n_big_defer[1]);
     fprintf(stderr, "[dbg] clusters chained by k_cluster_dp by class: %llu %llu %llu %llu, their anchors %llu %llu %llu %llu\n", h.cl_tot[0], h.cl_tot[1], h.cl_tot[2], h.cl_tot[3], h.cl_anchor_tot[0], h.cl_anchor_tot[1], h.cl_anchor_tot[2], h.cl_anchor_tot[3]);
     fprintf(stderr, "[dbg] reads (anchors) by sort class: <=64 %llu (%llu), <=256 %llu (%llu), <=512 %llu (%llu), <=1024 %llu (%llu), <=2048 %llu (%llu), <=4096 %llu (%llu), giant %llu (%llu)\n", h.sort_tot[6], h.sort_anchor_tot[6], h.sort_tot[0], h.sort_anchor_tot[0], h.sort_tot[1], h.sort_anchor_tot[1], h.sort_tot[2], h.sort_anchor_tot[2], h.sort_tot[3], h.sort_anchor_tot[3], h.sort_tot[4], h.sort_anchor_tot[4], h.sort_tot[5], h.sort_anchor_tot[5]);
+    for (int p = 0; p < 2; ++p) {      // what the rungs of k_sort_top are cut from (sh_sort_rungs.h): bin b holds n of 1025 + 64 b .. 1088 + 64 b
+        fprintf(stderr, "[dbg] tables 3 and 4, pass %d, reads (anchors) per 64-anchor bin from 1025:", p);
+        for (int b = 0; b < RUNG_HIST_BINS; ++b) fprintf(stderr, " %llu (%llu)", h.rung_hist_reads[p][b], h.rung_hist_anchors[p][b]);
+        fprintf(stderr, "\n");
+    }
     fprintf(stderr, "[dbg] pair pass mode 2: premises hold but too many bases outside the k-mers: LDS path %u, of which the middle check decided %u; repeat path %u, decided %u\n", h.pair_mid[0], h.pair_mid[1], h.pair_mid[2], h.pair_mid[3]);
     static const char *const lc_name[] = {"tried", "no singleton", "a seed above mid_occ", "singletons apart", "window grew / too many", "K size", "no margin over U_out", "lemma / no chain / tie", "decided", "decided, seeds filtered", "seeds not 2..64"};
     fprintf(stderr, "[dbg] local-cluster shortcut, reads (anchors the occurrence filter admits):");
