@@ -750,6 +750,19 @@ sh_status sh_dbg_sketch(int32_t device, const uint8_t *bases, const uint64_t *of
 sh_status sh_dbg_front_end(sh_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
                            uint32_t *k1info, uint8_t *route, uint64_t *rec_off, uint32_t *records, uint64_t rec_cap,
                            uint64_t *mz_off, uint64_t *mz_hash, uint32_t *mz_y, uint64_t mz_cap, int32_t *info);
+/* Test aid: the flag-only shortcuts over the repeat path's list alone (tests/test_local_cluster_gpu.py), on a short-read context with
+ * SH_F_CIGAR (anything else, a non-null d_trace, or options that leave ChainParams::ext_lemma at 0 without SCRUBBY_HIP_NO_LEMMA: SH_ERR_BAD_ARG).
+ * Resets the counters and a flags buffer of its own, runs the front end, then under mask (bit 0: k_pair_pass over the list, bit 1:
+ * k_local_cluster, always its counting instance) what sh_classify_device runs there, and nothing behind it.  Copies out, per read r:
+ *   k1info[r]   as the read kernel left it;
+ *   route[r]    bit 0: the front end put the read on the repeat list; bit 1: the list the shortcuts left over names it; bit 7: a list names it twice;
+ *   flags[r]    1: a shortcut decided the read (mapped), else 0;
+ * and for the call lc_why[11] (how each read of k_local_cluster's list ended: tried, no singleton, a seed above mid_occ, singletons apart,
+ * window, K size, margin, lemma, decided, decided with seeds filtered, seed count not 2 .. 64), pair_mid[4] (the pair pass's middle checks)
+ * and info[4]: the length of the repeat list, of the leftover list, whether k_pair_pass ran, whether k_local_cluster ran. */
+sh_status sh_dbg_repeat_shortcuts(sh_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                  const void *d_trace, int32_t mask, uint32_t *k1info, uint8_t *route, uint8_t *flags,
+                                  uint32_t *lc_why, uint32_t *pair_mid, int32_t *info);
 
 /* ---- Kraken arm: database inspection (DESIGN.md §7 "Database inspection"): what kraken2-inspect prints, as recalled from
  * dump_table.cc and CompactHashTable::GetValueCounts: PARITY WITH kraken2-inspect UNPINNED, like the rest of the arm.  One pass over

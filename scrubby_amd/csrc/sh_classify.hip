@@ -1180,7 +1180,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                     const int32_t dmax = (int32_t)mdx < mdy ? (int32_t)mdx : mdy;
                     const bool in = lane < n_k;
                     const uint32_t dg = (uint32_t)x - q, dg0 = (uint32_t)__builtin_amdgcn_readlane((int)dg, 0);
-                    const uint32_t qpv = (uint32_t)wave_shr1((int32_t)q, 0);
+                    // the predecessor's q from e_q (K as sorted, behind the barrier above), not by a lane shift: as `q - wave_shr1(q, 0)`, which the
+                    // compiler folds into one v_subrev_u32_dpp wave_shr:1, dq came out <= 0 on the device for every K and this branch was never
+                    // entered (tests/test_local_cluster_gpu.py)
+                    const uint32_t qpv = in && lane > 0 ? e_q[lane - 1] : 0u;
                     const int32_t dq = (int32_t)q - (int32_t)qpv;
                     const bool good = !in || (dg == dg0 && (lane == 0 || (dq > 0 && dq <= dmax)));
                     fast = P.ext_s1 != 0 && __popcll(stm) == 1 && (int32_t)n_k >= P.min_cnt && __ballot(!good) == 0;
@@ -4148,12 +4151,13 @@ static sh_status launch_k2(sh_ctx *c, Chunk &ch)
 }
 
 // Flag-only shortcuts over the repeat path's list d_big[0][0]: what a shortcut decides never reaches k_expand, the rest moves to the
-// other list of the pair.  Returns the side the repeat path starts from.
-static int repeat_list_shortcuts(sh_ctx *c, Chunk &ch)
+// other list of the pair.  Returns the side the repeat path starts from.  mask: which of them may run (sh_dbg_repeat_shortcuts runs one alone).
+enum { SHORTCUT_PAIR = 1, SHORTCUT_LOCAL = 2, SHORTCUT_BOTH = 3 };
+static int repeat_list_shortcuts(sh_ctx *c, Chunk &ch, int mask)
 {
     const hipStream_t s = ch.s;
     int cur0 = 0;
-    if (ch.pair_pass) {      // the repeat path's list: reads two singleton seeds decide never reach k_expand; the rest moves to the other list
+    if (ch.pair_pass && (mask & SHORTCUT_PAIR)) {      // the repeat path's list: reads two singleton seeds decide never reach k_expand; the rest moves to the other list
         K2Args pb = ch.b;
         pb.work = c->d_big[0][0]; pb.work_count = &c->d_ctr->n_big[0];
         pb.leftover = c->d_big[0][1]; pb.leftover_count = &c->d_ctr->n_big_defer[0]; pb.dbg_slot = 2;
@@ -4161,7 +4165,7 @@ static int repeat_list_shortcuts(sh_ctx *c, Chunk &ch)
         hipLaunchKernelGGL(k_pair_swap, dim3(1), dim3(1), 0, s, c->d_ctr);
         cur0 = 1;
     }
-    if (ch.k.t_mode && c->P.ext_lemma && c->use_k1 && !c->use_long && !(ch.k.dbg & DBG_NO_LOCAL_CLUSTER)) {      // reads whose singleton seeds' locus settles them
+    if ((mask & SHORTCUT_LOCAL) && ch.k.t_mode && c->P.ext_lemma && c->use_k1 && !c->use_long && !(ch.k.dbg & DBG_NO_LOCAL_CLUSTER)) {      // reads whose singleton seeds' locus settles them
         K2Args pb = ch.b;
         pb.work = c->d_big[0][cur0]; pb.work_count = &c->d_ctr->n_big[0];
         pb.leftover = c->d_big[0][cur0 ^ 1]; pb.leftover_count = &c->d_ctr->n_big_defer[0];
@@ -4789,7 +4793,7 @@ static sh_status classify_chunk(sh_ctx *c, const uint8_t *d_bases, const uint64_
     if (c->ext_long) SH_HIP(hipMemsetAsync(c->d_lr_drop, 0, n_reads * 4, s));
 
     // pass 0 (mid_occ) over the reads K1 routed to the repeat path and the shortcuts left, pass 1 (max_occ) over the reads pass 0 could not chain
-    int cur0 = repeat_list_shortcuts(c, ch), cur1 = 0;
+    int cur0 = repeat_list_shortcuts(c, ch, SHORTCUT_BOTH), cur1 = 0;
     SH_TRY(run_repeat_path(c, ch, ch.k, ch.b, cur0, cur1));
     SH_HIP(hipEventRecord(c->ev[3], s));
     SH_TRY(legacy_defers(c, ch, ch.b, ""));
@@ -4919,5 +4923,75 @@ extern "C" sh_status sh_dbg_front_end(sh_ctx *c, const uint8_t *d_bases, const u
         for (uint64_t r = 0; r < n_reads; ++r) { rec_off[r] = 0; mz_off[r] = 0; }
     }
     rec_off[n_reads] = n_rec; mz_off[n_reads] = n_mz;
+    return SH_OK;
+}
+
+// Test aid (tests/test_local_cluster_gpu.py): the flag-only shortcuts over the repeat path's list alone - launch_front_end and
+// fill_chunk_args as classify_chunk calls them, then repeat_list_shortcuts under `mask` (bit 0 k_pair_pass over the list, bit 1
+// k_local_cluster) with the statistics on, so that k_local_cluster<true> runs and says how each read ended.  Nothing behind the shortcuts runs:
+// a read they leave alone keeps flag 0 and is named by the leftover list.
+extern "C" sh_status sh_dbg_repeat_shortcuts(sh_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                             const void *d_trace, int32_t mask, uint32_t *k1info, uint8_t *route, uint8_t *flags,
+                                             uint32_t *lc_why, uint32_t *pair_mid, int32_t *info)
+{
+    SH_CHECK(c && d_offsets && k1info && route && flags && lc_why && pair_mid && info && (d_bases || n_bases == 0), SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: null argument");
+    SH_CHECK(mask >= 0 && mask <= SHORTCUT_BOTH, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: mask %d, not 0 .. 3", mask);
+    SH_CHECK(n_reads >= 1 && n_reads <= c->max_reads, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: %llu reads, the context takes 1 .. %llu", (unsigned long long)n_reads, (unsigned long long)c->max_reads);
+    SH_CHECK(d_trace == nullptr, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: trace mode has no shortcuts");
+    SH_CHECK(c->ext && !c->ext_long && c->use_k1 && !c->use_long, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: the context is not a short-read one with SH_F_CIGAR and the read kernel as its front end");
+    SH_CHECK(c->P.ext_lemma || c->sw.no_lemma, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: the options do not meet the premises of ChainParams::ext_lemma");
+    SH_HIP(hipSetDevice(c->idx->device));
+    std::vector<uint64_t> off(n_reads + 1);
+    SH_HIP(hipMemcpy(off.data(), d_offsets, 8 * (n_reads + 1), hipMemcpyDeviceToHost));
+    for (uint64_t r = 0; r < n_reads; ++r)
+        SH_CHECK(off[r] <= off[r + 1] && off[r + 1] - off[r] <= c->max_read_len, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: read %llu: offsets decrease or the read is longer than the context's %u", (unsigned long long)r, c->max_read_len);
+    SH_CHECK(off[n_reads] <= n_bases && n_bases <= c->max_bases, SH_ERR_BAD_ARG, "sh_dbg_repeat_shortcuts: offsets beyond n_bases, or more bases than the context's %llu", (unsigned long long)c->max_bases);
+    const hipStream_t s = nullptr;
+    c->cs = shi_call_switches();
+    DevBuf b_flags;
+    SH_HIP(b_flags.alloc(n_reads));
+    uint8_t *const d_flags = b_flags.as<uint8_t>();
+    SH_HIP(hipMemsetAsync(d_flags, 0, n_reads, s));
+    SH_HIP(hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), s));
+    SH_HIP(hipMemsetAsync(c->d_k1info, 0, n_reads * 4, s));
+    SH_HIP(hipMemsetAsync(c->sink.head, 0xff, n_reads * 4, s)); SH_HIP(hipMemsetAsync(c->sink.best, 0, n_reads * 8, s)); SH_HIP(hipMemsetAsync(c->sink.tie, 0, n_reads * 4, s));
+    Chunk ch{d_bases, d_offsets, n_reads, n_bases, d_flags, nullptr, s, nullptr};
+    c->cur_reads = n_reads;
+    SH_TRY(launch_front_end(c, d_bases, d_offsets, n_reads, n_bases, d_flags, nullptr, s));
+    SH_HIP(hipGetLastError());
+    SH_HIP(hipStreamSynchronize(s));
+    // the list as the front end left it: checked before a shortcut walks it, and kept, since the shortcuts write their leftovers over it
+    Counters ctr;
+    SH_HIP(hipMemcpy(&ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
+    const uint32_t n_list = ctr.n_big[0];
+    SH_CHECK(n_list <= n_reads, SH_ERR_HIP, "sh_dbg_repeat_shortcuts: the repeat list holds %u of %llu reads", n_list, (unsigned long long)n_reads);
+    std::vector<uint32_t> h(n_list);
+    if (n_list) SH_HIP(hipMemcpy(h.data(), c->d_big[0][0], 4 * (size_t)n_list, hipMemcpyDeviceToHost));
+    memset(route, 0, n_reads);
+    for (uint32_t r : h) {
+        SH_CHECK(r < n_reads, SH_ERR_HIP, "sh_dbg_repeat_shortcuts: the repeat list names read %u of %llu", r, (unsigned long long)n_reads);
+        route[r] |= (route[r] & 1) ? 0x80 : 1;
+    }
+    SH_TRY(fill_chunk_args(c, ch));
+    ch.b.dbg |= DBG_STATS; ch.k.dbg |= DBG_STATS;      // k_local_cluster<true>, and k_pair_pass counts pair_mid
+    const bool lc = (mask & SHORTCUT_LOCAL) && ch.k.t_mode && c->P.ext_lemma && !(ch.k.dbg & DBG_NO_LOCAL_CLUSTER);
+    const bool pair = (mask & SHORTCUT_PAIR) && ch.pair_pass;
+    const int cur0 = repeat_list_shortcuts(c, ch, mask);
+    SH_HIP(hipGetLastError());
+    SH_HIP(hipStreamSynchronize(s));
+    SH_HIP(hipMemcpy(&ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
+    const uint32_t n_left = ctr.n_big[0];
+    SH_CHECK(n_left <= n_list && (pair || lc ? ctr.n_big_total == n_list || n_list == 0 : cur0 == 0), SH_ERR_HIP, "sh_dbg_repeat_shortcuts: %u reads left over of a list of %u (counter %u)", n_left, n_list, ctr.n_big_total);
+    h.resize(n_left);
+    if (n_left) SH_HIP(hipMemcpy(h.data(), c->d_big[0][cur0], 4 * (size_t)n_left, hipMemcpyDeviceToHost));
+    for (uint32_t r : h) {
+        SH_CHECK(r < n_reads, SH_ERR_HIP, "sh_dbg_repeat_shortcuts: the leftover list names read %u of %llu", r, (unsigned long long)n_reads);
+        route[r] |= (route[r] & 2) ? 0x80 : 2;
+    }
+    SH_HIP(hipMemcpy(k1info, c->d_k1info, n_reads * 4, hipMemcpyDeviceToHost));
+    SH_HIP(hipMemcpy(flags, d_flags, n_reads, hipMemcpyDeviceToHost));
+    memcpy(lc_why, ctr.lc_why, sizeof(uint32_t) * (LC_N_SEED + 1));
+    memcpy(pair_mid, ctr.pair_mid, sizeof(ctr.pair_mid));
+    info[0] = (int32_t)n_list; info[1] = (int32_t)n_left; info[2] = pair ? 1 : 0; info[3] = lc ? 1 : 0;
     return SH_OK;
 }
