@@ -1,4 +1,4 @@
-"""Registers, scratch, LDS and waves per SIMD of the kernels that build late anchors, before and after a change, from two build logs:
+"""Registers, scratch, LDS and waves per SIMD of the kernels that build late anchors and of k_local_cluster, before and after a change, from two build logs:
     make -C scrubby_amd/csrc CXXFLAGS="<the Makefile's> -Rpass-analysis=kernel-resource-usage" 2> LOG      (once per tree)
     python scripts/kernel_resources.py BEFORE.log AFTER.log OUT.json
 Lists the kernels that lost a wave per SIMD or gained scratch (profiles/late_anchors_resources.json keeps the result); exit status 1 if any.
@@ -6,7 +6,7 @@ To be run again after a compiler update: stage_anchors / late_anchors steer the 
 segment) and the class left out in late_class() rests on these figures."""
 import json, re, subprocess, sys
 
-KERNELS = r"k_expand<false>|k_sort_top<|k_sort_lds<|k_giant_chunksort"
+KERNELS = r"k_expand<false>|k_sort_top<|k_sort_lds<|k_giant_chunksort|k_local_cluster<"
 FIELDS = (("sgprs", r"TotalSGPRs: (\d+)"), ("vgprs", r"    VGPRs: (\d+)"), ("agprs", r"AGPRs: (\d+)"), ("scratch_bytes_per_lane", r"ScratchSize \[bytes/lane\]: (\d+)"),
           ("waves_per_simd", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sgpr_spill", r"SGPRs Spill: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)"),
           ("lds_bytes_per_block", r"LDS Size \[bytes/block\]: (\d+)"))
@@ -18,7 +18,7 @@ def parse(path):
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-            name = re.sub(r"\(K3Args.*\)$", "", name).replace("void ", "")
+            name = re.sub(r"\(K[23]Args.*\)$", "", name).replace("void ", "")
             cur = name if re.match(KERNELS, name) else None
             if cur:
                 out[cur] = {}

@@ -44,6 +44,7 @@
 #include "sh_wave.h"
 #include "sh_merge4.h"
 #include "sh_sort_rungs.h"
+#include "sh_lc_search.h"
 #include "sh_sketch.h"
 #include "sh_chain.h"
 #include "sh_long.h"
@@ -1073,78 +1074,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             const uint32_t mdx = chain_max_dist_x(P, qlen);
             if (STATS && ok && hi - lo > 4u * mdx) why = LC_APART;
             ok = ok && hi - lo <= 4u * mdx;                       // singletons of one locus; far-apart ones on one contig: full path
-            const uint32_t rel = hiw >> 31;                      // strand relation of K's anchors
             const uint64_t w1m = (uint64_t)rec0.y << 32 | rec0.x;
             const uint64_t *__restrict__ lst = a.positions + (w1m >> SH_SLOT_NBITS);
             const bool multi = have0 && occ0 > 1u && !high0;
-            uint32_t c_l = s_in ? 1u : 0u, first_l = 0;
+            // the lane's list is searched once (round 0), then the answer grows with the window at its two ends (sh_lc_search.h): a round in
+            // which the entries just outside the lane's stretch stay outside - every read's last round - costs the lane no load
+            const LcQuery Q{hiw & 0x7fffffffu, rec0.w & 1u, hiw >> 31, occ0};      // rel: the strand relation of K's anchors
+            LcSearch ls;
+            ls.first = ls.stop = 0; ls.c = s_in ? 1u : 0u; ls.below = ls.above = LC_NONE;
             if (ok) {
                 for (int round = 0; round < 4; ++round) {
-                    const uint32_t wlo = lo > mdx ? lo - mdx : 0u, whi = hi + mdx < hi ? 0xffffffffu : hi + mdx;
+                    uint32_t wlo, whi;
+                    lc_window(lo, hi, mdx, wlo, whi);
                     uint32_t nlo = lo, nhi = hi;
                     if (multi) {
-                        // lower bound of the window in this seed's ascending occurrence list: 8-ary steps (7 independent loads a round instead
-                        // of one), then the entries from there 8 at a time
-                        const uint64_t key_lo = (uint64_t)(hiw & 0x7fffffffu) << 32 | (uint64_t)wlo << 1;
-                        uint32_t b = 0, len = occ0;
-                        while (len > 8u) {
-                            const uint32_t step = (len + 7u) >> 3;
-                            uint64_t pv[7];
-#pragma unroll
-                            for (uint32_t j = 0; j < 7u; ++j) { const uint32_t ix = b + (j + 1u) * step - 1u; pv[j] = ix < b + len ? lst[ix] : ~0ull; }
-                            uint32_t cnt = 0;
-#pragma unroll
-                            for (uint32_t j = 0; j < 7u; ++j) cnt += pv[j] < key_lo;
-                            const uint32_t nb = b + cnt * step;
-                            len = min(step, b + len - nb); b = nb;
-                        }
-                        {
-                            uint64_t pv[8];
-#pragma unroll
-                            for (uint32_t j = 0; j < 8u; ++j) pv[j] = j < len ? lst[b + j] : ~0ull;
-                            uint32_t cnt = 0;
-#pragma unroll
-                            for (uint32_t j = 0; j < 8u; ++j) cnt += pv[j] < key_lo;
-                            b += cnt;
-                        }
-                        first_l = b; c_l = 0;
-                        bool more = true;
-                        for (uint32_t t0 = b; more && t0 < occ0 && c_l <= 16u; t0 += 8u) {
-                            uint64_t pv[8];
-#pragma unroll
-                            for (uint32_t j = 0; j < 8u; ++j) pv[j] = t0 + j < occ0 ? lst[t0 + j] : ~0ull;
-#pragma unroll
-                            for (uint32_t j = 0; j < 8u; ++j) {
-                                const uint64_t pw = pv[j];
-                                if (!more || (uint32_t)(pw >> 32) != (hiw & 0x7fffffffu) || ((uint32_t)pw >> 1) > whi) { more = false; continue; }
-                                if ((((uint32_t)pw & 1u) != (rec0.w & 1u)) == (rel != 0)) { ++c_l; const uint32_t xp = (uint32_t)pw >> 1; nlo = min(nlo, xp); nhi = max(nhi, xp); }
-                            }
-                        }
+                        if (round == 0) lc_open(ls, lst, Q, wlo, whi); else lc_grow(ls, lst, Q, wlo, whi);
+                        nlo = min(nlo, ls.nlo); nhi = max(nhi, ls.nhi);
                     }
                     nlo = wave_all_min_u32(nlo); nhi = wave_all_max_u32(nhi);
-                    if (__ballot(c_l > 16u) != 0) { ok = false; if (STATS) why = LC_WINDOW; break; }
+                    if (__ballot(ls.c > LC_CAP) != 0) { ok = false; if (STATS) why = LC_WINDOW; break; }
                     if (nlo == lo && nhi == hi) break;
                     if (round == 3) { ok = false; if (STATS) why = LC_WINDOW; break; }
                     lo = nlo; hi = nhi;
                 }
             }
+            const uint32_t c_l = ls.c;
             const uint32_t n_k = ok ? wave_sum_u32(c_l) : 0u;
             if (STATS && ok && !(n_k >= 2 && n_k <= 64)) why = LC_K_SIZE;
             if (ok && n_k >= 2 && n_k <= 64) {
                 // K's anchors in generation order (seed order, then occurrence order): the order the full expansion gives them
                 const uint32_t ex = wave_excl_scan_u32(c_l, lane);
-                const uint32_t wlo = lo > mdx ? lo - mdx : 0u, whi = hi + mdx < hi ? 0xffffffffu : hi + mdx;
                 if (s_in) { e_x[ex] = xs; e_q[ex] = qs_; }
                 else if (multi && c_l) {
                     uint32_t o = 0;
-                    for (uint32_t t = first_l; t < occ0 && o < c_l; ++t) {
-                        const uint64_t pw = lst[t];
-                        if ((((uint32_t)pw & 1u) != (rec0.w & 1u)) != (rel != 0)) continue;
-                        if (((uint32_t)pw >> 1) > whi || ((uint32_t)pw >> 1) < wlo) continue;
+                    lc_collect(ls, lst, Q, [&](uint64_t pw) {
                         uint64_t x; uint32_t q;
                         make_anchor(pw, rec0.w, qlen, P.k, x, q);
                         e_x[ex + o] = x; e_q[ex + o] = q; ++o;
-                    }
+                    });
                 }
                 __syncthreads();
                 uint64_t x = lane < n_k ? e_x[lane] : ~0ull;
