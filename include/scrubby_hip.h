@@ -285,17 +285,18 @@ sh_status sh_classifier_run(const sh_classifier_config *cfg, sh_reads_result *ou
 sh_status sh_classifier_taxids(const char *report, const char *const *taxa, uint32_t n_taxa, const char *const *taxa_direct,
                                uint32_t n_direct, char *out, size_t cap, uint64_t *n_out);
 
-/* ---- `scrubby alignment`: cleaning from a precomputed alignment (PAF/GAF, or a one-column TXT of read ids) ---------
- * Cleaner::run_aligner_output (cleaner.rs:206-219), ReadAlignment::from / from_paf / from_txt (alignment.rs:33-114):
+/* ---- `scrubby alignment`: cleaning from a precomputed alignment (PAF/GAF, SAM/BAM, or a one-column TXT of read ids) ---------
+ * Cleaner::run_aligner_output (cleaner.rs:206-219), ReadAlignment::from / from_paf / from_txt / from_bam (alignment.rs:33-211):
  * a read is selected iff (query aligned length >= min_len OR query coverage >= min_cov) AND mapq >= min_mapq.
- * SAM/BAM/CRAM need the reference's optional htslib feature and are rejected here. */
+ * SAM and BAM (the reference's optional htslib feature) are read here: within the two formats the content decides, a gzip stream
+ * whose first inflated bytes are "BAM\1" is BAM, anything else is SAM text (sh_bam_* below).  CRAM is rejected by name. */
 typedef struct sh_alignment_config {
     const char *input[2];
     const char *output[2];
     uint32_t    n_files;
     int32_t     extract;
     const char *alignment;    /* -a */
-    const char *format;       /* "paf" | "gaf" | "txt", or NULL: by the file's (last) extension */
+    const char *format;       /* "paf" | "gaf" | "txt" | "sam" | "bam", or NULL: by the file's (last) extension */
     uint64_t    min_len;      /* -l */
     double      min_cov;      /* -c */
     uint32_t    min_mapq;     /* -q */
@@ -980,6 +981,47 @@ sh_status sh_gunzip_close(sh_gunzip *gz);
  * chunk counts as none.  Wrong starts cost rounds, never bytes. */
 sh_status sh_dbg_gunzip_starts(sh_inflater *inf, uint32_t chunk_bytes, const uint8_t *d_in, uint64_t n, const uint64_t *starts, uint64_t n_starts,
                                uint8_t *d_out, uint64_t out_cap, uint64_t *out_len, void *stream, sh_gunzip_stats *stats);
+
+/* ---- BAM records filtered on the device (sh_bam.hip): the reader behind `scrubby alignment -a x.bam` when
+ *      SCRUBBY_HIP_GUNZIP_DEVICE is 1 or 2 ----
+ * The rule (ReadAlignment::from_bam, alignment.rs:115-211): for every record that is not unmapped (flag & 4), qalen = the lengths of
+ * its CIGAR ops M and I (= and X count nothing), summed in 64 bits; qlen = l_seq; qcov = qlen ? (double)qalen / (double)qlen : 0; the
+ * record's name is selected iff (qalen >= min_len || qcov >= min_cov) && mapq >= min_mapq.  A name is the l_read_name - 1 bytes
+ * before the terminating NUL, compared as bytes (the reference's UTF-8 check is not reproduced).  The CIGAR is the CG:B,I tag's when
+ * n_cigar_op != 0, refID >= 0, pos >= 0, the first stored op is <l_seq>S and the record's first CG tag is B,I with a count
+ * >= n_cigar_op and < 2^29 (htslib's bam_tag2cigar as recalled: PARITY WITH htslib UNPINNED); else the stored one.
+ * A record may start at p when (judged on the bytes of it that lie in the window) block_size is in [32 + l_read_name + 4 * n_cigar_op
+ * + (l_seq + 1) / 2 + l_seq, 64 MiB] with l_seq >= 0, l_read_name >= 1, the name's last byte is 0, refID and next_refID lie in
+ * [-1, n_ref), pos and next_pos are >= -1.
+ *
+ * text[0, n) is a window of the inflated record stream; base its offset in the stream (for error messages only); entry the offset in
+ * the window of a record start.  Out: the names of the selected records, each followed by one NUL, in record order (duplicates stay),
+ * and *next_entry, the first chain position whose record does not lie in the window whole: the caller presents the bytes from there
+ * again, in front of new ones.  With last != 0 the chain must end at n, else SH_ERR_IO "truncated BAM record at <base + p>"; a chain
+ * position that is no record is SH_ERR_IO "not a BAM record at <base + p>": never a short or wrong output.  names_cap below
+ * sh_bam_names_bound(n - entry), or n above the scanner's size: SH_ERR_BAD_ARG naming the sizes, before any launch.
+ * stats: n_segments counts the segments (of sh_bam_segment() bytes, at fixed offsets of the window) in which a record of the chain
+ * starts; n_plausible the positions at which a record may start and n_fallback_segments the segments walked on the host because they
+ * hold more such positions than sh_bam_segment_cap() are the device path's (0 from the host). */
+typedef struct sh_bam_rule  { uint64_t min_len; double min_cov; uint32_t min_mapq; int32_t n_ref; } sh_bam_rule;
+typedef struct sh_bam_stats { uint64_t n_records, n_unmapped, n_selected, n_cg, n_segments, n_plausible, n_fallback_segments, name_bytes;
+                              float ms_probe, ms_chain, ms_filter, ms; } sh_bam_stats;
+typedef struct sh_bam_scanner sh_bam_scanner;  /* scratch for windows of up to max_bytes (below 2^31); one call at a time */
+/* host only: the header of text[0, n).  *stopped = 0: *n_ref and *first_record (the offset of the first record) are set; 1: needs more
+ * bytes; 2: not BAM */
+sh_status sh_bam_header(const uint8_t *text, uint64_t n, int32_t *n_ref, uint64_t *first_record, int32_t *stopped);
+uint32_t  sh_bam_segment(void);      /* bytes per segment */
+uint32_t  sh_bam_segment_cap(void);  /* plausible starts a segment's table holds */
+uint64_t  sh_bam_names_bound(uint64_t n);      /* the most name bytes n bytes of records give */
+sh_status sh_bam_scanner_create(int32_t device, uint64_t max_bytes, sh_bam_scanner **out);
+sh_status sh_bam_scanner_free(sh_bam_scanner *sc);
+sh_status sh_bam_filter_device(sh_bam_scanner *sc, const uint8_t *d_text, uint64_t n, uint64_t base, uint64_t entry, int32_t last, const sh_bam_rule *rule,
+                               uint8_t *d_names, uint64_t names_cap, uint64_t *names_len, uint64_t *next_entry, void *stream, sh_bam_stats *stats);
+/* the host mirror (no GPU): the same answer from the same code (sh_bam.h) in one serial walk */
+sh_status sh_bam_filter_host(const uint8_t *text, uint64_t n, uint64_t base, uint64_t entry, int32_t last, const sh_bam_rule *rule, uint8_t *names, uint64_t names_cap,
+                             uint64_t *names_len, uint64_t *next_entry, sh_bam_stats *stats);
+/* host only, for the tests of the table's size: counts[s] = the positions of segment s at which a record may start */
+sh_status sh_bam_plausible_host(const uint8_t *text, uint64_t n, int32_t n_ref, uint32_t *counts, uint64_t n_counts);
 
 #ifdef __cplusplus
 }

@@ -815,6 +815,76 @@ static bool gz_lines(const char *path, std::vector<std::string> &lines)
     return true;
 }
 
+// ---- SAM text (ReadAlignment::from_bam reads it through htslib, alignment.rs:115-211): the rule of sh_bam.h on the eleven mandatory fields --
+// Divergences, named: FLAG is decimal only (htslib also takes hexadecimal and the symbolic form); the CG tag of a SAM line is not
+// consulted (samtools writes the real CIGAR into the text).  PARITY WITH htslib UNPINNED.
+static bool sam_digits(const std::string &s, uint64_t max, uint64_t &v)
+{
+    if (s.empty() || s.size() > 18) return false;
+    v = 0;
+    for (char c : s) { if (c < '0' || c > '9') return false; v = v * 10 + (uint64_t)(c - '0'); }
+    return v <= max;
+}
+
+// CIGAR text: "*" (no ops) or <length><op> repeated, ops MIDNSHP=X.  qalen: M and I; qlen_cigar: what consumes the query (M I S = X)
+static bool sam_cigar(const std::string &s, uint64_t &qalen, uint64_t &qlen_cigar, bool &has_ops)
+{
+    qalen = qlen_cigar = 0; has_ops = false;
+    if (s == "*") return true;
+    if (s.empty()) return false;
+    for (size_t i = 0; i < s.size();) {
+        uint64_t len = 0;
+        size_t d = i;
+        for (; d < s.size() && s[d] >= '0' && s[d] <= '9'; ++d) { len = len * 10 + (uint64_t)(s[d] - '0'); if (len >= (1ull << 28)) return false; }      // 28 bits in BAM
+        if (d == i || d == s.size()) return false;
+        switch (s[d]) {
+        case 'M': case 'I': qalen += len; qlen_cigar += len; break;
+        case 'S': case '=': case 'X': qlen_cigar += len; break;
+        case 'D': case 'N': case 'H': case 'P': break;
+        default: return false;
+        }
+        has_ops = true;
+        i = d + 1;
+    }
+    return true;
+}
+
+static sh_status sam_ids(const char *path, uint64_t min_len, double min_cov, uint32_t min_mapq, std::unordered_set<std::string> &ids)
+{
+    std::vector<std::string> lines;
+    SH_CHECK(gz_lines(path, lines), SH_ERR_IO, "cannot read %s (missing, or a truncated gzip stream)", path);
+    for (size_t i = 0; i < lines.size(); ++i) {
+        const std::string &l = lines[i];
+        if (!l.empty() && l[0] == '@') continue;
+        auto f = split_tab(l);
+        SH_CHECK(f.size() >= 11 && !f[0].empty(), SH_ERR_IO, "%s: malformed SAM line %zu (%zu fields)", path, i + 1, f.size());
+        uint64_t flag, mapq, qalen, qlen_cigar;
+        bool has_ops;
+        SH_CHECK(sam_digits(f[1], 65535, flag), SH_ERR_IO, "%s: SAM line %zu: FLAG '%s' is not a decimal number below 65536", path, i + 1, f[1].c_str());
+        SH_CHECK(sam_digits(f[4], 255, mapq), SH_ERR_IO, "%s: SAM line %zu: MAPQ '%s' is not a number 0..255", path, i + 1, f[4].c_str());
+        SH_CHECK(sam_cigar(f[5], qalen, qlen_cigar, has_ops), SH_ERR_IO, "%s: SAM line %zu: CIGAR '%s' does not parse", path, i + 1, f[5].c_str());
+        SH_CHECK(!f[9].empty(), SH_ERR_IO, "%s: SAM line %zu: empty SEQ", path, i + 1);
+        const uint64_t qlen = f[9] == "*" ? 0 : f[9].size();
+        SH_CHECK(f[9] == "*" || !has_ops || qlen_cigar == qlen, SH_ERR_IO, "%s: SAM line %zu: CIGAR covers %llu query bases, SEQ has %llu", path, i + 1,
+                 (unsigned long long)qlen_cigar, (unsigned long long)qlen);
+        if (flag & 4) continue;
+        const double qcov = qlen == 0 ? 0.0 : (double)qalen / (double)qlen;
+        if ((qalen >= min_len || qcov >= min_cov) && mapq >= min_mapq) ids.insert(f[0]);
+    }
+    return SH_OK;
+}
+
+// the first inflated bytes of the file are "BAM\1"
+static bool holds_bam(const char *path)
+{
+    shc::In f;
+    if (!f.open(path)) return false;
+    char m[4];
+    size_t have = 0;
+    while (have < 4) { const long got = f.read(m + have, 4 - have); if (got <= 0) break; have += (size_t)got; }
+    return have == 4 && memcmp(m, "BAM\1", 4) == 0;
+}
+
 static sh_status alignment_ids(const char *path, const char *format, uint64_t min_len, double min_cov, uint32_t min_mapq, std::unordered_set<std::string> &ids)
 {
     std::string fmt = format ? format : "";
@@ -823,12 +893,16 @@ static sh_status alignment_ids(const char *path, const char *format, uint64_t mi
         size_t dot = p.rfind('.'), slash = p.rfind('/');
         std::string ext = (dot != std::string::npos && (slash == std::string::npos || dot > slash)) ? p.substr(dot + 1) : "";
         if (ext == "paf" || ext == "gaf") fmt = "paf"; else if (ext == "txt") fmt = "txt";
+        else if (ext == "sam" || ext == "bam" || ext == "cram") fmt = ext;
         else { sh_set_error("AlignmentInputFormatNotRecognized: %s", path); return SH_ERR_BAD_ARG; }
     }
     if (fmt == "gaf") fmt = "paf";
-    SH_CHECK(fmt == "paf" || fmt == "txt", SH_ERR_BAD_ARG, "AlignmentInputFormatInvalid: %s (SAM/BAM/CRAM need the reference's htslib feature)", fmt.c_str());
+    SH_CHECK(fmt != "cram", SH_ERR_BAD_ARG, "AlignmentInputFormatInvalid: cram (CRAM needs the reference's htslib feature and is not read here)");
+    SH_CHECK(fmt == "paf" || fmt == "txt" || fmt == "sam" || fmt == "bam", SH_ERR_BAD_ARG, "AlignmentInputFormatInvalid: %s", fmt.c_str());
     bool exists;
     if (file_is_empty(path, exists)) { SH_CHECK(exists, SH_ERR_IO, "cannot open %s", path); return SH_OK; }
+    // within SAM and BAM the content decides, as htslib sniffs it
+    if (fmt == "sam" || fmt == "bam") return holds_bam(path) ? shi_bam_ids(path, min_len, min_cov, min_mapq, ids) : sam_ids(path, min_len, min_cov, min_mapq, ids);
     std::vector<std::string> lines;
     SH_CHECK(gz_lines(path, lines), SH_ERR_IO, "cannot read %s (missing, or a truncated gzip stream)", path);
     if (fmt == "txt") { for (auto &l : lines) ids.insert(l); return SH_OK; }       // one id per line, verbatim

@@ -29,6 +29,9 @@ sh_status shi_kraken_run_legacy(const sh_kraken_config *c, sh_reads_result *res)
 sh_status shi_taxids_from_report(const char *report, const std::vector<std::string> &taxa_in, const std::vector<std::string> &direct_in,
                                  std::unordered_set<std::string> &out);
 void shi_mkdir_p(const std::string &dir);
+// `scrubby alignment` on a BAM file (sh_bam.hip): the names of the records the rule selects, added to ids.  The host path (zlib and
+// sh_bam_filter_host) unless SCRUBBY_HIP_GUNZIP_DEVICE is 1 or 2 and device 0 is usable
+sh_status shi_bam_ids(const char *path, uint64_t min_len, double min_cov, uint32_t min_mapq, std::unordered_set<std::string> &ids);
 // column 5 of kraken.reads for one unit (sh_k2_format_hits), appended to o; false = a code outside the taxonomy
 bool shi_k2_hitlist(std::string &o, const sh_k2_hit *e, uint64_t n, const uint32_t *external, uint64_t n_nodes, bool quick, uint32_t quick_taxid);
 // the Kraken arm's classification of one host batch for both writers: the results and, unless opts.quick, every unit's hit list

@@ -162,6 +162,18 @@ INFLATE_STATUS = ("ok", "bad block type", "bad code lengths", "invalid symbol", 
                   "bad gzip header", "second decode differs from the first", "ISIZE mismatch")
 SH_GUNZIP_FALLBACK = 10
 
+
+class BamRule(C.Structure):
+    _fields_ = [("min_len", C.c_uint64), ("min_cov", C.c_double), ("min_mapq", C.c_uint32), ("n_ref", C.c_int32)]
+
+
+class BamStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_unmapped", "n_selected", "n_cg", "n_segments", "n_plausible", "n_fallback_segments", "name_bytes")] + \
+               [(n, C.c_float) for n in ("ms_probe", "ms_chain", "ms_filter", "ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
 EXPORTS = [
     "sh_version", "sh_device_count", "sh_last_error", "sh_preset",
     "sh_index_build", "sh_index_build_device", "sh_index_build_fasta", "sh_index_save", "sh_index_load",
@@ -190,6 +202,8 @@ EXPORTS = [
     "sh_deflate_bound", "sh_deflater_create", "sh_deflate_device", "sh_gzip_member", "sh_deflater_free",
     "sh_bgzf_scan", "sh_inflater_create", "sh_inflate_members_device", "sh_gunzip_bgzf", "sh_inflater_free",
     "sh_gunzip_open", "sh_gunzip_feed_device", "sh_gunzip_feed", "sh_gunzip_close", "sh_dbg_gunzip_starts",
+    "sh_bam_header", "sh_bam_segment", "sh_bam_segment_cap", "sh_bam_names_bound", "sh_bam_scanner_create", "sh_bam_scanner_free",
+    "sh_bam_filter_device", "sh_bam_filter_host", "sh_bam_plausible_host",
 ]
 
 _LIB = None
@@ -266,9 +280,20 @@ def load():
     L.sh_gunzip_feed.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(GunzipStats)]
     L.sh_gunzip_close.argtypes = [vp]
     L.sh_dbg_gunzip_starts.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(GunzipStats)]
+    L.sh_bam_header.argtypes = [vp, u64, C.POINTER(i32), C.POINTER(u64), C.POINTER(i32)]
+    L.sh_bam_names_bound.argtypes = [u64]
+    L.sh_bam_scanner_create.argtypes = [i32, u64, C.POINTER(vp)]
+    L.sh_bam_scanner_free.argtypes = [vp]
+    L.sh_bam_filter_device.argtypes = [vp, vp, u64, u64, u64, i32, C.POINTER(BamRule), vp, u64, C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(BamStats)]
+    L.sh_bam_filter_host.argtypes = [vp, u64, u64, u64, i32, C.POINTER(BamRule), vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(BamStats)]
+    L.sh_bam_plausible_host.argtypes = [vp, u64, i32, vp, u64]
     for name in EXPORTS:
-        if name not in ("sh_version", "sh_device_count", "sh_last_error", "sh_index_set_size", "sh_deflate_bound"):
+        if name not in ("sh_version", "sh_device_count", "sh_last_error", "sh_index_set_size", "sh_deflate_bound", "sh_bam_segment", "sh_bam_segment_cap",
+                        "sh_bam_names_bound"):
             getattr(L, name).restype = i32
+    L.sh_bam_segment.restype = u32
+    L.sh_bam_segment_cap.restype = u32
+    L.sh_bam_names_bound.restype = u64
     L.sh_index_set_size.restype = u32
     L.sh_deflate_bound.restype = u64
     _LIB = L
@@ -802,6 +827,83 @@ class Gunzip:
     def close(self):
         if self.h:
             load().sh_gunzip_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_segment():
+    """Bytes per segment of the device BAM filter (sh_bam_segment)."""
+    return int(load().sh_bam_segment())
+
+
+def bam_segment_cap():
+    """Plausible record starts a segment's table holds (sh_bam_segment_cap)."""
+    return int(load().sh_bam_segment_cap())
+
+
+def bam_names_bound(n):
+    """The most name bytes n bytes of BAM records give: what a names buffer must hold (sh_bam_names_bound)."""
+    return int(load().sh_bam_names_bound(n))
+
+
+def bam_header(text):
+    """The BAM header of `text` (inflated bytes) -> (stopped, n_ref, first_record); stopped: 0 parsed, 1 needs more bytes, 2 not BAM."""
+    n = len(text)
+    src = np.frombuffer(text, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+    n_ref, first, stopped = C.c_int32(0), C.c_uint64(0), C.c_int32(0)
+    check(load().sh_bam_header(src.ctypes.data, n, C.byref(n_ref), C.byref(first), C.byref(stopped)))
+    return stopped.value, n_ref.value, first.value
+
+
+def bam_plausible_counts(text, n_ref):
+    """Per segment of `text`, the positions at which a record may start (sh_bam_plausible_host: the host mirror of k_bam_probe's test)."""
+    n = len(text)
+    n_seg = -(-n // bam_segment())
+    src = np.frombuffer(text, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+    counts = np.zeros(max(n_seg, 1), dtype=np.uint32)
+    check(load().sh_bam_plausible_host(src.ctypes.data, n, n_ref, counts.ctypes.data, n_seg))
+    return counts[:n_seg]
+
+
+def _bam_rule(n_ref, min_len, min_cov, min_mapq):
+    return BamRule(min_len, min_cov, min_mapq, n_ref)
+
+
+def bam_filter_host(text, n_ref, entry=0, last=True, min_len=0, min_cov=0.0, min_mapq=0, base=0, names_cap=None):
+    """The host mirror (sh_bam_filter_host) over `text`, a window of the inflated record stream -> (names bytes, next_entry, stats)."""
+    n = len(text)
+    src = np.frombuffer(text, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+    cap = bam_names_bound(max(n - entry, 0)) if names_cap is None else names_cap
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    rule, st, names_len, nxt = _bam_rule(n_ref, min_len, min_cov, min_mapq), BamStats(), C.c_uint64(0), C.c_uint64(0)
+    check(load().sh_bam_filter_host(src.ctypes.data, n, base, entry, int(last), C.byref(rule), out.ctypes.data, cap, C.byref(names_len), C.byref(nxt), C.byref(st)))
+    return out[:names_len.value].tobytes(), nxt.value, st.as_dict()
+
+
+class BamScanner:
+    """Owns an sh_bam_scanner: BAM records of windows of up to max_bytes filtered on the device."""
+
+    def __init__(self, max_bytes, device=0):
+        L = require_gpu()
+        self.h = C.c_void_p()
+        check(L.sh_bam_scanner_create(device, max_bytes, C.byref(self.h)))
+
+    def filter_device(self, d_text, n, n_ref, d_names, entry=0, last=True, min_len=0, min_cov=0.0, min_mapq=0, base=0, names_cap=None):
+        """d_text / d_names: torch uint8 CUDA tensors; the first n bytes of d_text -> (names_len, next_entry, stats)."""
+        cap = d_names.numel() if names_cap is None else names_cap
+        rule, st, names_len, nxt = _bam_rule(n_ref, min_len, min_cov, min_mapq), BamStats(), C.c_uint64(0), C.c_uint64(0)
+        check(load().sh_bam_filter_device(self.h, C.c_void_p(d_text.data_ptr()), n, base, entry, int(last), C.byref(rule), C.c_void_p(d_names.data_ptr()), cap,
+                                          C.byref(names_len), C.byref(nxt), _stream_ptr(), C.byref(st)))
+        return names_len.value, nxt.value, st.as_dict()
+
+    def close(self):
+        if self.h:
+            load().sh_bam_scanner_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
