@@ -682,6 +682,43 @@ sh_status sh_dbg_ksw_extd2(int32_t device, const uint8_t *blob, uint64_t blob_le
 typedef struct sh_dbg_ll_case { uint64_t q_off, t_off; int32_t qlen, tlen, a, b, sc_ambi, gapo, gape, pad; } sh_dbg_ll_case;
 typedef struct sh_dbg_ll_result { int32_t score, qe, te, pad; } sh_dbg_ll_result;
 sh_status sh_dbg_ksw_ll(int32_t device, const uint8_t *blob, uint64_t blob_len, const sh_dbg_ll_case *cases, int32_t n_cases, sh_dbg_ll_result *out);
+/* Test aids: the region bookkeeping between "a read's chains" and "a region survives mm_filter_regs" - mm_gen_regs' order, mm_set_parent,
+ * mm_select_sub, the split / insert steps of mm_align_skeleton - called directly (csrc/sh_dbg_align.hip; tests/test_regs_gpu.py compares with the
+ * oracle's mma_align_read_rows / mma_chain_post and with the plain model tests/regs_ref.py, integers only).
+ *
+ * sh_dbg_regs_short: align_read_wave of csrc/sh_align.h, one wave per read, over caller-made chains.  ref_packed / cstart: the reference as 4-bit
+ * codes and the contig starts (n_contigs + 1); bases / offsets: the reads (ASCII); cx / cq: the anchors (x = strand << 63 | contig << 32 | last
+ * reference base, q = last query base); recs / head: the chain records with their `next` links exactly as given, head[read] = the first record
+ * of the read or ~0u.  mode[read]: 0 every region, 1 flag_only (stops at the first survivor), 2 top_z: the record with the read's largest z
+ * alone, through the AlignLdsTop instance (modes 0 and 1: AlignLds).  Every wave's scratch is laid out for (max_read_len, reg_cap) as the
+ * product lays it out and lies between two guard bands of 4 KiB of a known byte; out.guard = how many of their bytes changed.
+ * out.done = 0: the read was given up with out.overflow (2 more chains than reg_cap, 3 more primaries than room, 4 query beyond the scratch,
+ * 5 reference window beyond it, 6 a split needs a slot beyond the region arrays).  book: row_cap pairs per read - the record index of each region
+ * mm_select_sub kept, in order, and of the record of its parent; keep: row_cap rows of eight per read - rs, re, qs, qe, mlen, blen, dp_max, cnt of
+ * each surviving region; out.n_book / out.n_keep count every row, stored or not.
+ * Refused with SH_ERR_BAD_ARG before any launch - these are what the chaining kernels guarantee the product: a `next` chain that does not end in
+ * ~0u within n_recs steps or leaves the table; a record with no anchors, anchors outside cx / cq, a negative score, or a z that is not chain_z of
+ * its first anchor; anchors of a record not strictly ascending in x and in q, not on one contig and strand, or whose k bases do not lie inside
+ * the contig and inside the read; an empty read; k < 1, e < 1, reg_cap < 1, max_read_len < 1; a mode other than 0, 1, 2. */
+typedef struct sh_dbg_chain_rec { uint32_t next, cnt; int32_t score; uint32_t key_f, key_i, yfl; uint64_t off, z; } sh_dbg_chain_rec;
+typedef struct sh_dbg_align_params {
+    int32_t k, min_cnt, min_sc, max_gap, bw, bw_long;
+    int32_t a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus, min_dp_max, best_n;
+    float pri_ratio, mask_level, max_clip_ratio;
+    int32_t lemma, unc_max;
+} sh_dbg_align_params;
+typedef struct sh_dbg_regs_out { int32_t n_aligned, n_regs, dp_max; uint32_t sig, overflow; int32_t done; uint32_t n_book, n_keep, guard, pad; } sh_dbg_regs_out;
+sh_status sh_dbg_regs_short(int32_t device, const uint8_t *ref_packed, const uint64_t *cstart, uint32_t n_contigs, const uint8_t *bases,
+                            const uint64_t *offsets, uint32_t n_reads, const uint64_t *cx, const uint32_t *cq, uint64_t n_anchors,
+                            const sh_dbg_chain_rec *recs, uint32_t n_recs, const uint32_t *head, const sh_dbg_align_params *params,
+                            uint32_t reg_cap, uint32_t max_read_len, const int32_t *mode, uint32_t row_cap,
+                            sh_dbg_regs_out *out, uint32_t *book, int32_t *keep);
+/* sh_dbg_regs_long: lr_set_parent0, then lr_select_sub0 (with lr_sync_regs0) of csrc/sh_long.h, one lane per case, over caller-made regions.
+ * tab: n_rows rows of nine ints - score, cnt, qs, qe, rs, re, rev, rid, inv; case i is the n rows from off.  rows: per kept region of case i, from
+ * row off on, six ints: its row in the case's table, id, parent, subsc, n_sub, strand_retained; n_kept[i] = how many.
+ * Refused before any launch: a case outside tab, n < 1 or n > 4096 (the scratch of a case), a region with qe <= qs. */
+typedef struct sh_dbg_lreg_case { uint64_t off; int32_t n, min_diff, best_n, min_strand_sc; float mask_level, pri_ratio; } sh_dbg_lreg_case;
+sh_status sh_dbg_regs_long(int32_t device, const int32_t *tab, uint64_t n_rows, const sh_dbg_lreg_case *cases, int32_t n_cases, int32_t *n_kept, int32_t *rows);
 /* Test aid: the variants of the chaining DP (mg_lchain_dp) and of the backtrack (mg_chain_backtrack) in csrc/sh_chain.h, called directly
  * (csrc/sh_dbg_chain.hip; tests/test_chain_gpu.py compares them with the oracle's mmo_chain_arrays, integers only).  One launch per DP variant,
  * one block per case, with the block size the product runs the variant with.

@@ -1374,9 +1374,17 @@ static const uint8_t nt4[256] = {
 #undef R4
 };
 
-void mma_align_read(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t *contig_start, uint32_t n_contigs,
-                    const uint8_t *seq, int32_t qlen, int32_t n_u, const uint64_t *u, mma_anchor *a,
-                    int32_t n_mini_pos, const uint64_t *mini_pos, mma_result *res)
+/* one bookkeeping row (MMA_BOOK_W ints): what chain_post left of a region.  chain: the region's index in u[] (or in the caller's table) */
+static void book_row(int32_t *row, int32_t chain, const reg_t *r)
+{
+    const int32_t v[MMA_BOOK_W] = { chain, r->parent, r->score, r->cnt, r->qs, r->qe, r->rs, r->re, r->rev, r->rid, r->subsc, r->n_sub, r->strand_retained };
+    memcpy(row, v, sizeof(v));
+}
+
+static void align_read_impl(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t *contig_start, uint32_t n_contigs,
+                            const uint8_t *seq, int32_t qlen, int32_t n_u, const uint64_t *u, mma_anchor *a,
+                            int32_t n_mini_pos, const uint64_t *mini_pos, mma_result *res,
+                            int32_t *book, int32_t book_cap, int32_t *n_book, int32_t *keep, int32_t keep_cap, int32_t *n_keep)
 {
     actx_t c;
     reg_t *regs;
@@ -1400,6 +1408,14 @@ void mma_align_read(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t
         n_regs = filter_strand_retained(n_regs, regs);
     }
     res->n_aligned = n_regs;
+    if (n_book) {      /* the rows: a region's chain is the one whose anchors start at its `as` (squeeze_a has not run yet) */
+        *n_book = n_regs;
+        for (i = 0; i < n_regs && i < book_cap; ++i) {
+            int32_t j, k = 0;
+            for (j = 0; j < n_u && k != regs[i].as; ++j) k += (int32_t)u[j];
+            book_row(book + (size_t)i * MMA_BOOK_W, j < n_u ? j : -1, &regs[i]);
+        }
+    }
 
     /* mm_align_skeleton */
     c.qseq0[0] = (uint8_t *)malloc((size_t)qlen * 2 + 16);
@@ -1439,8 +1455,46 @@ void mma_align_read(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t
         int j;
         for (j = 0; j < 8; ++j) { sig ^= (uint32_t)v[j]; sig *= 16777619u; }
         if (r->p && r->p->dp_max > res->dp_max) res->dp_max = r->p->dp_max;
+        if (keep && i < keep_cap) memcpy(keep + (size_t)i * MMA_KEEP_W, v, sizeof(v));
     }
+    if (n_keep) *n_keep = n_regs;
     res->sig = n_regs > 0 ? sig : 0;
     for (i = 0; i < n_regs; ++i) if (regs[i].p) { free(regs[i].p->cigar); free(regs[i].p); }
     free(regs);
+}
+
+void mma_align_read(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t *contig_start, uint32_t n_contigs,
+                    const uint8_t *seq, int32_t qlen, int32_t n_u, const uint64_t *u, mma_anchor *a,
+                    int32_t n_mini_pos, const uint64_t *mini_pos, mma_result *res)
+{
+    align_read_impl(o, ref_packed, contig_start, n_contigs, seq, qlen, n_u, u, a, n_mini_pos, mini_pos, res, 0, 0, 0, 0, 0, 0);
+}
+
+void mma_align_read_rows(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t *contig_start, uint32_t n_contigs,
+                         const uint8_t *seq, int32_t qlen, int32_t n_u, const uint64_t *u, mma_anchor *a,
+                         int32_t n_mini_pos, const uint64_t *mini_pos, mma_result *res,
+                         int32_t *book, int32_t book_cap, int32_t *n_book, int32_t *keep, int32_t keep_cap, int32_t *n_keep)
+{
+    *n_book = *n_keep = 0;
+    align_read_impl(o, ref_packed, contig_start, n_contigs, seq, qlen, n_u, u, a, n_mini_pos, mini_pos, res, book, book_cap, n_book, keep, keep_cap, n_keep);
+}
+
+int32_t mma_chain_post(float mask_level, float pri_ratio, int32_t min_diff, int32_t best_n, int32_t min_strand_sc,
+                       int32_t n, const int32_t *tab, int32_t *book)
+{
+    reg_t *r;
+    int i, k = n;
+    if (n <= 0) return 0;
+    r = (reg_t *)calloc((size_t)n, sizeof(reg_t));
+    for (i = 0; i < n; ++i) {
+        const int32_t *t = tab + (size_t)i * MMA_TAB_W;
+        r[i].id = i; r[i].parent = PARENT_UNSET; r[i].div = -1.0f;
+        r[i].score = t[0]; r[i].cnt = t[1]; r[i].qs = t[2]; r[i].qe = t[3]; r[i].rs = t[4]; r[i].re = t[5]; r[i].rev = t[6]; r[i].rid = t[7]; r[i].inv = t[8];
+        r[i].as = i;      /* no anchors here: the field carries the row's place in the table through the compaction */
+    }
+    set_parent(mask_level, INT_MAX, n, r);
+    select_sub(pri_ratio, min_diff, best_n, 1, min_strand_sc, &k, r);
+    for (i = 0; i < k; ++i) book_row(book + (size_t)i * MMA_BOOK_W, r[i].as, &r[i]);
+    free(r);
+    return k;
 }

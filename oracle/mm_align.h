@@ -48,6 +48,23 @@ void mma_align_read(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t
                     const uint8_t *seq, int32_t qlen, int32_t n_u, const uint64_t *u, mma_anchor *a,
                     int32_t n_mini_pos, const uint64_t *mini_pos /* mm_collect_matches' list, for mm_est_err */, mma_result *res);
 
+/* The same, saying more than the signature.  book: one row of MMA_BOOK_W ints per region after mm_set_parent / mm_select_sub (and, for
+ * !is_sr, after mm_est_err and the strand filter), in order: the index of its chain in u[], parent, score, cnt, qs, qe, rs, re, rev, rid,
+ * subsc, n_sub, strand_retained.  keep: one row of MMA_KEEP_W ints per region mm_filter_regs leaves - the eight values that go into sig:
+ * rs, re, qs, qe, mlen, blen, dp_max, cnt.  *n_book / *n_keep count every row; only the first book_cap / keep_cap are stored. */
+#define MMA_BOOK_W 13
+#define MMA_KEEP_W 8
+void mma_align_read_rows(const mmo_opts *o, const uint8_t *ref_packed, const uint64_t *contig_start, uint32_t n_contigs,
+                         const uint8_t *seq, int32_t qlen, int32_t n_u, const uint64_t *u, mma_anchor *a,
+                         int32_t n_mini_pos, const uint64_t *mini_pos, mma_result *res,
+                         int32_t *book, int32_t book_cap, int32_t *n_book, int32_t *keep, int32_t keep_cap, int32_t *n_keep);
+
+/* mm_set_parent + mm_select_sub (check_strand on) over a caller-made table of n regions, MMA_TAB_W ints each: score, cnt, qs, qe, rs, re, rev,
+ * rid, inv.  Returns how many are kept and their bookkeeping rows (room for n), whose first column is the region's row in the table. */
+#define MMA_TAB_W 9
+int32_t mma_chain_post(float mask_level, float pri_ratio, int32_t min_diff, int32_t best_n, int32_t min_strand_sc,
+                       int32_t n, const int32_t *tab, int32_t *book);
+
 /* ksw_ll_i16 (local alignment score, end of the best hit as upstream's striped scan reports it); used by the inversion tests */
 int mma_ksw_ll(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int gapo, int gape, int *qe, int *te);
 

@@ -98,6 +98,10 @@ def lib():
     L.mma_ksw_extd2.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int8, C.c_void_p, C.c_int8, C.c_int8, C.c_int8, C.c_int8,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.mma_gen_simple_mat.argtypes = [C.c_int, C.c_void_p, C.c_int8, C.c_int8, C.c_int8]
+    L.mma_align_read_rows.argtypes = [C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    L.mma_chain_post.argtypes = [C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.mma_chain_post.restype = C.c_int32
     L.mmo_index_n_keys.argtypes = [C.c_void_p]
     L.mmo_index_n_keys.restype = C.c_uint64
     L.mmo_index_n_positions.argtypes = [C.c_void_p]
@@ -190,6 +194,40 @@ def backtrack_arrays(o, f, p):
     n_u, n_v = C.c_int32(0), C.c_int64(0)
     lib().mmo_backtrack_arrays(C.byref(o), n, f.ctypes.data, p.ctypes.data, u.ctypes.data, v.ctypes.data, C.byref(n_u), C.byref(n_v))
     return _chain_list(f, p, u, v, n_u.value, n_v.value)
+
+
+BOOK_FIELDS = ("chain", "parent", "score", "cnt", "qs", "qe", "rs", "re", "rev", "rid", "subsc", "n_sub", "strand_retained")
+KEEP_FIELDS = ("rs", "re", "qs", "qe", "mlen", "blen", "dp_max", "cnt")
+TAB_FIELDS = ("score", "cnt", "qs", "qe", "rs", "re", "rev", "rid", "inv")
+
+
+def align_read_rows(o, ref_packed, contig_start, seq, u, ax, ay, mini_pos=None):
+    """mma_align_read_rows: the extension stage of one read over its chains u[] (score << 32 | cnt) and their anchors (ax, ay) in chain
+    order -> ((n_aligned, n_regs, dp_max, sig), book rows, keep rows), rows as int32 arrays with BOOK_FIELDS / KEEP_FIELDS columns."""
+    ref_packed = np.ascontiguousarray(ref_packed, np.uint8)
+    contig_start = np.ascontiguousarray(contig_start, np.uint64)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    u = np.ascontiguousarray(u, np.uint64)
+    a = np.empty((len(ax), 2), np.uint64)      # squeeze_a moves the anchors: a private copy
+    a[:, 0], a[:, 1] = ax, ay
+    mp = np.ascontiguousarray(mini_pos if mini_pos is not None else [], np.uint64)
+    cap = 2 * len(u) + 64      # every region can split off more than one tail; the counts say if this was too small
+    book, keep = np.zeros((cap, len(BOOK_FIELDS)), np.int32), np.zeros((cap, len(KEEP_FIELDS)), np.int32)
+    res = (C.c_int32 * 4)()
+    n_book, n_keep = C.c_int32(0), C.c_int32(0)
+    lib().mma_align_read_rows(C.byref(o), ref_packed.ctypes.data, contig_start.ctypes.data, len(contig_start) - 1, seq.ctypes.data, len(seq), len(u),
+                              u.ctypes.data, a.ctypes.data, len(mp), mp.ctypes.data, C.cast(res, C.c_void_p), book.ctypes.data, cap, C.byref(n_book),
+                              keep.ctypes.data, cap, C.byref(n_keep))
+    assert n_book.value <= cap and n_keep.value <= cap
+    return (res[0], res[1], res[2], res[3] & 0xffffffff), book[:n_book.value].copy(), keep[:n_keep.value].copy()
+
+
+def chain_post(mask_level, pri_ratio, min_diff, best_n, min_strand_sc, tab):
+    """mma_chain_post: mm_set_parent + mm_select_sub over a table of regions (TAB_FIELDS columns) -> the kept regions' BOOK_FIELDS rows"""
+    tab = np.ascontiguousarray(tab, np.int32).reshape(-1, len(TAB_FIELDS))
+    book = np.zeros((max(len(tab), 1), len(BOOK_FIELDS)), np.int32)
+    k = lib().mma_chain_post(mask_level, pri_ratio, min_diff, best_n, min_strand_sc, len(tab), tab.ctypes.data, book.ctypes.data)
+    return book[:k].copy()
 
 
 def sketch(seq, w, k, rid=0):

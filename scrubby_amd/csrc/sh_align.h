@@ -69,7 +69,7 @@ struct ChainSink {
     unsigned long long *best; uint32_t *tie;
 };
 
-__device__ inline uint64_t al_hash64(uint64_t key)
+__host__ __device__ inline uint64_t al_hash64(uint64_t key)
 {
     key = (~key + (key << 21));
     key = key ^ key >> 24;
@@ -80,20 +80,20 @@ __device__ inline uint64_t al_hash64(uint64_t key)
     key = (key + (key << 31));
     return key;
 }
-__device__ inline uint32_t al_wang(uint32_t key)
+__host__ __device__ inline uint32_t al_wang(uint32_t key)
 {
     key += ~(key << 15); key ^= (key >> 10); key += (key << 3); key ^= (key >> 6); key += ~(key << 11); key ^= (key >> 16);
     return key;
 }
 // mm_map_frag's hash of the (absent) query name, the query length and opt->seed = 11
-__device__ inline uint32_t region_hash(int32_t qlen)
+__host__ __device__ inline uint32_t region_hash(int32_t qlen)
 {
     uint32_t h = 0;
     h ^= al_wang((uint32_t)qlen) + al_wang(11u);
     return al_wang(h);
 }
 // mm_gen_regs' sort key of a chain whose first anchor is (x0, q0)
-__device__ inline unsigned long long chain_z(uint64_t x0, uint32_t q0, int32_t k, int32_t score, uint32_t cnt, uint32_t rhash, uint64_t yfl)
+__host__ __device__ inline unsigned long long chain_z(uint64_t x0, uint32_t q0, int32_t k, int32_t score, uint32_t cnt, uint32_t rhash, uint64_t yfl)
 {
     const uint64_t y0 = yfl | (uint64_t)(uint32_t)k << 32 | q0;
     const uint32_t h = (uint32_t)al_hash64((al_hash64(x0) + al_hash64(y0)) ^ rhash);
@@ -824,9 +824,20 @@ __device__ inline int32_t top_chain_settles(const AlignIn &in, const AlignParams
 // `mappings.len() > 0`); else every region is aligned and the counts / fingerprint are those of the oracle's trace.
 // top_z != 0: only the chain with that z - regs[0] of mm_gen_regs, which is aligned whatever the other chains are - goes through
 // mm_align1; a surviving region settles the read (n_regs > 0), none means the caller must run the full procedure on all chains.
-template <class LDS, bool CLK = false>
+//
+// HOOK: what a test wants to see of the bookkeeping (sh_dbg_regs_short, csrc/sh_dbg_align.hip).  The product's kernels take AlignNoHook, for
+// which every hook statement is compiled out, as the clocks are without CLK.  AlignRowsHook (lane 0 writes, into memory of the caller's):
+// book: per region mm_select_sub keeps, in order, the ChainRec index of its chain and of its parent's chain (the parent as mm_set_parent named
+// it: select_sub's aliasing changes which region a secondary is COMPARED with, never this); keep: per region that survives mm_filter_regs
+// the eight values that go into sig.  The counts go on beyond the caps, the stores do not.
+struct AlignNoHook { static constexpr bool on = false; };
+struct AlignRowsHook {
+    static constexpr bool on = true;
+    uint32_t *book; int32_t *keep; uint32_t book_cap, keep_cap, n_book, n_keep;
+};
+template <class LDS, bool CLK = false, class HOOK = AlignNoHook>
 __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, uint32_t read, bool flag_only, AlignScratch &A, LDS &Ls,
-                                       AlignOut &out, uint32_t *overflow, unsigned long long top_z = 0)
+                                       AlignOut &out, uint32_t *overflow, unsigned long long top_z = 0, HOOK *hk = nullptr)
 {
     const uint32_t lane = al_lane();
     const int32_t qlen = (int32_t)(in.offsets[read + 1] - in.offsets[read]);
@@ -930,6 +941,8 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
                 }
             } else j = k;
             if (j == k) {
+                // (never taken as the code stands: k <= i < n_u here, and n_u <= pri_cap in both instances - reg_cap by the check on n_u
+                // above when the regions are in scratch, NR <= NPRI when they are in LDS.  The check stays: it guards w[] and cov[].)
                 if (k >= pri_cap) { too_many = true; break; }
                 w[k++] = i; regs[i].parent = i;
             }
@@ -937,6 +950,13 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
         };
         if (rg) set_parent(A.pri, A.cov, (int32_t)A.reg_cap); else set_parent(Ls.pri, Ls.cov, (int32_t)LDS::NPRI);
         if (too_many) atomicExch(overflow, 3u);
+        auto note = [&](int32_t i, int32_t p) {      // HOOK: region i (its place in gen_regs' order) is kept; p: its parent's place
+            if constexpr (HOOK::on) {
+                if (hk->n_book < hk->book_cap) { hk->book[2 * hk->n_book] = rg ? cc_u32(ord + i) : ord[i]; hk->book[2 * hk->n_book + 1] = rg ? cc_u32(ord + p) : ord[p]; }
+                ++hk->n_book;
+            }
+        };
+        if constexpr (HOOK::on) if (!(P.pri_ratio > 0.0f) && !too_many) for (int32_t i = 0; i < n_u; ++i) note(i, regs[i].parent);
         // mm_select_sub (check_strand = 1, min_strand_sc = max_gap * 0.8), in place like upstream: r[p] is read AFTER earlier
         // regions moved up, so a parent index can alias a later region - kept literally
         if (P.pri_ratio > 0.0f && n_u > 0 && !too_many) {
@@ -955,13 +975,13 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
             for (int32_t i = 0; i < n_u; ++i) {
                 const RegLite ri = RD(i);
                 const int32_t p = ri.parent;
-                if (p == i) { regs[kk2++] = ri; continue; }
+                if (p == i) { note(i, p); regs[kk2++] = ri; continue; }
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
                 const RegLite rp = RD(p);
                 if ((ri.score >= rp.score * P.pri_ratio || ri.score + min_diff >= rp.score) && n_2nd < P.best_n) {
-                    if (!(ri.qs == rp.qs && ri.qe == rp.qe && ri.rid == rp.rid && ri.rs == rp.rs && ri.re == rp.re)) { regs[kk2++] = ri; ++n_2nd; }
+                    if (!(ri.qs == rp.qs && ri.qe == rp.qe && ri.rid == rp.rid && ri.rs == rp.rs && ri.re == rp.re)) { note(i, p); regs[kk2++] = ri; ++n_2nd; }
                 } else if (n_2nd < P.best_n && ri.score > min_strand_sc && rp.rev != ri.rev && rp.rid == ri.rid && ri.rs < rp.re && ri.re > rp.rs) {
-                    regs[kk2++] = ri; ++n_2nd;
+                    note(i, p); regs[kk2++] = ri; ++n_2nd;
                 }
             }
             n_regs = kk2;
@@ -1136,6 +1156,10 @@ __device__ inline bool align_read_wave(const AlignIn &in, const AlignParams &P, 
                 const int32_t v[8] = { r.rs, r.re, r.qs, r.qe, mlen, blen, dpm, r_cnt };
                 for (int32_t j = 0; j < 8; ++j) { sig ^= (uint32_t)v[j]; sig *= 16777619u; }
                 if (dpm > dp_best) dp_best = dpm;
+                if constexpr (HOOK::on) {
+                    if (hk->n_keep < hk->keep_cap) for (int32_t j = 0; j < 8; ++j) hk->keep[8 * hk->n_keep + j] = v[j];
+                    ++hk->n_keep;
+                }
                 ++n_keep;
             }
         }
