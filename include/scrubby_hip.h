@@ -762,6 +762,41 @@ typedef struct sh_dbg_stage_case { uint64_t rec_off, out_off; int32_t n_seed, ql
 sh_status sh_dbg_stage_anchors(int32_t device, const uint32_t *records, uint64_t n_records, const uint64_t *positions, uint64_t n_positions,
                                int32_t k, int32_t max_occ, int32_t max_max_occ, int32_t occ_dist, const sh_dbg_stage_case *cases, int32_t n_cases,
                                uint64_t n_out, uint64_t *out_x, uint32_t *out_q, uint64_t *ref_x, uint32_t *ref_q, uint32_t *total);
+/* Test aid: the long join of csrc/sh_long.h - mg_lchain_rmq's scoring pass in every form the product runs, and the two backtracks behind it -
+ * called directly (csrc/sh_dbg_long.hip; tests/test_long_join_gpu.py compares with the oracle's mmo_lchain_rmq_fill / mmo_backtrack_arrays and
+ * the plain model of tests/long_join_ref.py, integers only).  One launch per instance (they differ in LDS), one 64-lane block per case.
+ * x / y: n_total anchors, y = q_span << 32 | qpos; a case reads n of them from `off`, ascending in x.
+ * fill: 0 = none, f / p are taken from f_in / p_in; 1..5 lr_rmq_fill<512,F,F>, <4096,F,F>, <4096,F,FAT>, <1024,TREE,F>, <4096,TREE,F> as
+ *     lr_chains_wave calls them (the TREE ones with an LDS tree of 1664 / 1792 nodes); 6 lr_rmq_fill_tree (t zeroed, pools of n + 2 nodes);
+ *     7 the case cut at cuts[cut_off .. cut_off + n_cut) (indices into the case, each a stretch start), every run filled by
+ *     lr_rmq_fill<ring,TREE,F> with p_base = the run's start and bmin at start / 64 + run, as lr_coop_take calls it; 8 lr_coop_fill<ring>
+ *     itself when n >= coop_min (else as 4 / 5): the cases of one (ring, q_cap) that agree on every option the fill reads (k, max_gap,
+ *     bw_long, max_skip, rmq_inner_dist, rmq_size_cap, pen_gap, pen_skip) share one launch and one queue of q_cap slots, one owner block each
+ *     (q_cap 0: every run stays with its owner) - a run is filled with the options of the wave that takes it, and in the product a launch has
+ *     one set of them.  ring: 1024 or 4096, read by 7 and 8.
+ * bt: 0 = none; 1 lr_backtrack0; 2 lr_backtrack_wave - over the candidates f >= min_sc compacted and sorted by lr_sort, t zeroed, as
+ *     lr_chains_wave sets it up; max_drop is what the product passes bw_long for.  Skipped when the fill returned false.
+ * The outputs of case i start at o_i = the sum of n over the cases before it in f_in, p_in, f, p, t, v and u (at most min(cap_u, n) chains).
+ * On the device every array a case's block writes (f, p, t, v, u, pri, bmin of n / 64 + 1 entries plus one per run, the sort keys, the node
+ * pools) lies between two 4 KiB bands of one byte value; guard = the number of band bytes that changed.
+ * SH_ERR_BAD_ARG before any launch: a case outside the arrays, n < 1, x not ascending, a q_span other than k (the ring scores with k), the low
+ * words of x and y negative or their sum beyond int32 (the priority adds them as int32), a cut that is no stretch start (x jumps by more than
+ * max(max_gap, bw_long) or the high word changes), uploaded f / p that are no chaining state, a variant not listed. */
+typedef struct sh_dbg_long_case {
+    uint64_t off, cut_off;
+    int32_t n, fill, bt, ring;
+    int32_t k, max_gap, bw_long, max_skip, rmq_inner_dist, rmq_size_cap, min_cnt, min_sc, coop_min, coop_run, max_drop, cap_u, n_cut, q_cap;
+    float pen_gap, pen_skip;
+} sh_dbg_long_case;
+typedef struct sh_dbg_long_result { int32_t ok, n_tie, n_u, n_v, best, ovf, n_z, pad; uint64_t guard; } sh_dbg_long_result;
+sh_status sh_dbg_long_join(int32_t device, const uint64_t *x, const uint64_t *y, uint64_t n_total, const sh_dbg_long_case *cases, int32_t n_cases,
+                           const int32_t *f_in, const int32_t *p_in, const int32_t *cuts, sh_dbg_long_result *out,
+                           int32_t *f, int32_t *p, int32_t *t, uint64_t *u, int32_t *v);
+/* lr_sort of csrc/sh_long.h alone: one wave per case sorts the n >= 0 distinct pairs (k[off + j], v[off + j]) ascending; out_i = each pair's
+ * place j in the input.  The arrays reach as far as the cases say; what no case covers comes back unchanged with out_i = ~0u. */
+typedef struct sh_dbg_lr_sort_case { uint64_t off; int32_t n, pad; } sh_dbg_lr_sort_case;
+sh_status sh_dbg_lr_sort(int32_t device, const uint64_t *k, const uint64_t *v, const sh_dbg_lr_sort_case *cases, int32_t n_cases,
+                         uint64_t *out_k, uint64_t *out_v, uint32_t *out_i);
 
 /* Test aid: the three minimizer state machines of csrc/sh_sketch.h, called directly (csrc/sh_dbg_sketch.hip; tests/test_sketch_gpu.py compares
  * them with the oracle's mmo_sketch, integers only).  One lane per sequence, one launch per call.  bases / offsets: host arrays, sequence i is

@@ -180,7 +180,7 @@ EXPORTS = [
     "sh_index_info_get", "sh_index_export", "sh_index_export_ref", "sh_index_free",
     "sh_ctx_create", "sh_ctx_destroy", "sh_ctx_debug_list", "sh_classify_device", "sh_classify_batch",
     "sh_index_replicate", "sh_index_set_size", "sh_index_set_free", "sh_classify_sharded",
-    "sh_synth_ref_device", "sh_synth_reads_device", "sh_synth_long_reads_device", "sh_bench_gather", "sh_dbg_rmq_trace", "sh_dbg_wave_ops", "sh_dbg_ksw_extd2", "sh_dbg_ksw_ll", "sh_dbg_regs_short", "sh_dbg_regs_long", "sh_dbg_chain", "sh_dbg_block_sort", "sh_dbg_stage_anchors", "sh_dbg_sketch", "sh_dbg_front_end", "sh_dbg_repeat_shortcuts", "sh_pack_flags_device",
+    "sh_synth_ref_device", "sh_synth_reads_device", "sh_synth_long_reads_device", "sh_bench_gather", "sh_dbg_rmq_trace", "sh_dbg_wave_ops", "sh_dbg_ksw_extd2", "sh_dbg_ksw_ll", "sh_dbg_regs_short", "sh_dbg_regs_long", "sh_dbg_chain", "sh_dbg_block_sort", "sh_dbg_stage_anchors", "sh_dbg_long_join", "sh_dbg_lr_sort", "sh_dbg_sketch", "sh_dbg_front_end", "sh_dbg_repeat_shortcuts", "sh_pack_flags_device",
     "sh_reads_run", "sh_release_cached_ctx", "sh_host_get_id", "sh_host_filter_fastx", "sh_host_filter_fastx_stream", "sh_host_read_difference",
     "sh_classifier_run", "sh_classifier_taxids", "sh_alignment_run",
     "sh_k2_default_opts", "sh_k2_wave_tile", "sh_k2_open", "sh_k2_create", "sh_k2_insert_device", "sh_k2_insert_sequence_device",
@@ -255,6 +255,8 @@ def load():
     L.sh_dbg_chain.argtypes = [i32, vp, vp, u64, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.sh_dbg_block_sort.argtypes = [i32, vp, vp, u64, vp, i32, vp, vp]
     L.sh_dbg_stage_anchors.argtypes = [i32, vp, u64, vp, u64, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp]
+    L.sh_dbg_long_join.argtypes = [i32, vp, vp, u64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sh_dbg_lr_sort.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp]
     L.sh_dbg_sketch.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.sh_dbg_front_end.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp]
     L.sh_dbg_repeat_shortcuts.argtypes = [vp, vp, vp, u64, u64, vp, i32, vp, vp, vp, vp, vp, vp]

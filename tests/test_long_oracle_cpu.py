@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import long_cases as LC
+from tests import long_join_ref as JR
 from tests import workloads as W
 from tests.test_align_oracle_cpu import extd2, cigar_score
 
@@ -19,25 +20,13 @@ def test_krmq_tree_against_brute_force(oracle):
         assert L.mmo_rmq_selftest(seed, n_ops, key_range) == 0
 
 
-def _sc_simple(ai, aj, pen_gap, pen_skip, log2):
-    dq = int(np.int32(ai[1] & 0xffffffff)) - int(np.int32(aj[1] & 0xffffffff))
-    dr = int(np.int32((ai[0] - aj[0]) & 0xffffffff))
-    dd = abs(dr - dq); dg = min(dr, dq); span = (aj[1] >> 32) & 0xff
-    sc = min(span, dg)
-    exact = dd == 0 and dg <= span
-    if dd or dq > span:
-        lin = np.float32(np.float32(pen_gap) * np.float32(dd) + np.float32(pen_skip) * np.float32(dg))
-        lg = log2(np.float32(dd + 1)) if dd >= 1 else np.float32(0)
-        sc -= int(np.float32(lin + np.float32(0.5) * lg))
-    return sc, exact, dd
-
-
 def test_rmq_chaining_pass_against_a_plain_restatement(oracle):
-    """What mg_lchain_rmq asks of its trees, stated without trees: the active anchor of smallest priority with y in the window, then the
-    inner window in descending (y, i) order.  Random anchor sets with distinct priorities, so no tie rule is involved."""
+    """What mg_lchain_rmq asks of its trees, stated without trees (tests/long_join_ref.py): the active anchor of smallest priority with y in
+    the window, then the inner window in descending (y, i) order.  Random anchor sets with distinct priorities, so no tie rule is involved."""
     L = oracle.lib()
     L.mmo_lchain_rmq_fill.argtypes = [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    log2 = lambda x: np.float32(L.mmo_log2(C.c_float(float(x))))
+    v = np.concatenate([np.arange(2, 4000), 2 ** np.arange(12, 31), 2 ** np.arange(12, 31) + 1]).astype(np.float32)
+    assert [float(L.mmo_log2(C.c_float(float(t)))) for t in v] == [float(t) for t in JR.log2_f32(v)]      # the model's mg_log2 is the oracle's
     rng = np.random.default_rng(5)
     pen_gap, pen_skip, max_dist, inner, bw, max_skip = np.float32(0.12), np.float32(0.0), 5000, 1000, 20000, 25
     for it in range(12):
@@ -48,43 +37,9 @@ def test_rmq_chaining_pass_against_a_plain_restatement(oracle):
         a = np.zeros((n, 2), np.uint64); a[:, 0] = x; a[:, 1] = (np.uint64(15) << np.uint64(32)) | y
         f = np.zeros(n, np.int32); p = np.zeros(n, np.int64); t = np.zeros(n, np.int32)
         L.mmo_lchain_rmq_fill(max_dist, inner, bw, max_skip, 100000, pen_gap, pen_skip, n, a.ctypes.data, f.ctypes.data, p.ctypes.data, t.ctypes.data)
-        md = max(max_dist, bw); mdi = min(inner, md)
-        A = [(int(a[i, 0]), int(a[i, 1])) for i in range(n)]
-        F, Pp, T = [0] * n, [-1] * n, [0] * n
-        i0 = st = st_in = 0
-        root, inn = set(), set()
-        tie = False
-        for i in range(n):
-            xi, yi = A[i]; qi = int(np.int32(yi & 0xffffffff))
-            if i0 < i and A[i0][0] != xi:
-                root |= set(range(i0, i)); inn |= set(range(i0, i)); i0 = i
-            while st < i and xi > A[st][0] + md: root.discard(st); st += 1
-            while st_in < i and xi > A[st_in][0] + mdi: inn.discard(st_in); st_in += 1
-            max_f, max_j = 15, -1
-            pri = lambda j: -(F[j] + 0.5 * float(pen_gap) * (int(np.int32(A[j][0] & 0xffffffff)) + int(np.int32(A[j][1] & 0xffffffff))))
-            cand = [j for j in root if (qi - md < int(np.int32(A[j][1] & 0xffffffff)) < qi) or (int(np.int32(A[j][1] & 0xffffffff)) == qi and j == 0)]
-            if cand:
-                best = min(cand, key=pri)
-                tie |= sum(1 for j in cand if pri(j) == pri(best)) > 1
-                sc, exact, width = _sc_simple(A[i], A[best], pen_gap, pen_skip, log2); sc += F[best]
-                if width <= bw and sc > max_f: max_f, max_j = sc, best
-                if not exact and inn and qi > 0:
-                    n_skip = 0
-                    order = sorted((j for j in inn if int(np.int32(A[j][1] & 0xffffffff)) <= qi - 1), key=lambda j: (int(np.int32(A[j][1] & 0xffffffff)), j), reverse=True)
-                    for j in order:
-                        if int(np.int32(A[j][1] & 0xffffffff)) < qi - mdi: break
-                        sc, _, width = _sc_simple(A[i], A[j], pen_gap, pen_skip, log2); sc += F[j]
-                        if width <= bw:
-                            if sc > max_f:
-                                max_f, max_j = sc, j
-                                if n_skip > 0: n_skip -= 1
-                            elif T[j] == i:
-                                n_skip += 1
-                                if n_skip > max_skip: break
-                            if Pp[j] >= 0: T[Pp[j]] = i
-            F[i], Pp[i] = max_f, max_j
-        if not tie:
-            assert F == f.tolist() and Pp == p.tolist(), it
+        m = JR.join_model(a[:, 0], a[:, 1], max_dist, bw, inner, max_skip, 100000, pen_gap, pen_skip)
+        if not m["shared"]:
+            assert m["F"].tolist() == f.tolist() and m["P"].tolist() == p.tolist(), it
 
 
 def _plain_local(q, t, a, b, amb, o, e):
